@@ -133,6 +133,38 @@ def cell_launch_bytes(N, M, d, eb=4):
             "vertex_side": vertex, "total": edge + vertex}
 
 
+DUMP_MAX_ROWS = 16384       # --dump-outputs: larger state arrays are written as this many sampled rows
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: the whole dump stays below this
+
+
+def dump_outputs(out, variables, dump_dir):
+    """--dump-outputs: the arrays of one step's output dict (forward_device / capture_forward / the training step) ->
+    dump_dir/<name>.npy, float32.  Row-major state arrays of more than DUMP_MAX_ROWS rows keep a sample of rows drawn
+    with a fixed seed from the row count alone, so two runs (or two builds) of one workload write the same rows.
+    Returns {name: [rows written, rows computed]} of the sampled arrays, for the result line."""
+    import torch
+    arrays = {name: out[name] for name in ("predictions", "logits", "E_vote", "stats", "global_norm") if name in out}
+    for kind, state in sorted(out["last_states"].items()):
+        arrays["last_states_%s_c" % kind] = state.c
+        arrays["last_states_%s_h" % kind] = state.h
+    if variables is not None:
+        arrays["variables"] = variables
+    host, sampled = {}, {}
+    for name, t in arrays.items():
+        if t.dim() == 2 and t.shape[0] > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.RandomState(0).choice(t.shape[0], DUMP_MAX_ROWS, replace=False))
+            sampled[name] = [DUMP_MAX_ROWS, int(t.shape[0])]
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        host[name] = t.detach().to(torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dump_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), a)
+    return sampled
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -161,23 +193,40 @@ def main():
                                                                     "(skip parallel.BatchStager)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-baseline budget (bounded sample)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its LAST step as DIR/<name>.npy "
+                         "(float32; rank 0's shard): predictions, logits, E_vote, stats, the last LSTM states and, with "
+                         "--mode train, global_norm and the updated variables.  State arrays of more than %d rows are a "
+                         "fixed seeded sample of rows (the same rows on every run of the same workload)" % DUMP_MAX_ROWS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.plumbing and args.dump_outputs:
+        ap.error("--dump-outputs: a --plumbing run computes no model outputs")
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # `python bench.py --gpus N` without a launcher: start one.  One rank per GPU through torch.distributed.run on
+        # the loopback address (same command line the driver uses); the ranks' single JSON line is rank 0's.  The
+        # launcher is a child process and this one never loads torch or the HIP library: it only waits for it.
+        import signal
+        import socket
+        import subprocess
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+        s.close()
+        child = subprocess.Popen([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
+                                  str(args.gpus), "--master-addr", "127.0.0.1", "--master-port", str(port),
+                                  os.path.abspath(__file__)] + sys.argv[1:])
+        for sig in (signal.SIGTERM, signal.SIGINT):
+            signal.signal(sig, lambda signum, _frame: child.send_signal(signum))
+        rc = child.wait()
+        sys.exit(rc if rc >= 0 else 128 - rc)
 
     import torch
     import tspgnn
     from tspgnn import _lib
 
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: become one.  One rank per GPU through torch.distributed.run on
-        # the loopback address (same command line the driver uses); the ranks' single JSON line is rank 0's.
-        import socket
-        s = socket.socket()
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-        s.close()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
-                                  str(args.gpus), "--master-addr", "127.0.0.1", "--master-port", str(port),
-                                  os.path.abspath(__file__)] + sys.argv[1:])
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -255,6 +304,10 @@ def main():
         return dt, o
 
     elapsed, out = timed(step_fn, args.warmup, args.steps)
+    # (here, before the legs below overwrite the captured graph's output buffers and re-initialise the variables)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(out, sess.store.theta if args.mode == "train" else None, args.dump_outputs)
     loss = float(out["stats"][0].item())
     if not np.isfinite(loss):
         raise SystemExit("non-finite loss in the timed region")
@@ -762,6 +815,8 @@ def main():
             "host_pack_s": round(t_pack, 4),
             "loss": loss,
         }
+        if dumped is not None:
+            result["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "sampled_rows": dumped}
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

@@ -37,6 +37,33 @@ def test_bench_json_contract(cuda_device):
     assert r["value_is"] == "forward pass" and r["forward_value"] == r["value"] and r["range_guard_bits"] == 0
 
 
+def test_bench_dump_outputs(cuda_device, tmp_path):
+    """--dump-outputs DIR: after exactly --steps timed steps, the last step's outputs as float32 .npy files (at most
+    64 MB), the same arrays the result line's loss and guard describe."""
+    import numpy as np
+    d = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                          "--no-cpu-baseline", "--serve-batches", "0", "--train-steps", "0", "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["dump_outputs"]["dir"] == str(d)
+    names = sorted(p.name[:-4] for p in d.iterdir())
+    assert names == sorted(["E_vote", "logits", "predictions", "stats", "last_states_E_c", "last_states_E_h",
+                            "last_states_V_c", "last_states_V_h"])
+    a = {n: np.load(d / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    B, N, M = r["config"]["per_gpu_batch"], r["config"]["N"], r["config"]["M"]
+    assert a["predictions"].shape == a["logits"].shape == (B,) and a["E_vote"].shape == (M,)
+    assert a["last_states_V_h"].shape == (N, 64) and a["last_states_E_h"].shape[0] == min(M, 16384)
+    assert r["dump_outputs"]["sampled_rows"]["last_states_E_h"] == [16384, M]
+    assert a["stats"][0] == np.float32(r["loss"])
+    assert np.allclose(a["predictions"], 1 / (1 + np.exp(-a["logits"].astype(np.float64))), rtol=1e-5, atol=1e-7)
+
+
 def test_bench_two_ranks_gloo_on_one_gpu(cuda_device):
     """The N > 1 path of bench.py (rendezvous, barriers, max-over-ranks timing, the training all-reduce, rank 0
     printing alone) launched the way the driver launches it; gloo instead of RCCL so that two ranks can share
