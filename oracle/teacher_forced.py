@@ -1,0 +1,135 @@
+"""Teacher-forced references of the training step (TEST INFRASTRUCTURE -- the package never imports this).
+
+A backward pass that reads a tape differentiates each message-passing step AT THE STATES THE FORWARD STORED.  The
+references here do the same with the oracle: one oracle step (torch_oracle.step / step_bf16) per time step, evaluated at
+the tape's (H[t], C[t]) and differentiated by autograd, the vector-Jacobian products chained from the last step back to the
+initial embeddings.  Unlike the end-to-end oracle gradient -- whose own forward takes other rounding decisions, amplified over
+the recurrence -- such a reference differs from the device's gradient only by the arithmetic inside one step, so its bar can
+be far tighter; and when the tape is the oracle's own trajectory it IS the end-to-end gradient (tests/test_oracle.py).
+
+H, C: {"V": [T+1, rows, d], "E": [T+1, rows, d]} -- the layout of graphnn.Tape.H / Tape.C, bf16 or fp32, on any device.  A
+step is widened to ``dtype`` on ``device`` only when it is used: the peak memory is one step's graph, not the whole tape.
+"""
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import torch_oracle as TO
+
+
+def _step_fn(bf16, d):
+    """The oracle step of the semantics; bf16: with the edge cell folded exactly where the build folds it (d = 64,
+    LayerNormBasicLSTMCell.can_fold): the two forms round at different points (torch_oracle.step_bf16)."""
+    if not bf16:
+        return TO.step
+    return lambda *a, **kw: TO.step_bf16(*a, fold=(d == 64), **kw)
+
+
+def _uv(batch, device):
+    return torch.as_tensor(np.asarray(batch["ev_uv"]), dtype=torch.long, device=device)
+
+
+def bf16_tape_intermediates(tape):
+    """-> stored(t): the bf16-rounded intermediates a bf16-storage graphnn.Tape kept for step t, in the form of
+    torch_oracle.step_bf16's ``stored`` -- the message MLPs' hidden activations (Tape.acts: the vertex cell's entry holds
+    E_msg_V over the edges, the edge cell's V_msg_E over the vertices), the V<-E aggregate (Tape.X["V"]), the vertex
+    messages (Tape.X["E"]) and the projected messages (Tape.ZX["E"], bf16 blocked by 16 rows -> row-major) of a folded edge
+    cell, or the E<-V aggregate (Tape.X["E"]) of one that is not."""
+    N = tape.H["V"].shape[1]
+
+    def stored(t):
+        common = {"E_msg_V": tape.acts[("V", 0)][:, t], "vagg": tape.X["V"][t], "V_msg_E": tape.acts[("E", 0)][:, t]}
+        if "E" not in tape.ZX:
+            return dict(common, eagg=tape.X["E"][t])
+        z = tape.ZX["E"][t]
+        pad, w = z.shape
+        zx = z.view(pad // 16, w // 16, 4, 16, 4).permute(0, 3, 1, 2, 4).reshape(pad, w)[:N]
+        return dict(common, y2=tape.X["E"][t], zx=zx)
+    return stored
+
+
+def _stored_at(stored, t, device, dtype):
+    if stored is None:
+        return None
+    return {k: v.to(device=device, dtype=dtype) for k, v in stored(t).items()}
+
+
+def forced_grads(params, batch, T, H, C, *, bf16, device, dtype, weights=None, stored=None):
+    """Back-propagation through time of the message passing (bf16=True: in the bf16-storage semantics, roundings passed
+    straight through), one step at a time at the stored states H[t], C[t], then through the initial embeddings and the vote
+    head.  ``params``: the variables (NumPy); ``weights`` (default: params): the values the graph is evaluated at -- e.g. a
+    perturbed copy of the variables, on the same tape.  ``stored`` (bf16 only; e.g. bf16_tape_intermediates(tape)): the
+    step's rounded intermediates are the device's too, not re-rounded by the oracle.
+    -> {name: gradient (NumPy float64)} WITHOUT the L2 term."""
+    tp = TO.to_torch(params if weights is None else weights, dtype, requires_grad=True, device=device)
+    names, plist = list(params.keys()), [tp[k] for k in params]
+    total = [torch.zeros_like(p) for p in plist]
+    uv = _uv(batch, device)
+    step = _step_fn(bf16, H["V"].shape[2])
+
+    def leaf(a):
+        return a.to(device=device, dtype=dtype).detach().requires_grad_(True)
+
+    def vjp(scalar, leaves):
+        g = torch.autograd.grad(scalar, leaves + plist, allow_unused=True)
+        for k, gk in enumerate(g[len(leaves):]):
+            if gk is not None:
+                total[k] += gk
+        return [torch.zeros_like(l) if gi is None else gi for l, gi in zip(leaves, g[:len(leaves)])]
+    Eh = leaf(H["E"][T])
+    dEh, = vjp(TO.vote_head(tp, batch, Eh)["loss"], [Eh])
+    shape = lambda x: (x.shape[1], x.shape[2])
+    dVh = torch.zeros(shape(H["V"]), dtype=dtype, device=device)
+    dVc = torch.zeros(shape(C["V"]), dtype=dtype, device=device)
+    dEc = torch.zeros(shape(C["E"]), dtype=dtype, device=device)
+    for t in range(T - 1, -1, -1):
+        leaves = [leaf(H["V"][t]), leaf(C["V"][t]), leaf(H["E"][t]), leaf(C["E"][t])]
+        kw = {"stored": _stored_at(stored, t, device, dtype)} if stored is not None else {}
+        nVh, nVc, nEh, nEc = step(tp, uv, *leaves, **kw)
+        scalar = (nVh * dVh).sum() + (nVc * dVc).sum() + (nEh * dEh).sum() + (nEc * dEc).sum()
+        del nVh, nVc, nEh, nEc
+        dVh, dVc, dEh, dEc = vjp(scalar, leaves)
+        del leaves, scalar
+    V0, E0 = TO.initial_embeddings(tp, batch)      # (their rounding for storage passes the gradient through)
+    vjp((V0 * dVh).sum() + (E0 * dEh).sum(), [])
+    return OrderedDict((k, g.detach().to(torch.float64).cpu().numpy()) for k, g in zip(names, total))
+
+
+def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.float64, stored=None):
+    """Every row of every stored state H[t+1], C[t+1] against one oracle step from the stored (H[t], C[t]), t = 0..T-1.
+    -> {"V.h" | "V.c" | "E.h" | "E.c": statistics over all rows of all steps}:
+         max    largest |stored - oracle|,            sumsq  sum of the squared differences,   n  entries compared,
+         scale  largest |oracle| entry,
+         ulps   largest |stored - oracle| in bf16 ulps of the entry's own binade (2^(floor(log2 max(|stored|, |oracle|)) - 7)),
+         whole  entries that differ by at least one such ulp,
+         ulps_top  ``ulps`` over the entries at or above 2^-8 of the step's largest |oracle| entry (bf16's own range).
+    ``stored``: as in forced_grads."""
+    tp = TO.to_torch(params, dtype, device=device)
+    uv = _uv(batch, device)
+    step = _step_fn(bf16, H["V"].shape[2])
+    keys = (("V", "h"), ("V", "c"), ("E", "h"), ("E", "c"))
+    acc = {"%s.%s" % k: {"max": 0.0, "sumsq": 0.0, "n": 0, "scale": 0.0, "ulps": 0.0, "whole": 0, "ulps_top": 0.0}
+           for k in keys}
+    w = lambda a: a.to(device=device, dtype=dtype)
+    with torch.no_grad():
+        for t in range(T):
+            kw = {"stored": _stored_at(stored, t, device, dtype)} if stored is not None else {}
+            nxt = step(tp, uv, w(H["V"][t]), w(C["V"][t]), w(H["E"][t]), w(C["E"][t]), **kw)
+            for (v, part), ref in zip(keys, nxt):
+                got = w((H if part == "h" else C)[v][t + 1])
+                a = acc["%s.%s" % (v, part)]
+                diff = (got - ref).abs()
+                ulp = torch.exp2(torch.floor(torch.log2(torch.maximum(got.abs(), ref.abs()).clamp_min(1e-30))) - 7)
+                units = diff / ulp
+                a["max"] = max(a["max"], float(diff.max()))
+                a["sumsq"] += float((diff.to(torch.float64) ** 2).sum())
+                a["n"] += diff.numel()
+                a["scale"] = max(a["scale"], float(ref.abs().max()))
+                a["ulps"] = max(a["ulps"], float(units.max()))
+                a["whole"] += int((units >= 1).sum())
+                top = ref.abs() >= 2.0 ** -8 * float(ref.abs().max())
+                a["ulps_top"] = max(a["ulps_top"], float(units[top].max()) if bool(top.any()) else 0.0)
+                del got, diff, ulp, units
+            del nxt
+    return acc

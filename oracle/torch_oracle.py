@@ -35,10 +35,10 @@ CLIP_NORM = 0.65  # model.py:15
 ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-8  # tf.train.AdamOptimizer defaults
 
 
-def to_torch(params, dtype=torch.float64, requires_grad=False):
+def to_torch(params, dtype=torch.float64, requires_grad=False, device=None):
     out = OrderedDict()
     for k, v in params.items():
-        t = torch.tensor(np.asarray(v), dtype=dtype)
+        t = torch.tensor(np.asarray(v), dtype=dtype, device=device)
         t.requires_grad_(requires_grad)
         out[k] = t
     return out
@@ -97,33 +97,39 @@ def dense_ev(ev_uv, n_total, dtype):
 
 
 def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, trace=None):
-    """GraphNN.__call__ for the TSP wiring (graphnn.py:134-179, model.py:57-94).
-    Both updates read the *old* states (new_states is a fresh dict, graphnn.py:143)."""
+    """GraphNN.__call__ for the TSP wiring (graphnn.py:134-179, model.py:57-94): ``time_steps`` iterations of ``step``."""
     N = V0.shape[0]
-    uv = torch.as_tensor(np.asarray(ev_uv), dtype=torch.long)
+    uv = torch.as_tensor(np.asarray(ev_uv), dtype=torch.long, device=V0.device)
     if dense and EV is None:
-        EV = dense_ev(ev_uv, N, V0.dtype)
+        EV = dense_ev(ev_uv, N, V0.dtype).to(V0.device)
     Vh, Vc = V0, torch.zeros_like(V0)  # graphnn.py:135-138
     Eh, Ec = E0, torch.zeros_like(E0)
     for t in range(int(time_steps)):
-        # V <- LSTM_V( EV^T x E_msg_V(E.h) )
-        y = mlp(Eh, params, "TSP/E_msg_V")
-        if dense:
-            vagg = EV.t() @ y  # tf.matmul(..., adjoint_a=True)
-        else:
-            vagg = torch.zeros_like(Vh).index_add(0, uv[:, 0], y).index_add(0, uv[:, 1], y)
-        # E <- LSTM_E( EV x V_msg_E(V.h) )
-        y2 = mlp(Vh, params, "TSP/V_msg_E")
-        if dense:
-            eagg = EV @ y2
-        else:
-            eagg = y2[uv[:, 0]] + y2[uv[:, 1]]
-        nVh, nVc = lnlstm_cell(vagg, Vh, Vc, params, "V")
-        nEh, nEc = lnlstm_cell(eagg, Eh, Ec, params, "E")
-        Vh, Vc, Eh, Ec = nVh, nVc, nEh, nEc
+        Vh, Vc, Eh, Ec = step(params, uv, Vh, Vc, Eh, Ec, EV=EV if dense else None)
         if trace is not None:
             trace.append((Vh.detach().clone(), Eh.detach().clone()))
     return {"V": (Vh, Vc), "E": (Eh, Ec)}
+
+
+def step(params, uv, Vh, Vc, Eh, Ec, EV=None):
+    """One message-passing step of message_passing (graphnn.py:143-170): -> the next (Vh, Vc, Eh, Ec).  Both updates
+    read the *old* states (new_states is a fresh dict, graphnn.py:143).  uv: long tensor [M,2]; EV given: the
+    adjacency products by the dense block-diagonal matrix (tf.matmul op for op) instead of index_add / gather."""
+    # V <- LSTM_V( EV^T x E_msg_V(E.h) )
+    y = mlp(Eh, params, "TSP/E_msg_V")
+    if EV is not None:
+        vagg = EV.t() @ y  # tf.matmul(..., adjoint_a=True)
+    else:
+        vagg = torch.zeros_like(Vh).index_add(0, uv[:, 0], y).index_add(0, uv[:, 1], y)
+    # E <- LSTM_E( EV x V_msg_E(V.h) )
+    y2 = mlp(Vh, params, "TSP/V_msg_E")
+    if EV is not None:
+        eagg = EV @ y2
+    else:
+        eagg = y2[uv[:, 0]] + y2[uv[:, 1]]
+    nVh, nVc = lnlstm_cell(vagg, Vh, Vc, params, "V")
+    nEh, nEc = lnlstm_cell(eagg, Eh, Ec, params, "E")
+    return nVh, nVc, nEh, nEc
 
 
 def _rb(x):
@@ -133,30 +139,40 @@ def _rb(x):
     return x + (x.to(torch.bfloat16).to(x.dtype) - x).detach()
 
 
-def message_passing_bf16(params, ev_uv, V0, E0, time_steps):
+def message_passing_bf16(params, ev_uv, V0, E0, time_steps, fold=True):
     """The build's bf16-storage mode (BASELINE config 5: "bf16 embeddings with fp32 accumulate"; the reference has
     no reduced-precision path, this restates where tsp-gnn_amd rounds): embeddings h, every stored MLP activation,
     the V<-E aggregate and the projected vertex messages Zx = V_msg_E(V.h) Kx are rounded to bf16, GEMM weights are
     the variables rounded to bf16, sums accumulate in the working precision; the cell state c, LayerNorm, biases
-    and gates are not rounded.  The edge cell is evaluated in the folded form (EV y) Kx = EV (y Kx)."""
-    uv = torch.as_tensor(np.asarray(ev_uv), dtype=torch.long)
+    and gates are not rounded.  The edge cell is evaluated in the folded form (EV y) Kx = EV (y Kx) (``fold``: see step_bf16)."""
+    uv = torch.as_tensor(np.asarray(ev_uv), dtype=torch.long, device=V0.device)
     Vh, Vc = _rb(V0), torch.zeros_like(V0)
     Eh, Ec = _rb(E0), torch.zeros_like(E0)
     for t in range(int(time_steps)):
-        Vh, Vc, Eh, Ec = step_bf16(params, uv, Vh, Vc, Eh, Ec)
+        Vh, Vc, Eh, Ec = step_bf16(params, uv, Vh, Vc, Eh, Ec, fold=fold)
     return {"V": (Vh, Vc), "E": (Eh, Ec)}
 
 
-def step_bf16(params, uv, Vh, Vc, Eh, Ec):
+def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True):
     """One message-passing step of message_passing_bf16 on stored (bf16-valued) h and fp32-class c: -> the next
-    (Vh, Vc, Eh, Ec), h rounded for storage.  uv: long tensor [M,2]."""
+    (Vh, Vc, Eh, Ec), h rounded for storage.  uv: long tensor [M,2].
+    ``fold``: the edge cell's input in the folded form, z = Zx[u] + Zx[v] + h Kh with Zx = bf16(y Kx) -- what the build runs
+    at d = 64 (LayerNormBasicLSTMCell.can_fold) --, or (False) op for op, z = [bf16(y[u] + y[v]) | h] K -- what it runs at
+    the other widths: the two round at different points.
+    ``stored`` (optional): values a device stored for this step's bf16-rounded intermediates, used IN PLACE of the
+    oracle's own rounding (straight through, like it): "E_msg_V" / "V_msg_E" the hidden activations of the message MLPs
+    [3, rows, d], "vagg" the V<-E aggregate [N, d], "y2" the vertex messages [N, d], "zx" the projected messages [N, 4d]."""
     d = Vh.shape[1]
+    stored = stored or {}
 
-    def mlp_b(x, prefix):
+    def pin(x, s):
+        return _rb(x) if s is None else x + (s.to(x.dtype) - x).detach()
+
+    def mlp_b(x, prefix, acts=None, out=None):
         for i in range(4):
             W = _rb(params["%s_MLP_layer_%d/kernel" % (prefix, i + 1)])
             x = x @ W + params["%s_MLP_layer_%d/bias" % (prefix, i + 1)]
-            x = _rb(torch.relu(x) if i < 3 else x)
+            x = pin(torch.relu(x), None if acts is None else acts[i]) if i < 3 else pin(x, out)
         return x
 
     def cell_b(z, c, cell):
@@ -171,15 +187,20 @@ def step_bf16(params, uv, Vh, Vc, Eh, Ec):
         return _rb(torch.relu(new_c) * torch.sigmoid(o)), new_c
     KV = _rb(params["TSP/V_cell/layer_norm_basic_lstm_cell/kernel"])
     KE = _rb(params["TSP/E_cell/layer_norm_basic_lstm_cell/kernel"])
-    y = mlp_b(Eh, "TSP/E_msg_V")
-    vagg = _rb(torch.zeros_like(Vh).index_add(0, uv[:, 0], y).index_add(0, uv[:, 1], y))
-    zx = _rb(mlp_b(Vh, "TSP/V_msg_E") @ KE[:d])
+    y = mlp_b(Eh, "TSP/E_msg_V", acts=stored.get("E_msg_V"))
+    vagg = pin(torch.zeros_like(Vh).index_add(0, uv[:, 0], y).index_add(0, uv[:, 1], y), stored.get("vagg"))
+    y2 = mlp_b(Vh, "TSP/V_msg_E", acts=stored.get("V_msg_E"), out=stored.get("y2"))
     nVh, nVc = cell_b(torch.cat([vagg, Vh], dim=1) @ KV, Vc, "V")
-    nEh, nEc = cell_b(zx[uv[:, 0]] + zx[uv[:, 1]] + Eh @ KE[d:], Ec, "E")
+    if fold:
+        zx = pin(y2 @ KE[:d], stored.get("zx"))
+        nEh, nEc = cell_b(zx[uv[:, 0]] + zx[uv[:, 1]] + Eh @ KE[d:], Ec, "E")
+    else:
+        eagg = pin(y2[uv[:, 0]] + y2[uv[:, 1]], stored.get("eagg"))
+        nEh, nEc = cell_b(torch.cat([eagg, Eh], dim=1) @ KE, Ec, "E")
     return nVh, nVc, nEh, nEc
 
 
-def forward(params, batch, time_steps, dense=False, trace=None, bf16=False):
+def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold=True):
     """build_network forward (model.py:18-157) on a packed batch.
 
     batch: dict with ev_uv int[M,2], W[M], C[M], route_exists[B], n_vertices[B], n_edges[B].
@@ -187,7 +208,7 @@ def forward(params, batch, time_steps, dense=False, trace=None, bf16=False):
     """
     V0, E0 = initial_embeddings(params, batch)
     if bf16:
-        last = message_passing_bf16(params, batch["ev_uv"], V0, E0, time_steps)
+        last = message_passing_bf16(params, batch["ev_uv"], V0, E0, time_steps, fold=fold)
     else:
         last = message_passing(params, batch["ev_uv"], V0, E0, time_steps, dense=dense, trace=trace)
     out = vote_head(params, batch, last["E"][0])
@@ -200,8 +221,8 @@ def initial_embeddings(params, batch):
     some = params["V_init"]
     dtype = some.dtype
     d = some.shape[1]
-    W = torch.as_tensor(np.asarray(batch["W"]), dtype=dtype).reshape(-1, 1)
-    C = torch.as_tensor(np.asarray(batch["C"]), dtype=dtype).reshape(-1, 1)
+    W = torch.as_tensor(np.asarray(batch["W"]), dtype=dtype, device=some.device).reshape(-1, 1)
+    C = torch.as_tensor(np.asarray(batch["C"]), dtype=dtype, device=some.device).reshape(-1, 1)
     N = int(np.asarray(batch["n_vertices"]).astype(np.int64).sum())
     # model.py:43
     E0 = mlp(torch.cat([W, C], dim=1), params, "E_init_MLP")
@@ -213,7 +234,7 @@ def initial_embeddings(params, batch):
 def vote_head(params, batch, E_n):
     """model.py:107-157 from the final edge embeddings: votes, per-problem mean, predictions, metrics, loss."""
     dtype = E_n.dtype
-    labels = torch.as_tensor(np.asarray(batch["route_exists"]), dtype=dtype)
+    labels = torch.as_tensor(np.asarray(batch["route_exists"]), dtype=dtype, device=E_n.device)
     n_edges = np.asarray(batch["n_edges"]).astype(np.int64)
     # model.py:128
     E_vote = mlp(E_n, params, "E_vote").reshape(-1)
@@ -246,11 +267,11 @@ def sigmoid_cross_entropy_with_logits(x, z):
     return torch.clamp(x, min=0) - x * z + torch.log1p(torch.exp(-x.abs()))
 
 
-def loss_and_grads(params_np, batch, time_steps, dtype=torch.float64, dense=False, bf16=False):
+def loss_and_grads(params_np, batch, time_steps, dtype=torch.float64, dense=False, bf16=False, fold=True):
     """tf.gradients(loss + 1e-10 * sum l2_loss(var)) (model.py:163-166), unclipped.  bf16=True: of the bf16-storage
     forward (message_passing_bf16), roundings passed straight through, gradients w.r.t. the unrounded variables."""
     params = to_torch(params_np, dtype=dtype, requires_grad=True)
-    out = forward(params, batch, time_steps, dense=dense, bf16=bf16)
+    out = forward(params, batch, time_steps, dense=dense, bf16=bf16, fold=fold)
     vars_cost = sum((p ** 2).sum() / 2 for p in params.values())
     total = out["loss"] + L2NORM_SCALING * vars_cost
     grads = torch.autograd.grad(total, list(params.values()))

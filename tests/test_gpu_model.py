@@ -10,6 +10,7 @@ import tspgnn
 from conftest import batch_from_tuple, load_pack, rel_err
 from oracle import params as P
 from oracle import torch_oracle as TO
+from oracle import teacher_forced as TF
 
 pytestmark = pytest.mark.gpu
 
@@ -720,45 +721,12 @@ def test_bf16_storage_mode(cuda_device, name, d, T):
     assert abs(float(loss) - ref["loss"].item()) < 5e-4
 
 
-def teacher_forced_bf16_grads(params_np, batch, T, H, C):
-    """Back-propagation through time of the bf16-storage forward, step by step on the STORED states of a run: the
-    vector-Jacobian product of every step (oracle step_bf16 in float64, roundings straight through) is taken at the
-    H[t], C[t] the device kept -- exactly what a backward pass that reads a tape computes.  Unlike the end-to-end
-    oracle gradient (whose own forward takes different rounding decisions, amplified over the recurrence), this
-    differs from the device's only by the roundings inside one step.  -> {name: gradient} without the L2 term."""
-    params = TO.to_torch(params_np, torch.float64, requires_grad=True)
-    names, plist = list(params.keys()), list(params.values())
-    total = [torch.zeros_like(p) for p in plist]
-    uv = torch.as_tensor(np.asarray(batch["ev_uv"]), dtype=torch.long)
-
-    def leaf(a):
-        return torch.tensor(np.asarray(a, dtype=np.float64), requires_grad=True)
-
-    def vjp(scalar, leaves):
-        g = torch.autograd.grad(scalar, leaves + plist, allow_unused=True)
-        for k, gk in enumerate(g[len(leaves):]):
-            if gk is not None:
-                total[k] += gk
-        return [torch.zeros_like(l) if gi is None else gi for l, gi in zip(leaves, g[:len(leaves)])]
-    Eh = leaf(H["E"][T])
-    dEh, = vjp(TO.vote_head(params, batch, Eh)["loss"], [Eh])
-    dVh, dVc, dEc = torch.zeros(H["V"][T].shape, dtype=torch.float64), torch.zeros(C["V"][T].shape, dtype=torch.float64), \
-        torch.zeros(C["E"][T].shape, dtype=torch.float64)
-    for t in range(T - 1, -1, -1):
-        leaves = [leaf(H["V"][t]), leaf(C["V"][t]), leaf(H["E"][t]), leaf(C["E"][t])]
-        nVh, nVc, nEh, nEc = TO.step_bf16(params, uv, *leaves)
-        dVh, dVc, dEh, dEc = vjp((nVh * dVh).sum() + (nVc * dVc).sum() + (nEh * dEh).sum() + (nEc * dEc).sum(), leaves)
-    V0, E0 = TO.initial_embeddings(params, batch)      # (their rounding for storage passes the gradient through)
-    vjp((V0 * dVh).sum() + (E0 * dEh).sum(), [])
-    return {k: g.detach().numpy() for k, g in zip(names, total)}
-
-
 @pytest.mark.parametrize("name,d,T", [("n5_B2", 32, 3), ("ragged_B6", 64, 4), ("n20_B32", 64, 6), ("ragged_B6", 128, 3)])
 def test_bf16_storage_training_gradients(cuda_device, name, d, T):
     """Mixed-precision training in the bf16-storage mode: bf16 tape, fp32 gradients of the function the forward
     evaluated (roundings passed straight through, GEMM weights rounded to bf16), fp32 master variables.
       (a) tight: against step-by-step autograd on the float64 oracle AT THE STATES THE DEVICE STORED
-          (teacher_forced_bf16_grads);
+          (oracle/teacher_forced.forced_grads);
       (b) end to end: against autograd through the oracle's own bf16 forward.  That gradient is itself only defined up
           to the rounding decisions of its forward -- a 1e-6 relative perturbation of the variables moves it by
           percents on these batches (the +-dev instance pairs nearly cancel in the mean) -- so the device's gradient is
@@ -777,13 +745,11 @@ def test_bf16_storage_training_gradients(cuda_device, name, d, T):
     g = model.store.grad_dict()
     tape = out["tape"]
     assert tape.H["E"].dtype == torch.bfloat16 and tape.C["E"].dtype == torch.float32
-    H = {v: tape.H[v].to(torch.float32).cpu().numpy() for v in ("V", "E")}
-    Cs = {v: tape.C[v].cpu().numpy() for v in ("V", "E")}
     batch = {"ev_uv": t[0].uv, "W": t[1], "C": t[2], "route_exists": t[3], "n_vertices": t[4], "n_edges": t[5]}
 
     def l2_dist(a, b):
         return float(np.sqrt(sum(((a[k] - b[k]) ** 2).sum() for k in b) / sum((b[k] ** 2).sum() for k in b)))
-    forced = teacher_forced_bf16_grads(params, batch, T, H, Cs)
+    forced = TF.forced_grads(params, batch, T, tape.H, tape.C, bf16=True, device="cpu", dtype=torch.float64)
     gscale = max(np.abs(forced[k]).max() for k in forced)
     worst = max(np.abs(g[k] - forced[k]).max() / max(np.abs(forced[k]).max(), 1e-2 * gscale) for k in forced)
     tight = l2_dist(g, forced)

@@ -297,3 +297,62 @@ def test_sigmoid_cross_entropy_follows_tensorflows_documented_form():
         assert (got[ok] - naive[ok]).abs().max() < 1e-12
         # the saturated ends: the loss is |x| on the wrong side of the label, ~0 on the right side
         assert abs(float(got[2]) - (800.0 if z == 1.0 else 0.0)) < 1e-12 and abs(float(got[3]) - (0.0 if z == 1.0 else 800.0)) < 1e-12
+
+
+def _trajectory(params_t, batch, T, bf16, fold=True):
+    """The oracle's own states, stacked like graphnn.Tape.H / Tape.C: {"V": [T+1, rows, d], "E": ...}."""
+    V0, E0 = TO.initial_embeddings(params_t, batch)
+    uv = torch.as_tensor(np.asarray(batch["ev_uv"]), dtype=torch.long)
+    Vh, Eh = (TO._rb(V0), TO._rb(E0)) if bf16 else (V0, E0)
+    Vc, Ec = torch.zeros_like(V0), torch.zeros_like(E0)
+    H, C = {"V": [Vh], "E": [Eh]}, {"V": [Vc], "E": [Ec]}
+    for _ in range(T):
+        if bf16:
+            Vh, Vc, Eh, Ec = TO.step_bf16(params_t, uv, Vh, Vc, Eh, Ec, fold=fold)
+        else:
+            Vh, Vc, Eh, Ec = TO.step(params_t, uv, Vh, Vc, Eh, Ec)
+        for v, h, c in (("V", Vh, Vc), ("E", Eh, Ec)):
+            H[v].append(h)
+            C[v].append(c)
+    return {v: torch.stack(H[v]) for v in H}, {v: torch.stack(C[v]) for v in C}
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name,d,T", [("n5_B2", 32, 3), ("ragged_B6", 64, 4)])
+def test_iterated_step_equals_message_passing(name, d, T, bf16):
+    """torch_oracle.step / step_bf16 (either form of the edge cell) applied T times reproduce message_passing /
+    message_passing_bf16 bit for bit -- the step the teacher-forced references (oracle/teacher_forced.py) evaluate is the
+    forward's own."""
+    batch = pack_batch(name)
+    params = TO.to_torch(P.init_params(d, seed=3, perturb=True))
+    V0, E0 = TO.initial_embeddings(params, batch)
+    for fold in ((True, False) if bf16 else (True,)):
+        ref = TO.message_passing_bf16(params, batch["ev_uv"], V0, E0, T, fold=fold) if bf16 else \
+            TO.message_passing(params, batch["ev_uv"], V0, E0, T)
+        H, C = _trajectory(params, batch, T, bf16, fold)
+        for v in ("V", "E"):
+            assert torch.equal(H[v][T], ref[v][0]) and torch.equal(C[v][T], ref[v][1]), (v, fold)
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("name,d,T", [("n5_B2", 32, 3), ("ragged_B6", 64, 4)])
+def test_teacher_forced_gradients_on_the_oracles_own_trajectory(name, d, T, bf16):
+    """oracle/teacher_forced.forced_grads on the oracle's OWN states is the end-to-end gradient (TO.loss_and_grads without
+    the L2 term): what makes it a trustworthy reference for a device gradient computed from a device tape.  Also, the
+    forward check forced_step_errors finds nothing to report on an exact trajectory."""
+    from oracle import teacher_forced as TF
+    batch = pack_batch(name)
+    params = P.init_params(d, seed=3, perturb=True)
+    fold = d == 64    # (the bf16 edge cell is folded where the build folds it: teacher_forced._step_fn)
+    _, ref = TO.loss_and_grads(params, batch, T, dtype=torch.float64, bf16=bf16, fold=fold)
+    ref = {k: ref[k] - TO.L2NORM_SCALING * np.asarray(params[k], dtype=np.float64) for k in ref}
+    with torch.no_grad():
+        H, C = _trajectory(TO.to_torch(params), batch, T, bf16, fold)
+    got = TF.forced_grads(params, batch, T, H, C, bf16=bf16, device="cpu", dtype=torch.float64)
+    assert list(got) == list(ref)
+    gscale = max(float(np.abs(g).max()) for g in ref.values())
+    for k in ref:
+        assert np.abs(got[k] - ref[k]).max() <= 1e-12 * max(float(np.abs(ref[k]).max()), 1e-3 * gscale), k
+    errs = TF.forced_step_errors(params, batch, T, H, C, bf16=bf16, device="cpu")
+    for k, e in errs.items():
+        assert e["max"] == 0.0 and e["n"] == T * H[k[0]].shape[1] * d, (k, e)
