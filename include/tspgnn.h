@@ -433,6 +433,28 @@ int tspgnn_segment_mean_f32(const float* vote, const int32_t* seg, float* logits
 int tspgnn_bce_metrics_f32(const float* logits, const float* labels, float* pred, float* stats,
                            int B, void* stream);
 
+/*
+ * One bracket update of the tour-cost binary search for n_inst instances at once (get_cost's loop,
+ * experiments/binary_search.py:53-75).  Instance i owns the k graphs g = i*k + j of the batch; seg:[n_inst*k+1] is the
+ * batch's edge offsets.  State: lo, hi:[n_inst] fp64 bracket, iters:[n_inst], pred_out:[n_inst] (the prediction
+ * get_cost would return).  An instance is active while lo < w*(1-stopping_delta) || w*(1+stopping_delta) < hi,
+ * w = (hi+lo)/2, evaluated in fp64 as Python does.
+ *   mode 0 (init): writes the first probes of every active instance; reads no predictions (pred may be NULL).
+ *   mode 1 (step): every active instance reads its k predictions pred:[n_inst*k] and applies get_cost's k == 1 rule
+ *                  (p < threshold moves lo, anything else -- NaN included -- moves hi) or its k > 1 rule (probes
+ *                  lo + (hi-lo)*((j+1)/(k+1.0)), bracket around the first p >= threshold, pred_out = preds[min(first,
+ *                  k-1)]); iters += 1; then writes its next probes.  Inactive instances are never touched.
+ * Probe write: WC[e*2+1] = (float)probe (round to nearest) for every edge e of every active graph; column 0 is never
+ * written.  The threshold is compared in fp32, as NumPy compares a float32 prediction with a Python float.
+ * n_active:[1] = number of instances active after the launch (zeroed on `stream` first, so a captured round recounts).
+ * guard: the f16x2 range guard word (VariableStore.h2_guard): if guard[0] & 3 or guard[2] is set, the launch changes
+ * no state and no probe (it still counts the active instances).  Bit-identical to the host loop for the same
+ * predictions.  n_inst == 0 is a no-op.
+ */
+int tspgnn_cost_search_step(double* lo, double* hi, int* iters, float* pred_out, int* n_active, const float* pred,
+                            float* WC, const int32_t* seg, const int* guard, int n_inst, int k, double threshold,
+                            double stopping_delta, int mode, void* stream);
+
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 
 /*

@@ -8,7 +8,7 @@ from . import _lib  # noqa: F401  (raises ImportError if libtspgnn.so is missing
 from ._lib import TspgnnError
 from .graphnn import GraphNN, LSTMStateTuple, DeviceAdjacency, LayerNormBasicLSTMCell
 from .instance_loader import InstanceLoader, SparseEV, read_graph, write_graph, synthetic_batch, random_instance
-from .binary_search import get_cost
+from .binary_search import get_cost, get_costs
 from .mlp import Mlp
 from .parallel import BatchPrefetcher, BatchStager, shard_instances
 from .model import build_network, Session, global_variables_initializer
@@ -21,6 +21,6 @@ from . import experiments
 __all__ = [
     "TspgnnError", "GraphNN", "LSTMStateTuple", "DeviceAdjacency", "LayerNormBasicLSTMCell", "InstanceLoader",
     "SparseEV", "read_graph", "write_graph", "synthetic_batch", "random_instance", "Mlp", "build_network",
-    "Session", "global_variables_initializer", "get_cost", "BatchPrefetcher", "BatchStager", "shard_instances", "VariableStore", "get_default_store", "reset_default_store",
+    "Session", "global_variables_initializer", "get_cost", "get_costs", "BatchPrefetcher", "BatchStager", "shard_instances", "VariableStore", "get_default_store", "reset_default_store",
     "load_weights", "save_weights", "run_batch", "summarize_epoch",
 ]

@@ -336,17 +336,19 @@ class Session(object):
                 guard[0:1].zero_()
         return bool(bits)
 
-    def capture_forward(self, batch):
+    def capture_forward(self, batch, epilogue=None):
         """Captures one forward pass over a resident batch into a HIP graph (hipStreamBeginCapture via
         torch.cuda.CUDAGraph: every libtspgnn launch goes to torch's current stream, so the capture sees
         all of them) and returns ``replay() -> outputs``.  The T-step loop is ~200 launches of 5-90 us
         kernels; replaying the graph removes the per-launch host cost.  The captured graph reads the
-        packed weights that were current at capture time: re-capture after the variables change."""
+        packed weights that were current at capture time: re-capture after the variables change.
+        ``epilogue(outputs)``, if given, enqueues more work on the current stream after the forward: it is
+        captured into the same graph (the warm-up passes do not run it) -- get_costs' bracket update."""
         b = batch if isinstance(batch, DeviceBatch) else self.prepare(batch)
         self.forward_device(b)          # warm-up: builds packed-weight caches (and vets their range) outside the capture
         if self.range_exceeded():       # this batch's activations leave the f16x2 range: capture it on bf16x3
             with self.model["gnn"].forced_off_h2():
-                return self.capture_forward(b)
+                return self.capture_forward(b, epilogue)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(device=self.device)
@@ -356,6 +358,8 @@ class Session(object):
         torch.cuda.current_stream().wait_stream(side)
         with torch.cuda.graph(graph):
             out = self.forward_device(b)
+            if epilogue is not None:
+                epilogue(out)
         version = self.store.version
 
         def replay():
