@@ -18,12 +18,14 @@ import torch
 from . import torch_oracle as TO
 
 
-def _step_fn(bf16, d):
-    """The oracle step of the semantics; bf16: with the edge cell folded exactly where the build folds it (d = 64,
-    LayerNormBasicLSTMCell.can_fold): the two forms round at different points (torch_oracle.step_bf16)."""
+def _step_fn(bf16, d, fold=None):
+    """The oracle step of the semantics; bf16: with the edge cell folded exactly where the build's TRAINING forward folds it
+    (d = 64, LayerNormBasicLSTMCell.can_fold), or as ``fold`` says: the two forms round at different points
+    (torch_oracle.step_bf16).  The inference forward folds at every width (oracle/device_reference.INFERENCE_FOLD)."""
     if not bf16:
         return TO.step
-    return lambda *a, **kw: TO.step_bf16(*a, fold=(d == 64), **kw)
+    fold = (d == 64) if fold is None else bool(fold)
+    return lambda *a, **kw: TO.step_bf16(*a, fold=fold, **kw)
 
 
 def _uv(batch, device):
@@ -96,7 +98,7 @@ def forced_grads(params, batch, T, H, C, *, bf16, device, dtype, weights=None, s
     return OrderedDict((k, g.detach().to(torch.float64).cpu().numpy()) for k, g in zip(names, total))
 
 
-def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.float64, stored=None):
+def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.float64, stored=None, fold=None):
     """Every row of every stored state H[t+1], C[t+1] against one oracle step from the stored (H[t], C[t]), t = 0..T-1.
     -> {"V.h" | "V.c" | "E.h" | "E.c": statistics over all rows of all steps}:
          max    largest |stored - oracle|,            sumsq  sum of the squared differences,   n  entries compared,
@@ -104,10 +106,10 @@ def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.floa
          ulps   largest |stored - oracle| in bf16 ulps of the entry's own binade (2^(floor(log2 max(|stored|, |oracle|)) - 7)),
          whole  entries that differ by at least one such ulp,
          ulps_top  ``ulps`` over the entries at or above 2^-8 of the step's largest |oracle| entry (bf16's own range).
-    ``stored``: as in forced_grads."""
+    ``stored``: as in forced_grads.  ``fold``: the bf16 edge cell's form (default: the training forward's, _step_fn)."""
     tp = TO.to_torch(params, dtype, device=device)
     uv = _uv(batch, device)
-    step = _step_fn(bf16, H["V"].shape[2])
+    step = _step_fn(bf16, H["V"].shape[2], fold)
     keys = (("V", "h"), ("V", "c"), ("E", "h"), ("E", "c"))
     acc = {"%s.%s" % k: {"max": 0.0, "sumsq": 0.0, "n": 0, "scale": 0.0, "ulps": 0.0, "whole": 0, "ulps_top": 0.0}
            for k in keys}

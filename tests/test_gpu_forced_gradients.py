@@ -15,12 +15,11 @@ import torch
 
 from oracle import params as P
 from oracle import teacher_forced as TF
+from oracle.device_reference import SPREAD_DRAWS, spread_draw as _spread_draw
 
 pytestmark = pytest.mark.gpu
 
 C2_T = 32
-SPREAD_DRAWS = 8
-SPREAD_REL = 2.0 ** -22     # the f16x2 packing's weight precision
 
 
 def _batch_dict(t):
@@ -43,13 +42,6 @@ def _train_with_tape(t, params, d, T, gemm=None, bf16=False):
     torch.cuda.synchronize()
     g = {k: np.asarray(v, dtype=np.float64) for k, v in model.store.grad_dict().items()}
     return g, out["tape"], float(out["stats"][0].item())
-
-
-def _spread_draw(params, draw):
-    """Every entry of every variable moved by 2^-22 relative, signs from a generator seeded by ``draw``."""
-    rng = np.random.RandomState(104729 + draw)
-    return {k: np.asarray(v, dtype=np.float64) * (1.0 + (rng.randint(0, 2, size=np.shape(v)) * 2 - 1) * SPREAD_REL)
-            for k, v in params.items()}
 
 
 def _norm(a):

@@ -777,6 +777,7 @@ class GraphNN(object):
         # f16x2 inference forward: the whole T-step loop as ONE launch of resident workgroups (tspgnn_mp_loop_h2) where the
         # wiring and the batch allow it (_loop_launch); False / TSPGNN_LOOP=0 = one row-sum + one cell launch per step
         self.persistent_loop = True
+        self._launched_loop = None   # launched_loop
         # training (f16x2): a message MLP's last linear layer pushed through the row-sum into the receiving cell, as in the
         # inference plan (one Dense layer less per edge row in the forward, the backward and the weight gradients)
         self.push_training = os.environ.get("TSPGNN_PUSH_TRAINING", "1") != "0"
@@ -928,6 +929,7 @@ class GraphNN(object):
         (graphnn.py:128-183).  Embeddings are fp32 device tensors; matrices may be SparseEV,
         DeviceAdjacency, or dense numpy / torch arrays (converted once per call)."""
         self.check_run(adjacency_matrices, initial_embeddings, time_steps, LSTM_initial_states)
+        self._launched_loop = None
         some = next(iter(initial_embeddings.values()))
         device = some.device
         mats, dense_mats = {}, {}
@@ -1124,6 +1126,13 @@ class GraphNN(object):
         if arith == "h2" and (self._h2_force_off or self._h2_off_at == self.store.assignments):
             return "x3"
         return arith
+
+    @property
+    def launched_loop(self):
+        """Which form the last call ran its T steps in: "loop" (one launch of tspgnn_mp_loop_h2), "resident" (one launch
+        of tspgnn_mp_resident_h2) or None (the stepwise launches -- also when a batch had a loop plan but _loop_launch
+        declined the wiring or the device declined the launch)."""
+        return self._launched_loop
 
     def training_packs_h2(self):
         """A training step of this network packs weights into fp16 pieces (the f16x2 forward and backward, or the bf16-storage
@@ -1449,6 +1458,7 @@ class GraphNN(object):
                     raise
                 unsupported[0] = True
                 return None
+            self._launched_loop = kind
             return {ve: out_e, vv: out_v}
         return launch
 
