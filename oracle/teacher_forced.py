@@ -135,3 +135,87 @@ def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.floa
                 del got, diff, ulp, units
             del nxt
     return acc
+
+
+# ---------------------------------------------------------------- the bars (tests/test_gpu_forced_gradients.py)
+FP32_FLOOR = 1e-5               # BASELINE.json's relative tolerance
+BF16_L2 = 3e-3                  # bf16 storage: the gradient's L2 distance, relative to its L2 norm
+BF16_WORST = 8e-3               # ... the worst variable's largest error, relative to max(its largest entry, 1e-2 of all)
+BF16_ROW_RMS = 0.1 * 2.0 ** -8  # ... every stored row: rms of the error, relative to the tensor's largest entry
+BF16_C_MAX = 2.0 ** -7          # ... the fp32 cell states: the largest error, relative to the same
+BF16_H_ULPS = 2.0               # ... the bf16 h (pinned reference): ulps of the entry's own binade, in bf16's range
+
+
+def _norm(a):
+    return float(np.sqrt((np.asarray(a, dtype=np.float64) ** 2).sum()))
+
+
+def fp32_gradient_check(g, f64, f32, draws, rows):
+    """The bar of an fp32-class training backward (any GEMM arithmetic of the fp32 mode, no arithmetic-specific slack), per
+    variable, with scale = max(its largest entry, 1e-3 of the largest entry overall):
+        max(1e-5 scale,  2 x |f32 - f64| (what the same teacher-forced reference loses in float32 on the variable),
+            2 x max over the draws |draw - f64| (the float64 reference at weights moved by 2^-22: an f16x2-packed weight is
+            that far off, and the kernel computes the exact gradient of such a network)),
+    the same bar for the variable's 2-norm, and every stored row within 1e-5 of its tensor's scale.
+    g: the device's gradients; f64, f32: forced_grads in float64 / float32; draws: forced_grads in float64 at
+    device_reference.spread_draw weights; rows: forced_step_errors.  All gradients {name: array}.
+    -> {"ratios": [(err / bar, name, err / scale, bar / scale, norm err / norm bar)], worst first,
+        "rows": {state: largest error / scale}, "failures": [what exceeds its bar]}."""
+    gscale = max(float(np.abs(v).max()) for v in f64.values())
+    ratios = []
+    for k in f64:
+        spread = max([float(np.abs(d[k] - f64[k]).max()) for d in draws], default=0.0)
+        spread_norm = max([abs(_norm(d[k]) - _norm(f64[k])) for d in draws], default=0.0)
+        scale = max(float(np.abs(f64[k]).max()), 1e-3 * gscale)
+        bar = max(FP32_FLOOR * scale, 2.0 * float(np.abs(f32[k] - f64[k]).max()), 2.0 * spread)
+        err = float(np.abs(g[k] - f64[k]).max())
+        nscale = max(_norm(f64[k]), 1e-3 * gscale)
+        nbar = max(FP32_FLOOR * nscale, 2.0 * abs(_norm(f32[k]) - _norm(f64[k])), 2.0 * spread_norm)
+        nerr = abs(_norm(g[k]) - _norm(f64[k]))
+        ratios.append((err / bar, k, err / scale, bar / scale, nerr / nbar))
+    ratios.sort(reverse=True)
+    fwd = {k: e["max"] / e["scale"] for k, e in rows.items()}
+    failures = [(k, "err %.3e bar %.3e (relative to scale), norm ratio %.3f" % (e, b, nr))
+                for r, k, e, b, nr in ratios if not (r < 1.0 and nr < 1.0)]
+    failures += [(k, "row error %.3e of the scale" % e) for k, e in fwd.items() if not e < FP32_FLOOR]
+    return {"ratios": ratios, "rows": fwd, "failures": failures}
+
+
+def _l2_dist(a, b):
+    return float(np.sqrt(sum(((a[k] - b[k]) ** 2).sum() for k in b) / sum((b[k] ** 2).sum() for k in b)))
+
+
+def gradient_report(g, ref):
+    """-> (L2 distance of g from ref relative to ref's L2 norm, [(largest error / max(largest entry, 1e-2 of the largest
+    overall), name)] worst first)."""
+    gscale = max(float(np.abs(v).max()) for v in ref.values())
+    per = sorted(((float(np.abs(g[k] - ref[k]).max()) / max(float(np.abs(ref[k]).max()), 1e-2 * gscale), k) for k in ref),
+                 reverse=True)
+    return _l2_dist(g, ref), per
+
+
+def bf16_gradient_check(g, pinned, rerounded, rows, rows_rr):
+    """The bars of the bf16-storage training backward (tests/test_gpu_model.py::test_bf16_storage_training_gradients sets
+    and explains them) against the teacher-forced bf16 reference, pinned (forced_grads / forced_step_errors with the tape's
+    stored intermediates) and re-rounded (without):
+        the gradient against either: L2 < 3e-3, worst variable < 8e-3 (gradient_report);
+        every stored row against either: rms below 0.1 bf16 ulp (2^-8) of the tensor's largest entry, and the fp32 c
+            no entry more than 2^-7 of that scale off;
+        the bf16 h against the pinned one: no entry in bf16's range more than 2 ulps of its own binade off, none more
+            than 2 ulps of the tensor's scale.
+    -> {"pinned": (L2, per-variable), "rerounded": (L2, per-variable), "failures": [what exceeds its bar]}."""
+    out = {"pinned": gradient_report(g, pinned), "rerounded": gradient_report(g, rerounded), "failures": []}
+    for name in ("rerounded", "pinned"):
+        l2, per = out[name]
+        if not (l2 < BF16_L2 and per[0][0] < BF16_WORST):
+            out["failures"].append((name, "gradient L2 %.2e, worst %s" % (l2, per[:5])))
+    for name, errs in (("pinned", rows), ("re-rounded", rows_rr)):
+        for k, e in errs.items():
+            if not np.sqrt(e["sumsq"] / e["n"]) / e["scale"] < BF16_ROW_RMS:
+                out["failures"].append((name, k, "row rms", e))
+            if k.endswith(".c") and not e["max"] / e["scale"] < BF16_C_MAX:
+                out["failures"].append((name, k, "c max", e))
+    for k in ("V.h", "E.h"):
+        if not (rows[k]["ulps_top"] <= BF16_H_ULPS and rows[k]["max"] / rows[k]["scale"] <= BF16_H_ULPS * 2.0 ** -8):
+            out["failures"].append(("pinned", k, "h ulps", rows[k]))
+    return out

@@ -453,6 +453,88 @@ def test_adam_clip_step(cuda_device):
     assert np.abs(moved - moved_ref).max() < 1e-5 * np.abs(moved_ref).max()
 
 
+def _adam(theta, g, m, v, l2, clip, lr_t, b1, b2, eps, device, counter=None):
+    """One tspgnn_adam_clip_step_f32 on device buffers (in place) -> global norm it reported."""
+    gn = empty((1,), device); wsz = ws("tspgnn_adam_workspace_floats", device=device)
+    _lib.call("tspgnn_adam_clip_step_f32", _lib.ptr(theta), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), theta.numel(), l2, clip,
+              lr_t, b1, b2, eps, _lib.ptr(gn), _lib.ptr(wsz), _lib.ptr(counter), None, None)
+    torch.cuda.synchronize()
+    return gn.item()
+
+
+@pytest.mark.parametrize("counter", [False, True])
+def test_adam_step_reproduces_tensorflow_adam_test_basic(cuda_device, counter):
+    """AdamOptimizerTest.testBasic (tests/test_oracle.py pins it on the oracle) through the kernel: var0 = [1, 2] and
+    var1 = [3, 4] as one flat buffer, constant gradients [0.1, 0.1, 0.01, 0.01], lr 1e-3, beta1 0.9, beta2 0.999, epsilon
+    1e-8, no L2 term and clip <= 0 (no clipping: the scale = 1 branch), three steps -- with the bias-corrected rate from the
+    host, or the base rate and the device's step counter.  The variables reach [0.997, 1.997, 2.997, 3.997] (to the 1e-6
+    of the TF test); m and v stay within 4 fp32 ulps of their closed forms under a constant gradient, (1 - beta1^t) g and
+    (1 - beta2^t) g^2, with the fp32 values of beta1 and beta2 that the kernel receives."""
+    lr, b1, b2, eps = 1e-3, 0.9, 0.999, 1e-8
+    g0 = np.array([0.1, 0.1, 0.01, 0.01], dtype=np.float32)
+    theta, g, m, v = (dev(a, cuda_device) for a in (np.array([1.0, 2.0, 3.0, 4.0]), g0, np.zeros(4), np.zeros(4)))
+    cnt = None
+    if counter:
+        cnt = torch.zeros((1,), dtype=torch.int32, device=cuda_device); _KEEP.append(cnt)
+    b1f, b2f = float(np.float32(b1)), float(np.float32(b2))
+    for t in range(1, 4):
+        lr_t = lr if counter else lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
+        gn = _adam(theta, g, m, v, 0.0, 0.0, float(lr_t), b1, b2, eps, cuda_device, cnt)
+        assert abs(gn - np.sqrt((g0.astype(np.float64) ** 2).sum())) < 1e-7      # reported even when nothing is clipped
+        assert np.array_equal(g.cpu().numpy(), g0)                                # l2 = 0: the gradient is left as it was
+        if counter:
+            assert int(cnt.item()) == t
+        for got, want in ((m, (1 - b1f ** t) * g0.astype(np.float64)), (v, (1 - b2f ** t) * g0.astype(np.float64) ** 2)):
+            got = got.cpu().numpy()
+            ulps = np.abs(got.astype(np.float64) - want) / np.spacing(want.astype(np.float32))
+            assert ulps.max() <= 4, (t, got, want, ulps)
+    assert np.abs(theta.cpu().numpy().astype(np.float64) - [0.997, 1.997, 2.997, 3.997]).max() < 1e-6, theta.cpu().numpy()
+
+
+@pytest.mark.parametrize("clip,scaled", [(4.0, True), (10.0, False)])
+def test_adam_clip_reproduces_tensorflow_clip_by_global_norm(cuda_device, clip, scaled):
+    """ClipTest.testClipByGlobalNormClipped (tests/test_oracle.py pins it on the oracle) through the kernel: x0 = [[-2, 0, 0],
+    [4, 0, 0]] and x1 = [1, -2] as one flat gradient, clip 4 -> global norm exactly 5, and the clipped gradient [-1.6, 0, 0,
+    3.2, 0, 0, 0.8, -1.6].  With lr_t = 0 and beta1 = 0 the kernel's m IS the clipped gradient and the variables stay put.
+    Below the clip (10) the scale is exactly 1: m is the gradient bit for bit."""
+    g0 = np.array([-2.0, 0.0, 0.0, 4.0, 0.0, 0.0, 1.0, -2.0], dtype=np.float32)
+    th0 = np.arange(1, 9, dtype=np.float32)
+    theta, g, m, v = (dev(a, cuda_device) for a in (th0, g0, np.zeros(8), np.zeros(8)))
+    gn = _adam(theta, g, m, v, 0.0, clip, 0.0, 0.0, 0.999, 1e-8, cuda_device)
+    assert gn == 5.0
+    want = np.array([-1.6, 0.0, 0.0, 3.2, 0.0, 0.0, 0.8, -1.6]) if scaled else g0.astype(np.float64)
+    got = m.cpu().numpy()
+    if scaled:
+        assert (np.abs(got.astype(np.float64) - want) <= np.abs(np.spacing(want.astype(np.float32)))).all(), got
+    else:
+        assert np.array_equal(got, g0), got
+    assert np.array_equal(theta.cpu().numpy(), th0)
+
+
+def test_bce_metrics_reproduce_tensorflow_sigmoid_cross_entropy(cuda_device):
+    """tf.nn.sigmoid_cross_entropy_with_logits' documented values (tests/test_oracle.py pins them on the oracle) through
+    tspgnn_bce_metrics_f32, one logit per call (B = 1: stats[0] is the value itself): log 2 at x = 0 whatever the label,
+    0.31326168751822286 at x = 1, z = 1 and 2.1269280110429727 at x = -2, z = 1 (and x = 2, z = 0), and the ends where the
+    naive form breaks, |x| = 50 and 800 -- the loss within 4 fp32 ulps (fp32 exp and log1p carry about one each) of the
+    stable form max(x, 0) - x z + log1p(exp(-|x|)) in float64 (0 exactly where that is 0); acc, TP, FP, TN and FN exactly, with tf.round's half to even at p = 0.5."""
+    import math
+    cases = [(0.0, 0.0, math.log(2.0)), (0.0, 1.0, math.log(2.0)), (1.0, 1.0, 0.31326168751822286),
+             (-2.0, 1.0, 2.1269280110429727), (2.0, 0.0, 2.1269280110429727)]
+    for x in (-800.0, -50.0, 50.0, 800.0):
+        for z in (0.0, 1.0):
+            cases.append((x, z, max(x, 0.0) - x * z + math.log1p(math.exp(-abs(x)))))
+    pred, stats = empty((1,), cuda_device), empty((6,), cuda_device)
+    for x, z, want in cases:
+        lg, lb = dev(np.array([x]), cuda_device), dev(np.array([z]), cuda_device)
+        _lib.call("tspgnn_bce_metrics_f32", _lib.ptr(lg), _lib.ptr(lb), _lib.ptr(pred), _lib.ptr(stats), 1, None)
+        torch.cuda.synchronize()
+        s = stats.cpu().numpy().astype(np.float64)
+        assert abs(s[0] - want) <= 4 * np.spacing(np.float32(want)), (x, z, s[0], want)
+        p = 1.0 / (1.0 + math.exp(-x)) if x > -700 else 0.0
+        eq = float(z == np.rint(p))        # (p = 0.5 at x = 0 rounds to 0; |x| >= 50 saturates p in fp32)
+        assert s[1:].tolist() == [eq, z * eq, z * (1 - eq), (1 - z) * eq, (1 - z) * (1 - eq)], (x, z, s)
+
+
 @pytest.mark.parametrize("d,rows,n_src", [(64, 700, 41), (32, 33, 9)])
 def test_mlp_backward_gather_init_equals_explicit_gather(cuda_device, d, rows, n_src):
     """tspgnn_mlp_bwd_task.uv: the chain starts from dY[u] + dY[v] -- bit-identical to gather2_sum followed by the

@@ -44,6 +44,10 @@ def _inputs(name):
         return tspgnn.synthetic_batch([200] * 32, seed=7), P.init_params(64, seed=9, perturb=True), 64, 8
     if name == "32x200d128":
         return tspgnn.synthetic_batch([200] * 32, seed=7), P.init_params(128, seed=3, perturb=True), 128, 8
+    if name == "128x40d32":
+        return tspgnn.synthetic_batch([40] * 128, seed=5), P.init_params(32, seed=9, perturb=True), 32, 32
+    if name == "32x200d32":
+        return tspgnn.synthetic_batch([200] * 32, seed=7), P.init_params(32, seed=9, perturb=True), 32, 8
     raise KeyError(name)
 
 
@@ -183,6 +187,9 @@ E2E = {
     "c4": [("default", {}, g, None, None) for g in ARITH],
     "32x200": [("resident", RESIDENT, "f16x2", "resident", "resident"), ("default", {}, "f16x2", None, None)],
     "32x200d128": [("default", {}, "f32", None, None)],
+    # d = 32: the one-launch loops are d = 64 only, so the stepwise launches run the <32> templates at size
+    "128x40d32": [("default", {}, g, None, None) for g in ARITH],
+    "32x200d32": [("default", {}, g, None, None) for g in ARITH],
 }
 
 

@@ -10,6 +10,7 @@ import torch
 from conftest import GOLDEN, load_pack, rel_err
 from oracle import np_oracle as NO
 from oracle import params as P
+from oracle import teacher_forced as TF
 from oracle import torch_oracle as TO
 
 
@@ -340,7 +341,6 @@ def test_teacher_forced_gradients_on_the_oracles_own_trajectory(name, d, T, bf16
     """oracle/teacher_forced.forced_grads on the oracle's OWN states is the end-to-end gradient (TO.loss_and_grads without
     the L2 term): what makes it a trustworthy reference for a device gradient computed from a device tape.  Also, the
     forward check forced_step_errors finds nothing to report on an exact trajectory."""
-    from oracle import teacher_forced as TF
     batch = pack_batch(name)
     params = P.init_params(d, seed=3, perturb=True)
     fold = d == 64    # (the bf16 edge cell is folded where the build folds it: teacher_forced._step_fn)
@@ -356,3 +356,73 @@ def test_teacher_forced_gradients_on_the_oracles_own_trajectory(name, d, T, bf16
     errs = TF.forced_step_errors(params, batch, T, H, C, bf16=bf16, device="cpu")
     for k, e in errs.items():
         assert e["max"] == 0.0 and e["n"] == T * H[k[0]].shape[1] * d, (k, e)
+
+
+def _synthetic_gradients(rng):
+    return {"a": rng.randn(7, 5), "b": 1e-2 * rng.randn(13), "c": 3.0 * rng.randn(4, 4)}
+
+
+def _rows(scale, max_rel=0.0, rms_rel=0.0, ulps_top=0.0):
+    n = 1000
+    return {k: {"max": max_rel * scale, "sumsq": n * (rms_rel * scale) ** 2, "n": n, "scale": scale, "ulps": ulps_top,
+                "whole": 0, "ulps_top": ulps_top} for k in ("V.h", "V.c", "E.h", "E.c")}
+
+
+def test_fp32_gradient_bar_catches_one_entry_at_three_times_its_bar():
+    """teacher_forced.fp32_gradient_check on synthetic gradients: the bar of a variable is the largest of the 1e-5 floor, twice
+    the float32 reference's error and twice the spread over the draws; one entry 3x its bar away fails (in the entry and,
+    alone in its variable, in the 2-norm), 0.5x passes.  A stored row at 3x / 0.5x of the 1e-5 bar likewise."""
+    rng = np.random.RandomState(5)
+    f64 = _synthetic_gradients(rng)
+    gscale = max(np.abs(v).max() for v in f64.values())
+    for source in ("floor", "f32", "spread"):
+        f32 = {k: v.copy() for k, v in f64.items()}
+        draws = [{k: v.copy() for k, v in f64.items()} for _ in range(3)]
+        k, i = "a", (2, 3)
+        scale = max(np.abs(f64[k]).max(), 1e-3 * gscale)
+        if source == "f32":
+            f32[k][i] += 4e-4 * scale                    # the float32 reference loses 4e-4 here: bar 8e-4 scale
+        elif source == "spread":
+            draws[1][k][i] -= 3e-4 * scale               # one draw moves it 3e-4: bar 6e-4 scale
+        bar = {"floor": 1e-5, "f32": 8e-4, "spread": 6e-4}[source] * scale
+        for factor, ok in ((0.5, True), (3.0, False)):
+            g = {kk: v.copy() for kk, v in f64.items()}
+            j = (0, 0) if source == "floor" else (4, 1)   # (not the entry the references move: their norm terms then differ)
+            g[k][j] += factor * bar
+            res = TF.fp32_gradient_check(g, f64, f32, draws, _rows(1.0))
+            assert (not res["failures"]) == ok, (source, factor, res["failures"], res["ratios"][:2])
+            assert res["ratios"][0][1] == k and abs(res["ratios"][0][0] - factor) < 1e-6 * factor
+    g = {k: v.copy() for k, v in f64.items()}
+    assert not TF.fp32_gradient_check(g, f64, f64, [], _rows(2.0, max_rel=0.5e-5))["failures"]
+    bad = TF.fp32_gradient_check(g, f64, f64, [], _rows(2.0, max_rel=3e-5))["failures"]
+    assert len(bad) == 4 and {b[0] for b in bad} == {"V.h", "V.c", "E.h", "E.c"}
+
+
+def test_bf16_gradient_bars_catch_three_times_and_pass_half():
+    """teacher_forced.bf16_gradient_check on synthetic gradients and row statistics: each bar (L2 3e-3, worst variable 8e-3,
+    row rms 0.1 * 2^-8, c max 2^-7, h 2 ulps in range) at 3x fails, at 0.5x passes -- against either reference where the bar
+    applies to both, against the pinned one only for the h ulps."""
+    rng = np.random.RandomState(6)
+    ref = _synthetic_gradients(rng)
+    gscale = max(np.abs(v).max() for v in ref.values())
+    good = _rows(1.0)
+    assert not TF.bf16_gradient_check(ref, ref, ref, good, good)["failures"]
+    # worst variable: one entry of "b" (scale 1e-2 of the largest overall) off by factor x 8e-3 of that scale
+    for factor, ok in ((0.5, True), (3.0, False)):
+        g = {k: v.copy() for k, v in ref.items()}
+        g["b"][3] += factor * 8e-3 * max(np.abs(ref["b"]).max(), 1e-2 * gscale)
+        for pinned, rerounded in ((ref, g), (g, ref)):    # (g against itself: 0; the other reference sees the error)
+            res = TF.bf16_gradient_check(g, pinned, rerounded, good, good)
+            assert (not res["failures"]) == ok, (factor, res["failures"])
+    # L2: every entry off by the same relative amount
+    for factor, ok in ((0.5, True), (3.0, False)):
+        g = {k: v * (1 + factor * 3e-3) for k, v in ref.items()}
+        res = TF.bf16_gradient_check(g, g, ref, good, good)
+        assert (not res["failures"]) == ok and res["rerounded"][0] == pytest.approx(factor * 3e-3, rel=1e-9)
+    for field, bar, kw in (("rms", 0.1 * 2.0 ** -8, "rms_rel"), ("c max", 2.0 ** -7, "max_rel"), ("h", 2.0, "ulps_top")):
+        for factor, ok in ((0.5, True), (3.0, False)):
+            rows = _rows(1.0, **{kw: factor * bar})
+            for pinned_rows, rr_rows in ((rows, good), (good, rows)):
+                res = TF.bf16_gradient_check(ref, ref, ref, pinned_rows, rr_rows)
+                expect_fail = not ok and (field != "h" or pinned_rows is rows)
+                assert bool(res["failures"]) == expect_fail, (field, factor, res["failures"])

@@ -778,6 +778,7 @@ class GraphNN(object):
         # wiring and the batch allow it (_loop_launch); False / TSPGNN_LOOP=0 = one row-sum + one cell launch per step
         self.persistent_loop = True
         self._launched_loop = None   # launched_loop
+        self._last_backward = None   # last_backward
         # training (f16x2): a message MLP's last linear layer pushed through the row-sum into the receiving cell, as in the
         # inference plan (one Dense layer less per edge row in the forward, the backward and the weight gradients)
         self.push_training = os.environ.get("TSPGNN_PUSH_TRAINING", "1") != "0"
@@ -1133,6 +1134,17 @@ class GraphNN(object):
         of tspgnn_mp_resident_h2) or None (the stepwise launches -- also when a batch had a loop plan but _loop_launch
         declined the wiring or the device declined the launch)."""
         return self._launched_loop
+
+    @property
+    def last_backward(self):
+        """What the last backward pass ran (None before the first): {"forward": the tape's arithmetic -- "h2" (f16x2),
+        "x3" (bf16x3), "f32" or "bf16" (bf16 storage); "backward": "h2" (the f16x2 cell kernels: only after an f16x2
+        forward), "f32" (the fp32-MFMA kernels), "bf16-native" (the bf16-reading kernels on the tape as it is) or
+        "bf16-widened" (fp32 kernels on widened tape slices); per variable "folded" (the cell's adjacency product folded
+        through its kernel), "pushed" (the message MLP's last layer pushed into the cell), "fused_data" (the pushed cell's
+        data gradient inside its backward launch) and "projected" (a folded cell's dy = dZx Kx^T inside the message MLP's
+        launch); "chunk_steps" and "chunks": the weight gradients' chunking of the T steps}."""
+        return self._last_backward
 
     def training_packs_h2(self):
         """A training step of this network packs weights into fp16 pieces (the f16x2 forward and backward, or the bf16-storage
@@ -2096,6 +2108,12 @@ class GraphNN(object):
                 and not rc.get((v, 0)) and not pushed[v] and self.mlp_backward_h2 and T > 0
                 and self._msg_MLPs[u0["msg"]].backward_task_takes_projection(tape.acts_at((v, 0), 0)[0],
                                                                               4 * self._RNN_cells[v].d))
+        arith = getattr(tape, "arith", None)
+        self._last_backward = {
+            "forward": arith or "f32",
+            "backward": ("bf16-native" if native else "bf16-widened") if arith == "bf16" else (bwd_arith or "f32"),
+            "folded": {v: folded[v] is not None for v in self.var}, "pushed": {v: bool(pushed[v]) for v in self.var},
+            "fused_data": dict(fused_data), "projected": dict(projected), "chunk_steps": CH, "chunks": -(-T // CH)}
         for t in range(T - 1, -1, -1):
             k = t % CH      # slot of step t in the chunk buffers (chunks start at multiples of CH)
             ndH = {v: torch.empty((n[v], d), **f32) for v, d in self.var.items()}
