@@ -455,6 +455,36 @@ int tspgnn_cost_search_step(double* lo, double* hi, int* iters, float* pred_out,
                             float* WC, const int32_t* seg, const int* guard, int n_inst, int k, double threshold,
                             double stopping_delta, int mode, void* stream);
 
+/* ------------------------------------------------------------------ tour labelling (dataset.py:9-50, Concorde's role) */
+
+/*
+ * Batched multi-start iterated local search for symmetric TSP instances (tspgnn/dataset.py solve_tours).  Instance i has
+ * n[i] vertices (4 <= n[i] <= n_max <= 128) and a dense fp32 weight matrix W + w_off[i] of n[i] x n[i] (row-major,
+ * symmetric; absent edges carry a penalty weight chosen by the caller).  One workgroup per instance holds the matrix in
+ * LDS; each of its `restarts` (1..16) wave64 chains runs a best-improvement descent (2-opt, and Or-opt moves of 1-3
+ * vertices in either orientation; a move must gain more than 1e-6 * cost / n; at most 4 n^2 moves per descent), then
+ * `kicks` double-bridge kicks, each followed by a descent and accepted when no worse.  Chain 0 starts from
+ * init_tours + t_off[i] when init_tours is not NULL and that tour is a permutation of 0..n[i]-1; every other start is a
+ * random permutation.  Randomness is keyed on (seed, index[i], chain, kick) only -- index[i] is the instance's position
+ * in the caller's list (index == NULL: i) -- so a result does not depend on how the caller splits its batch into launches.
+ * Out: tours + t_off[i] (n[i] int32) = the best chain's tour in canonical form (tour[0] = 0, tour[1] < tour[n-1]);
+ * costs[i] = its fp32 cost under W.  n_inst == 0 is a no-op; n_max > 128: TSPGNN_EUNSUPPORTED.
+ */
+int tspgnn_tour_search(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                       const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks,
+                       unsigned long long seed, int32_t* tours, float* costs, void* stream);
+
+/*
+ * Held-Karp 1-tree lower bound by subgradient ascent, one wave64 per instance, same W / w_off / n layout as
+ * tspgnn_tour_search.  Each of at most `iters` steps builds the minimum 1-tree under W[u][v] + pi_u + pi_v (Prim on
+ * vertices 1..n-1, plus the two cheapest edges at vertex 0) and moves pi along (degree - 2) with the Polyak step
+ * lambda * (upper[i] - L) / |g|^2, lambda = 2 halved after 8 steps without a new best.  The best multipliers' 1-tree is
+ * rebuilt in fp64 and lb[i] = its value less 8 n DBL_EPSILON times the sum of its terms' magnitudes: a lower bound on
+ * every tour's cost under W, rounding included.
+ */
+int tspgnn_tour_lower_bound(const float* W, const long long* w_off, const int* n, const float* upper, int n_inst,
+                            int n_max, int iters, double* lb, void* stream);
+
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 
 /*

@@ -1,0 +1,78 @@
+"""Times GPU labelling (tspgnn.dataset) at the reference's dataset shapes: the training set (2^15 instances, n 20-40),
+the test set (2^10) and n = 80.  Reports the search, bound and file-writing seconds separately, the certified fraction
+at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per shape.
+
+    python tools/dataset_bench.py [--shapes train,test,n80] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
+"""
+import argparse
+import json
+import os
+import random
+import shutil
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tsp-gnn_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from tspgnn import dataset  # noqa: E402
+
+SHAPES = {"train": (2 ** 15, 20, 40), "test": (2 ** 10, 20, 40), "n80": (2 ** 10, 80, 80)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="train,test,n80")
+    ap.add_argument("--restarts", type=int, default=dataset.DEFAULT_RESTARTS)
+    ap.add_argument("--kicks", type=int, default=dataset.DEFAULT_KICKS)
+    ap.add_argument("--lb-iters", type=int, default=dataset.DEFAULT_LB_ITERS)
+    ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
+    ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
+    ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "dataset_bench needs an MI355X"
+    # warm-up: load the code objects outside the timed runs
+    dataset.solve_tours([(np.triu(np.ones((20, 20)), 1), np.random.RandomState(0).rand(20, 20))], kicks=1)
+    for name in a.shapes.split(","):
+        samples, nmin, nmax = SHAPES[name]
+        samples = a.samples or samples
+        random.seed(1)
+        np.random.seed(1)
+        t0 = time.perf_counter()
+        graphs = dataset.draw_instances(nmin, nmax, samples=samples)
+        t_draw = time.perf_counter() - t0
+        tm = {}
+        res = dataset.solve_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs],
+                                  restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, timings=tm)
+        t_write = None
+        if not a.no_write:
+            out = a.out or tempfile.mkdtemp(prefix="dsbench_")
+            os.makedirs(out, exist_ok=True)
+            t0 = time.perf_counter()
+            for i, (g, r) in enumerate(zip(graphs, res)):
+                dataset.write_graph(np.triu(g[0]), g[1], filepath=os.path.join(out, "%d.graph" % i), route=r.tour)
+            t_write = time.perf_counter() - t0
+            if a.out is None:
+                shutil.rmtree(out)
+        c = dataset.certify(res, 0.02)
+        gap = np.array([(r.cost - r.lb) / r.cost for r in res])
+        print(json.dumps({
+            "shape": name, "samples": samples, "n": [nmin, nmax], "restarts": a.restarts, "kicks": a.kicks,
+            "lb_iters": a.lb_iters, "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
+            "search_s": round(tm["search"], 3), "bound_s": round(tm["bound"], 3),
+            "write_s": None if t_write is None else round(t_write, 3),
+            "feasible": float(np.mean([r.feasible for r in res])),
+            "certified_0.02": round(c["fraction"], 4), "label0": round(float(c["label0"].mean()), 4),
+            "label1": round(float(c["label1"].mean()), 4),
+            "gap": {"median": float(np.median(gap)), "p90": float(np.percentile(gap, 90)),
+                    "p99": float(np.percentile(gap, 99)), "max": float(gap.max()),
+                    "zero": float(np.mean(gap <= 1e-9))},
+        }), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -86,6 +86,9 @@ SIGNATURES = {
     "tspgnn_bucket_unpack_f32": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "tspgnn_cost_search_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p],
+    "tspgnn_tour_search": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                           ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_lower_bound": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",

@@ -1,0 +1,377 @@
+"""Labelled TSP instances: the counterpart of the reference's ``dataset.py`` (create_graph, create_dataset, solve).
+
+The reference labels every instance with Concorde (dataset.py:9-50).  Here the label comes from two HIP kernels
+(csrc/tour_search.hip): ``tspgnn_tour_search``, a batched multi-start iterated local search that returns a short tour,
+and ``tspgnn_tour_lower_bound``, the Held-Karp 1-tree bound that certifies how far that tour can be from the optimum.
+Neither is an exact solver; a label is trusted when ``certify`` says the bound and the tour settle it for the target
+cost ``create_batch`` will feed.
+
+Instance generation (create_graph, create_dataset) draws from the global ``random`` / ``np.random`` in exactly the
+reference's order, so a script that seeds them as the reference's train.py does gets the reference's instances.
+"""
+import collections
+import os
+import random
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from .instance_loader import route_cost, write_graph
+
+MAX_N = 128
+
+# Defaults measured on the MI355X at the reference's training shape (n 20-40): 8 chains of 96 kicks label
+# 2^15 instances in a few seconds, and on n 5-13 they match exact optima; 400 subgradient steps bring the median
+# (cost - lb) / cost under 1 %.  More restarts and kicks only pay at larger n.
+DEFAULT_RESTARTS = 8
+DEFAULT_KICKS = 96
+DEFAULT_LB_ITERS = 400
+DEFAULT_CHUNK = 8192
+
+TourResult = collections.namedtuple("TourResult", ["tour", "cost", "lb", "feasible", "target"])
+TourResult.__doc__ = """One solved instance.
+tour: list of vertex ids, canonical (starts at 0, tour[1] < tour[-1]); cost: fp64 cycle cost with w(i,j) = Mw[min, max];
+lb: a lower bound on every tour that uses real edges only (nan when not computed, inf when no such tour exists for n < 4);
+feasible: the tour uses real edges only; target: Q = n * route_cost(Mw_file, tour), the cost create_batch derives from the
+written file (instance_loader.py:70 pairs route[-1] with route[1]; Mw_file is zero off the upper-triangular edge set)."""
+
+
+def _edge_mask(Ma):
+    A = np.asarray(Ma) != 0
+    A = A | A.T
+    np.fill_diagonal(A, False)
+    return A
+
+
+def _check(k, Ma, Mw):
+    Ma = np.asarray(Ma)
+    Mw = np.asarray(Mw, dtype=np.float64)
+    if Ma.ndim != 2 or Ma.shape[0] != Ma.shape[1] or Mw.shape != Ma.shape:
+        raise ValueError("instance %d: Ma %s and Mw %s must be the same square shape" % (k, Ma.shape, Mw.shape))
+    n = Ma.shape[0]
+    if n < 1:
+        raise ValueError("instance %d: empty graph" % k)
+    if n > MAX_N:
+        raise ValueError("instance %d: n=%d exceeds the tour kernels' limit of %d vertices" % (k, n, MAX_N))
+    w = np.triu(Mw, 1)[np.triu(_edge_mask(Ma), 1)]
+    if w.size and (not np.all(np.isfinite(w)) or w.min() < 0):
+        raise ValueError("instance %d: edge weights must be finite and non-negative" % k)
+    return Ma, Mw, n
+
+
+def _penalised(A, Mw):
+    """[b,n,n] fp32 matrices for the kernels: w(i,j) = Mw[min, max] on edges, n * max(real weight) + 1 off them, rounded
+    towards -inf so that the lower bound computed on them is a lower bound for the fp64 weights too."""
+    b, n, _ = Mw.shape
+    up = np.triu(Mw, 1)
+    w = up + up.transpose(0, 2, 1)
+    mx = np.where(A, w, 0.0).reshape(b, -1).max(axis=1)
+    pen = n * mx + 1.0
+    W = np.where(A, w, pen[:, None, None])
+    idx = np.arange(n)
+    W[:, idx, idx] = 0.0
+    W32 = W.astype(np.float32)
+    over = W32.astype(np.float64) > W
+    W32[over] = np.nextafter(W32[over], np.float32(-np.inf))
+    return W32
+
+
+def _cycle_cost(Mw, tours):
+    """fp64 cost of [b,n] tours under w(i,j) = Mw[min(i,j), max(i,j)], summed in tour order."""
+    nxt = np.roll(tours, -1, axis=1)
+    lo, hi = np.minimum(tours, nxt), np.maximum(tours, nxt)
+    b = np.arange(tours.shape[0])[:, None]
+    w = Mw[b, lo, hi]
+    out = np.zeros(tours.shape[0])
+    for k in range(tours.shape[1]):   # sequential, as the host computes any tour cost
+        out += w[:, k]
+    return out
+
+
+def _host_small(Ma, Mw, n):
+    """n < 4: there is one tour (0, 1, ..., n-1); its cost is exact, so it is its own bound."""
+    tour = list(range(n))
+    A = _edge_mask(Ma)
+    pairs = list(zip(tour, tour[1:] + tour[:1])) if n > 1 else []
+    feasible = all(A[a, b] for a, b in pairs)
+    cost = float(sum(Mw[min(a, b), max(a, b)] for a, b in pairs))
+    return tour, cost, (cost if feasible else float("inf")), feasible
+
+
+def _target(Ma, Mw, tour):
+    n = len(tour)
+    mw_file = np.where(np.triu(_edge_mask(Ma), 1), np.asarray(Mw, dtype=np.float64), 0.0)
+    return n * route_cost(mw_file, tour) if n > 1 else 0.0
+
+
+def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=0, init_tours=None, lower_bound=True,
+                device=None, lb_iters=DEFAULT_LB_ITERS, chunk=DEFAULT_CHUNK, index=None, timings=None):
+    """Solve symmetric TSP instances on the GPU, many at once.
+
+    instances: list of (Ma, Mw); Ma upper-triangular or symmetric (nonzero = edge), Mw [n,n] with w(i,j) = Mw[min, max].
+    Edges absent from Ma cost n * max(real weight) + 1, more than any tour over real edges.
+    restarts: wave64 chains per instance (1..16); kicks: double-bridge kicks per chain; seed: the generator's key.
+    init_tours: optional list (None entries allowed) of starting tours for chain 0 -- create_dataset passes the planted
+    cycle, so a planted graph always gets a feasible tour.
+    lower_bound: also run the Held-Karp bound (lb_iters subgradient steps).  chunk: instances per launch.
+    index: the key of each instance in the generator (default: its position in ``instances``); results depend on
+    (seed, index, restarts, kicks) only, never on ``chunk``.
+    timings: optional dict that receives the seconds spent in 'pack', 'search' and 'bound' (device-synchronised).
+    n < 4 is solved on the host; n > 128 raises ValueError before anything is launched.
+
+    Returns a list of TourResult (tour, cost, lb, feasible, target).
+    """
+    if not 1 <= restarts <= 16:
+        raise ValueError("restarts=%d must be in [1, 16]" % restarts)
+    if kicks < 0 or lb_iters < 1 or chunk < 1:
+        raise ValueError("kicks, lb_iters and chunk must be non-negative / positive")
+    t0 = time.perf_counter()
+    checked = [_check(k, Ma, Mw) for k, (Ma, Mw) in enumerate(instances)]
+    B = len(checked)
+    index = np.arange(B, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64).reshape(-1)
+    if index.shape[0] != B or (B and index.min() < 0):
+        raise ValueError("index must hold one non-negative key per instance")
+    if init_tours is not None and len(init_tours) != B:
+        raise ValueError("init_tours must hold one entry (or None) per instance")
+    out = [None] * B
+    big = [k for k in range(B) if checked[k][2] >= 4]
+    for k in range(B):
+        if checked[k][2] < 4:
+            Ma, Mw, n = checked[k]
+            tour, cost, lb, feas = _host_small(Ma, Mw, n)
+            out[k] = TourResult(tour, cost, lb if lower_bound else float("nan"), feas, _target(Ma, Mw, tour))
+    if not big:
+        return out
+    # pack, grouped by n so that the penalties, costs and targets are array operations
+    ns = np.array([checked[k][2] for k in big], dtype=np.int32)
+    order = np.argsort(ns, kind="stable")            # launch order: by n (similar work per workgroup)
+    big = [big[k] for k in order]
+    ns = ns[order]
+    sq = ns.astype(np.int64) ** 2
+    w_off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
+    t_off = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    Wflat = np.empty(int(sq.sum()), dtype=np.float32)
+    init = np.full(int(ns.sum()), -1, dtype=np.int32)
+    groups = {}
+    for pos, k in enumerate(big):
+        groups.setdefault(int(ns[pos]), []).append(pos)
+    stacked = {}
+    for n, poss in groups.items():
+        A = np.stack([_edge_mask(checked[big[p]][0]) for p in poss])
+        Mw = np.stack([checked[big[p]][1] for p in poss])
+        W32 = _penalised(A, Mw)
+        for g, p in enumerate(poss):
+            Wflat[w_off[p]:w_off[p] + n * n] = W32[g].reshape(-1)
+            if init_tours is not None and init_tours[big[p]] is not None:
+                it = np.asarray(init_tours[big[p]], dtype=np.int64).reshape(-1)
+                if it.shape[0] != n or not np.array_equal(np.sort(it), np.arange(n)):
+                    raise ValueError("init_tours[%d] is not a permutation of 0..%d" % (big[p], n - 1))
+                init[t_off[p]:t_off[p] + n] = it
+        stacked[n] = (A, Mw)
+    has_init = init_tours is not None and any(t is not None for t in init_tours)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    G = len(big)
+    with torch.cuda.device(dev):
+        d_W = torch.from_numpy(Wflat).to(dev)
+        d_woff = torch.from_numpy(w_off).to(dev)
+        d_toff = torch.from_numpy(t_off).to(dev)
+        d_n = torch.from_numpy(ns).to(dev)
+        d_idx = torch.from_numpy(np.ascontiguousarray(index[big])).to(dev)
+        d_init = torch.from_numpy(init).to(dev) if has_init else None
+        d_tours = torch.empty(int(ns.sum()), dtype=torch.int32, device=dev)
+        d_cost = torch.empty(G, dtype=torch.float32, device=dev)
+        d_lb = torch.empty(G, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        st = _lib.current_stream()
+        for c0 in range(0, G, chunk):
+            c1 = min(G, c0 + chunk)
+            _lib.call("tspgnn_tour_search", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                      _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
+                      int(restarts), int(kicks), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours), _lib.ptr(d_cost[c0:c1]),
+                      st)
+        torch.cuda.synchronize(dev)
+        t2 = time.perf_counter()
+        if lower_bound:
+            for c0 in range(0, G, chunk):
+                c1 = min(G, c0 + chunk)
+                _lib.call("tspgnn_tour_lower_bound", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                          _lib.ptr(d_cost[c0:c1]), c1 - c0, int(ns[c0:c1].max()), int(lb_iters), _lib.ptr(d_lb[c0:c1]),
+                          st)
+        torch.cuda.synchronize(dev)
+        t3 = time.perf_counter()
+        tours = d_tours.cpu().numpy().astype(np.int64)
+        lbs = d_lb.cpu().numpy() if lower_bound else np.full(G, np.nan)
+    for n, poss in groups.items():
+        A, Mw = stacked[n]
+        T = np.stack([tours[t_off[p]:t_off[p] + n] for p in poss])
+        cost = _cycle_cost(Mw, T)
+        nxt = np.roll(T, -1, axis=1)
+        feas = A[np.arange(len(poss))[:, None], T, nxt].all(axis=1)
+        for g, p in enumerate(poss):
+            k = big[p]
+            tour = [int(x) for x in T[g]]
+            out[k] = TourResult(tour, float(cost[g]), float(lbs[p]), bool(feas[g]),
+                                _target(checked[k][0], checked[k][1], tour))
+    if timings is not None:
+        timings["pack"] = timings.get("pack", 0.0) + (t1 - t0)
+        timings["search"] = timings.get("search", 0.0) + (t2 - t1)
+        timings["bound"] = timings.get("bound", 0.0) + (t3 - t2)
+    return out
+
+
+def solve(Ma, Mw, **kw):
+    """The reference's contract (dataset.py:9-50): the tour as a list, or None when the best tour found needs an edge
+    absent from Ma.  Keyword arguments go to solve_tours."""
+    r = solve_tours([(Ma, Mw)], lower_bound=False, **kw)[0]
+    return r.tour if r.feasible else None
+
+
+def certify(results, dev=0.02):
+    """Which labels are provably right for the target create_batch feeds (instance_loader.py:70-73).
+
+    results: a list of TourResult, or create_dataset's summary (its 'cost', 'lb', 'target', 'feasible' arrays).
+    With Q = target: the label-0 copy, fed (1-dev) Q, is certified iff lb > (1-dev) Q (no tour is that short); the
+    label-1 copy, fed (1+dev) Q, iff the tour is feasible and cost <= (1+dev) Q.
+    Returns a dict of bool arrays 'label0', 'label1', 'both' and the float 'fraction' (of 'both')."""
+    if isinstance(results, dict):
+        cost, lb, Q, feas = (np.asarray(results[k], dtype=np.float64) for k in ("cost", "lb", "target", "feasible"))
+        feas = feas.astype(bool)
+    else:
+        cost = np.array([r.cost for r in results], dtype=np.float64)
+        lb = np.array([r.lb for r in results], dtype=np.float64)
+        Q = np.array([r.target for r in results], dtype=np.float64)
+        feas = np.array([r.feasible for r in results], dtype=bool)
+    label0 = lb > (1.0 - dev) * Q
+    label1 = feas & (cost <= (1.0 + dev) * Q)
+    both = label0 & label1
+    return {"label0": label0, "label1": label1, "both": both, "fraction": float(both.mean()) if both.size else 1.0}
+
+
+def floyd_warshall(Mw):
+    """All-pairs shortest-path lengths of the complete graph with weights Mw (the reference's networkx closure,
+    dataset.py:87-101); the diagonal is 0."""
+    D = np.array(Mw, dtype=np.float64, copy=True)
+    n = D.shape[0]
+    np.fill_diagonal(D, 0.0)
+    for k in range(n):
+        np.minimum(D, D[:, k:k + 1] + D[k:k + 1, :], out=D)
+    np.fill_diagonal(D, 0.0)
+    return D
+
+
+def _draw_graph(n, connectivity, distances="euc_2D", metric=True):
+    """create_graph's draws (dataset.py:52-108) in the reference's order on the global np.random: the adjacency pairs,
+    then the points or the weights, then the planted permutation.  Returns (symmetric Ma, Mw, permutation, nodes)."""
+    Ma = np.zeros((n, n))
+    Mw = np.zeros((n, n))
+    iu = np.triu_indices(n, 1)   # the (i, j > i) loop order of dataset.py:60-64 and :77-81
+    adj = (np.random.rand(iu[0].size) < connectivity).astype(np.float64)
+    Ma[iu] = adj
+    Ma[iu[1], iu[0]] = adj
+    nodes = None
+    if distances == "euc_2D":
+        nodes = np.random.rand(n, 2)
+        d = nodes[:, None, :] - nodes[None, :, :]
+        sq = d ** 2
+        Mw = np.sqrt(sq[..., 0] + sq[..., 1])   # sum() of a 2-vector: (0 + x0) + x1
+        np.fill_diagonal(Mw, 0.0)
+    elif distances == "random":
+        w = np.random.rand(iu[0].size)
+        Mw[iu] = w
+        Mw[iu[1], iu[0]] = w
+    if metric and distances != "euc_2D":
+        Mw = floyd_warshall(Mw)
+    permutation = [int(x) for x in np.random.permutation(n)]
+    for i, j in zip(permutation, permutation[1:] + permutation[:1]):
+        Ma[i, j] = Ma[j, i] = 1
+    return Ma, Mw, permutation, nodes
+
+
+def create_graph(n, connectivity, distances="euc_2D", metric=True, **solve_kw):
+    """dataset.py:52-116: a random graph with a planted Hamiltonian cycle, labelled with the best tour found.
+    Returns (np.triu(Ma), Mw, route, nodes); raises Exception('Unsolvable') as the reference does when that tour needs an
+    absent edge (it cannot here: the planted cycle is the search's first start).  solve_kw go to solve_tours."""
+    Ma, Mw, perm, nodes = _draw_graph(n, connectivity, distances, metric)
+    solve_kw.setdefault("lower_bound", False)
+    r = solve_tours([(Ma, Mw)], init_tours=[perm], **solve_kw)[0]
+    if not r.feasible:
+        raise Exception("Unsolvable")
+    return np.triu(Ma), Mw, r.tour, nodes
+
+
+def draw_instances(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True):
+    """The instance stream of create_dataset (dataset.py:126-133): per sample random.randint(nmin, nmax), then
+    np.random.uniform(conn_min, conn_max), then create_graph's draws.  Returns a list of (Ma, Mw, permutation, nodes)."""
+    out = []
+    for _ in range(samples):
+        n = random.randint(nmin, nmax)
+        out.append(_draw_graph(n, np.random.uniform(conn_min, conn_max), distances=distances, metric=metric))
+    return out
+
+
+def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True,
+                   require_certified=None, max_redraw_rounds=20, verbose=False, **solve_kw):
+    """dataset.py:118-143: draw ``samples`` instances (the reference's stream), label them on the GPU in batches with
+    the planted cycle as a starting tour, and write ``{path}/{i}.graph`` with write_graph.
+
+    require_certified=None | dev: redraw (from the same global RNG, after the whole stream) every instance whose labels
+    ``certify(.., dev)`` cannot prove, for at most max_redraw_rounds rounds, then raise RuntimeError if any remain.
+    Redrawing BIASES the distribution: it drops the instances whose optimum sits close to the quirk target, which are the
+    hardest ones, and the set no longer matches the reference's stream from the first redrawn index on.
+    solve_kw go to solve_tours (restarts, kicks, seed, lb_iters, chunk, device).
+
+    Returns a summary dict: samples, n (per instance), cost, lb, target, feasible, gap = (cost - lb) / cost,
+    certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'}.
+    """
+    os.makedirs(path, exist_ok=True)
+    graphs = draw_instances(nmin, nmax, conn_min, conn_max, samples, distances, metric)
+    times = {}
+    solve_kw.setdefault("lower_bound", True)
+
+    def label(idx, keys):
+        res = solve_tours([(graphs[i][0], graphs[i][1]) for i in idx], init_tours=[graphs[i][2] for i in idx],
+                          index=keys, timings=times, **solve_kw)
+        for r in res:
+            if not r.feasible:
+                raise Exception("Unsolvable")
+        return res
+
+    results = label(list(range(samples)), np.arange(samples))
+    redrawn = 0
+    if require_certified is not None:
+        for rnd in range(1, max_redraw_rounds + 1):
+            bad = np.nonzero(~certify(results, require_certified)["both"])[0]
+            if bad.size == 0:
+                break
+            for i in bad:
+                n = graphs[i][0].shape[0]
+                graphs[i] = _draw_graph(n, np.random.uniform(conn_min, conn_max), distances=distances, metric=metric)
+            redrawn += int(bad.size)
+            new = label(list(bad), rnd * samples + bad)
+            for i, r in zip(bad, new):
+                results[i] = r
+        else:
+            if not certify(results, require_certified)["both"].all():
+                raise RuntimeError("create_dataset: instances still uncertified after %d redraw rounds" % max_redraw_rounds)
+    t0 = time.perf_counter()
+    for i, (g, r) in enumerate(zip(graphs, results)):
+        write_graph(np.triu(g[0]), g[1], filepath="{}/{}.graph".format(path, i), route=r.tour)
+        if verbose and samples >= 20 and (i + 1) % (samples // 20) == 0:
+            print("Dataset creation {}% complete".format(int(100 * (i + 1) / samples)), flush=True)
+    times["write"] = time.perf_counter() - t0
+    summary = {
+        "samples": samples,
+        "n": np.array([g[0].shape[0] for g in graphs]),
+        "cost": np.array([r.cost for r in results]),
+        "lb": np.array([r.lb for r in results]),
+        "target": np.array([r.target for r in results]),
+        "feasible": np.array([r.feasible for r in results]),
+        "redrawn": redrawn,
+        "times": times,
+    }
+    summary["gap"] = (summary["cost"] - summary["lb"]) / np.where(summary["cost"] > 0, summary["cost"], 1.0)
+    summary["certified_fraction"] = certify(summary, 0.02 if require_certified is None else require_certified)["fraction"]
+    return summary
