@@ -5,6 +5,7 @@
 
 Unlike the reference's __main__, -seed is applied: random and np.random are seeded with it before the first draw, so
 the instance stream is the one the reference's train.py gets after its own seeding (train.py seeds both the same way).
+Instances of up to 256 vertices are labelled (tspgnn.label_tours).
 --metric, as in the reference, turns the metric closure OFF for random distances.
 """
 import argparse

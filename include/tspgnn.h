@@ -485,6 +485,27 @@ int tspgnn_tour_search(const float* W, const long long* w_off, const int* n, con
 int tspgnn_tour_lower_bound(const float* W, const long long* w_off, const int* n, const float* upper, int n_inst,
                             int n_max, int iters, double* lb, void* stream);
 
+/*
+ * tspgnn_tour_search for instances of up to 256 vertices (dataset.py:9-50): the same search, moves, kicks, keys and
+ * canonical output, on the packed strict upper triangle.  W + w_off[i] holds n[i] (n[i] - 1) / 2 fp32 values, row-major:
+ * w(a, b) for a < b sits at a (2 n - 3 - a) / 2 - 1 + b.  4 <= n[i] <= n_max <= 256; n_max > 256: TSPGNN_EUNSUPPORTED.
+ * The workgroup keeps the triangle and three tours of n_max int32 ids per chain in LDS, 2 n_max (n_max - 1) +
+ * 12 restarts n_max bytes, which must fit 163 712 (160 KiB less 128 static): at n_max = 256 restarts <= 10, at
+ * n_max <= 242 all 16 fit.  A larger restarts is TSPGNN_EINVAL, and the message names the limit.  For n <= 128 the tours
+ * and costs equal tspgnn_tour_search's bit for bit, given the same seed, index, restarts and kicks.
+ */
+int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                           const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks,
+                           unsigned long long seed, int32_t* tours, float* costs, void* stream);
+
+/*
+ * tspgnn_tour_lower_bound on the packed triangle of tspgnn_tour_search_tri (dataset.py:9-50): the same subgradient
+ * ascent, fp64 re-evaluation and margin; a lane owns the vertices l, l+64, l+128 and l+192.  n_max <= 256
+ * (above: TSPGNN_EUNSUPPORTED).  For n <= 128, lb[i] equals tspgnn_tour_lower_bound's bit for bit.
+ */
+int tspgnn_tour_lower_bound_tri(const float* W, const long long* w_off, const int* n, const float* upper, int n_inst,
+                                int n_max, int iters, double* lb, void* stream);
+
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 
 /*

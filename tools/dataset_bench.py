@@ -1,8 +1,10 @@
 """Times GPU labelling (tspgnn.dataset) at the reference's dataset shapes: the training set (2^15 instances, n 20-40),
-the test set (2^10) and n = 80.  Reports the search, bound and file-writing seconds separately, the certified fraction
+the test set (2^10), n = 80, and n = 200 and 256 (label_tours on the triangle kernels).  Reports the search, bound and file-writing seconds separately, the certified fraction
 at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per shape.
 
-    python tools/dataset_bench.py [--shapes train,test,n80] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
+    python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
+
+Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
 """
 import argparse
 import json
@@ -21,22 +23,24 @@ import torch  # noqa: E402
 
 from tspgnn import dataset  # noqa: E402
 
-SHAPES = {"train": (2 ** 15, 20, 40), "test": (2 ** 10, 20, 40), "n80": (2 ** 10, 80, 80)}
+SHAPES = {"train": (2 ** 15, 20, 40), "test": (2 ** 10, 20, 40), "n80": (2 ** 10, 80, 80), "n200": (2 ** 10, 200, 200),
+          "n256": (2 ** 10, 256, 256)}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="train,test,n80")
-    ap.add_argument("--restarts", type=int, default=dataset.DEFAULT_RESTARTS)
-    ap.add_argument("--kicks", type=int, default=dataset.DEFAULT_KICKS)
-    ap.add_argument("--lb-iters", type=int, default=dataset.DEFAULT_LB_ITERS)
+    ap.add_argument("--restarts", type=int, default=None)
+    ap.add_argument("--kicks", type=int, default=None)
+    ap.add_argument("--lb-iters", type=int, default=None)
     ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_bench needs an MI355X"
     # warm-up: load the code objects outside the timed runs
-    dataset.solve_tours([(np.triu(np.ones((20, 20)), 1), np.random.RandomState(0).rand(20, 20))], kicks=1)
+    for n in (20, 130):
+        dataset.label_tours([(np.triu(np.ones((n, n)), 1), np.random.RandomState(0).rand(n, n))], kicks=1, lb_iters=1)
     for name in a.shapes.split(","):
         samples, nmin, nmax = SHAPES[name]
         samples = a.samples or samples
@@ -46,8 +50,12 @@ def main():
         graphs = dataset.draw_instances(nmin, nmax, samples=samples)
         t_draw = time.perf_counter() - t0
         tm = {}
-        res = dataset.solve_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs],
+        res = dataset.label_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs],
                                   restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, timings=tm)
+        large = nmax > dataset.MAX_N
+        restarts = a.restarts or (dataset.DEFAULT_RESTARTS_LARGE if large else dataset.DEFAULT_RESTARTS)
+        kicks = a.kicks if a.kicks is not None else (dataset.DEFAULT_KICKS_LARGE if large else dataset.DEFAULT_KICKS)
+        lb_iters = a.lb_iters or (dataset.DEFAULT_LB_ITERS_LARGE if large else dataset.DEFAULT_LB_ITERS)
         t_write = None
         if not a.no_write:
             out = a.out or tempfile.mkdtemp(prefix="dsbench_")
@@ -61,8 +69,8 @@ def main():
         c = dataset.certify(res, 0.02)
         gap = np.array([(r.cost - r.lb) / r.cost for r in res])
         print(json.dumps({
-            "shape": name, "samples": samples, "n": [nmin, nmax], "restarts": a.restarts, "kicks": a.kicks,
-            "lb_iters": a.lb_iters, "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
+            "shape": name, "samples": samples, "n": [nmin, nmax], "restarts": restarts, "kicks": kicks,
+            "lb_iters": lb_iters, "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
             "search_s": round(tm["search"], 3), "bound_s": round(tm["bound"], 3),
             "write_s": None if t_write is None else round(t_write, 3),
             "feasible": float(np.mean([r.feasible for r in res])),

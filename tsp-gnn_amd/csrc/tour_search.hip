@@ -4,6 +4,10 @@
 //   tspgnn_tour_lower_bound  the Held-Karp 1-tree bound by subgradient ascent, one wave64 per instance, the final 1-tree
 //                            re-evaluated in fp64 so that the reported value is a lower bound under rounding.
 // Both are issue-bound on LDS reads and VALU work: an instance reads its n*n weights from memory once.
+// Each has two layouts of the weights, one device body: the dense matrix (tspgnn_tour_search / _lower_bound, n <= 128)
+// and the packed strict upper triangle (the _tri entry points, n <= 256, 130 560 B at n = 256).  The bodies read a weight
+// only through the layout's W(a, b), and both layouts hold the same fp32 value for w(a, b), so for n <= 128 the two give
+// the same bits.
 //
 // Termination: every loop below has a fixed trip-count bound.  A descent accepts a move only on a strict improvement of
 // more than kEpsRel * cost / n and makes at most 4 n^2 moves; the kick and subgradient counts are arguments.  There is no
@@ -16,9 +20,9 @@
 namespace tspgnn {
 namespace {
 
-constexpr int kMaxN = 128;
 constexpr int kMaxChains = 16;
 constexpr float kEpsRel = 1e-6f;   // a move must gain more than kEpsRel * (cost / n): ~16 ulp of a mean edge
+constexpr size_t kLdsBytes = 160 * 1024;   // gfx950: LDS per workgroup, static and dynamic together
 
 // Intra-wave LDS hand-off: lanes of one wave write, other lanes of the same wave read.  A wave executes its LDS
 // operations in order; this only keeps the compiler from moving accesses across the point.
@@ -28,8 +32,41 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Row stride of the LDS weight matrix: odd, so a column read by 32 consecutive rows touches 32 distinct banks.
-__device__ __forceinline__ int lds_stride(int n) { return n | 1; }
+// The dense layout: row stride n | 1, odd, so a column read by 32 consecutive rows touches 32 distinct banks.
+struct SquareW {
+    static constexpr int kMaxN = 128;
+    const float* w;
+    int s;
+    __host__ __device__ static size_t floats(int n) { return (size_t)n * (size_t)(n | 1); }
+    __device__ static SquareW stage(float* lds, const float* src, int n, int tid, int nt) {
+        const int s = n | 1;
+        for (int e = tid; e < n * n; e += nt) lds[(e / n) * s + e % n] = src[e];
+        return {lds, s};
+    }
+    __device__ __forceinline__ float operator()(int a, int b) const { return w[a * s + b]; }
+};
+
+// The packed strict upper triangle, row-major: w(a, b) = w[off(min) + max], off(r) = r (2n - 3 - r) / 2 - 1 (r (2n-3-r)
+// is even).  Callers never ask for the diagonal, which the layout does not hold.
+struct TriW {
+    static constexpr int kMaxN = 256;
+    const float* w;
+    int k;   // 2n - 3
+    __host__ __device__ static size_t floats(int n) { return (size_t)n * (size_t)(n - 1) / 2; }
+    __device__ static TriW stage(float* lds, const float* src, int n, int tid, int nt) {
+        const int m = n * (n - 1) / 2;
+        for (int e = tid; e < m; e += nt) lds[e] = src[e];
+        return {lds, 2 * n - 3};
+    }
+    __device__ __forceinline__ float operator()(int a, int b) const {
+        const int lo = min(a, b), hi = max(a, b);
+        return w[hi - 1 + (int)(__umul24((unsigned)lo, (unsigned)(k - lo)) >> 1)];
+    }
+};
+
+// The move codes below keep a tour position in 8 bits, and one_tree gives a lane kMaxN / 64 vertices.
+static_assert(SquareW::kMaxN - 1 <= 0xff && TriW::kMaxN - 1 <= 0xff, "move codes hold positions 0..255");
+static_assert(SquareW::kMaxN % kWave == 0 && TriW::kMaxN % kWave == 0, "one_tree's vertices per lane");
 
 // Counter-based generator: splitmix64 finaliser over (seed, instance index in the caller's list, chain, kick, draw).
 // Nothing depends on blockIdx, so results do not depend on how the caller chunks its batch.
@@ -66,9 +103,10 @@ __device__ __forceinline__ T wave_sum(T v) {
     return v;
 }
 
-__device__ __forceinline__ float tour_cost(const float* W, int s, const int* t, int n, int lane) {
+template <class WA>
+__device__ __forceinline__ float tour_cost(const WA& W, const int* t, int n, int lane) {
     float acc = 0.f;
-    for (int k = lane; k < n; k += kWave) acc += W[t[k] * s + t[k + 1 < n ? k + 1 : 0]];
+    for (int k = lane; k < n; k += kWave) acc += W(t[k], t[k + 1 < n ? k + 1 : 0]);
     return wave_sum(acc);
 }
 
@@ -91,8 +129,9 @@ struct Strider {
 };
 
 // Best-improvement descent on tour *t (scratch *u; the two are swapped per applied move).  Returns the tour's cost.
-__device__ float descend(const float* W, int s, int*& t, int*& u, int n, int lane) {
-    float cost = tour_cost(W, s, t, n, lane);
+template <class WA>
+__device__ float descend(const WA& W, int*& t, int*& u, int n, int lane) {
+    float cost = tour_cost(W, t, n, lane);
     const int cap = 4 * n * n;
     for (int mv = 0; mv < cap; ++mv) {
         float best = FLT_MAX;
@@ -102,7 +141,7 @@ __device__ float descend(const float* W, int s, int*& t, int*& u, int n, int lan
             const int i = p.i, j = p.j;
             if (j > i + 1 && !(i == 0 && j == n - 1)) {
                 const int a = t[i], b = t[i + 1], c = t[j], e = t[j + 1 < n ? j + 1 : 0];
-                const float d = (W[a * s + c] + W[b * s + e]) - (W[a * s + b] + W[c * s + e]);
+                const float d = (W(a, c) + W(b, e)) - (W(a, b) + W(c, e));
                 const int cd = (i << 8) | j;
                 if (d < best || (d == best && cd < code)) {
                     best = d;
@@ -123,10 +162,10 @@ __device__ float descend(const float* W, int s, int*& t, int*& u, int n, int lan
                 if (ip < 0) ip += n;
                 if (q1 >= n) q1 -= n;
                 const int prev = t[ip], s0 = t[i], sl = t[ie], nx = t[in], a = t[q], b = t[q1];
-                const float gain = W[prev * s + nx] - (W[prev * s + s0] + W[sl * s + nx]);
-                const float ab = W[a * s + b];
-                const float fwd = (W[a * s + s0] + W[sl * s + b]) - ab;
-                const float rev = (W[a * s + sl] + W[s0 * s + b]) - ab;
+                const float gain = W(prev, nx) - (W(prev, s0) + W(sl, nx));
+                const float ab = W(a, b);
+                const float fwd = (W(a, s0) + W(sl, b)) - ab;
+                const float rev = (W(a, sl) + W(s0, b)) - ab;
                 const bool use_rev = L > 1 && rev < fwd;
                 const float d = gain + (use_rev ? rev : fwd);
                 const int cd = kOrOpt | (use_rev ? 1 << 29 : 0) | (L << 26) | (i << 8) | q;
@@ -158,7 +197,7 @@ __device__ float descend(const float* W, int s, int*& t, int*& u, int n, int lan
         int* x = t;
         t = u;
         u = x;
-        cost = tour_cost(W, s, t, n, lane);
+        cost = tour_cost(W, t, n, lane);
     }
     return cost;
 }
@@ -184,6 +223,7 @@ __device__ void double_bridge(const int* src, int* dst, int n, uint64_t r, int l
     wave_sync();
 }
 
+template <class WA>
 __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     const float* __restrict__ Wg, const long long* __restrict__ w_off, const int* __restrict__ n_arr,
     const int32_t* __restrict__ init, const long long* __restrict__ t_off, const long long* __restrict__ index, int n_max,
@@ -200,14 +240,9 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
         if (threadIdx.x == 0) costs[inst] = __int_as_float(0x7fc00000);
         return;
     }
-    const int s = lds_stride(n);
-    const float* W = lds;
-    {
-        const float* src = Wg + w_off[inst];
-        for (int e = threadIdx.x; e < n * n; e += blockDim.x) lds[(e / n) * s + e % n] = src[e];
-    }
-    // per chain: three tours of n vertex ids (current, work, scratch) after the matrix
-    int* base = reinterpret_cast<int*>(lds + n_max * lds_stride(n_max)) + wave * 3 * n_max;
+    const WA W = WA::stage(lds, Wg + w_off[inst], n, threadIdx.x, blockDim.x);
+    // per chain: three tours of n vertex ids (current, work, scratch) after the weights
+    int* base = reinterpret_cast<int*>(lds + WA::floats(n_max)) + wave * 3 * n_max;
     int* cur = base;
     int* work = base + n_max;
     int* scr = base + 2 * n_max;
@@ -243,10 +278,10 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
         }
         wave_sync();
     }
-    float best = descend(W, s, cur, scr, n, lane);
+    float best = descend(W, cur, scr, n, lane);
     for (int kick = 0; kick < kicks; ++kick) {
         double_bridge(cur, work, n, draw(seed, gi, wave, kick, 0), lane);
-        const float c = descend(W, s, work, scr, n, lane);
+        const float c = descend(W, work, scr, n, lane);
         if (c <= best) {   // no worse: accept (the chain's current tour is always its best)
             int* x = cur;
             cur = work;
@@ -288,73 +323,94 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
 
 // ---------------------------------------------------------------------------------------------------------- lower bound
 
-// Minimum 1-tree under the costs c(u,v) = W[u][v] + pi_u + pi_v, evaluated in T: Prim's tree on vertices 1..n-1 plus the two
-// cheapest edges at vertex 0.  Lane l owns vertices l and l+64.  Returns sum c(edges) - 2 sum pi; deg[] (LDS) gets the
-// 1-tree degrees; *mag gets sum |c(edges)| + 2 sum |pi| (the scale of the rounding error).
-template <typename T>
-__device__ T one_tree(const float* W, int s, int n, T pi0, T pi1, int lane, int* deg, T* mag) {
+// Minimum 1-tree under the costs c(u,v) = W(u,v) + pi_u + pi_v, evaluated in T: Prim's tree on vertices 1..n-1 plus the two
+// cheapest edges at vertex 0.  Lane l owns the K vertices l, l+64, ... (pi[j] is vertex l + 64 j's).  Returns sum c(edges)
+// - 2 sum pi; deg[] (LDS) gets the 1-tree degrees; *mag gets sum |c(edges)| + 2 sum |pi| (the scale of the rounding
+// error).  Vertices past n take no part and add nothing to a lane's sums, so the result does not depend on K.
+template <typename T, int K, class WA>
+__device__ T one_tree(const WA& W, int n, const T (&pi)[K], int lane, int* deg, T* mag) {
     const T inf = (T)FLT_MAX * (T)4;
-    const int v0 = lane, v1 = lane + kWave;
-    const bool ok0 = v0 < n, ok1 = v1 < n;
-    if (ok0) deg[v0] = 0;
-    if (ok1) deg[v1] = 0;
+    int v[K];
+    bool ok[K], in[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        v[j] = lane + j * kWave;
+        ok[j] = v[j] < n;
+        if (ok[j]) deg[v[j]] = 0;
+        in[j] = !ok[j] || v[j] <= 1;
+    }
     wave_sync();
-    bool in0 = !ok0 || v0 <= 1, in1 = !ok1;
-    const T pir = __shfl(pi0, 1);
-    T key0 = in0 ? inf : (T)W[s + v0] + pir + pi0;
-    T key1 = in1 ? inf : (T)W[s + v1] + pir + pi1;
-    int par0 = 1, par1 = 1;
+    const T pir = __shfl(pi[0], 1);
+    T key[K];
+    int par[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        key[j] = in[j] ? inf : (T)W(1, v[j]) + pir + pi[j];
+        par[j] = 1;
+    }
     T tree = 0, amag = 0;
     for (int step = 0; step < n - 2; ++step) {
         T k = inf;
         int who = INT_MAX;
-        if (!in0) {
-            k = key0;
-            who = v0;
-        }
-        if (!in1 && key1 < k) {
-            k = key1;
-            who = v1;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (!in[j] && (j == 0 || key[j] < k)) {
+                k = key[j];
+                who = v[j];
+            }
         }
         wave_argmin(k, who);
         const int u = who;
         tree += k;
         amag += k < 0 ? -k : k;
-        if (v0 == u) {
-            in0 = true;
-            atomicAdd(&deg[par0], 1);
-            atomicAdd(&deg[u], 1);
-        }
-        if (v1 == u) {
-            in1 = true;
-            atomicAdd(&deg[par1], 1);
-            atomicAdd(&deg[u], 1);
-        }
-        const T pu = u < kWave ? __shfl(pi0, u) : __shfl(pi1, u - kWave);
-        if (!in0) {
-            const T c = (T)W[u * s + v0] + pu + pi0;
-            if (c < key0) {
-                key0 = c;
-                par0 = u;
+        T pu = __shfl(pi[0], u & (kWave - 1));
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (v[j] == u) {
+                in[j] = true;
+                atomicAdd(&deg[par[j]], 1);
+                atomicAdd(&deg[u], 1);
+            }
+            if (j > 0) {
+                const T x = __shfl(pi[j], u & (kWave - 1));
+                if (u / kWave == j) pu = x;
             }
         }
-        if (!in1) {
-            const T c = (T)W[u * s + v1] + pu + pi1;
-            if (c < key1) {
-                key1 = c;
-                par1 = u;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (!in[j]) {
+                const T c = (T)W(u, v[j]) + pu + pi[j];
+                if (c < key[j]) {
+                    key[j] = c;
+                    par[j] = u;
+                }
             }
         }
     }
-    // the two cheapest edges at vertex 0 (pi_0 is lane 0's pi0)
-    const T piz = __shfl(pi0, 0);
-    const T c0 = (ok0 && v0 >= 1) ? (T)W[v0] + piz + pi0 : inf;
-    const T c1 = ok1 ? (T)W[v1] + piz + pi1 : inf;
-    T m1 = c0 < c1 || (c0 == c1) ? c0 : c1;
-    int e1 = c0 <= c1 ? v0 : v1;
+    // the two cheapest edges at vertex 0 (pi_0 is lane 0's pi[0]); per lane the smallest, ties to the smaller vertex
+    const T piz = __shfl(pi[0], 0);
+    T c[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) c[j] = (ok[j] && v[j] >= 1) ? (T)W(0, v[j]) + piz + pi[j] : inf;
+    T m1 = c[0];
+    int e1 = v[0];
+#pragma unroll
+    for (int j = 1; j < K; ++j) {
+        if (c[j] < m1) {
+            m1 = c[j];
+            e1 = v[j];
+        }
+    }
     wave_argmin(m1, e1);
-    T m2 = (v0 == e1) ? c1 : (v1 == e1 ? c0 : (c0 <= c1 ? c0 : c1));
-    int e2 = (v0 == e1) ? v1 : (v1 == e1 ? v0 : (c0 <= c1 ? v0 : v1));
+    T m2 = inf;
+    int e2 = INT_MAX;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (v[j] != e1 && c[j] < m2) {
+            m2 = c[j];
+            e2 = v[j];
+        }
+    }
     if (m2 == inf) e2 = INT_MAX;
     wave_argmin(m2, e2);
     wave_sync();
@@ -363,8 +419,15 @@ __device__ T one_tree(const float* W, int s, int n, T pi0, T pi1, int lane, int*
         atomicAdd(&deg[e1], 1);
         atomicAdd(&deg[e2], 1);
     }
-    T psum = (ok0 ? pi0 : (T)0) + (ok1 ? pi1 : (T)0);
-    T pmag = (ok0 ? (pi0 < 0 ? -pi0 : pi0) : (T)0) + (ok1 ? (pi1 < 0 ? -pi1 : pi1) : (T)0);
+    T psum = (ok[0] ? pi[0] : (T)0) + (ok[1] ? pi[1] : (T)0);
+    T pmag = (ok[0] ? (pi[0] < 0 ? -pi[0] : pi[0]) : (T)0) + (ok[1] ? (pi[1] < 0 ? -pi[1] : pi[1]) : (T)0);
+#pragma unroll
+    for (int j = 2; j < K; ++j) {
+        if (ok[j]) {
+            psum += pi[j];
+            pmag += pi[j] < 0 ? -pi[j] : pi[j];
+        }
+    }
     psum = wave_sum(psum);
     pmag = wave_sum(pmag);
     wave_sync();
@@ -372,63 +435,118 @@ __device__ T one_tree(const float* W, int s, int n, T pi0, T pi1, int lane, int*
     return tree + m1 + m2 - 2 * psum;
 }
 
+template <class WA>
 __global__ __launch_bounds__(kWave) void tour_lower_bound_kernel(const float* __restrict__ Wg,
                                                                  const long long* __restrict__ w_off,
                                                                  const int* __restrict__ n_arr,
                                                                  const float* __restrict__ upper, int n_max, int iters,
                                                                  double* __restrict__ lb) {
+    constexpr int K = WA::kMaxN / kWave;
     extern __shared__ float lds[];
-    __shared__ int deg[kMaxN];
+    __shared__ int deg[WA::kMaxN];
     const int inst = blockIdx.x, lane = threadIdx.x;
     const int n = n_arr[inst];
     if (n < 4 || n > n_max) {
         if (lane == 0) lb[inst] = __longlong_as_double(0x7ff8000000000000ll);
         return;
     }
-    const int s = lds_stride(n);
-    {
-        const float* src = Wg + w_off[inst];
-        for (int e = lane; e < n * n; e += kWave) lds[(e / n) * s + e % n] = src[e];
-    }
+    const WA W = WA::stage(lds, Wg + w_off[inst], n, lane, kWave);
     __syncthreads();
     const float ub = upper[inst];
-    const int v0 = lane, v1 = lane + kWave;
-    float pi0 = 0.f, pi1 = 0.f, bp0 = 0.f, bp1 = 0.f, best = -FLT_MAX, lambda = 2.f, mag;
+    float pi[K], bp[K], best = -FLT_MAX, lambda = 2.f, mag;
+#pragma unroll
+    for (int j = 0; j < K; ++j) pi[j] = bp[j] = 0.f;
     int stall = 0;
     for (int it = 0; it < iters; ++it) {
-        const float L = one_tree<float>(lds, s, n, pi0, pi1, lane, deg, &mag);
+        const float L = one_tree<float>(W, n, pi, lane, deg, &mag);
         if (L > best) {
             best = L;
-            bp0 = pi0;
-            bp1 = pi1;
+#pragma unroll
+            for (int j = 0; j < K; ++j) bp[j] = pi[j];
             stall = 0;
         } else if (++stall >= 8) {   // halving schedule: no improvement in 8 steps
             lambda *= 0.5f;
             stall = 0;
         }
-        const int g0 = v0 < n ? deg[v0] - 2 : 0, g1 = v1 < n ? deg[v1] - 2 : 0;
-        const int gg = wave_sum(g0 * g0 + g1 * g1);
+        int g[K], g2 = 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            g[j] = lane + j * kWave < n ? deg[lane + j * kWave] - 2 : 0;
+            g2 += g[j] * g[j];
+        }
+        const int gg = wave_sum(g2);
         if (gg == 0 || lambda < 1e-6f) break;   // the 1-tree is a tour (optimal), or the step has vanished
         const float gap = fmaxf(ub - L, 1e-4f * fabsf(L) + 1e-30f);
         const float t = lambda * gap / (float)gg;   // Polyak step towards the tour-search upper bound
-        pi0 += t * (float)g0;
-        pi1 += t * (float)g1;
+#pragma unroll
+        for (int j = 0; j < K; ++j) pi[j] += t * (float)g[j];
         wave_sync();
     }
     // the best multipliers' 1-tree, again from scratch in fp64 (the fp32 Prim above may pick a non-minimal tree under
     // rounding), less a margin for the fp64 rounding of the c(u,v) sums and the accumulation
-    double dmag;
-    const double L = one_tree<double>(lds, s, n, (double)bp0, (double)bp1, lane, deg, &dmag);
+    double dpi[K], dmag;
+#pragma unroll
+    for (int j = 0; j < K; ++j) dpi[j] = (double)bp[j];
+    const double L = one_tree<double>(W, n, dpi, lane, deg, &dmag);
     if (lane == 0) lb[inst] = L - 8.0 * (double)n * DBL_EPSILON * dmag;
 }
 
-template <typename K>
+template <class K>
 int allow_lds(K kernel, size_t bytes) {
     if (bytes <= 64 * 1024) return TSPGNN_OK;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)bytes);
     if (e != hipSuccess) return fail((int)e, "tour kernels: hipFuncSetAttribute: %s", hipGetErrorString(e));
     return TSPGNN_OK;
+}
+
+// Static LDS of tour_search_kernel (s_cost, s_tour); the dynamic part must fit beside it.
+constexpr size_t kSearchStaticLds = kMaxChains * (sizeof(float) + sizeof(int));
+
+// The chains that fit at n_max: the weights plus three tours of n_max int32 ids per chain.
+template <class WA>
+int chains_fit(int n_max) {
+    const size_t free_bytes = kLdsBytes - kSearchStaticLds - WA::floats(n_max) * sizeof(float);
+    const size_t c = free_bytes / ((size_t)3 * n_max * sizeof(int));
+    return c < (size_t)kMaxChains ? (int)c : kMaxChains;
+}
+
+template <class WA>
+int search(const char* entry, const char* what, const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+           const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks,
+           unsigned long long seed, int32_t* tours, float* costs, void* stream) {
+    TSPGNN_REQUIRE(n_inst >= 0, "%s: n_inst=%d", what, n_inst);
+    if (n_inst == 0) return TSPGNN_OK;
+    if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
+    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
+    TSPGNN_REQUIRE(restarts >= 1 && restarts <= kMaxChains, "%s: restarts=%d not in [1, %d]", what, restarts,
+                   kMaxChains);
+    TSPGNN_REQUIRE(restarts <= chains_fit<WA>(n_max), "%s: restarts=%d: at n_max=%d at most %d chains fit in LDS", what,
+                   restarts, n_max, chains_fit<WA>(n_max));
+    TSPGNN_REQUIRE(kicks >= 0, "%s: kicks=%d", what, kicks);
+    TSPGNN_REQUIRE(W && w_off && n && t_off && tours && costs, "%s: null pointer", what);
+    const size_t lds = (WA::floats(n_max) + (size_t)3 * restarts * n_max) * sizeof(float);
+    int rc = allow_lds(tour_search_kernel<WA>, lds);
+    if (rc) return rc;
+    tour_search_kernel<WA><<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
+        W, w_off, n, init_tours, t_off, index, n_max, kicks, seed, tours, costs);
+    return launched(entry);
+}
+
+template <class WA>
+int lower_bound(const char* entry, const char* what, const float* W, const long long* w_off, const int* n, const float* upper, int n_inst,
+                int n_max, int iters, double* lb, void* stream) {
+    TSPGNN_REQUIRE(n_inst >= 0, "%s: n_inst=%d", what, n_inst);
+    if (n_inst == 0) return TSPGNN_OK;
+    if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
+    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
+    TSPGNN_REQUIRE(iters >= 1, "%s: iters=%d", what, iters);
+    TSPGNN_REQUIRE(W && w_off && n && upper && lb, "%s: null pointer", what);
+    const size_t lds = WA::floats(n_max) * sizeof(float);
+    int rc = allow_lds(tour_lower_bound_kernel<WA>, lds);
+    if (rc) return rc;
+    tour_lower_bound_kernel<WA><<<(unsigned)n_inst, kWave, lds, as_stream(stream)>>>(W, w_off, n, upper, n_max, iters, lb);
+    return launched(entry);
 }
 
 }  // namespace
@@ -439,33 +557,25 @@ using namespace tspgnn;
 extern "C" int tspgnn_tour_search(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                   const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
                                   int kicks, unsigned long long seed, int32_t* tours, float* costs, void* stream) {
-    TSPGNN_REQUIRE(n_inst >= 0, "tour_search: n_inst=%d", n_inst);
-    if (n_inst == 0) return TSPGNN_OK;
-    if (n_max > kMaxN) return fail(TSPGNN_EUNSUPPORTED, "tour_search: n_max=%d exceeds %d", n_max, kMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "tour_search: n_max=%d must be at least 4", n_max);
-    TSPGNN_REQUIRE(restarts >= 1 && restarts <= kMaxChains, "tour_search: restarts=%d not in [1, %d]", restarts,
-                   kMaxChains);
-    TSPGNN_REQUIRE(kicks >= 0, "tour_search: kicks=%d", kicks);
-    TSPGNN_REQUIRE(W && w_off && n && t_off && tours && costs, "tour_search: null pointer");
-    const size_t lds = ((size_t)n_max * (n_max | 1) + (size_t)3 * restarts * n_max) * sizeof(float);
-    int rc = allow_lds(tour_search_kernel, lds);
-    if (rc) return rc;
-    tour_search_kernel<<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
-        W, w_off, n, init_tours, t_off, index, n_max, kicks, seed, tours, costs);
-    return launched("tspgnn_tour_search");
+    return search<SquareW>("tspgnn_tour_search", "tour_search", W, w_off, n, init_tours, t_off, index, n_inst, n_max,
+                           restarts, kicks, seed, tours, costs, stream);
 }
 
 extern "C" int tspgnn_tour_lower_bound(const float* W, const long long* w_off, const int* n, const float* upper,
                                        int n_inst, int n_max, int iters, double* lb, void* stream) {
-    TSPGNN_REQUIRE(n_inst >= 0, "tour_lower_bound: n_inst=%d", n_inst);
-    if (n_inst == 0) return TSPGNN_OK;
-    if (n_max > kMaxN) return fail(TSPGNN_EUNSUPPORTED, "tour_lower_bound: n_max=%d exceeds %d", n_max, kMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "tour_lower_bound: n_max=%d must be at least 4", n_max);
-    TSPGNN_REQUIRE(iters >= 1, "tour_lower_bound: iters=%d", iters);
-    TSPGNN_REQUIRE(W && w_off && n && upper && lb, "tour_lower_bound: null pointer");
-    const size_t lds = (size_t)n_max * (n_max | 1) * sizeof(float);
-    int rc = allow_lds(tour_lower_bound_kernel, lds);
-    if (rc) return rc;
-    tour_lower_bound_kernel<<<(unsigned)n_inst, kWave, lds, as_stream(stream)>>>(W, w_off, n, upper, n_max, iters, lb);
-    return launched("tspgnn_tour_lower_bound");
+    return lower_bound<SquareW>("tspgnn_tour_lower_bound", "tour_lower_bound", W, w_off, n, upper, n_inst, n_max, iters,
+                                lb, stream);
+}
+
+extern "C" int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                                      const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
+                                      int kicks, unsigned long long seed, int32_t* tours, float* costs, void* stream) {
+    return search<TriW>("tspgnn_tour_search_tri", "tour_search_tri", W, w_off, n, init_tours, t_off, index, n_inst, n_max,
+                        restarts, kicks, seed, tours, costs, stream);
+}
+
+extern "C" int tspgnn_tour_lower_bound_tri(const float* W, const long long* w_off, const int* n, const float* upper,
+                                           int n_inst, int n_max, int iters, double* lb, void* stream) {
+    return lower_bound<TriW>("tspgnn_tour_lower_bound_tri", "tour_lower_bound_tri", W, w_off, n, upper, n_inst, n_max,
+                             iters, lb, stream);
 }

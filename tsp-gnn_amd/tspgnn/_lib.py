@@ -89,6 +89,9 @@ SIGNATURES = {
     "tspgnn_tour_search": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                            ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_lower_bound": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "tspgnn_tour_search_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                               ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_lower_bound_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
 }
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",

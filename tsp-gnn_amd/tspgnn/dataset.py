@@ -21,6 +21,7 @@ from . import _lib
 from .instance_loader import route_cost, write_graph
 
 MAX_N = 128
+MAX_N_TRI = 256   # label_tours: the triangle kernels (n 129-256)
 
 # Defaults measured on the MI355X at the reference's training shape (n 20-40): 8 chains of 96 kicks label
 # 2^15 instances in a few seconds, and on n 5-13 they match exact optima; 400 subgradient steps bring the median
@@ -28,6 +29,13 @@ MAX_N = 128
 DEFAULT_RESTARTS = 8
 DEFAULT_KICKS = 96
 DEFAULT_LB_ITERS = 400
+# n 129-256 (label_tours on the triangle kernels; DESIGN.md §12, 2^10 instances at n 200 and 256): the search, not the
+# bound, limits certification there, and it keeps gaining with kicks (certified at dev 0.02, n 200: 0.36 / 0.87 / 0.94 at
+# 96 / 384 / 768 kicks; n 256: 0.11 / 0.68 / 0.92), while 1 000 bound steps change nothing.  384 kicks cost 11 s of
+# search per 2^10 instances at n 200, 18 s at n 256.
+DEFAULT_RESTARTS_LARGE = 8
+DEFAULT_KICKS_LARGE = 384
+DEFAULT_LB_ITERS_LARGE = 400
 DEFAULT_CHUNK = 8192
 
 TourResult = collections.namedtuple("TourResult", ["tour", "cost", "lb", "feasible", "target"])
@@ -45,7 +53,7 @@ def _edge_mask(Ma):
     return A
 
 
-def _check(k, Ma, Mw):
+def _check(k, Ma, Mw, max_n=MAX_N):
     Ma = np.asarray(Ma)
     Mw = np.asarray(Mw, dtype=np.float64)
     if Ma.ndim != 2 or Ma.shape[0] != Ma.shape[1] or Mw.shape != Ma.shape:
@@ -53,8 +61,8 @@ def _check(k, Ma, Mw):
     n = Ma.shape[0]
     if n < 1:
         raise ValueError("instance %d: empty graph" % k)
-    if n > MAX_N:
-        raise ValueError("instance %d: n=%d exceeds the tour kernels' limit of %d vertices" % (k, n, MAX_N))
+    if n > max_n:
+        raise ValueError("instance %d: n=%d exceeds the tour kernels' limit of %d vertices" % (k, n, max_n))
     w = np.triu(Mw, 1)[np.triu(_edge_mask(Ma), 1)]
     if w.size and (not np.all(np.isfinite(w)) or w.min() < 0):
         raise ValueError("instance %d: edge weights must be finite and non-negative" % k)
@@ -72,6 +80,22 @@ def _penalised(A, Mw):
     W = np.where(A, w, pen[:, None, None])
     idx = np.arange(n)
     W[:, idx, idx] = 0.0
+    W32 = W.astype(np.float32)
+    over = W32.astype(np.float64) > W
+    W32[over] = np.nextafter(W32[over], np.float32(-np.inf))
+    return W32
+
+
+def _penalised_tri(A, Mw):
+    """[b, n(n-1)/2] fp32 strict upper triangles, row-major, for the _tri kernels: the values of _penalised at (i < j),
+    with the same penalty and the same rounding towards -inf."""
+    b, n, _ = Mw.shape
+    iu = np.triu_indices(n, 1)
+    w = Mw[:, iu[0], iu[1]] + 0.0   # as _penalised's up + up.T: -0 becomes +0
+    a = A[:, iu[0], iu[1]]
+    mx = np.where(a, w, 0.0).max(axis=1) if w.shape[1] else np.zeros(b)
+    pen = n * mx + 1.0
+    W = np.where(a, w, pen[:, None])
     W32 = W.astype(np.float32)
     over = W32.astype(np.float64) > W
     W32[over] = np.nextafter(W32[over], np.float32(-np.inf))
@@ -123,18 +147,35 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
 
     Returns a list of TourResult (tour, cost, lb, feasible, target).
     """
+    t0 = time.perf_counter()
+    checked, index = _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, MAX_N)
+    return _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0,
+                  tri=False)
+
+
+def _check_counts(restarts, kicks, lb_iters, chunk):
     if not 1 <= restarts <= 16:
         raise ValueError("restarts=%d must be in [1, 16]" % restarts)
     if kicks < 0 or lb_iters < 1 or chunk < 1:
         raise ValueError("kicks, lb_iters and chunk must be non-negative / positive")
-    t0 = time.perf_counter()
-    checked = [_check(k, Ma, Mw) for k, (Ma, Mw) in enumerate(instances)]
+
+
+def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, max_n):
+    _check_counts(restarts, kicks, lb_iters, chunk)
+    checked = [_check(k, Ma, Mw, max_n) for k, (Ma, Mw) in enumerate(instances)]
     B = len(checked)
     index = np.arange(B, dtype=np.int64) if index is None else np.asarray(index, dtype=np.int64).reshape(-1)
     if index.shape[0] != B or (B and index.min() < 0):
         raise ValueError("index must hold one non-negative key per instance")
     if init_tours is not None and len(init_tours) != B:
         raise ValueError("init_tours must hold one entry (or None) per instance")
+    return checked, index
+
+
+def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0, tri):
+    """solve_tours on checked instances, n < 4 on the host and the rest on the square kernels (tri=False, n <= 128) or
+    the triangle kernels (tri=True, n <= 256)."""
+    B = len(checked)
     out = [None] * B
     big = [k for k in range(B) if checked[k][2] >= 4]
     for k in range(B):
@@ -149,7 +190,7 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
     order = np.argsort(ns, kind="stable")            # launch order: by n (similar work per workgroup)
     big = [big[k] for k in order]
     ns = ns[order]
-    sq = ns.astype(np.int64) ** 2
+    sq = ns.astype(np.int64) * (ns - 1) // 2 if tri else ns.astype(np.int64) ** 2   # floats per instance
     w_off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
     t_off = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
     Wflat = np.empty(int(sq.sum()), dtype=np.float32)
@@ -161,9 +202,9 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
     for n, poss in groups.items():
         A = np.stack([_edge_mask(checked[big[p]][0]) for p in poss])
         Mw = np.stack([checked[big[p]][1] for p in poss])
-        W32 = _penalised(A, Mw)
+        W32 = (_penalised_tri if tri else _penalised)(A, Mw)
         for g, p in enumerate(poss):
-            Wflat[w_off[p]:w_off[p] + n * n] = W32[g].reshape(-1)
+            Wflat[w_off[p]:w_off[p] + sq[p]] = W32[g].reshape(-1)
             if init_tours is not None and init_tours[big[p]] is not None:
                 it = np.asarray(init_tours[big[p]], dtype=np.int64).reshape(-1)
                 if it.shape[0] != n or not np.array_equal(np.sort(it), np.arange(n)):
@@ -171,6 +212,8 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
                 init[t_off[p]:t_off[p] + n] = it
         stacked[n] = (A, Mw)
     has_init = init_tours is not None and any(t is not None for t in init_tours)
+    search, bound = ("tspgnn_tour_search_tri", "tspgnn_tour_lower_bound_tri") if tri else \
+        ("tspgnn_tour_search", "tspgnn_tour_lower_bound")
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     G = len(big)
     with torch.cuda.device(dev):
@@ -188,7 +231,7 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
         st = _lib.current_stream()
         for c0 in range(0, G, chunk):
             c1 = min(G, c0 + chunk)
-            _lib.call("tspgnn_tour_search", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+            _lib.call(search, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                       _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
                       int(restarts), int(kicks), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours), _lib.ptr(d_cost[c0:c1]),
                       st)
@@ -197,7 +240,7 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
         if lower_bound:
             for c0 in range(0, G, chunk):
                 c1 = min(G, c0 + chunk)
-                _lib.call("tspgnn_tour_lower_bound", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                _lib.call(bound, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                           _lib.ptr(d_cost[c0:c1]), c1 - c0, int(ns[c0:c1].max()), int(lb_iters), _lib.ptr(d_lb[c0:c1]),
                           st)
         torch.cuda.synchronize(dev)
@@ -222,10 +265,50 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
     return out
 
 
+def tri_chains_fit(n):
+    """The most restarts tspgnn_tour_search_tri takes at n_max = n: its LDS holds the n (n-1) / 2 fp32 triangle and
+    three tours of n int32 ids per chain in 163 712 bytes (160 KiB less its 128 static bytes): 10 at n = 256."""
+    return min(16, (163712 - 2 * n * (n - 1)) // (12 * n))
+
+
+def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, init_tours=None, lower_bound=True,
+                device=None, chunk=DEFAULT_CHUNK, index=None, timings=None):
+    """solve_tours for instances of up to MAX_N_TRI = 256 vertices, split by n: n < 4 on the host, 4-128 on the square
+    kernels (exactly solve_tours), 129-256 on the packed-triangle kernels (tspgnn_tour_search_tri /
+    tspgnn_tour_lower_bound_tri); n > 256 raises ValueError before anything is launched.
+
+    restarts, kicks, lb_iters: None takes DEFAULT_* for n <= 128 and DEFAULT_*_LARGE for n > 128; a value applies to both.
+    For n > 128 restarts may not exceed tri_chains_fit(largest n) (10 at n = 256).  The other arguments are solve_tours'.
+    Results come back in input order; each depends on (seed, its index, restarts, kicks) only, never on chunk or on which
+    other instances share the call.
+    """
+    t0 = time.perf_counter()
+    small = (DEFAULT_RESTARTS if restarts is None else restarts, DEFAULT_KICKS if kicks is None else kicks,
+             DEFAULT_LB_ITERS if lb_iters is None else lb_iters)
+    large = (DEFAULT_RESTARTS_LARGE if restarts is None else restarts,
+             DEFAULT_KICKS_LARGE if kicks is None else kicks, DEFAULT_LB_ITERS_LARGE if lb_iters is None else lb_iters)
+    _check_counts(*large, chunk)
+    checked, index = _validate(instances, *small, chunk, index, init_tours, MAX_N_TRI)
+    n_big = max([c[2] for c in checked if c[2] > MAX_N], default=0)
+    if n_big and large[0] > tri_chains_fit(n_big):
+        raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS" % (large[0], n_big, tri_chains_fit(n_big)))
+    out = [None] * len(checked)
+    for tri, (r, k, it) in ((False, small), (True, large)):
+        sel = [i for i, c in enumerate(checked) if (c[2] > MAX_N) == tri]
+        if not sel:
+            continue
+        inits = None if init_tours is None else [init_tours[i] for i in sel]
+        res = _solve([checked[i] for i in sel], index[sel], inits, r, k, seed, lower_bound, device, it, chunk, timings,
+                     t0 if not tri else time.perf_counter(), tri)
+        for i, x in zip(sel, res):
+            out[i] = x
+    return out
+
+
 def solve(Ma, Mw, **kw):
     """The reference's contract (dataset.py:9-50): the tour as a list, or None when the best tour found needs an edge
-    absent from Ma.  Keyword arguments go to solve_tours."""
-    r = solve_tours([(Ma, Mw)], lower_bound=False, **kw)[0]
+    absent from Ma.  Keyword arguments go to label_tours."""
+    r = label_tours([(Ma, Mw)], lower_bound=False, **kw)[0]
     return r.tour if r.feasible else None
 
 
@@ -293,10 +376,10 @@ def _draw_graph(n, connectivity, distances="euc_2D", metric=True):
 def create_graph(n, connectivity, distances="euc_2D", metric=True, **solve_kw):
     """dataset.py:52-116: a random graph with a planted Hamiltonian cycle, labelled with the best tour found.
     Returns (np.triu(Ma), Mw, route, nodes); raises Exception('Unsolvable') as the reference does when that tour needs an
-    absent edge (it cannot here: the planted cycle is the search's first start).  solve_kw go to solve_tours."""
+    absent edge (it cannot here: the planted cycle is the search's first start).  solve_kw go to label_tours."""
     Ma, Mw, perm, nodes = _draw_graph(n, connectivity, distances, metric)
     solve_kw.setdefault("lower_bound", False)
-    r = solve_tours([(Ma, Mw)], init_tours=[perm], **solve_kw)[0]
+    r = label_tours([(Ma, Mw)], init_tours=[perm], **solve_kw)[0]
     if not r.feasible:
         raise Exception("Unsolvable")
     return np.triu(Ma), Mw, r.tour, nodes
@@ -321,7 +404,7 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     ``certify(.., dev)`` cannot prove, for at most max_redraw_rounds rounds, then raise RuntimeError if any remain.
     Redrawing BIASES the distribution: it drops the instances whose optimum sits close to the quirk target, which are the
     hardest ones, and the set no longer matches the reference's stream from the first redrawn index on.
-    solve_kw go to solve_tours (restarts, kicks, seed, lb_iters, chunk, device).
+    solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device); n up to 256.
 
     Returns a summary dict: samples, n (per instance), cost, lb, target, feasible, gap = (cost - lb) / cost,
     certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'}.
@@ -332,7 +415,7 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     solve_kw.setdefault("lower_bound", True)
 
     def label(idx, keys):
-        res = solve_tours([(graphs[i][0], graphs[i][1]) for i in idx], init_tours=[graphs[i][2] for i in idx],
+        res = label_tours([(graphs[i][0], graphs[i][1]) for i in idx], init_tours=[graphs[i][2] for i in idx],
                           index=keys, timings=times, **solve_kw)
         for r in res:
             if not r.feasible:
