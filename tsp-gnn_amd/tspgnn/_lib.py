@@ -293,8 +293,24 @@ def task_array(tasks):
     return (type(tasks[0]) * len(tasks))(*tasks)
 
 
+def launches(by_width):
+    """{width: [tasks]} -> [(task_array, width)] in dict order, then list order.  The ABI takes at most 4 tasks per launch."""
+    return [(task_array(tasks[k:k + 4]), d) for d, tasks in by_width.items() for k in range(0, len(tasks), 4)]
+
+
 def call_multi(name, tasks, d):
-    """Launch a list of MlpTask / LstmTask structures with one tspgnn_*_multi_f32 call."""
+    """Launch a list (or task_array) of at most 4 task structures of width ``d`` with one tspgnn_*_multi_* call."""
     if isinstance(tasks, list):
-        tasks = (type(tasks[0]) * len(tasks))(*tasks)
+        tasks = task_array(tasks)
     call(name, ctypes.cast(tasks, c_void_p), len(tasks), d, current_stream())
+
+
+def call_by_width(name, by_width):
+    """call_multi for every launch of launches(by_width)."""
+    for tasks, d in launches(by_width):
+        call_multi(name, tasks, d)
+
+
+def ptrs(fields):
+    """{field: value} with every tensor replaced by its device pointer: keyword arguments of a task structure."""
+    return {k: v.data_ptr() if torch.is_tensor(v) else v for k, v in fields.items()}

@@ -35,6 +35,9 @@ LN_GATES = ("input", "transform", "forget", "output", "state")
 # GraphNN.gemm -> suffix of the split-operand entry points (None: the fp32-MFMA kernels) and bytes per packed weight
 GEMM_ARITH = {"f16x2": "h2", "bf16x3": "x3", "f32": None}
 SPLIT_BYTES = {"x3": 6, "h2": 4}
+# LayerNormBasicLSTMCell.packed: form -> (split arithmetic of the pack kernel, None = fp32 fragment order; transposed)
+PACK_FORMS = {"f32": (None, False), "f32T": (None, True), "x3": ("x3", False), "h2": ("h2", False), "h2T": ("h2", True),
+              "bf16": ("x3", False), "bf16T": ("x3", True)}
 
 
 def _pad16(rows):
@@ -167,7 +170,13 @@ class Tape(object):
     the forward stored (C stays fp32) and the accessors below widen a step -- or a range of steps for the weight
     gradients -- to the fp32 operands the backward kernels take."""
 
-    native = False   # bf16 tape consumed as it is by the bf16-reading backward kernels (no widened copies)
+    def __init__(self):
+        self.arith = None    # the forward's arithmetic: "h2" (f16x2), "x3" (bf16x3), None (fp32 MFMA) or "bf16" (bf16 storage)
+        self.folded = {}     # {var: its loop entry when the adjacency product is folded through the cell's kernel, else None}
+        self.pushed = {}     # {var: the message MLP's last layer was pushed into the cell}
+        self.rc = {}         # {(var, i): True when the backward recomputes this entry's hidden activations}
+        self.fused = False   # the message MLPs of step t+1 ran in the cell launch of step t
+        self.native = False  # bf16 tape consumed as it is by the bf16-reading backward kernels (no widened copies)
 
     def _f32(self, x):
         return x if (x.dtype == torch.float32 or self.native) else x.to(torch.float32)
@@ -325,16 +334,38 @@ class LayerNormBasicLSTMCell(object):
     def kernel(self):
         return self.store.view(self.base + "/kernel")
 
-    def kernel_packed(self):
-        """The kernel in MFMA fragment order (tspgnn_pack_weights_f32), cached per weight version."""
+    def packed(self, part, form, centered=False, pushed=None):
+        """Kernel rows ``part`` ("K": all, "Kx": [0, dx), "Kh": [dx, dx+d)) in the byte layout ``form``, cached per weight
+        version; the buffer is reused across versions (captured graphs hold its address).
+          "f32": MFMA fragment order (tspgnn_pack_weights_f32); "f32T": of the transpose [4d, rows], by that kernel's flag
+          "x3": three bf16 pieces (tspgnn_pack_weights_x3); "h2": two fp16 pieces of 2^s K (tspgnn_pack_weights_h2, which
+                also raises the store's range guard word); "h2T": of the transposed rows
+          "bf16" / "bf16T": rounded to bf16 in fragment order = piece 0 of the "x3" packing (of the transposed rows), a
+                view of that buffer: one pack launch serves both
+        ``centered``: each gate's columns centred first (_center_gates), a packing of its own.
+        ``pushed`` = a message MLP: part "K" of the product K' = [W Kx ; Kh] (pushed_kernel) instead of the kernel."""
+        arith, transposed = PACK_FORMS[form]
+        lo, hi = {"K": (0, self.dx + self.d), "Kx": (0, self.dx), "Kh": (self.dx, self.dx + self.d)}[part]
+
         def build(out):
-            K = self.kernel()
+            K = self.kernel()[lo:hi] if pushed is None else self.pushed_kernel(pushed)[0]
+            if centered:
+                K = _center_gates(K, self.d)
+            if arith is None:
+                if out is None:
+                    out = torch.empty_like(K)
+                kr, nc = (4 * self.d, hi - lo) if transposed else (hi - lo, 4 * self.d)
+                _lib.call("tspgnn_pack_weights_f32", _lib.ptr(K), _lib.ptr(out), kr, nc, int(transposed), _lib.current_stream())
+                return out
+            if transposed:
+                K = K.t().contiguous()
             if out is None:
-                out = torch.empty_like(K)
-            _lib.call("tspgnn_pack_weights_f32", _lib.ptr(K), _lib.ptr(out), self.dx + self.d, 4 * self.d,
-                      0, _lib.current_stream())
+                out = torch.empty(SPLIT_BYTES[arith] * K.numel(), dtype=torch.uint8, device=K.device)
+            _pack_split(self.store, arith, K, out, K.shape[0], K.shape[1])
             return out
-        return self.store.packed(("lstm", self.base), build)
+        key = ("lstm", part, arith, transposed, centered, self.base, None if pushed is None else pushed.layer_names[-1])
+        buf = self.store.packed(key, build)
+        return buf[:buf.numel() // 3] if form.startswith("bf16") else buf
 
     def ln(self):
         return self.store.span(self.base + "/input/gamma", self.base + "/state/beta")
@@ -348,25 +379,11 @@ class LayerNormBasicLSTMCell(object):
             raise ValueError("cell input must be [%d,%d], got %s" % (rows, self.dx, tuple(inputs.shape)))
         x = inputs if inputs.is_contiguous() else inputs.contiguous()
         h_out, c_out = out if out is not None else (torch.empty_like(h), torch.empty_like(c))
-        _lib.call("tspgnn_lnlstm_fwd_f32", _lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(self.kernel_packed()),
+        _lib.call("tspgnn_lnlstm_fwd_f32", _lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(self.packed("K", "f32")),
                   _lib.ptr(self.ln()), _lib.ptr(h_out), _lib.ptr(c_out), rows, self.d, _lib.current_stream())
         return h_out, LSTMStateTuple(c=c_out, h=h_out)
 
     # ------------------------------------------------------------------ backward
-    def kernel_t_packed(self):
-        """pack(K^T) ([4d, dx+d]) for the data gradient [dx | dh] = dz K^T."""
-        if (self.dx + self.d) not in (64, 128, 256):
-            raise NotImplementedError("LSTM backward needs dx+d in {64,128,256} (got %d)" % (self.dx + self.d))
-
-        def build(out):
-            K = self.kernel()
-            if out is None:
-                out = torch.empty_like(K)
-            _lib.call("tspgnn_pack_weights_f32", _lib.ptr(K), _lib.ptr(out), 4 * self.d, self.dx + self.d, 1,
-                      _lib.current_stream())
-            return out
-        return self.store.packed(("lstmT", self.base), build)
-
     def ln_grad(self):
         return self.store.grad_span(self.base + "/input/gamma", self.base + "/state/beta")
 
@@ -377,81 +394,35 @@ class LayerNormBasicLSTMCell(object):
     def can_fold(self):
         return self.d == 64 and self.dx == 64
 
-    def _packed_slice(self, key, rows_lo, rows_hi, transposed):
-        def build(out):
-            K = self.kernel()[rows_lo:rows_hi]
-            if out is None:
-                out = torch.empty_like(K)
-            kr, nc = (4 * self.d, rows_hi - rows_lo) if transposed else (rows_hi - rows_lo, 4 * self.d)
-            _lib.call("tspgnn_pack_weights_f32", _lib.ptr(K), _lib.ptr(out), kr, nc, 1 if transposed else 0,
-                      _lib.current_stream())
-            return out
-        return self.store.packed((key, self.base), build)
-
-    def _packed_split(self, arith, key, rows_lo, rows_hi, centered=False):
-        """Split-operand packing of kernel rows [rows_lo, rows_hi) as a byte tensor: ``arith`` = "x3" (three bf16
-        pieces, tspgnn_pack_weights_x3) or "h2" (two fp16 pieces of 2^s K, tspgnn_pack_weights_h2).  ``centered``: of
-        the kernel with each gate's columns centred (_center_gates) -- a packing of its own."""
-        def build(out):
-            K = self.kernel()[rows_lo:rows_hi]
-            if centered:
-                K = _center_gates(K, self.d)
-            if out is None:
-                out = torch.empty(SPLIT_BYTES[arith] * K.numel(), dtype=torch.uint8, device=K.device)
-            _pack_split(self.store, arith, K, out, rows_hi - rows_lo, 4 * self.d)
-            return out
-        return self.store.packed((key + "." + arith + (".c" if centered else ""), self.base), build)
-
-    def _packed_x3(self, key, rows_lo, rows_hi):
-        return self._packed_split("x3", key, rows_lo, rows_hi)
-
-    def _packed_bf16(self, key, rows_lo, rows_hi):
-        """Kernel rows [rows_lo, rows_hi) rounded to bf16 in MFMA fragment order: piece 0 of the bf16x3 packing."""
-        n = (rows_hi - rows_lo) * 4 * self.d
-        return self._packed_x3(key, rows_lo, rows_hi)[:2 * n]
+    def _forward_task(self, state, out, K, struct=_lib.LstmTask, **fields):
+        """A tspgnn_lstm_task (``struct`` = _lib.LstmTaskB: tspgnn_lstm_task_bf16) over the rows of state.h, out = (h_out,
+        c_out): the fields every form shares; the others by field name (tensors as their device pointers), zero where
+        not named."""
+        fields.setdefault("rows", state.h.shape[0])
+        return struct(h=_lib.ptr(state.h), c=_lib.ptr(state.c), K=_lib.ptr(K), ln=_lib.ptr(self.ln()), h_out=_lib.ptr(out[0]),
+                      c_out=_lib.ptr(out[1]), **_lib.ptrs(fields))
 
     def task_bf16(self, x, h, c, h_out, c_out, rows, adj=None, state_in_blocked=False, state_out_blocked=False):
         """tspgnn_lstm_task_bf16 over ``rows`` rows: x, h, h_out bf16; c, c_out fp32; the states blocked by 16 rows when
         flagged (padded buffers).  With adj, the gather-init form: x is the blocked bf16 Zx of the source rows, K = Kh."""
-        if adj is None:
-            K = self._packed_bf16("lstm.x3", 0, self.dx + self.d)
-            return _lib.LstmTaskB(_lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(K), _lib.ptr(self.ln()),
-                                  _lib.ptr(h_out), _lib.ptr(c_out), rows, None, None, int(state_in_blocked),
-                                  int(state_out_blocked))
-        K = self._packed_bf16("lstm.kh.x3", self.dx, self.dx + self.d)
-        return _lib.LstmTaskB(None, 0, _lib.ptr(h), _lib.ptr(c), _lib.ptr(K), _lib.ptr(self.ln()), _lib.ptr(h_out),
-                              _lib.ptr(c_out), rows, _lib.ptr(adj.uv), _lib.ptr(x), int(state_in_blocked),
-                              int(state_out_blocked))
+        form = dict(x=x, dx=self.dx) if adj is None else dict(uv=adj.uv, Zx=x)
+        return self._forward_task(LSTMStateTuple(c=c, h=h), (h_out, c_out), self.packed("K" if adj is None else "Kh", "bf16"),
+                                  struct=_lib.LstmTaskB, rows=rows, state_in_blocked=int(state_in_blocked),
+                                  state_out_blocked=int(state_out_blocked), **form)
 
     def x3_ok(self):
         """The split-operand cell kernels cover this shape (tspgnn_lnlstm_fwd_multi_x3 / _h2)."""
         return self.d in (32, 64) and self.dx % 32 == 0
 
-    def kx_packed(self):
-        return self._packed_slice("lstm.kx", 0, self.dx, False)
-
-    def kh_packed(self):
-        return self._packed_slice("lstm.kh", self.dx, self.dx + self.d, False)
-
-    def kx_t_packed(self):
-        return self._packed_slice("lstm.kxT", 0, self.dx, True)
-
-    def kh_t_packed(self):
-        return self._packed_slice("lstm.khT", self.dx, self.dx + self.d, True)
-
     def task(self, x, state, out, arith=None, centered=False):
-        K = self._packed_split(arith, "lstm", 0, self.dx + self.d, centered) if arith else self.kernel_packed()
-        return _lib.LstmTask(_lib.ptr(x), self.dx, _lib.ptr(state.h), _lib.ptr(state.c), _lib.ptr(K),
-                             _lib.ptr(self.ln()), _lib.ptr(out[0]), _lib.ptr(out[1]), state.h.shape[0], None, None,
-                             None, None, self._flag(arith), int(centered))
+        return self._forward_task(state, out, self.packed("K", arith or "f32", centered), x=x, dx=self.dx,
+                                  range_flag=self._flag(arith), z_centered=int(centered))
 
     def gather_task(self, adj, zx, state, out, arith=None, centered=False):
         """``centered``: Kh AND the Kx behind zx were centred per gate (the caller projects with
-        _packed_split(..., "lstm.kx", ..., centered=True))."""
-        K = self._packed_split(arith, "lstm.kh", self.dx, self.dx + self.d, centered) if arith else self.kh_packed()
-        return _lib.LstmTask(None, 0, _lib.ptr(state.h), _lib.ptr(state.c), _lib.ptr(K),
-                             _lib.ptr(self.ln()), _lib.ptr(out[0]), _lib.ptr(out[1]), state.h.shape[0],
-                             _lib.ptr(adj.uv), _lib.ptr(zx), None, None, self._flag(arith), int(centered))
+        packed("Kx", arith, centered=True))."""
+        return self._forward_task(state, out, self.packed("Kh", arith or "f32", centered), uv=adj.uv, Zx=zx,
+                                  range_flag=self._flag(arith), z_centered=int(centered))
 
     def _flag(self, arith):
         """The range_flag of an f16x2 task (include/tspgnn.h): the store's guard word."""
@@ -473,9 +444,9 @@ class LayerNormBasicLSTMCell(object):
             kfull, zb, kt = out
             st = _lib.current_stream()
             kfull[dx:].copy_(self.kernel()[dx:])
-            _lib.call("tspgnn_linear_f32", _lib.ptr(W), dx, _lib.ptr(self.kx_packed()), None, 0, _lib.ptr(kfull[:dx]),
+            _lib.call("tspgnn_linear_f32", _lib.ptr(W), dx, _lib.ptr(self.packed("Kx", "f32")), None, 0, _lib.ptr(kfull[:dx]),
                       4 * d, 0, W.shape[0], st)
-            _lib.call("tspgnn_linear_f32", _lib.ptr(b.view(1, -1)), dx, _lib.ptr(self.kx_packed()), None, 0, _lib.ptr(zb),
+            _lib.call("tspgnn_linear_f32", _lib.ptr(b.view(1, -1)), dx, _lib.ptr(self.packed("Kx", "f32")), None, 0, _lib.ptr(zb),
                       4 * d, 0, 1, st)
             _lib.call("tspgnn_pack_weights_f32", _lib.ptr(kfull), _lib.ptr(kt), 4 * d, dx + d, 1, st)
             return (kfull, zb, kt)
@@ -485,52 +456,29 @@ class LayerNormBasicLSTMCell(object):
         """For a cell whose input is a row-sum aggregation of ``mlp``'s output: (pack(K'), b Kx) of pushed_kernel in the
         packing of ``arith``.  The cell then takes the row-sum of the LAST HIDDEN activation as its input and starts z
         at degree * (b Kx).  One Dense(d) layer less on every edge row per step."""
-        d, dx = self.d, self.dx
-        last = mlp.layer_names[-1]
-
-        def build(out):
-            kfull, zb, _ = self.pushed_kernel(mlp)
-            if centered:   # (K' and b Kx centred per gate: tspgnn_lstm_task.z_centered)
-                kfull = _center_gates(kfull, d)
-            if out is None:
-                out = torch.empty(SPLIT_BYTES[arith] * (dx + d) * 4 * d, dtype=torch.uint8, device=kfull.device) if arith \
-                    else torch.empty((dx + d, 4 * d), dtype=torch.float32, device=kfull.device)
-            st = _lib.current_stream()
-            if arith:
-                _pack_split(self.store, arith, kfull, out, dx + d, 4 * d)
-            else:
-                _lib.call("tspgnn_pack_weights_f32", _lib.ptr(kfull), _lib.ptr(out), dx + d, 4 * d, 0, st)
-            return out
-        packed = self.store.packed(("lstm.pushed." + (arith or "f32") + (".c" if centered else ""), self.base, last), build)
+        packed = self.packed("K", arith or "f32", centered, pushed=mlp)
         if not centered:
             return packed, self.pushed_kernel(mlp)[1]
-        zb_c = self.store.packed(("lstm.pushed.zb.c", self.base, last),
-                                 lambda out: _center_gates(self.pushed_kernel(mlp)[1], d) if out is None
-                                 else out.copy_(_center_gates(self.pushed_kernel(mlp)[1], d)))
+        # (K' and b Kx centred per gate: tspgnn_lstm_task.z_centered)
+        zb_c = self.store.packed(("lstm.pushed.zb.c", self.base, mlp.layer_names[-1]),
+                                 lambda out: _center_gates(self.pushed_kernel(mlp)[1], self.d) if out is None
+                                 else out.copy_(_center_gates(self.pushed_kernel(mlp)[1], self.d)))
         return packed, zb_c
+
+    def _backward_task(self, h, c, K, dh_out, dc_out, dz, dc_in, ws, **fields):
+        """A tspgnn_lstm_bwd_task over the rows of h: the fields every form shares; the others by field name (tensors as
+        their device pointers), zero where not named."""
+        return _lib.LstmBwdTask(h=_lib.ptr(h), c=_lib.ptr(c), K=_lib.ptr(K), ln=_lib.ptr(self.ln()), dh_out=_lib.ptr(dh_out),
+                                dc_out=_lib.ptr(dc_out), dz=_lib.ptr(dz), dc_in=_lib.ptr(dc_in),
+                                ln_grad=_lib.ptr(self.ln_grad()), workspace=_lib.ptr(ws), rows=h.shape[0], **_lib.ptrs(fields))
 
     def pushed_backward_task(self, x, h, c, dh_out, dc_out, dz, dc_in, ws, kp, zb, deg, defer=False, data=None):
         """Backward task (tspgnn_lnlstm_bwd_multi_h2) of pushed_task: K = pushed_bias_pack's f16x2 K', z restarts at
         deg * zb.  ``data`` = (f16x2 packing of K'^T, dx_out, dh_in): the data gradient [dx_out | dh_in] = dz K'^T formed in
         the same launch (tspgnn_lstm_bwd_task.KTg) instead of by pushed_backward_data."""
         ktg, dx_out, dh_in = data if data is not None else (None, None, None)
-        return _lib.LstmBwdTask(_lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(kp), _lib.ptr(self.ln()),
-                                _lib.ptr(dh_out), _lib.ptr(dc_out), _lib.ptr(dz), _lib.ptr(dc_in), _lib.ptr(self.ln_grad()),
-                                _lib.ptr(ws), h.shape[0], None, None, None, _lib.ptr(dh_in), 1 if defer else 0, _lib.ptr(zb),
-                                _lib.ptr(deg), _lib.ptr(ktg), _lib.ptr(dx_out))
-
-    def pushed_kernel_t_h2(self, mlp):
-        """f16x2 packing of K'^T ([4d, dx+d], K' of pushed_kernel): the weight operand of the data gradient formed inside
-        tspgnn_lnlstm_bwd_multi_h2 (tspgnn_lstm_bwd_task.KTg)."""
-        last = mlp.layer_names[-1]
-
-        def build(out):
-            KT = self.pushed_kernel(mlp)[0].t().contiguous()
-            if out is None:
-                out = torch.empty(SPLIT_BYTES["h2"] * KT.numel(), dtype=torch.uint8, device=KT.device)
-            _pack_split(self.store, "h2", KT, out, 4 * self.d, self.dx + self.d)
-            return out
-        return self.store.packed(("lstm.pushed.kT.h2", self.base, last), build)
+        return self._backward_task(h, c, kp, dh_out, dc_out, dz, dc_in, ws, x=x, dx=self.dx, dxh=dh_in,
+                                   defer_reduce=int(defer), zbias=zb, zscale=deg, KTg=ktg, dxg=dx_out)
 
     def fuses_pushed_data_gradient(self):
         """The pushed cell's data gradient can ride in its backward launch (f16x2, d == dx == 64)."""
@@ -564,9 +512,9 @@ class LayerNormBasicLSTMCell(object):
         W, b = self.store.view(last + "/kernel"), self.store.view(last + "/bias")
         f32 = dict(dtype=torch.float32, device=W.device)
         dW, db = torch.empty((W.shape[0], dx), **f32), torch.empty((1, dx), **f32)
-        _lib.call("tspgnn_linear_f32", _lib.ptr(g_wkx), 4 * d, _lib.ptr(self.kx_t_packed()), _lib.ptr(dW), dx, None, 0, 0,
+        _lib.call("tspgnn_linear_f32", _lib.ptr(g_wkx), 4 * d, _lib.ptr(self.packed("Kx", "f32T")), _lib.ptr(dW), dx, None, 0, 0,
                   g_wkx.shape[0], st)
-        _lib.call("tspgnn_linear_f32", _lib.ptr(g_zb), 4 * d, _lib.ptr(self.kx_t_packed()), _lib.ptr(db), dx, None, 0, 0, 1, st)
+        _lib.call("tspgnn_linear_f32", _lib.ptr(g_zb), 4 * d, _lib.ptr(self.packed("Kx", "f32T")), _lib.ptr(db), dx, None, 0, 0, 1, st)
         self.store.grad_view(last + "/kernel").add_(dW)
         self.store.grad_view(last + "/bias").add_(db.view(-1))
         packed = torch.empty_like(g_wkx)
@@ -579,106 +527,61 @@ class LayerNormBasicLSTMCell(object):
 
     def pushed_task(self, x, state, out, kp, zb, deg, arith=None, centered=False):
         """Cell task whose kernel operand is pushed_bias_pack's K' (either packing) and z starts at deg * zb."""
-        return _lib.LstmTask(_lib.ptr(x), self.dx, _lib.ptr(state.h), _lib.ptr(state.c), _lib.ptr(kp), _lib.ptr(self.ln()),
-                             _lib.ptr(out[0]), _lib.ptr(out[1]), state.h.shape[0], None, None, _lib.ptr(zb), _lib.ptr(deg),
-                             self._flag(arith), int(centered))
+        return self._forward_task(state, out, kp, x=x, dx=self.dx, zbias=zb, zscale=deg, range_flag=self._flag(arith),
+                                  z_centered=int(centered))
 
     def premultiply(self, y, out=None, scale=None):
         """Zx = y Kx  ([n_src, 4d]); ``scale``: times 2^s for an f16x2 cell, whose z carries that factor."""
         if out is None:
             out = torch.empty((y.shape[0], 4 * self.d), dtype=torch.float32, device=y.device)
         if scale is None:
-            _lib.call("tspgnn_linear_f32", _lib.ptr(y), self.dx, _lib.ptr(self.kx_packed()), None, 0, _lib.ptr(out),
+            _lib.call("tspgnn_linear_f32", _lib.ptr(y), self.dx, _lib.ptr(self.packed("Kx", "f32")), None, 0, _lib.ptr(out),
                       4 * self.d, 0, y.shape[0], _lib.current_stream())
             return out
         # the f16x2 cells' projected-message format: times 2^s, blocked by 16 source rows (include/tspgnn.h)
         n, d4 = y.shape[0], 4 * self.d
         flat = torch.zeros((_pad16(n), d4), dtype=torch.float32, device=y.device)
-        _lib.call("tspgnn_linear_f32", _lib.ptr(y), self.dx, _lib.ptr(self.kx_packed()), None, 0, _lib.ptr(flat), d4, 0, n,
+        _lib.call("tspgnn_linear_f32", _lib.ptr(y), self.dx, _lib.ptr(self.packed("Kx", "f32")), None, 0, _lib.ptr(flat), d4, 0, n,
                   _lib.current_stream())
         out.view(-1, d4 // 16, 4, 16, 4).copy_(flat.mul_(scale).view(-1, 16, d4 // 16, 4, 4).permute(0, 2, 3, 1, 4))
         return out
 
-    def gather_call(self, adj, zx, state, out=None):
-        c, h = state.c, state.h
-        rows = h.shape[0]
-        h_out, c_out = out if out is not None else (torch.empty_like(h), torch.empty_like(c))
-        _lib.call("tspgnn_lnlstm_gather_fwd_f32", _lib.ptr(adj.uv), _lib.ptr(zx), _lib.ptr(h), _lib.ptr(c),
-                  _lib.ptr(self.kh_packed()), _lib.ptr(self.ln()), _lib.ptr(h_out), _lib.ptr(c_out), rows, zx.shape[0],
-                  self.d, _lib.current_stream())
-        return h_out, LSTMStateTuple(c=c_out, h=h_out)
-
-    def _packed_h2_t(self, key, rows_lo, rows_hi):
-        """f16x2 packing of the TRANSPOSE of kernel rows [rows_lo, rows_hi) ([4d, rows]): the weight operand of the data
-        gradient dz K^T in tspgnn_lnlstm_bwd_multi_h2."""
-        def build(out):
-            KT = self.kernel()[rows_lo:rows_hi].t().contiguous()
-            if out is None:
-                out = torch.empty(SPLIT_BYTES["h2"] * KT.numel(), dtype=torch.uint8, device=KT.device)
-            _pack_split(self.store, "h2", KT, out, 4 * self.d, rows_hi - rows_lo)
-            return out
-        return self.store.packed((key + ".h2", self.base), build)
-
     def backward_task(self, x, h, c, dh_out, dc_out, dz, dc_in, ws, defer=False, arith=None):
-        K = self._packed_split("h2", "lstm", 0, self.dx + self.d) if arith == "h2" else self.kernel_packed()
-        return _lib.LstmBwdTask(_lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(K),
-                                _lib.ptr(self.ln()), _lib.ptr(dh_out), _lib.ptr(dc_out), _lib.ptr(dz), _lib.ptr(dc_in),
-                                _lib.ptr(self.ln_grad()), _lib.ptr(ws), h.shape[0], None, None, None, None,
-                                1 if defer else 0)
+        return self._backward_task(h, c, self.packed("K", "h2" if arith == "h2" else "f32"), dh_out, dc_out, dz, dc_in, ws,
+                                   x=x, dx=self.dx, defer_reduce=int(defer))
 
     def gather_backward_task(self, adj, zx, h, c, dh_out, dc_out, dz, dc_in, ws, dh_in=None, defer=False, arith=None):
         """``dh_in`` given (d == 64): dh_in = dz Kh^T is formed in the same launch, from dz in registers.
         ``defer``: LayerNorm-gradient partials accumulate in ``ws`` (see backward_finish).
         ``arith`` = "h2": operands for tspgnn_lnlstm_bwd_multi_h2 (``zx`` as the f16x2 forward wrote it)."""
         fuse = dh_in is not None and self.d == 64
-        if arith == "h2":
-            K = self._packed_split("h2", "lstm.kh", self.dx, self.dx + self.d)
-            KT = self._packed_h2_t("lstm.khT", self.dx, self.dx + self.d) if fuse else None
-        else:
-            K, KT = self.kh_packed(), (self.kh_t_packed() if fuse else None)
-        return _lib.LstmBwdTask(None, 0, _lib.ptr(h), _lib.ptr(c), _lib.ptr(K), _lib.ptr(self.ln()),
-                                _lib.ptr(dh_out), _lib.ptr(dc_out), _lib.ptr(dz), _lib.ptr(dc_in),
-                                _lib.ptr(self.ln_grad()), _lib.ptr(ws), h.shape[0], _lib.ptr(adj.uv), _lib.ptr(zx),
-                                _lib.ptr(KT), _lib.ptr(dh_in) if fuse else None, 1 if defer else 0)
+        form = "h2" if arith == "h2" else "f32"
+        return self._backward_task(h, c, self.packed("Kh", form), dh_out, dc_out, dz, dc_in, ws, uv=adj.uv, Zx=zx,
+                                   KT=self.packed("Kh", form + "T") if fuse else None, dxh=dh_in if fuse else None,
+                                   defer_reduce=int(defer))
 
     # ---- bf16-storage tape (tspgnn_lnlstm_bwd_multi_bf16 and friends, include/tspgnn.h)
-    def _packed_bf16_t(self, key, rows_lo, rows_hi):
-        """bf16 packing of the TRANSPOSE of kernel rows [rows_lo, rows_hi) ([4d, rows]): W of tspgnn_linear_bf16w_f32 for
-        the data gradient dz K^T."""
-        def build(out):
-            KT = self.kernel()[rows_lo:rows_hi].t().contiguous()
-            if out is None:
-                out = torch.empty(SPLIT_BYTES["x3"] * KT.numel(), dtype=torch.uint8, device=KT.device)
-            _pack_split(self.store, "x3", KT, out, 4 * self.d, rows_hi - rows_lo)
-            return out
-        return self.store.packed((key + ".x3", self.base), build)[:2 * 4 * self.d * (rows_hi - rows_lo)]
 
     def backward_task_bf16(self, x, h, c, dh_out, dc_out, dz, dc_in, ws, adj=None, zx=None):
         """tspgnn_lnlstm_bwd_multi_bf16 task: x / h (and zx: the blocked projected messages, gather-init mode with adj)
         are the tape's bf16 arrays."""
-        if adj is not None:
-            K = self._packed_bf16("lstm.kh.x3", self.dx, self.dx + self.d)
-            return _lib.LstmBwdTask(None, 0, _lib.ptr(h), _lib.ptr(c), _lib.ptr(K), _lib.ptr(self.ln()), _lib.ptr(dh_out),
-                                    _lib.ptr(dc_out), _lib.ptr(dz), _lib.ptr(dc_in), _lib.ptr(self.ln_grad()), _lib.ptr(ws),
-                                    h.shape[0], _lib.ptr(adj.uv), _lib.ptr(zx), None, None, 1)
-        K = self._packed_bf16("lstm.x3", 0, self.dx + self.d)
-        return _lib.LstmBwdTask(_lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(K), _lib.ptr(self.ln()),
-                                _lib.ptr(dh_out), _lib.ptr(dc_out), _lib.ptr(dz), _lib.ptr(dc_in), _lib.ptr(self.ln_grad()),
-                                _lib.ptr(ws), h.shape[0], None, None, None, None, 1)
+        form = dict(x=x, dx=self.dx) if adj is None else dict(uv=adj.uv, Zx=zx)
+        return self._backward_task(h, c, self.packed("K" if adj is None else "Kh", "bf16"), dh_out, dc_out, dz, dc_in, ws,
+                                   defer_reduce=1, **form)
 
     def backward_data_bf16(self, dz, dx_out, dh_in):
         """[dx | dh] = dz K^T on the bf16 matrix cores (the weights are bf16-exact in this mode)."""
-        W = self._packed_bf16_t("lstm.T", 0, self.dx + self.d)
+        W = self.packed("K", "bf16T")
         _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(W), _lib.ptr(dx_out), self.dx,
                   _lib.ptr(dh_in), self.d, 0, dz.shape[0], _lib.current_stream())
 
     def gather_backward_data_bf16(self, adj, dz, dh_in, dzx, dy):
         """dh = dz Kh^T, dZx = EV^T dz, dy = dZx Kx^T (gather_backward_data with bf16-exact weights)."""
         st = _lib.current_stream()
-        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self._packed_bf16_t("lstm.khT", self.dx,
-                  self.dx + self.d)), None, 0, _lib.ptr(dh_in), self.d, 0, dz.shape[0], st)
+        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("Kh", "bf16T")),
+                  None, 0, _lib.ptr(dh_in), self.d, 0, dz.shape[0], st)
         adj.matmul(dz, transpose=True, out=dzx)
-        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self._packed_bf16_t("lstm.kxT", 0, self.dx)),
+        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.packed("Kx", "bf16T")),
                   None, 0, _lib.ptr(dy), self.dx, 0, dzx.shape[0], st)
 
     def backward_finish(self, ws):
@@ -687,37 +590,22 @@ class LayerNormBasicLSTMCell(object):
 
     def backward_data(self, dz, dx_out, dh_in):
         """[dx | dh] = dz K^T."""
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.kernel_t_packed()), _lib.ptr(dx_out),
+        if (self.dx + self.d) not in (64, 128, 256):
+            raise NotImplementedError("LSTM backward needs dx+d in {64,128,256} (got %d)" % (self.dx + self.d))
+        _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("K", "f32T")), _lib.ptr(dx_out),
                   self.dx, _lib.ptr(dh_in), self.d, 0, dz.shape[0], _lib.current_stream())
-
-    def kx_t_packed_h2(self):
-        """f16x2 packing of Kx^T ([4d, dx]): dy = dZx Kx^T inside the source MLP's backward launch
-        (tspgnn_mlp_bwd_task.pre_X)."""
-        return self._packed_h2_t("lstm.kxT", 0, self.dx)
 
     def gather_backward_data(self, adj, dz, dh_in, dzx, dy):
         """dh = dz Kh^T (unless the cell launch already formed it: dh_in None), dZx = EV^T dz, dy = dZx Kx^T (``dy`` None:
         left to the source MLP's backward launch)."""
         st = _lib.current_stream()
         if dh_in is not None:
-            _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.kh_t_packed()), None, 0, _lib.ptr(dh_in),
+            _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("Kh", "f32T")), None, 0, _lib.ptr(dh_in),
                       self.d, 0, dz.shape[0], st)
         adj.matmul(dz, transpose=True, out=dzx)
         if dy is None:
             return
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.kx_t_packed()), None, 0, _lib.ptr(dy),
-                  self.dx, 0, dzx.shape[0], st)
-
-    def gather_backward(self, adj, zx, h, c, dh_out, dc_out, dz, dc_in, dh_in, dzx, dy, ws):
-        """Backward of gather_call + premultiply: dz, dc_in, dh_in = dz Kh^T, dzx = EV^T dz, dy = dzx Kx^T."""
-        rows, st = h.shape[0], _lib.current_stream()
-        _lib.call("tspgnn_lnlstm_gather_bwd_f32", _lib.ptr(adj.uv), _lib.ptr(zx), _lib.ptr(h), _lib.ptr(c),
-                  _lib.ptr(self.kh_packed()), _lib.ptr(self.ln()), _lib.ptr(dh_out), _lib.ptr(dc_out), _lib.ptr(dz),
-                  _lib.ptr(dc_in), _lib.ptr(self.ln_grad()), _lib.ptr(ws), rows, self.d, st)
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.kh_t_packed()), None, 0, _lib.ptr(dh_in),
-                  self.d, 0, rows, st)
-        adj.matmul(dz, transpose=True, out=dzx)
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.kx_t_packed()), None, 0, _lib.ptr(dy),
+        _lib.call("tspgnn_linear_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.packed("Kx", "f32T")), None, 0, _lib.ptr(dy),
                   self.dx, 0, dzx.shape[0], st)
 
     def backward_weights_folded(self, y_all, dzx_all, rows_src, h_all, dz_all, rows):
@@ -727,16 +615,6 @@ class LayerNormBasicLSTMCell(object):
         wgrad(y_all, dzx_all, rows_src, self.dx, 4 * self.d, gK[:self.dx], None, ws)
         ws = _lib.workspace("tspgnn_wgrad_workspace_floats", rows, self.d, 4 * self.d, device=dz_all.device)
         wgrad(h_all, dz_all, rows, self.d, 4 * self.d, gK[self.dx:], None, ws)
-
-    def backward(self, x, h, c, dh_out, dc_out, dz, dc_in, dx_out, dh_in, ws):
-        """One step: (dh_out, dc_out) -> dz (kept for the weight gradient), dc_in, dx_out, dh_in; the
-        LayerNorm parameter gradients are accumulated into the store's gradient buffer."""
-        rows, st = h.shape[0], _lib.current_stream()
-        _lib.call("tspgnn_lnlstm_bwd_f32", _lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(self.kernel_packed()),
-                  _lib.ptr(self.ln()), _lib.ptr(dh_out), _lib.ptr(dc_out), _lib.ptr(dz), _lib.ptr(dc_in),
-                  _lib.ptr(self.ln_grad()), _lib.ptr(ws), rows, self.d, st)
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.kernel_t_packed()), _lib.ptr(dx_out),
-                  self.dx, _lib.ptr(dh_in), self.d, 0, rows, st)
 
     def backward_weights(self, x_all, h_all, dz_all, rows):
         """dK += [x|h]^T dz over all time steps at once (rows = T * rows_per_step)."""
@@ -1046,14 +924,15 @@ class GraphNN(object):
                         if folded[v] is not None:
                             cv = self._RNN_cells[v]
                             zxs[v] = torch.empty((_pad16(rows), 4 * self.var[v]), **bf)
-                            pw, po = cv._packed_bf16("lstm.kx", 0, cv.dx), zxs[v]
+                            pw, po = cv.packed("Kx", "bf16"), zxs[v]
                         n = mlp.n_square
                         # a plain message (no projection rides behind it): the last layer's columns interleaved in the
                         # packing, 16-byte stores of Y (tspgnn_mlp_task_bf16.y_interleaved)
                         il = pw is None and d % 32 == 0 and os.environ.get("TSPGNN_BF16_INTERLEAVE", "1") != "0"
                         mlp_tasks.setdefault(d, []).append(_lib.MlpTaskB(
-                            _lib.ptr(y), _lib.ptr(mlp.wb_packed_bf16(0, n - 1, d, interleave_last=il)), _lib.ptr(out), rows, n,
-                            mlp.relu_mask(0, n), _lib.ptr(pw), _lib.ptr(po), None, 0, int(blk_in[src]), int(il)))
+                            X=_lib.ptr(y), wb=_lib.ptr(mlp.wb_packed_bf16(0, n - 1, d, interleave_last=il)), Y=_lib.ptr(out),
+                            rows=rows, n_layers=n, relu_mask=mlp.relu_mask(0, n), proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po),
+                            x_blocked=int(blk_in[src]), y_interleaved=int(il)))
                         y = out
                     msg_out[(v, i)] = y
             for v, d in self.var.items():
@@ -1089,8 +968,8 @@ class GraphNN(object):
             mlp_calls = []
             for d, ts in mlp_tasks.items():
                 for group in ([t for t in ts if not t.proj_w], [t for t in ts if t.proj_w]):
-                    mlp_calls += [(_lib.task_array(group[k:k + 4]), d) for k in range(0, len(group), 4)]
-            cell_calls = [(_lib.task_array(ts[k:k + 4]), d) for d, ts in cell_tasks.items() for k in range(0, len(ts), 4)]
+                    mlp_calls += _lib.launches({d: group})
+            cell_calls = _lib.launches(cell_tasks)
             built[key] = (mlp_calls, mid, cell_calls)
             return built[key]
         keep.append(built)
@@ -1269,9 +1148,9 @@ class GraphNN(object):
             pw = po = None
             if folded[v] is not None:
                 cv = self._RNN_cells[v]
-                pw, po = cv._packed_split(arith, "lstm.kx", 0, cv.dx, cen), zxs[p][v]
+                pw, po = cv.packed("Kx", arith, cen), zxs[p][v]
             out = mo[p].get((v, i))
-            return (mlp.wb_packed_split(arith, 0, n - 1, d), n, mlp.relu_mask(0, n), out, pw, po)
+            return (mlp.wb_packed(0, n - 1, d, arith), n, mlp.relu_mask(0, n), out, pw, po)
 
         def cell_tasks(p, with_messages, first):
             """Launches of a step of parity p; ``first``: the step reads the caller's (row-major) states; a step
@@ -1315,11 +1194,13 @@ class GraphNN(object):
                 if with_messages:   # the message MLP that reads this variable's new h in the next step
                     (cv, ci), = consumers[v]
                     wb, n, mask, mout, pw, po = message(cv, ci, 1 - p)
-                    ct = _lib.CellMlpTask(t, _lib.ptr(wb), n, mask, _lib.ptr(mout), _lib.ptr(pw), _lib.ptr(po), s_in, s_out)
+                    ct = _lib.CellMlpTask(t, mlp_wb=_lib.ptr(wb), mlp_layers=n, relu_mask=mask, mlp_out=_lib.ptr(mout),
+                                          proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po), state_in_blocked=s_in,
+                                          state_out_blocked=s_out)
                 else:
-                    ct = _lib.CellMlpTask(t, None, 0, 0, None, None, None, s_in, s_out)
+                    ct = _lib.CellMlpTask(t, state_in_blocked=s_in, state_out_blocked=s_out)
                 tasks.setdefault(d, []).append(ct)
-            calls = [(_lib.task_array(ts[k:k + 4]), d) for d, ts in tasks.items() for k in range(0, len(ts), 4)]
+            calls = _lib.launches(tasks)
             return mid, calls
 
         # messages of step 0 from the initial states
@@ -1332,9 +1213,10 @@ class GraphNN(object):
                     mout = torch.empty((y.shape[0], self._msg_MLPs[u["msg"]].sizes[-1]), **f32)
                     keep.append(mout)
                 pre.setdefault(self._msg_MLPs[u["msg"]].sizes[-1], []).append(
-                    _lib.MlpTask(_lib.ptr(y), _lib.ptr(wb), _lib.ptr(mout), None, 0, y.shape[0], n, mask,
-                                 _lib.ptr(pw), _lib.ptr(po), self.store.h2_flag_ptr() if arith == "h2" else None))
-        pre_calls = [(_lib.task_array(ts[k:k + 4]), d) for d, ts in pre.items() for k in range(0, len(ts), 4)]
+                    _lib.MlpTask(X=_lib.ptr(y), wb=_lib.ptr(wb), Y=_lib.ptr(mout), rows=y.shape[0], n_layers=n, relu_mask=mask,
+                                 proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po),
+                                 range_flag=self.store.h2_flag_ptr() if arith == "h2" else None))
+        pre_calls = _lib.launches(pre)
         built = {}
         self._plan_keep = keep
         # the cells' packings are made here, not at the first step: the caller vets their range (check_h2_weights) between
@@ -1342,11 +1224,11 @@ class GraphNN(object):
         for v in self.var:
             cell = self._RNN_cells[v]
             if folded[v] is not None:
-                cell._packed_split(arith, "lstm.kh", cell.dx, cell.dx + cell.d, cen)
+                cell.packed("Kh", arith, cen)
             elif pushed[v]:
                 cell.pushed_bias_pack(self._msg_MLPs[self.loop[v][0]["msg"]], arith=arith, centered=cen)
             else:
-                cell._packed_split(arith, "lstm", 0, cell.dx + cell.d, cen)
+                cell.packed("K", arith, cen)
 
         loop_launch = self._loop_launch(states, mats, folded, pushed, consumers, message, first_state, arith, cen, keep) \
             if arith == "h2" else None
@@ -1414,8 +1296,8 @@ class GraphNN(object):
             v_K, zb = cell_v.pushed_bias_pack(mlp_e, arith=arith, centered=cen)
             deg = adj.row_degrees(True)
         else:
-            v_K, zb, deg = cell_v._packed_split(arith, "lstm", 0, cell_v.dx + cell_v.d, cen), None, None
-        e_K = cell_e._packed_split(arith, "lstm.kh", cell_e.dx, cell_e.dx + cell_e.d, cen)
+            v_K, zb, deg = cell_v.packed("K", arith, cen), None, None
+        e_K = cell_e.packed("Kh", arith, cen)
         out_e = LSTMStateTuple(c=torch.empty((M, 64), **f32), h=torch.empty((M, 64), **f32))
         out_v = LSTMStateTuple(c=torch.empty((N, 64), **f32), h=torch.empty((N, 64), **f32))
         vagg = [torch.empty((N, 64), **f32), torch.empty((N, 64), **f32)]
@@ -1511,7 +1393,7 @@ class GraphNN(object):
                         if folded[v] is not None:   # Zx = msg(y) Kx rides in the MLP launch
                             zxs[v] = torch.empty((_pad16(y.shape[0]), 4 * self.var[v]), **f32)
                             cv = self._RNN_cells[v]
-                            proj = (cv._packed_split(arith, "lstm.kx", 0, cv.dx) if arith else cv.kx_packed(), zxs[v])
+                            proj = (cv.packed("Kx", arith or "f32"), zxs[v])
                         mlp_tasks.setdefault(mlp.sizes[-1], []).append(mlp.task(y, out, proj=proj, arith=arith))
                         y = out
                     msg_out[(v, i)] = y
@@ -1553,8 +1435,8 @@ class GraphNN(object):
                 keep.append(x)
             keep.append(msg_out)
 
-            mlp_calls = [(_lib.task_array(ts[k:k + 4]), d) for d, ts in mlp_tasks.items() for k in range(0, len(ts), 4)]
-            lstm_calls = [(_lib.task_array(ts[k:k + 4]), d) for d, ts in lstm_tasks.items() for k in range(0, len(ts), 4)]
+            mlp_calls = _lib.launches(mlp_tasks)
+            lstm_calls = _lib.launches(lstm_tasks)
 
             mlp_fn = "tspgnn_mlp_fwd_multi_" + (arith or "f32")
             lstm_fn = "tspgnn_lnlstm_fwd_multi_" + (arith or "f32")
@@ -1596,9 +1478,7 @@ class GraphNN(object):
                         keep.append(yc)
                     y = out
                 msg_out[(v, i)] = y
-        for d, ts in tasks.items():
-            for k in range(0, len(ts), 4):
-                _lib.call_multi("tspgnn_mlp_fwd_multi_f32", ts[k:k + 4], d)
+        _lib.call_by_width("tspgnn_mlp_fwd_multi_f32", tasks)
         # ---- B: adjacency products (or, for a folded cell, Zx = y Kx on the source rows)
         cell_in = {}
         for v in self.var:
@@ -1631,9 +1511,7 @@ class GraphNN(object):
                 keep.append(x)
                 t = cell.task(x, st, out)
             tasks.setdefault(d, []).append(t)
-        for d, ts in tasks.items():
-            for k in range(0, len(ts), 4):
-                _lib.call_multi("tspgnn_lnlstm_fwd_multi_f32", ts[k:k + 4], d)
+        _lib.call_by_width("tspgnn_lnlstm_fwd_multi_f32", tasks)
         return new_states
 
     # ---------------------------------------------------------------- training: forward with a tape
@@ -1691,8 +1569,6 @@ class GraphNN(object):
             for i, u in enumerate(self.loop[v]):
                 if "msg" in u and "var" in u:
                     tape.acts[(v, i)] = None     # allocated below, once the arithmetic (hence the tape's form) is known
-        tape.fused = False
-        tape.rc = {}
 
         def alloc_acts():
             for (v, i) in tape.acts:
@@ -1710,6 +1586,8 @@ class GraphNN(object):
         # cells' backward recomputes z in the same arithmetic (tspgnn_lnlstm_bwd_multi_h2; the tape's projected
         # messages ZX carry the factor 2^s both sides expect); with bf16x3 the backward is fp32 MFMA.
         arith = self._split_arith({v: initial_embeddings[v].shape[0] for v in self.var})
+        pushable = {v: bool(self.push_training and not self.fuse_training_messages and self._pushable(v, mats, tape.folded))
+                    for v in self.var}
         if arith == "h2":
             # the step's f16x2 packings up front (they are cached for the tasks below), so that the guard can veto them
             # before any kernel multiplies with them
@@ -1717,16 +1595,16 @@ class GraphNN(object):
             # one with the PRODUCT [W Kx ; Kh] -- which can leave the range on its own --, the others with the whole kernel)
             for v, cell in self._RNN_cells.items():
                 if tape.folded[v] is not None:
-                    cell._packed_split("h2", "lstm.kh", cell.dx, cell.dx + cell.d)
+                    cell.packed("Kh", "h2")
                     if "msg" in tape.folded[v]:
-                        cell._packed_split("h2", "lstm.kx", 0, cell.dx)
-                elif self.push_training and not self.fuse_training_messages and self._pushable(v, mats, tape.folded):
+                        cell.packed("Kx", "h2")
+                elif pushable[v]:
                     cell.pushed_bias_pack(self._msg_MLPs[self.loop[v][0]["msg"]], arith="h2")
                 else:
-                    cell._packed_split("h2", "lstm", 0, cell.dx + cell.d)
+                    cell.packed("K", "h2")
             for mlp in self._msg_MLPs.values():
                 if len(mlp._chunks()) == 1:
-                    mlp.wb_packed_split("h2", 0, mlp.n_square - 1, mlp.sizes[-1])
+                    mlp.wb_packed(0, mlp.n_square - 1, mlp.sizes[-1], "h2")
             if not self.check_h2_weights():
                 arith = self._split_arith({v: initial_embeddings[v].shape[0] for v in self.var})
         tape.arith = arith
@@ -1734,8 +1612,7 @@ class GraphNN(object):
         lstm_fn = "tspgnn_lnlstm_fwd_multi_" + (arith or "f32")
         # pushed cells (f16x2): the tape's X[v] holds the row-sum of the message MLP's LAST HIDDEN activation and the cell
         # runs with K' = [W Kx ; Kh], z starting at degree * (b Kx) (LayerNormBasicLSTMCell.pushed_kernel)
-        tape.pushed = {v: bool(arith == "h2" and self.push_training and not self.fuse_training_messages
-                               and self._pushable(v, mats, tape.folded)) for v in self.var}
+        tape.pushed = {v: arith == "h2" and pushable[v] for v in self.var}
         # recomputed message MLPs (tspgnn_mlp_bwd_rc_h2): the pushed entries whose prefix the kernel covers
         for v in self.var:
             if tape.pushed[v] and self.recompute_messages:
@@ -1752,7 +1629,7 @@ class GraphNN(object):
             proj = None
             if tape.folded[v] is not None:
                 cv = self._RNN_cells[v]
-                proj = (cv._packed_split(arith, "lstm.kx", 0, cv.dx) if arith else cv.kx_packed(), tape.ZX[v][t])
+                proj = (cv.packed("Kx", arith or "f32"), tape.ZX[v][t])
             return out, proj
 
         def messages(t):
@@ -1795,9 +1672,7 @@ class GraphNN(object):
                             mlp_tasks.setdefault(mlp.sizes[-1], []).append(task)
                         y = out
                     msg_out[(v, i)] = y
-            for d, ts in mlp_tasks.items():
-                for k in range(0, len(ts), 4):
-                    _lib.call_multi(mlp_fn, ts[k:k + 4], d)
+            _lib.call_by_width(mlp_fn, mlp_tasks)
             return msg_out
 
         def aggregate(t, msg_out):
@@ -1866,16 +1741,14 @@ class GraphNN(object):
                             pw, po = proj if proj is not None else (None, None)
                             k = mlp.n_square
                             saved = acts[:, t + 1] if k > 1 else None
-                        ct = _lib.CellMlpTask(task, _lib.ptr(mlp.wb_packed_split(arith, 0, k - 1, d)), k, mlp.relu_mask(0, k),
-                                              _lib.ptr(out), _lib.ptr(pw), _lib.ptr(po), 0, 0,
-                                              _lib.ptr(saved), acts.stride(0))
+                        ct = _lib.CellMlpTask(task, mlp_wb=_lib.ptr(mlp.wb_packed(0, k - 1, d, arith)), mlp_layers=k,
+                                              relu_mask=mlp.relu_mask(0, k), mlp_out=_lib.ptr(out), proj_w=_lib.ptr(pw),
+                                              proj_out=_lib.ptr(po), mlp_acts=_lib.ptr(saved), mlp_acts_stride=acts.stride(0))
                         nxt[(cv, ci)] = out
                     else:
-                        ct = _lib.CellMlpTask(task, None, 0, 0, None, None, None, 0, 0, None, 0)
+                        ct = _lib.CellMlpTask(task)
                     tasks.setdefault(d, []).append(ct)
-                for d, ts in tasks.items():
-                    for k in range(0, len(ts), 4):
-                        _lib.call_multi("tspgnn_lnlstm_mlp_fwd_multi_h2", ts[k:k + 4], d)
+                _lib.call_by_width("tspgnn_lnlstm_mlp_fwd_multi_h2", tasks)
                 msg_out = nxt
         else:
             for t in range(T):
@@ -1884,9 +1757,7 @@ class GraphNN(object):
                 lstm_tasks = {}
                 for v, d in self.var.items():
                     lstm_tasks.setdefault(d, []).append(cell_task(v, t))
-                for d, ts in lstm_tasks.items():
-                    for k in range(0, len(ts), 4):
-                        _lib.call_multi(lstm_fn, ts[k:k + 4], d)
+                _lib.call_by_width(lstm_fn, lstm_tasks)
         states = {v: LSTMStateTuple(c=tape.C[v][T], h=tape.H[v][T]) for v in self.var}
         return states, tape
 
@@ -1921,18 +1792,17 @@ class GraphNN(object):
                         pw = po = None
                         if tape.folded[v] is not None:
                             cv = self._RNN_cells[v]
-                            pw, po = cv._packed_bf16("lstm.kx", 0, cv.dx), tape.ZX[v][t]
+                            pw, po = cv.packed("Kx", "bf16"), tape.ZX[v][t]
                         k = mlp.n_square
-                        task = _lib.MlpTaskB(_lib.ptr(y), _lib.ptr(mlp.wb_packed_bf16(0, k - 1, d)), _lib.ptr(out), y.shape[0], k,
-                                             mlp.relu_mask(0, k), _lib.ptr(pw), _lib.ptr(po),
-                                             _lib.ptr(acts[:, t]) if k > 1 else None, acts.stride(0))
+                        task = _lib.MlpTaskB(X=_lib.ptr(y), wb=_lib.ptr(mlp.wb_packed_bf16(0, k - 1, d)), Y=_lib.ptr(out),
+                                             rows=y.shape[0], n_layers=k, relu_mask=mlp.relu_mask(0, k), proj_w=_lib.ptr(pw),
+                                             proj_out=_lib.ptr(po), acts=_lib.ptr(acts[:, t]) if k > 1 else None,
+                                             acts_stride=acts.stride(0))
                         (with_proj if pw is not None else plain).setdefault(d, []).append(task)
                         y = out
                     msg_out[(v, i)] = y
             for group in (plain, with_proj):   # (projections in their own launch: see _run_bf16)
-                for d, ts in group.items():
-                    for k in range(0, len(ts), 4):
-                        _lib.call_multi("tspgnn_mlp_fwd_multi_bf16", ts[k:k + 4], d)
+                _lib.call_by_width("tspgnn_mlp_fwd_multi_bf16", group)
             cells = {}
             for v, d in self.var.items():
                 cell = self._RNN_cells[v]
@@ -1954,9 +1824,7 @@ class GraphNN(object):
                         torch.cat(inputs, dim=1, out=tape.X[v][t])
                     task = cell.task_bf16(tape.X[v][t], tape.H[v][t], tape.C[v][t], tape.H[v][t + 1], tape.C[v][t + 1], n[v])
                 cells.setdefault(d, []).append(task)
-            for d, ts in cells.items():
-                for k in range(0, len(ts), 4):
-                    _lib.call_multi("tspgnn_lnlstm_fwd_multi_bf16", ts[k:k + 4], d)
+            _lib.call_by_width("tspgnn_lnlstm_fwd_multi_bf16", cells)
 
     def backward(self, tape, dstates):
         """Back-propagation through time of forward_train.  dstates: {var: (dh, dc)} gradients w.r.t. the
@@ -1966,7 +1834,7 @@ class GraphNN(object):
         bf16-storage tape: gradients are fp32 throughout (the fp32-MFMA backward kernels on the widened tape), taken
         of the function the forward evaluated -- stored values as they were rounded, GEMM weights rounded to bf16,
         every rounding passed straight through -- and land on the fp32 master variables."""
-        if getattr(tape, "arith", None) == "bf16":
+        if tape.arith == "bf16":
             names = [c.base + "/kernel" for c in self._RNN_cells.values()]
             names += [ln + "/kernel" for m in self._msg_MLPs.values() for ln in m.layer_names]
             with self.store.rounded_to_bf16(names):
@@ -1996,26 +1864,26 @@ class GraphNN(object):
         f32 = dict(dtype=torch.float32, device=device)
         n = {v: tape.H[v].shape[1] for v in self.var}
         folded = tape.folded
-        bwd_arith = "h2" if getattr(tape, "arith", None) == "h2" else None   # the cells' backward follows the forward
+        bwd_arith = "h2" if tape.arith == "h2" else None   # the cells' backward follows the forward
         # bf16-storage tape: the bf16-reading backward kernels take the tape's arrays as they are (widths 64 / 128; the
         # narrow widths widen slices of the tape for the fp32 kernels instead)
-        native = getattr(tape, "arith", None) == "bf16" and all(d in (64, 128) for d in self.var.values()) \
+        native = tape.arith == "bf16" and all(d in (64, 128) for d in self.var.values()) \
             and all(c.dx % 64 == 0 for c in self._RNN_cells.values()) \
             and os.environ.get("TSPGNN_BF16_BACKWARD", "native") == "native"
         tape.native = native
         # Weight gradients are one reduction per variable over a CHUNK of time steps: all T when the gradients w.r.t.
         # the pre-activations of the chunk (4d + the MLP layers' d floats per row and step) fit the budget -- the C2
         # case, ~6 GB -- else the largest chunk that does (a C5 shard: 84 GB for all 64 steps)
-        pushed = getattr(tape, "pushed", None) or {v: False for v in self.var}
-        rc = getattr(tape, "rc", None) or {}      # entries whose backward recomputes the hidden activations and forms the
+        pushed = tape.pushed
+        rc = tape.rc                              # entries whose backward recomputes the hidden activations and forms the
                                                   # weight gradients in the same launch (no chunk buffers)
         per_step = sum(n[v] * 4 * d * 4 for v, d in self.var.items())
         per_step += sum(self._msg_MLPs[self.loop[v][i]["msg"]].n_square * n[self.loop[v][i]["var"]]
                         * self.var[self.loop[v][i]["var"]] * 4 * (0 if rc.get((v, i)) else 1)
                         for (v, i) in tape.acts)
         per_step += sum(tape.X[v].shape[1] * 4 * self.var[v] * 4 for v in self.var if folded[v] is not None)   # DZX
-        per_step += sum(n[v] * 4 for v in self.var if (getattr(tape, "pushed", None) or {}).get(v))          # degrees
-        if getattr(tape, "arith", None) == "bf16" and not native:
+        per_step += sum(n[v] * 4 for v in self.var if pushed[v])          # degrees
+        if tape.arith == "bf16" and not native:
             # widened fp32 copies of the chunk's tape slices (h, cell inputs, hidden activations) for the fp32 reductions
             per_step += sum(n[v] * d * 4 + tape.X[v].shape[1] * tape.X[v].shape[2] * 4 for v, d in self.var.items())
             per_step += sum(a.shape[0] * a.shape[2] * a.shape[3] * 4 for a in tape.acts.values())
@@ -2038,7 +1906,7 @@ class GraphNN(object):
                 mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
                 if mlp.backward_h2_ok(acts):
                     for l0, nl in mlp._chunks():
-                        mlp.wt_packed_h2(l0, l0 + nl - 1, mlp.sizes[-1])
+                        mlp.wt_packed(l0, l0 + nl - 1, mlp.sizes[-1], h2=True)
             guard = store.h2_guard()
             bits = int(guard[1].item())
             guard[1:2].zero_()
@@ -2108,7 +1976,7 @@ class GraphNN(object):
                 and not rc.get((v, 0)) and not pushed[v] and self.mlp_backward_h2 and T > 0
                 and self._msg_MLPs[u0["msg"]].backward_task_takes_projection(tape.acts_at((v, 0), 0)[0],
                                                                               4 * self._RNN_cells[v].d))
-        arith = getattr(tape, "arith", None)
+        arith = tape.arith
         self._last_backward = {
             "forward": arith or "f32",
             "backward": ("bf16-native" if native else "bf16-widened") if arith == "bf16" else (bwd_arith or "f32"),
@@ -2140,7 +2008,7 @@ class GraphNN(object):
                     kp, zb = cell.pushed_bias_pack(push[v]["mlp"], arith="h2")
                     # (d == dx == 64: [d(aggregate) | dh] = dz K'^T rides in this launch as a second phase of the task's
                     # workgroups -- one launch less per step)
-                    data = (cell.pushed_kernel_t_h2(push[v]["mlp"]), dX[v], ndH[v]) if fused_data[v] else None
+                    data = (cell.packed("K", "h2T", pushed=push[v]["mlp"]), dX[v], ndH[v]) if fused_data[v] else None
                     task = cell.pushed_backward_task(tape.x(v, t), h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v], ws[v], kp, zb,
                                                      push[v]["deg"], defer=True, data=data)
                 else:
@@ -2149,9 +2017,7 @@ class GraphNN(object):
                     task = cell.backward_task(x_t, h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v], ws[v], defer=True,
                                               arith=bwd_arith)
                 tasks.setdefault(d, []).append(task)
-            for d, ts in tasks.items():
-                for j in range(0, len(ts), 4):
-                    _lib.call_multi("tspgnn_lnlstm_bwd_multi_" + ("bf16" if native else (bwd_arith or "f32")), ts[j:j + 4], d)
+            _lib.call_by_width("tspgnn_lnlstm_bwd_multi_" + ("bf16" if native else (bwd_arith or "f32")), tasks)
             # ---- 2: data gradients of the cell GEMMs; these WRITE dh, the message paths below ACCUMULATE into it
             for v in self.var:
                 cell = self._RNN_cells[v]
@@ -2225,11 +2091,11 @@ class GraphNN(object):
                             cell = self._RNN_cells[v]
                             if src not in targets:
                                 task = mlp.backward_task(None, acts_t, acts_stride, None, dpre[:, k], dpre.stride(0), ndH[src],
-                                                         True, h2=True, pre=(DZX[v][k], cell.kx_t_packed_h2()))
+                                                         True, h2=True, pre=(DZX[v][k], cell.packed("Kx", "h2T")))
                                 mlp_tasks.append(((self.var[src], True), task, None))
                                 targets.append(src)
                                 continue
-                            _lib.call("tspgnn_linear_f32", _lib.ptr(DZX[v][k]), 4 * cell.d, _lib.ptr(cell.kx_t_packed()), None, 0,
+                            _lib.call("tspgnn_linear_f32", _lib.ptr(DZX[v][k]), 4 * cell.d, _lib.ptr(cell.packed("Kx", "f32T")), None, 0,
                                       _lib.ptr(dy), cell.dx, 0, DZX[v][k].shape[0], _lib.current_stream())
                         if pushed[v]:   # the chain ends at the last hidden activation (a relu layer: masked by its output)
                             task = mlp.backward_prefix_task(dpre.shape[0], dy, acts_t, acts_stride, acts_t[dpre.shape[0] - 1],
@@ -2253,8 +2119,7 @@ class GraphNN(object):
             for key, task, _ in mlp_tasks:
                 by_d.setdefault(key, []).append(task)
             for (d, h2), ts in by_d.items():
-                for j in range(0, len(ts), 4):
-                    _lib.call_multi("tspgnn_mlp_bwd_multi_" + ("h2" if h2 else "f32"), ts[j:j + 4], d)
+                _lib.call_by_width("tspgnn_mlp_bwd_multi_" + ("h2" if h2 else "f32"), {d: ts})
             for mlp, task, _ in rc_tasks:
                 _lib.call("tspgnn_mlp_bwd_rc_h2", ctypes.cast(ctypes.pointer(task), ctypes.c_void_p), mlp.sizes[-1],
                           _lib.current_stream())

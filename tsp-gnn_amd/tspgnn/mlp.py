@@ -108,65 +108,50 @@ class Mlp(object):
         last = len(self.layer_names) - 1 if last is None else last
         return self.store.span(self.layer_names[first] + "/kernel", self.layer_names[last] + "/bias")
 
-    def wb_packed(self, first, last, d):
-        """[pack(W),b,...] for square layers first..last: the weights in MFMA fragment order
-        (tspgnn_pack_weights_f32), cached until the variables change."""
+    def _cached(self, key, first, last, numel, dtype, fill):
+        """The tensor ``fill(out)`` writes for layers first..last, cached until the variables change; the buffer is reused
+        across weight versions (captured graphs hold its address)."""
         def build(out):
-            src = self.wb(first, last)
             if out is None:
-                out = torch.empty_like(src)
-            st = _lib.current_stream()
-            per = d * d + d
-            for j in range(last - first + 1):
-                o = j * per
-                _lib.call("tspgnn_pack_weights_f32", _lib.ptr(src[o:o + d * d]), _lib.ptr(out[o:o + d * d]), d, d, 0, st)
-                out[o + d * d:o + per].copy_(src[o + d * d:o + per])
+                out = torch.empty(numel, dtype=dtype, device=self.store.theta.device)
+            fill(out)
             return out
-        return self.store.packed(("mlp", self.name, first, last), build)
+        return self.store.packed((key, self.name, first, last), build)
 
-    def wb_packed_split(self, arith, first, last, d):
-        """Byte tensor of {split pack(W), bias [d*4 B]} per square layer first..last for the split-operand kernels,
-        cached until the variables change.  ``arith`` = "x3": three bf16 pieces (3*d*d*2 B, tspgnn_pack_weights_x3);
-        "h2": two fp16 pieces of 2^s W (2*d*d*2 B, tspgnn_pack_weights_h2) next to 2^s b."""
-        nb = {"x3": 6, "h2": 4}[arith]
+    def wb_packed(self, first, last, d, arith=None):
+        """[pack(W), b, ...] for square layers first..last.  ``arith`` None: fp32, the weights in MFMA fragment order
+        (tspgnn_pack_weights_f32).  "x3" / "h2": a byte tensor of {split pack(W), bias [d*4 B]} per layer for the
+        split-operand kernels -- three bf16 pieces (3*d*d*2 B, tspgnn_pack_weights_x3), or two fp16 pieces of 2^s W
+        (2*d*d*2 B) next to 2^s b (tspgnn_pack_mlp_h2: every layer in one launch)."""
+        n = last - first + 1
+        nw = {None: d * d, "x3": 6 * d * d, "h2": 4 * d * d}[arith]            # packed weights of a layer, in elements of out
+        per_src, per = d * d + d, nw + (d if arith is None else 4 * d)
 
-        def build(out):
-            src = self.wb(first, last)
-            per_src, per = d * d + d, nb * d * d + 4 * d
-            if out is None:
-                out = torch.empty((last - first + 1) * per, dtype=torch.uint8, device=src.device)
-            st = _lib.current_stream()
-            if arith == "h2":      # every layer, weights and scaled biases, in one launch
-                _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(src), _lib.ptr(out), d, last - first + 1, 0,
-                          self.store.h2_absmax_ptr(), st)
-                return out
-            for j in range(last - first + 1):
-                o, q = j * per_src, j * per
-                if arith == "h2":
-                    _lib.call("tspgnn_pack_weights_h2", _lib.ptr(src[o:o + d * d]), _lib.ptr(out[q:q + nb * d * d]), d, d,
-                              self.store.h2_absmax_ptr(), st)
+        def fill(out):
+            src, st = self.wb(first, last), _lib.current_stream()
+            if arith == "h2":
+                _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(src), _lib.ptr(out), d, n, 0, self.store.h2_absmax_ptr(), st)
+                return
+            for j in range(n):
+                W, bias = src[j * per_src:j * per_src + d * d], src[j * per_src + d * d:(j + 1) * per_src]
+                if arith is None:
+                    _lib.call("tspgnn_pack_weights_f32", _lib.ptr(W), _lib.ptr(out[j * per:j * per + nw]), d, d, 0, st)
+                    out[j * per + nw:(j + 1) * per].copy_(bias)
                 else:
-                    _lib.call("tspgnn_pack_weights_" + arith, _lib.ptr(src[o:o + d * d]), _lib.ptr(out[q:q + nb * d * d]), d, d, st)
-                bias = src[o + d * d:o + per_src]
-                if arith == "h2":
-                    bias = bias * _lib.lib.tspgnn_h2_weight_scale()
-                out[q + nb * d * d:q + per].copy_(bias.view(torch.uint8))
-            return out
-        return self.store.packed(("mlp." + arith, self.name, first, last), build)
-
-    def wb_packed_x3(self, first, last, d):
-        return self.wb_packed_split("x3", first, last, d)
+                    _lib.call("tspgnn_pack_weights_x3", _lib.ptr(W), _lib.ptr(out[j * per:j * per + nw]), d, d, st)
+                    out[j * per + nw:(j + 1) * per].copy_(bias.view(torch.uint8))
+        return self._cached("mlp." + (arith or "f32"), first, last, n * per, torch.float32 if arith is None else torch.uint8, fill)
 
     def wb_packed_bf16(self, first, last, d, interleave_last=False):
         """Byte tensor of {bf16 pack(W) [d*d*2 B] (weights rounded to bf16, fragment order), b [d*4 B]} per square
         layer first..last for the bf16-storage kernels, cached until the variables change.  ``interleave_last``: the
         last layer's output columns permuted for tspgnn_mlp_task_bf16.y_interleaved (packed column 16t+4g+j holds true
         column 32(t/2)+8g+4(t%2)+j)."""
-        def build(out):
-            src = self.wb_packed_x3(first, last, d)
-            per3, per = 6 * d * d + 4 * d, 2 * d * d + 4 * d
-            if out is None:
-                out = torch.empty((last - first + 1) * per, dtype=torch.uint8, device=src.device)
+        per = 2 * d * d + 4 * d
+
+        def fill(out):
+            src = self.wb_packed(first, last, d, "x3")
+            per3 = 6 * d * d + 4 * d
             for j in range(last - first + 1):
                 out[j * per:j * per + 2 * d * d].copy_(src[j * per3:j * per3 + 2 * d * d])            # piece 0
                 out[j * per + 2 * d * d:(j + 1) * per].copy_(src[j * per3 + 6 * d * d:(j + 1) * per3])  # bias
@@ -181,31 +166,27 @@ class Mlp(object):
                 _lib.call("tspgnn_pack_weights_x3", _lib.ptr(W), _lib.ptr(tmp), d, d, _lib.current_stream())
                 out[j * per:j * per + 2 * d * d].copy_(tmp[:2 * d * d])
                 out[j * per + 2 * d * d:(j + 1) * per].copy_(wb[d * d:d * d + d][perm].contiguous().view(torch.uint8))
-            return out
-        return self.store.packed(("mlp.bf16" + (".il" if interleave_last else ""), self.name, first, last), build)
+        return self._cached("mlp.bf16" + (".il" if interleave_last else ""), first, last, (last - first + 1) * per,
+                            torch.uint8, fill)
 
-    def wt_packed(self, first, last, d):
-        """pack(W_l^T) for square layers first..last back to back (data-gradient kernels)."""
-        def build(out):
-            if out is None:
-                out = torch.empty((last - first + 1) * d * d, dtype=torch.float32, device=self.store.theta.device)
+    def wt_packed(self, first, last, d, h2=False):
+        """pack(W_l^T) for square layers first..last back to back (data-gradient kernels): fp32 fragment order, or with
+        ``h2`` tspgnn_pack_weights_h2(W_l^T) (two fp16 pieces of 2^s W_l^T, 4 d d bytes a layer; max |2^s W| joins the
+        store's range guard)."""
+        n = last - first + 1
+
+        def fill(out):
             st = _lib.current_stream()
-            for j in range(last - first + 1):
+            if h2:
+                _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(self.wb(first, last)), _lib.ptr(out), d, n, 1,
+                          self.store.h2_absmax_ptr(), st)
+                return
+            for j in range(n):
                 W = self.store.view(self.layer_names[first + j] + "/kernel")
                 _lib.call("tspgnn_pack_weights_f32", _lib.ptr(W), _lib.ptr(out[j * d * d:(j + 1) * d * d]), d, d, 1, st)
-            return out
-        return self.store.packed(("mlpT", self.name, first, last), build)
-
-    def wt_packed_h2(self, first, last, d):
-        """tspgnn_pack_weights_h2(W_l^T) (two fp16 pieces of 2^s W_l^T, 4 d d bytes) for square layers first..last back
-        to back: the data-gradient operand of tspgnn_mlp_bwd_rc_h2."""
-        def build(out):
-            if out is None:
-                out = torch.empty((last - first + 1) * 4 * d * d, dtype=torch.uint8, device=self.store.theta.device)
-            _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(self.wb(first, last)), _lib.ptr(out), d, last - first + 1, 1,
-                      self.store.h2_absmax_ptr(), _lib.current_stream())     # (max |2^s W| joins the store's range guard)
-            return out
-        return self.store.packed(("mlpT.h2", self.name, first, last), build)
+        if h2:
+            return self._cached("mlpT.h2", first, last, n * 4 * d * d, torch.uint8, fill)
+        return self._cached("mlpT", first, last, n * d * d, torch.float32, fill)
 
     def recompute_ok(self, n_layers):
         """tspgnn_mlp_bwd_rc_h2 covers the first ``n_layers`` square layers of this Mlp (d = 64, one to three layers)."""
@@ -218,11 +199,11 @@ class Mlp(object):
         the weight gradients formed in the same launch: they accumulate in ``partial`` (backward_rc_partial()) over the
         launches of a backward pass and are folded by backward_rc_finish()."""
         kind, d, n_sq, head = self._plan
-        return _lib.MlpBwdRcTask(_lib.ptr(x), _lib.ptr(self.wb_packed_split("h2", 0, n_layers - 1, d)),
-                                 _lib.ptr(self.wt_packed_h2(0, n_layers - 1, d)), _lib.ptr(y_out), _lib.ptr(dY),
-                                 _lib.ptr(gather_uv), _lib.ptr(dX), 1 if accumulate else 0,
-                                 dY.shape[0] if gather_uv is None else gather_uv.shape[0], n_layers,
-                                 self.relu_mask(0, n_layers), None, 0, None, 0, _lib.ptr(partial))
+        return _lib.MlpBwdRcTask(X=_lib.ptr(x), wb=_lib.ptr(self.wb_packed(0, n_layers - 1, d, "h2")),
+                                 wt=_lib.ptr(self.wt_packed(0, n_layers - 1, d, h2=True)), Yout=_lib.ptr(y_out),
+                                 dY=_lib.ptr(dY), uv=_lib.ptr(gather_uv), dX=_lib.ptr(dX), accumulate_dx=int(accumulate),
+                                 rows=dY.shape[0] if gather_uv is None else gather_uv.shape[0], n_layers=n_layers,
+                                 relu_mask=self.relu_mask(0, n_layers), partial=_lib.ptr(partial))
 
     def backward_rc_partial(self, n_layers):
         kind, d, n_sq, head = self._plan
@@ -254,11 +235,14 @@ class Mlp(object):
         kind, d, n_sq, head = self._plan
         if kind != "square" or head or len(self._chunks()) != 1:
             return None
-        pw, po = (proj if proj is not None else (None, None))
-        wb = self.wb_packed_split(arith, 0, n_sq - 1, d) if arith else self.wb_packed(0, n_sq - 1, d)
-        return _lib.MlpTask(_lib.ptr(x), _lib.ptr(wb), _lib.ptr(out), _lib.ptr(acts),
-                            acts_stride, x.shape[0], n_sq, self.relu_mask(0, n_sq), _lib.ptr(pw), _lib.ptr(po),
-                            self.store.h2_flag_ptr() if arith == "h2" else None)
+        return self._task(x, out, n_sq, arith, acts, acts_stride, proj if proj is not None else (None, None))
+
+    def _task(self, x, out, n_layers, arith, acts=None, acts_stride=0, proj=(None, None)):
+        """tspgnn_mlp_task of the first ``n_layers`` square layers over the rows of x, weights in the packing of ``arith``."""
+        return _lib.MlpTask(X=_lib.ptr(x), wb=_lib.ptr(self.wb_packed(0, n_layers - 1, self._plan[1], arith)), Y=_lib.ptr(out),
+                            acts=_lib.ptr(acts), acts_stride=acts_stride, rows=x.shape[0], n_layers=n_layers,
+                            relu_mask=self.relu_mask(0, n_layers), proj_w=_lib.ptr(proj[0]), proj_out=_lib.ptr(proj[1]),
+                            range_flag=self.store.h2_flag_ptr() if arith == "h2" else None)
 
     def prefix_task(self, x, out, n_layers, arith=None, acts=None, acts_stride=0):
         """Task running only the first ``n_layers`` square layers (the rest is folded elsewhere); ``acts``: the hidden
@@ -266,10 +250,7 @@ class Mlp(object):
         kind, d, n_sq, head = self._plan
         if kind != "square" or head or len(self._chunks()) != 1 or not (1 <= n_layers <= n_sq):
             return None
-        wb = self.wb_packed_split(arith, 0, n_layers - 1, d) if arith else self.wb_packed(0, n_layers - 1, d)
-        return _lib.MlpTask(_lib.ptr(x), _lib.ptr(wb), _lib.ptr(out), _lib.ptr(acts) if n_layers > 1 else None, acts_stride,
-                            x.shape[0], n_layers, self.relu_mask(0, n_layers), None, None,
-                            self.store.h2_flag_ptr() if arith == "h2" else None)
+        return self._task(x, out, n_layers, arith, acts if n_layers > 1 else None, acts_stride)
 
     def _chunks(self):
         kind, d, n_sq, head = self._plan
@@ -304,11 +285,11 @@ class Mlp(object):
             first = l0 == 0
             yo = y_out if last else acts[l0 + n - 1]
             dst = dX if first else torch.empty_like(dY)
-            wt = self.wt_packed_h2(l0, l0 + n - 1, d) if h2 else self.wt_packed(l0, l0 + n - 1, d)
-            task = _lib.MlpBwdTask(_lib.ptr(g), _lib.ptr(wt),
-                                   _lib.ptr(acts[l0]) if n > 1 else None, acts_stride, _lib.ptr(yo), _lib.ptr(dpre[l0]),
-                                   dpre_stride, _lib.ptr(dst), 1 if (accumulate and first) else 0, rows, n,
-                                   self.relu_mask(l0, n), None, _bf16_flag(acts))
+            wt = self.wt_packed(l0, l0 + n - 1, d, h2)
+            task = _lib.MlpBwdTask(dY=_lib.ptr(g), wt=_lib.ptr(wt), acts=_lib.ptr(acts[l0]) if n > 1 else None,
+                                   acts_stride=acts_stride, Yout=_lib.ptr(yo), dpre=_lib.ptr(dpre[l0]), dpre_stride=dpre_stride,
+                                   dX=_lib.ptr(dst), accumulate_dx=int(accumulate and first), rows=rows, n_layers=n,
+                                   relu_mask=self.relu_mask(l0, n), acts_bf16=_bf16_flag(acts))
             _lib.call_multi("tspgnn_mlp_bwd_multi_" + ("h2" if h2 else "f32"), [task], d)
             g = dst
 
@@ -328,16 +309,19 @@ class Mlp(object):
         kind, d, n_sq, head = self._plan
         if len(self._chunks()) != 1:
             return None
-        wt = self.wt_packed_h2(0, n_sq - 1, d) if h2 else self.wt_packed(0, n_sq - 1, d)
         if pre is not None:
-            return _lib.MlpBwdTask(None, _lib.ptr(wt), _lib.ptr(acts), acts_stride, _lib.ptr(y_out), _lib.ptr(dpre),
-                                   dpre_stride, _lib.ptr(dX), 1 if accumulate else 0, pre[0].shape[0], n_sq,
-                                   self.relu_mask(0, n_sq), None, _bf16_flag(acts), _lib.ptr(pre[0]), _lib.ptr(pre[1]),
-                                   pre[0].shape[1])
-        return _lib.MlpBwdTask(_lib.ptr(dY), _lib.ptr(wt), _lib.ptr(acts), acts_stride,
-                               _lib.ptr(y_out), _lib.ptr(dpre), dpre_stride, _lib.ptr(dX), 1 if accumulate else 0,
-                               dY.shape[0] if gather_uv is None else gather_uv.shape[0], n_sq, self.relu_mask(0, n_sq),
-                               _lib.ptr(gather_uv), _bf16_flag(acts))
+            return self._backward_task(n_sq, None, acts, acts_stride, y_out, dpre, dpre_stride, dX, accumulate, h2,
+                                       rows=pre[0].shape[0], pre_X=_lib.ptr(pre[0]), pre_wt=_lib.ptr(pre[1]),
+                                       pre_k=pre[0].shape[1])
+        return self._backward_task(n_sq, dY, acts, acts_stride, y_out, dpre, dpre_stride, dX, accumulate, h2,
+                                   rows=dY.shape[0] if gather_uv is None else gather_uv.shape[0], uv=_lib.ptr(gather_uv))
+
+    def _backward_task(self, n_layers, dY, acts, acts_stride, y_out, dpre, dpre_stride, dX, accumulate, h2, **fields):
+        """tspgnn_mlp_bwd_task of the first ``n_layers`` square layers (one kernel); ``fields``: rows and the form's own."""
+        return _lib.MlpBwdTask(dY=_lib.ptr(dY), wt=_lib.ptr(self.wt_packed(0, n_layers - 1, self._plan[1], h2)),
+                               acts=_lib.ptr(acts), acts_stride=acts_stride, Yout=_lib.ptr(y_out), dpre=_lib.ptr(dpre),
+                               dpre_stride=dpre_stride, dX=_lib.ptr(dX), accumulate_dx=int(accumulate), n_layers=n_layers,
+                               relu_mask=self.relu_mask(0, n_layers), acts_bf16=_bf16_flag(acts), **fields)
 
     def backward_task_takes_projection(self, acts, k):
         """backward_task(..., pre=...) is available (tspgnn_mlp_bwd_multi_h2 at width 64, one kernel, fp32 tape)."""
@@ -351,11 +335,8 @@ class Mlp(object):
         kind, d, n_sq, head = self._plan
         if len(self._chunks()) != 1 or not (1 <= n_layers <= n_sq):
             return None
-        wt = self.wt_packed_h2(0, n_layers - 1, d) if h2 else self.wt_packed(0, n_layers - 1, d)
-        return _lib.MlpBwdTask(_lib.ptr(dY), _lib.ptr(wt), _lib.ptr(acts), acts_stride,
-                               _lib.ptr(y_out), _lib.ptr(dpre), dpre_stride, _lib.ptr(dX), 1 if accumulate else 0,
-                               dY.shape[0] if gather_uv is None else gather_uv.shape[0], n_layers,
-                               self.relu_mask(0, n_layers), _lib.ptr(gather_uv), _bf16_flag(acts))
+        return self._backward_task(n_layers, dY, acts, acts_stride, y_out, dpre, dpre_stride, dX, accumulate, h2,
+                                   rows=dY.shape[0] if gather_uv is None else gather_uv.shape[0], uv=_lib.ptr(gather_uv))
 
     def backward_task_fuses_gather(self, dY):
         """backward_task(..., gather_uv=...) is available: one kernel covers the chain and dY is a plain fp32 array."""
@@ -382,27 +363,20 @@ class Mlp(object):
                 or not x.is_contiguous() or x.shape[1] != self.input_size:
             return self(x)
         last = self.layer_names[-1]
-        flag = self.store.h2_flag_ptr() if arith == "h2" else None
-        wb = _lib.ptr(self.wb_packed_split(arith, 0, n_sq - 1, d))
         if head and arith == "h2":     # Dense(1) taken in the same launch, the hidden rows never written
             y = torch.empty((x.shape[0], 1), dtype=torch.float32, device=x.device)
-            task = _lib.MlpTask(_lib.ptr(x), wb, None, None, 0, x.shape[0], n_sq, self.relu_mask(0, n_sq), None, None, flag)
+            task = self._task(x, None, n_sq, arith)
             _lib.call("tspgnn_mlp_head_fwd_h2", ctypes.cast(ctypes.pointer(task), ctypes.c_void_p), _lib.ptr(self.store.view(last + "/kernel")),
                       _lib.ptr(self.store.view(last + "/bias")), _lib.ptr(y), d, _lib.current_stream())
             return y
         out = torch.empty((x.shape[0], d), dtype=torch.float32, device=x.device)
-        task = _lib.MlpTask(_lib.ptr(x), wb, _lib.ptr(out), None, 0, x.shape[0], n_sq, self.relu_mask(0, n_sq), None, None,
-                            flag)
-        _lib.call_multi("tspgnn_mlp_fwd_multi_" + arith, [task], d)
+        _lib.call_multi("tspgnn_mlp_fwd_multi_" + arith, [self._task(x, out, n_sq, arith)], d)
         if not head:
             return out
         y = torch.empty((x.shape[0], 1), dtype=torch.float32, device=x.device)
         _lib.call("tspgnn_rowdot_f32", _lib.ptr(out), _lib.ptr(self.store.view(last + "/kernel")),
                   _lib.ptr(self.store.view(last + "/bias")), _lib.ptr(y), x.shape[0], d, _lib.current_stream())
         return y
-
-    def forward_x3(self, x):
-        return self.forward_split(x, "x3")
 
     def __call__(self, inputs, save=None):
         """inputs: fp32 device tensor [rows, input_size].  ``save`` (optional list) receives the
