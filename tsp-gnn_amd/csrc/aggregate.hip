@@ -4,6 +4,8 @@
 // 16 lanes), the small [N,d] operand stays L2-resident.
 #include "common.h"
 
+#include <type_traits>
+
 namespace tspgnn {
 
 // ---------------------------------------------------------------- E <- V : gather, 2 nnz / row
@@ -41,6 +43,9 @@ __global__ __launch_bounds__(256) void gather2_sum_kernel(const int2* __restrict
 // in ascending order, the groups are then combined with wavefront shuffles in a fixed
 // order (deterministic result).  Edge ids of the row are fetched with one coalesced load
 // per 64 edges and broadcast by shuffle instead of one dependent scalar load per edge.
+// The row loads of kRowsumInflight consecutive steps are issued before the first of their additions waits: the steps'
+// loads are independent, only the additions are ordered, and one load per wait leaves a vertex of ~40 edges a chain of ten
+// memory round trips.  The additions keep their order (mp_loop_h2 / mp_resident_h2 restate it bit for bit).
 // CB > 1: rows wider than 16 float4 are split into CB column blocks of LPR float4, one wavefront each (adjacent
 // wavefronts of a workgroup): four times the wavefronts and RPW rows in flight per load instead of one 1 KiB row at a
 // time -- a wide row-sum is otherwise bound by the latency of its ~n dependent-in-order batches of loads.
@@ -49,45 +54,65 @@ __device__ __forceinline__ void csr_rowsum_body(const int* __restrict__ rowptr, 
                                                 const float* __restrict__ val, const float4* __restrict__ X,
                                                 float4* __restrict__ Y, int N, unsigned blk, unsigned nblk) {
     constexpr int RPW = kWave / LPR;
+    constexpr int U = kRowsumInflight < LPR ? kRowsumInflight : LPR;   // a 64-edge id batch holds LPR row batches
     // XCD-aware order: workgroup b runs on XCD b % 8 (observed dispatch order; speed only).  Give each
     // XCD one contiguous eighth of the vertices, so the ~n vertices of one graph -- which together read
     // every edge row of that graph TWICE (once per endpoint) -- share one L2 and the second read hits.
     const unsigned nb = nblk, q = nb >> 3, r = nb & 7, xcd = blk & 7, slot = blk >> 3;
     const unsigned vb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;  // bijective for any nb
-    const int wv = (int)(((long long)vb * blockDim.x + threadIdx.x) >> 6);
+    // the 64 lanes of a wavefront share wv: saying so keeps rowptr, the loop bounds and the step tests in scalar registers
+    const int wv = __builtin_amdgcn_readfirstlane((int)(((long long)vb * blockDim.x + threadIdx.x) >> 6));
     const int v = wv / CB;
-    if (v >= N) return;  // wave-uniform
+    if (v >= N) return;
     const int lane = threadIdx.x & 63;
     const int sub = lane / LPR;
     const int c = (wv % CB) * LPR + lane % LPR;   // float4 column within the LPR*CB-wide row
     const int beg = rowptr[v], end = rowptr[v + 1];
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto add = [&](const float4& x, float w) {
+        if (VALUED) {
+            acc.x = fmaf(w, x.x, acc.x);
+            acc.y = fmaf(w, x.y, acc.y);
+            acc.z = fmaf(w, x.z, acc.z);
+            acc.w = fmaf(w, x.w, acc.w);
+        } else {
+            acc.x += x.x;
+            acc.y += x.y;
+            acc.z += x.z;
+            acc.w += x.w;
+        }
+    };
     for (int base = beg; base < end; base += kWave) {
         const int cnt = min(kWave, end - base);
         const int my_e = (lane < cnt) ? eid[base + lane] : 0;
         float my_w = 1.0f;
         if (VALUED) my_w = (lane < cnt) ? val[base + lane] : 0.f;
-#pragma unroll 4
-        for (int k0 = 0; k0 < cnt; k0 += RPW) {
-            const int k = k0 + sub;
-            const int src = min(k, cnt - 1);
-            const int e = __shfl(my_e, src);
-            const float w = VALUED ? __shfl(my_w, src) : 1.0f;
-            if (k < cnt) {
-                const float4 x = X[(long long)e * (LPR * CB) + c];
-                if (VALUED) {
-                    acc.x = fmaf(w, x.x, acc.x);
-                    acc.y = fmaf(w, x.y, acc.y);
-                    acc.z = fmaf(w, x.z, acc.z);
-                    acc.w = fmaf(w, x.w, acc.w);
-                } else {
-                    acc.x += x.x;
-                    acc.y += x.y;
-                    acc.z += x.z;
-                    acc.w += x.w;
-                }
+        // U steps at a time: their id shuffles, then their row loads back to back, then their additions in ascending k.
+        // A chunk that lies inside the list (FULL) is straight-line code; only the list's last chunk tests k < cnt per
+        // lane, and requests no row beyond the list.
+        auto chunk = [&](int k0, auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            float4 x[U];
+            float w[U];
+            int e[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = FULL ? k0 + u * RPW + sub : min(k0 + u * RPW + sub, cnt - 1);
+                e[u] = __builtin_amdgcn_ds_bpermute(src << 2, my_e);
+                w[u] = VALUED ? __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(my_w))) : 1.0f;
             }
-        }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                x[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (FULL || k0 + u * RPW + sub < cnt) x[u] = X[(long long)e[u] * (LPR * CB) + c];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (FULL || k0 + u * RPW + sub < cnt) add(x[u], w[u]);
+        };
+        int k0 = 0;
+        for (; k0 + U * RPW <= cnt; k0 += U * RPW) chunk(k0, std::true_type{});
+        if (k0 < cnt) chunk(k0, std::false_type{});
     }
 #pragma unroll
     for (int off = LPR; off < kWave; off <<= 1) {

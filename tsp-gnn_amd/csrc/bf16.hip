@@ -10,6 +10,8 @@
 #include "bf16_tile.h"
 #include "mfma_tile.h"
 
+#include <type_traits>
+
 namespace tspgnn {
 
 constexpr int kMaxTasksB = 4;
@@ -66,24 +68,43 @@ template <int LPR>
 __global__ __launch_bounds__(256) void csr_rowsum_bf16_kernel(const int* __restrict__ rowptr, const int* __restrict__ eid,
                                                               const uint4* __restrict__ X, uint4* __restrict__ Y, int N) {
     constexpr int RPW = kWave / LPR;
+    constexpr int U = kRowsumInflight < LPR ? kRowsumInflight : LPR;   // a 64-edge id batch holds LPR row batches
     // XCD-aware vertex order (workgroup b runs on XCD b % 8): each XCD owns a contiguous eighth of the vertices, so
     // the two reads of every edge row (one per endpoint) meet in one L2 -- see csr_rowsum_body in aggregate.hip
     const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const unsigned vb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;  // bijective for any nb
-    const int v = (int)(((long long)vb * blockDim.x + threadIdx.x) >> 6);
-    if (v >= N) return;  // wave-uniform
+    // the 64 lanes of a wavefront share v: saying so keeps rowptr, the loop bounds and the chunk tests in scalar registers
+    const int v = __builtin_amdgcn_readfirstlane((int)(((long long)vb * blockDim.x + threadIdx.x) >> 6));
+    if (v >= N) return;
     const int lane = threadIdx.x & 63, sub = lane / LPR, c = lane % LPR;
     const int beg = rowptr[v], end = rowptr[v + 1];
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int base = beg; base < end; base += kWave) {
         const int cnt = min(kWave, end - base);
         const int my_e = (lane < cnt) ? eid[base + lane] : 0;
-#pragma unroll 4
-        for (int k0 = 0; k0 < cnt; k0 += RPW) {
-            const int k = k0 + sub;
-            const int e = __shfl(my_e, min(k, cnt - 1));
-            if (k < cnt) add8(acc, X[(long long)e * LPR + c]);
-        }
+        // U steps at a time: id shuffles, row loads back to back, additions in ascending k; only the list's last chunk
+        // tests k < cnt per lane (see csr_rowsum_body in aggregate.hip)
+        auto chunk = [&](int k0, auto full) {
+            constexpr bool FULL = decltype(full)::value;
+            uint4 x[U];
+            int e[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int src = FULL ? k0 + u * RPW + sub : min(k0 + u * RPW + sub, cnt - 1);
+                e[u] = __builtin_amdgcn_ds_bpermute(src << 2, my_e);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                x[u] = make_uint4(0u, 0u, 0u, 0u);
+                if (FULL || k0 + u * RPW + sub < cnt) x[u] = X[(long long)e[u] * LPR + c];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (FULL || k0 + u * RPW + sub < cnt) add8(acc, x[u]);
+        };
+        int k0 = 0;
+        for (; k0 + U * RPW <= cnt; k0 += U * RPW) chunk(k0, std::true_type{});
+        if (k0 < cnt) chunk(k0, std::false_type{});
     }
 #pragma unroll
     for (int off = LPR; off < kWave; off <<= 1) {
