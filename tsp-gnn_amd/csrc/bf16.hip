@@ -8,28 +8,12 @@
 // converted in registers into the next layer's B operand.  d = 128 fits here (Kh[128,512] bf16 = 128 KB of LDS).
 #include "common.h"
 #include "bf16_tile.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 
 #include <type_traits>
 
 namespace tspgnn {
-
-constexpr int kMaxTasksB = 4;
-
-static int split_blocks_b(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
-}
 
 // ---------------------------------------------------------------------------------- aggregation (bf16 rows)
 // One 16-byte lane = 8 bf16; LPR = d/8 lanes per row.  Sums in fp32, one rounding at the store.
@@ -140,8 +124,8 @@ __global__ __launch_bounds__(256) void bf16_to_f32_kernel(const __bf16* __restri
 // ---------------------------------------------------------------------------------- MLP (bf16)
 // wb: n_layers blocks of { bf16 packed[D*D] (piece 0 of pack_weights_x3), float bias[D] }; proj_w: bf16 packed [D,4D].
 struct MlpTableB {
-    tspgnn_mlp_task_bf16 task[kMaxTasksB];
-    int blk_end[kMaxTasksB];
+    tspgnn_mlp_task_bf16 task[kMaxTasks];
+    int blk_end[kMaxTasks];
     int n;
 };
 
@@ -268,9 +252,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_fwd_bf16_kernel(const MlpTableB t
 // ---------------------------------------------------------------------------------- LN-LSTM (bf16)
 // K: bf16 packed kernel[dx+D, 4D] (or Kh[D,4D] in gather-init mode: z starts at Zx[u] + Zx[v], Zx bf16 [n_src,4D]).
 struct LstmTableB {
-    tspgnn_lstm_task_bf16 task[kMaxTasksB];
-    int blk_end[kMaxTasksB];
-    int kbc[kMaxTasksB];  // k-blocks per LDS chunk; >= all of K: resident
+    tspgnn_lstm_task_bf16 task[kMaxTasks];
+    int blk_end[kMaxTasks];
+    int kbc[kMaxTasks];  // k-blocks per LDS chunk; >= all of K: resident
     int n;
 };
 
@@ -479,7 +463,7 @@ __global__ __launch_bounds__(NW * 64) void lnlstm_fwd_bf16_kernel(const LstmTabl
 template <int D, int NW, bool PROJ>
 static int launch_mlp_b(const tspgnn_mlp_task_bf16* tasks, int n, hipStream_t st) {
     MlpTableB tt;
-    long long cost[kMaxTasksB];
+    long long cost[kMaxTasks];
     long long tiles_all = 0;
     size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
@@ -488,19 +472,15 @@ static int launch_mlp_b(const tspgnn_mlp_task_bf16* tasks, int n, hipStream_t st
         const size_t lay = (size_t)tasks[k].n_layers * (D * D * 2 + D * 4);
         lds_w = lds_w > need ? lds_w : need;
         lds_w = lds_w > lay ? lds_w : lay;
-        cost[k] = ((long long)tasks[k].rows + 15) / 16 * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += ((long long)tasks[k].rows + 15) / 16;
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
     }
     tt.n = n;
     const size_t lds_bytes = lds_w + 16;
     if (lds_bytes > 160 * 1024) return fail(TSPGNN_EUNSUPPORTED, "mlp_fwd_bf16: %zu bytes of weights do not fit LDS", lds_bytes);
-    int grid = n_cus();
-    const long long max_grid = (tiles_all + NW - 1) / NW;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_b(cost, n, grid, tt.blk_end);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_bf16_kernel<D, NW, PROJ>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "mlp_fwd_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, NW), tt.blk_end);
+    const int rc = set_dynamic_lds(&mlp_fwd_bf16_kernel<D, NW, PROJ>, lds_bytes, "mlp_fwd_bf16");
+    if (rc) return rc;
     mlp_fwd_bf16_kernel<D, NW, PROJ><<<grid, NW * 64, lds_bytes, st>>>(tt);
     return launched("tspgnn_mlp_fwd_multi_bf16");
 }
@@ -511,7 +491,7 @@ static int launch_lstm_b(const tspgnn_lstm_task_bf16* tasks, int n, hipStream_t 
     const size_t per_kb = (size_t)32 * 4 * D * 2;
     const size_t budget = 156 * 1024 - head;
     LstmTableB tt;
-    long long cost[kMaxTasksB];
+    long long cost[kMaxTasks];
     long long tiles_all = 0;
     size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
@@ -522,19 +502,15 @@ static int launch_lstm_b(const tspgnn_lstm_task_bf16* tasks, int n, hipStream_t 
         if (kbc < 1) return fail(TSPGNN_EUNSUPPORTED, "lnlstm_fwd_bf16: d=%d does not fit LDS", D);
         tt.kbc[k] = kbc;
         if ((size_t)kbc * per_kb > lds_w) lds_w = (size_t)kbc * per_kb;
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * (KBT + 4) * (kbc < KBT ? 2 : 1);
         tiles_all += tiles;
     }
     tt.n = n;
     const size_t lds_bytes = lds_w + head;
-    int grid = n_cus();
-    const long long max_grid = (tiles_all + NW - 1) / NW;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_b(cost, n, grid, tt.blk_end);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_fwd_bf16_kernel<D, NW, STAGED>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "lnlstm_fwd_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, NW), tt.blk_end);
+    const int rc = set_dynamic_lds(&lnlstm_fwd_bf16_kernel<D, NW, STAGED>, lds_bytes, "lnlstm_fwd_bf16");
+    if (rc) return rc;
     lnlstm_fwd_bf16_kernel<D, NW, STAGED><<<grid, NW * 64, lds_bytes, st>>>(tt);
     return launched("tspgnn_lnlstm_fwd_multi_bf16");
 }
@@ -577,24 +553,18 @@ extern "C" int tspgnn_csr_rowsum_bf16(const int32_t* rowptr, const int32_t* eid,
 }
 
 extern "C" int tspgnn_mlp_fwd_multi_bf16(const tspgnn_mlp_task_bf16* tasks, int n_tasks, int d, void* stream) {
-    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasksB, "mlp_fwd_multi_bf16: 1..%d tasks", kMaxTasksB);
+    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "mlp_fwd_multi_bf16: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "mlp_fwd_bf16: d=%d must be 32, 64 or 128", d);
-    tspgnn_mlp_task_bf16 live[kMaxTasksB];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_mlp_task_bf16& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "mlp_fwd_bf16: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_fwd_bf16: n_layers=%d must be in 1..4", t.n_layers);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.X && t.wb && t.Y, "mlp_fwd_bf16: null pointer");
-        TSPGNN_REQUIRE(!t.proj_w || t.proj_out, "mlp_fwd_bf16: projection needs proj_out");
+    tspgnn_mlp_task_bf16 live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](tspgnn_mlp_task_bf16& t) {
+        const int rc = check_mlp_task(t, d, "mlp_fwd_bf16");
+        if (rc || t.rows == 0) return rc;
         TSPGNN_REQUIRE(t.acts_stride >= 0, "mlp_fwd_bf16: acts_stride=%lld", t.acts_stride);
         TSPGNN_REQUIRE(!t.y_interleaved || (!t.proj_w && !t.acts), "mlp_fwd_bf16: y_interleaved excludes a projection and saved activations");
-        live[n] = t;
-        if (live[n].acts && live[n].acts_stride == 0) live[n].acts_stride = (long long)t.rows * d;
-        ++n;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     bool proj = false;
     for (int k = 0; k < n; ++k) proj = proj || live[k].proj_w != nullptr;
@@ -613,22 +583,21 @@ static bool bf16_cell_staged() {
 }
 
 extern "C" int tspgnn_lnlstm_fwd_multi_bf16(const tspgnn_lstm_task_bf16* tasks, int n_tasks, int d, void* stream) {
-    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasksB, "lnlstm_fwd_multi_bf16: 1..%d tasks", kMaxTasksB);
+    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_fwd_multi_bf16: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "lnlstm_fwd_bf16: d=%d must be 32, 64 or 128", d);
-    tspgnn_lstm_task_bf16 live[kMaxTasksB];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_lstm_task_bf16& t = tasks[k];
+    tspgnn_lstm_task_bf16 live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [](const tspgnn_lstm_task_bf16& t) {
         TSPGNN_REQUIRE(t.rows >= 0, "lnlstm_fwd_bf16: rows=%d", t.rows);
         TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "lnlstm_fwd_bf16: dx=%d must be a non-negative multiple of 32", t.dx);
-        if (t.rows == 0) continue;
+        if (t.rows == 0) return TSPGNN_OK;
         // (c == NULL: the zero cell state of a run's first step, nothing is read)
         TSPGNN_REQUIRE(t.h && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x), "lnlstm_fwd_bf16: null pointer");
         TSPGNN_REQUIRE(t.h_out != t.h && t.c_out != t.c, "lnlstm_fwd_bf16: outputs may not alias inputs");
         TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "lnlstm_fwd_bf16: gather-init mode needs dx == 0 and Zx");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     // staged edge task (see lnlstm_fwd_bf16_kernel): d = 128 at two wavefronts per SIMD (256 registers: 289 -> 248 us per
     // C5-shard launch), d = 64 at three (144 registers: 25.9 -> 22.5 us per C2-sized launch)

@@ -32,6 +32,9 @@ void reduce_partials2(const float* partial, int n_chunks, long long stride, floa
 
 constexpr int kWave = 64;  // CDNA wavefront
 
+// Tasks per tspgnn_*_multi_* launch: the extent of every task table passed to a kernel (host side: launch_plan.h).
+constexpr int kMaxTasks = 4;
+
 // CSR row-sums (aggregate.hip, bf16.hip): row-load steps of one vertex in flight per wavefront before the first addition
 // waits.  Measured 4 / 8 / a whole 64-edge batch (profiles/rowsum_inflight_ab.txt): 4 and 8 tie, 4 keeps every
 // instantiation under 64 registers (8 wavefronts per SIMD); the whole batch is slower than one load per wait at C2.

@@ -13,6 +13,7 @@
 // so activations never leave registers between layers and never cross lanes.  The same
 // fragment shape (float4 at column q*16+g*4 of a row) is used for global loads and stores.
 #include "common.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 
 namespace tspgnn {
@@ -57,8 +58,6 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restri
 // of one time step): the workgroups are split among the tasks in proportion to their tiles, and each
 // workgroup stages the weights of its own task.  The small vertex-side problem then rides along with
 // the large edge-side one instead of paying its own launch, staging and tail.
-constexpr int kMaxTasks = 4;
-
 struct MlpTaskTable {
     tspgnn_mlp_task task[kMaxTasks];
     int blk_end[kMaxTasks];  // exclusive prefix: task k owns workgroups [blk_end[k-1], blk_end[k])
@@ -317,22 +316,6 @@ __global__ __launch_bounds__(512) void lnlstm_fwd_chunked_kernel(const float* __
     }
 }
 
-// Workgroups per task, proportional to cost[k] (at least one each); grid = sum.
-static int split_blocks(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
-}
-
 template <int D, int MAXL>
 static int launch_mlp(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
     MlpTaskTable tt;
@@ -340,9 +323,8 @@ static int launch_mlp(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
     long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        if (tt.task[k].acts && tt.task[k].acts_stride == 0) tt.task[k].acts_stride = (long long)tasks[k].rows * D;
-        cost[k] = ((long long)tasks[k].rows + 15) / 16 * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += ((long long)tasks[k].rows + 15) / 16;
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
     }
     tt.n = n;
     // LDS per block decides residency: D=64 -> 65 KiB -> 2 blocks (16 waves) per CU.
@@ -356,9 +338,7 @@ static int launch_mlp(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
         grid = n_cus();
         nw = 16;
     }
-    const long long max_grid = (tiles_all + nw - 1) / nw;     // at least one tile per wave
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks(cost, n, grid, tt.blk_end);
+    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
     mlp_fwd_kernel<D, MAXL><<<grid, nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_fwd_f32");
 }
@@ -370,9 +350,8 @@ static int launch_lnlstm_chunked(const tspgnn_lstm_task& t, hipStream_t st) {
     // chunk = as many 16-row blocks of K as fit 128 KiB
     const int qc = (int)((128 * 1024) / (16 * 4 * D * sizeof(float)));
     const size_t chunked = (size_t)qc * 16 * 4 * D * sizeof(float) + extra;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_fwd_chunked_kernel<D>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)chunked);
-    if (e != hipSuccess) return fail((int)e, "lnlstm_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const int rc = set_dynamic_lds(&lnlstm_fwd_chunked_kernel<D>, chunked, "lnlstm_fwd");
+    if (rc) return rc;
     int grid = n_cus();
     const int rounds = (tiles + 7) / 8;
     if (grid > rounds) grid = rounds;
@@ -406,7 +385,7 @@ static int launch_lnlstm(const tspgnn_lstm_task* tasks, int n, hipStream_t st) {
     long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * ((tasks[k].dx + D) / 16 + 3);  // k-blocks + ~3 blocks' worth of epilogue
         tiles_all += tiles;
     }
@@ -415,22 +394,21 @@ static int launch_lnlstm(const tspgnn_lstm_task* tasks, int n, hipStream_t st) {
     // tile gets a matrix pipe to itself; many tiles: one workgroup per CU, two wavefronts per SIMD.
     int grid = n_cus();
     const int nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks(cost, n, grid, tt.blk_end);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_fwd_kernel<D, 8>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)resident);
-    if (e != hipSuccess) return fail((int)e, "lnlstm_fwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
+    const int rc = set_dynamic_lds(&lnlstm_fwd_kernel<D, 8>, resident, "lnlstm_fwd");
+    if (rc) return rc;
     lnlstm_fwd_kernel<D, 8><<<grid, nw * 64, resident, st>>>(tt);
     return launched("tspgnn_lnlstm_fwd_f32");
 }
 
-static int check_mlp_task(const tspgnn_mlp_task& t, int d) {
-    TSPGNN_REQUIRE(t.rows >= 0, "mlp_fwd: rows=%d", t.rows);
-    TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_fwd: n_layers=%d must be in 1..4", t.n_layers);
+// (the projection's requirement holds for an empty task too, unlike check_mlp_task's)
+static int check_mlp_task_f32(tspgnn_mlp_task& t, int d) {
+    const int rc = check_mlp_shape(t, "mlp_fwd");
+    if (rc) return rc;
     TSPGNN_REQUIRE(d != 128 || t.n_layers <= 2, "mlp_fwd: d=128 holds at most 2 layers in LDS (got %d)", t.n_layers);
     TSPGNN_REQUIRE(t.rows == 0 || (t.X && t.wb && t.Y), "mlp_fwd: null pointer");
     TSPGNN_REQUIRE(!t.proj_w || (t.proj_out && (d == 32 || d == 64)), "mlp_fwd: projection needs proj_out and d in {32,64}");
+    default_stride(t.acts, &t.acts_stride, t.rows, d);
     return TSPGNN_OK;
 }
 
@@ -467,13 +445,9 @@ extern "C" int tspgnn_mlp_fwd_multi_f32(const tspgnn_mlp_task* tasks, int n_task
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "mlp_fwd_multi: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "mlp_fwd: d=%d must be 32, 64 or 128", d);
     tspgnn_mlp_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const int rc = check_mlp_task(tasks[k], d);
-        if (rc) return rc;
-        if (tasks[k].rows > 0) live[n++] = tasks[k];
-    }
-    if (n == 0) return TSPGNN_OK;
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](tspgnn_mlp_task& t) { return check_mlp_task_f32(t, d); });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     switch (d) {
         case 32: return launch_mlp<32, 4>(live, n, st);
@@ -494,13 +468,9 @@ extern "C" int tspgnn_lnlstm_fwd_multi_f32(const tspgnn_lstm_task* tasks, int n_
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_fwd_multi: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "lnlstm_fwd: d=%d must be 32, 64 or 128", d);
     tspgnn_lstm_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const int rc = check_lstm_task(tasks[k], d);
-        if (rc) return rc;
-        if (tasks[k].rows > 0) live[n++] = tasks[k];
-    }
-    if (n == 0) return TSPGNN_OK;
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_task& t) { return check_lstm_task(t, d); });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     switch (d) {
         case 32: return launch_lnlstm<32>(live, n, st);

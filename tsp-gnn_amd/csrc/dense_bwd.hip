@@ -6,6 +6,7 @@
 //   * wgrad       : dW += X^T dY, db += colsum(dY): rows are the contraction, split over wavefronts with
 //                   a deterministic two-stage reduction (per-chunk partials, then one pass over chunks)
 #include "common.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 #include "bf16_tile.h"
 #include "lstm_bwd_tile.h"
@@ -728,41 +729,21 @@ static int launch_linear(const float* X, int kin, const float* Wp, float* Y1, in
     int qc = QT;
     if ((size_t)QT * per_q + 16 > 150 * 1024) qc = (int)((128 * 1024) / per_q);
     const size_t lds_bytes = (size_t)qc * per_q + 16;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_kernel<NT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "linear: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    int rc = set_dynamic_lds(&linear_kernel<NT>, lds_bytes, "linear");
+    if (rc) return rc;
     const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
     int grid = n_cus() * per_cu;
     if constexpr (NT % 4 == 0) {
         if (qc >= QT && tiles <= n_cus() * 4) {   // few tiles: split each tile's columns over four wavefronts
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_split_kernel<NT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) return fail((int)e, "linear: hipFuncSetAttribute: %s", hipGetErrorString(e));
+            if ((rc = set_dynamic_lds(&linear_split_kernel<NT>, lds_bytes, "linear"))) return rc;
             linear_split_kernel<NT><<<(tiles + 1) / 2, 512, lds_bytes, st>>>(X, kin, Wp, Y1, n1, Y2, n2, acc2, rows, tiles);
             return launched("tspgnn_linear_f32");
         }
     }
     const int nw = (qc >= QT && tiles <= grid * 4) ? 4 : 8;
-    const int max_grid = (tiles + nw - 1) / nw;
-    if (grid > max_grid) grid = max_grid;
+    grid = clamp_grid(grid, tiles, nw);
     linear_kernel<NT><<<grid, nw * 64, lds_bytes, st>>>(X, kin, Wp, Y1, n1, Y2, n2, acc2, rows, tiles, qc);
     return launched("tspgnn_linear_f32");
-}
-
-// Workgroups per task, proportional to cost[k] (at least one each); returns the grid.
-static int split_blocks_bwd(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
 }
 
 template <int D>
@@ -793,7 +774,7 @@ static int launch_lnlstm_bwd(const tspgnn_lstm_bwd_task* tasks, int n, hipStream
                 return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd: the fused data gradient needs d=64, dx=0 and K, K^T resident in LDS");
         }
         if (need > lds_k) lds_k = need;
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * (QT + 8);  // k-blocks + ~8 blocks' worth of elementwise backward
         tiles_all += tiles;
     }
@@ -801,23 +782,12 @@ static int launch_lnlstm_bwd(const tspgnn_lstm_bwd_task* tasks, int n, hipStream
     int nw = NWMAX;
     if (!any_chunked && tiles_all <= (long long)n_cus() * 4) nw = 4;
     const size_t lds_bytes = lds_k + extra(nw);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_bwd_kernel<D, NWMAX>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "lnlstm_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    int grid = n_cus();
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_bwd(cost, n, grid, tt.blk_end);
-    lnlstm_bwd_kernel<D, NWMAX><<<grid, nw * 64, lds_bytes, st>>>(tt);
-    int rc = launched("tspgnn_lnlstm_bwd_f32");
+    int rc = set_dynamic_lds(&lnlstm_bwd_kernel<D, NWMAX>, lds_bytes, "lnlstm_bwd");
     if (rc) return rc;
-    for (int k = 0; k < n; ++k) {
-        if (tasks[k].defer_reduce) continue;
-        const int nblk = tt.blk_end[k] - (k ? tt.blk_end[k - 1] : 0);
-        reduce_partials(tasks[k].workspace, nblk, 10 * D, tasks[k].ln_grad, 10 * D, 1.0f, 1, st);
-        if ((rc = launched("tspgnn_lnlstm_bwd_f32(reduce)"))) return rc;
-    }
-    return TSPGNN_OK;
+    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, nw), tt.blk_end);
+    lnlstm_bwd_kernel<D, NWMAX><<<grid, nw * 64, lds_bytes, st>>>(tt);
+    if ((rc = launched("tspgnn_lnlstm_bwd_f32"))) return rc;
+    return reduce_ln_partials(tasks, n, tt.blk_end, D, st, "tspgnn_lnlstm_bwd_f32(reduce)");
 }
 
 template <int D, int MAXL>
@@ -827,9 +797,7 @@ static int launch_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_t s
     long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        if (tt.task[k].acts && tt.task[k].acts_stride == 0) tt.task[k].acts_stride = (long long)tasks[k].rows * D;
-        if (tt.task[k].dpre && tt.task[k].dpre_stride == 0) tt.task[k].dpre_stride = (long long)tasks[k].rows * D;
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * tasks[k].n_layers;
         tiles_all += tiles;
     }
@@ -838,9 +806,7 @@ static int launch_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_t s
     const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
     int grid = n_cus() * per_cu;
     const int nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_bwd(cost, n, grid, tt.blk_end);
+    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
     // (one flag per launch: the tasks of a launch come from one tape)
     if (tasks[0].acts_bf16) mlp_bwd_kernel<D, MAXL, true><<<grid, nw * 64, 0, st>>>(tt);
     else mlp_bwd_kernel<D, MAXL, false><<<grid, nw * 64, 0, st>>>(tt);
@@ -885,20 +851,14 @@ extern "C" int tspgnn_lnlstm_bwd_multi_f32(const tspgnn_lstm_bwd_task* tasks, in
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_bwd_multi: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "lnlstm_bwd: d=%d must be 32, 64 or 128", d);
     tspgnn_lstm_bwd_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_lstm_bwd_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "lnlstm_bwd: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 16 == 0, "lnlstm_bwd: dx=%d must be a non-negative multiple of 16", t.dx);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.h && t.c && t.K && t.ln && t.dz && t.dc_in && t.ln_grad && t.workspace && (t.dx == 0 || t.x),
-                       "lnlstm_bwd: null pointer");
-        TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx && (d == 32 || d == 64)),
-                       "lnlstm_bwd: gather-init mode needs dx == 0, Zx and d in {32,64}");
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_bwd_task& t) {
+        const int rc = check_lstm_bwd_task(t, d, true, "lnlstm_bwd");
+        if (rc || t.rows == 0) return rc;
         TSPGNN_REQUIRE(!t.zbias && !t.KTg, "lnlstm_bwd: a bias-init z / a streamed data gradient are f16x2 features (tspgnn_lnlstm_bwd_multi_h2)");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     switch (d) {
         case 32: return launch_lnlstm_bwd<32>(live, n, st);
@@ -934,23 +894,14 @@ extern "C" int tspgnn_mlp_bwd_multi_f32(const tspgnn_mlp_bwd_task* tasks, int n_
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "mlp_bwd_multi: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "mlp_bwd: d=%d must be 32, 64 or 128", d);
     tspgnn_mlp_bwd_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_mlp_bwd_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "mlp_bwd: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_bwd: n_layers=%d must be in 1..4", t.n_layers);
-        if (d == 128 && t.n_layers > 2)
-            return fail(TSPGNN_EUNSUPPORTED, "mlp_bwd: d=128 holds at most 2 layers in LDS (got %d)", t.n_layers);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.dY && t.wt, "mlp_bwd: null pointer");
-        const unsigned inner = t.relu_mask & ((1u << (t.n_layers - 1)) - 1u);
-        TSPGNN_REQUIRE(!inner || t.acts, "mlp_bwd: relu layers need the saved activations");
-        TSPGNN_REQUIRE(!((t.relu_mask >> (t.n_layers - 1)) & 1u) || t.Yout, "mlp_bwd: relu on the last layer needs Yout");
-        TSPGNN_REQUIRE(n == 0 || (t.acts_bf16 != 0) == (live[0].acts_bf16 != 0), "mlp_bwd: the tasks of a launch share acts_bf16");
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [&](tspgnn_mlp_bwd_task& t) {
+        const int rc = check_mlp_bwd_task(t, d, n ? live : nullptr, "mlp_bwd");
+        if (rc || t.rows == 0) return rc;
         TSPGNN_REQUIRE(!t.pre_X, "mlp_bwd: pre_X is an f16x2 feature (tspgnn_mlp_bwd_multi_h2)");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     switch (d) {
         case 32: return launch_mlp_bwd<32, 4>(live, n, st);

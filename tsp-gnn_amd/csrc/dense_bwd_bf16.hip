@@ -10,6 +10,7 @@
 // Gradients stay fp32 end to end: dz, dc, dh are fp32 arrays as in the fp32 mode.
 #include "bf16_tile.h"
 #include "common.h"
+#include "launch_plan.h"
 #include "lstm_bwd_tile.h"
 #include "mfma_tile.h"
 
@@ -154,21 +155,6 @@ __global__ __launch_bounds__(NW * 64) void lnlstm_bwd_bf16_kernel(const LstmBwdT
     }
 }
 
-static int split_blocks_bwd_b(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
-}
-
 template <int D>
 static int launch_lnlstm_bwd_bf16(const tspgnn_lstm_bwd_task* tasks, int n, hipStream_t st) {
     // D=128 keeps 4D/16 + temporaries > 256 registers live: one wavefront per SIMD (512-register budget)
@@ -180,7 +166,6 @@ static int launch_lnlstm_bwd_bf16(const tspgnn_lstm_bwd_task* tasks, int n, hipS
     long long cost[kMaxTasks];
     long long tiles_all = 0;
     size_t lds_k = 0;
-    int grid_cap = 1 << 30;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
         const int KBT = (tasks[k].dx + D) / 32;
@@ -189,32 +174,20 @@ static int launch_lnlstm_bwd_bf16(const tspgnn_lstm_bwd_task* tasks, int n, hipS
         if (kbc < 1) return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd_bf16: d=%d does not fit LDS", D);
         tt.qc[k] = kbc;
         if ((size_t)kbc * per_kb > lds_k) lds_k = (size_t)kbc * per_kb;
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * (KBT + 12) * (kbc < KBT ? 2 : 1);
         tiles_all += tiles;
-        (void)grid_cap;
     }
     tt.n = n;
     const size_t lds_bytes = lds_k + tail;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_bwd_bf16_kernel<D, NWMAX>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "lnlstm_bwd_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    int grid = n_cus();
-    const long long max_grid = (tiles_all + NWMAX - 1) / NWMAX;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_bwd_b(cost, n, grid, tt.blk_end);
+    int rc = set_dynamic_lds(&lnlstm_bwd_bf16_kernel<D, NWMAX>, lds_bytes, "lnlstm_bwd_bf16");
+    if (rc) return rc;
+    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, NWMAX), tt.blk_end);
     // (the workspace holds one row of LayerNorm-gradient partials per workgroup of a task: n_cus + 8 rows,
     // tspgnn_lnlstm_bwd_workspace_floats)
     lnlstm_bwd_bf16_kernel<D, NWMAX><<<grid, NWMAX * 64, lds_bytes, st>>>(tt);
-    int rc = launched("tspgnn_lnlstm_bwd_multi_bf16");
-    if (rc) return rc;
-    for (int k = 0; k < n; ++k) {
-        if (tasks[k].defer_reduce) continue;
-        const int nblk = tt.blk_end[k] - (k ? tt.blk_end[k - 1] : 0);
-        reduce_partials(tasks[k].workspace, nblk, 10 * D, tasks[k].ln_grad, 10 * D, 1.0f, 1, st);
-        if ((rc = launched("tspgnn_lnlstm_bwd_multi_bf16(reduce)"))) return rc;
-    }
-    return TSPGNN_OK;
+    if ((rc = launched("tspgnn_lnlstm_bwd_multi_bf16"))) return rc;
+    return reduce_ln_partials(tasks, n, tt.blk_end, D, st, "tspgnn_lnlstm_bwd_multi_bf16(reduce)");
 }
 
 // ------------------------------------------------------------------------------------ Y = X W, W bf16 (fragment order)
@@ -291,9 +264,8 @@ static int launch_linear_bf16w(const float* X, int kin, const __bf16* Wp, int nt
                                int n2, int acc2, int rows, hipStream_t st) {
     const int tiles = (rows + 15) / 16;
     const size_t lds_bytes = (size_t)kin * NT * 16 * 2 + 16;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_bf16w_kernel<NT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "linear_bf16w: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const int rc = set_dynamic_lds(&linear_bf16w_kernel<NT>, lds_bytes, "linear_bf16w");
+    if (rc) return rc;
     int grid = n_cus() * (lds_bytes > 80 * 1024 ? 1 : 2);
     const int nw = 8;
     const int max_grid = (tiles + nw - 1) / nw;
@@ -310,19 +282,14 @@ extern "C" int tspgnn_lnlstm_bwd_multi_bf16(const tspgnn_lstm_bwd_task* tasks, i
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_bwd_multi_bf16: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "lnlstm_bwd_bf16: d=%d must be 32, 64 or 128", d);
     tspgnn_lstm_bwd_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_lstm_bwd_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "lnlstm_bwd_bf16: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "lnlstm_bwd_bf16: dx=%d must be a non-negative multiple of 32", t.dx);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.h && t.c && t.K && t.ln && t.dz && t.dc_in && t.ln_grad && t.workspace && (t.dx == 0 || t.x),
-                       "lnlstm_bwd_bf16: null pointer");
-        TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "lnlstm_bwd_bf16: gather-init mode needs dx == 0 and Zx");
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_bwd_task& t) {
+        const int rc = check_lstm_bwd_task(t, d, false, "lnlstm_bwd_bf16");
+        if (rc || t.rows == 0) return rc;
         TSPGNN_REQUIRE(!t.KT && !t.dxh && !t.zbias && !t.KTg, "lnlstm_bwd_bf16: no fused data gradient / bias-init in this mode");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     if (d == 32) return launch_lnlstm_bwd_bf16<32>(live, n, st);
     if (d == 64) return launch_lnlstm_bwd_bf16<64>(live, n, st);

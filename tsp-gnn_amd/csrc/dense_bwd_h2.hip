@@ -16,6 +16,7 @@
 //     of the row are scaled back.
 #include "common.h"
 #include "h2_tile.h"
+#include "launch_plan.h"
 #include "lstm_bwd_tile.h"
 #include "mfma_tile.h"
 
@@ -296,21 +297,6 @@ __global__ __launch_bounds__(NW * 64) void lnlstm_bwd_h2_kernel(const LstmBwdTas
     }
 }
 
-static int split_blocks_bwd_h2(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
-}
-
 template <int D>
 static int launch_lnlstm_bwd_h2(const tspgnn_lstm_bwd_task* tasks, int n, hipStream_t st) {
 #ifndef H2_BWD_NW
@@ -331,7 +317,7 @@ static int launch_lnlstm_bwd_h2(const tspgnn_lstm_bwd_task* tasks, int n, hipStr
             return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd_h2: dx=%d, d=%d%s does not fit LDS", tasks[k].dx, D,
                         tasks[k].KT ? " with K^T" : "");
         if (need > lds_k) lds_k = need;
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * ((tasks[k].dx + D) / 32 + (tasks[k].KT ? 2 : 0) + (tasks[k].KTg ? 5 : 0) + 10);
         tiles_all += tiles;
     }
@@ -339,23 +325,12 @@ static int launch_lnlstm_bwd_h2(const tspgnn_lstm_bwd_task* tasks, int n, hipStr
     int nw = NWMAX;
     if (tiles_all <= (long long)n_cus() * 4) nw = 4;
     const size_t lds_bytes = lds_k + extra(nw);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_bwd_h2_kernel<D, NWMAX>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "lnlstm_bwd_h2: hipFuncSetAttribute: %s", hipGetErrorString(e));
-    int grid = n_cus();
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_bwd_h2(cost, n, grid, tt.blk_end);
-    lnlstm_bwd_h2_kernel<D, NWMAX><<<grid, nw * 64, lds_bytes, st>>>(tt);
-    int rc = launched("tspgnn_lnlstm_bwd_multi_h2");
+    int rc = set_dynamic_lds(&lnlstm_bwd_h2_kernel<D, NWMAX>, lds_bytes, "lnlstm_bwd_h2");
     if (rc) return rc;
-    for (int k = 0; k < n; ++k) {
-        if (tasks[k].defer_reduce) continue;
-        const int nblk = tt.blk_end[k] - (k ? tt.blk_end[k - 1] : 0);
-        reduce_partials(tasks[k].workspace, nblk, 10 * D, tasks[k].ln_grad, 10 * D, 1.0f, 1, st);
-        if ((rc = launched("tspgnn_lnlstm_bwd_multi_h2(reduce)"))) return rc;
-    }
-    return TSPGNN_OK;
+    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, nw), tt.blk_end);
+    lnlstm_bwd_h2_kernel<D, NWMAX><<<grid, nw * 64, lds_bytes, st>>>(tt);
+    if ((rc = launched("tspgnn_lnlstm_bwd_multi_h2"))) return rc;
+    return reduce_ln_partials(tasks, n, tt.blk_end, D, st, "tspgnn_lnlstm_bwd_multi_h2(reduce)");
 }
 
 }  // namespace tspgnn
@@ -366,24 +341,18 @@ extern "C" int tspgnn_lnlstm_bwd_multi_h2(const tspgnn_lstm_bwd_task* tasks, int
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_bwd_multi_h2: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64, "lnlstm_bwd_h2: d=%d must be 32 or 64", d);
     tspgnn_lstm_bwd_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_lstm_bwd_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "lnlstm_bwd_h2: rows=%d", t.rows);
-        TSPGNN_REQUIRE((long long)t.rows * (4 * d > t.dx ? 4 * d : t.dx) < (1ll << 30), "lnlstm_bwd_h2: rows=%d too large for 32-bit offsets",
-                       t.rows);
-        TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "lnlstm_bwd_h2: dx=%d must be a non-negative multiple of 32", t.dx);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.h && t.c && t.K && t.ln && t.dz && t.dc_in && t.ln_grad && t.workspace && (t.dx == 0 || t.x),
-                       "lnlstm_bwd_h2: null pointer");
-        TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "lnlstm_bwd_h2: gather-init mode needs dx == 0 and Zx");
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_bwd_task& t) {
+        int rc = check_rows_32bit(t.rows, t.dx, d, "lnlstm_bwd_h2");
+        if (!rc) rc = check_lstm_bwd_task(t, d, false, "lnlstm_bwd_h2");
+        if (rc || t.rows == 0) return rc;
         TSPGNN_REQUIRE(!t.KT || (t.dxh && t.dx == 0), "lnlstm_bwd_h2: the fused data gradient needs dxh and dx == 0");
         TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "lnlstm_bwd_h2: zbias needs zscale and excludes gather-init mode");
         TSPGNN_REQUIRE(!t.KTg || (d == 64 && t.dx == 64 && t.dxg && t.dxh && !t.KT && !t.uv),
                        "lnlstm_bwd_h2: the streamed data gradient needs d == dx == 64, dxg, dxh and excludes KT / gather-init mode");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     return d == 32 ? launch_lnlstm_bwd_h2<32>(live, n, st) : launch_lnlstm_bwd_h2<64>(live, n, st);
 }

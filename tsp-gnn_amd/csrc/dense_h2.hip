@@ -27,6 +27,7 @@
 // fragment of one layer is the next layer's B operand in the same lane).  A k-block covers 32 features: lane (rl, g)
 // supplies the 8 features 16*(2kb + (j>>2)) + 4g + (j&3), j = 0..7; the packed weights use the same permutation.
 #include "common.h"
+#include "launch_plan.h"
 #include "h2_tile.h"
 #include "mfma_tile.h"
 
@@ -109,15 +110,13 @@ __global__ __launch_bounds__(256) void pack_mlp_h2_kernel(const float* __restric
     }
 }
 
-constexpr int kMaxTasksH2 = 4;
-
 // ---------------------------------------------------------------------------------- MLP (f16x2)
 // Task fields as tspgnn_mlp_task; wb points at n_layers blocks of { fp16 packed[2*D*D] , float bias[D] (= 2^s b) };
 // proj_w at an fp16 packed [2 * D * 4D] matrix; proj_out = 2^s * (Y P) in the blocked layout of h2_tile.h: it feeds the
 // scaled z of an f16x2 cell.
 struct MlpTaskTableH2 {
-    tspgnn_mlp_task task[kMaxTasksH2];
-    int blk_end[kMaxTasksH2];
+    tspgnn_mlp_task task[kMaxTasks];
+    int blk_end[kMaxTasks];
     int n;
     // tspgnn_mlp_head_fwd_h2 (one task): y[row] = <last layer's output row, head_w> + head_b[0], taken while the row is
     // still in registers; the task's Y may then be NULL (nothing is written for it)
@@ -247,12 +246,12 @@ __global__ __launch_bounds__(1024) void mlp_fwd_h2_kernel(const MlpTaskTableH2 t
 //     they do not fit together).  The second staging is issued as soon as the last wavefront has left the K GEMM
 //     and lands behind the LayerNorm / gate arithmetic.
 struct CellTaskTableH2 {
-    tspgnn_cell_mlp_task task[kMaxTasksH2];
-    int blk_end[kMaxTasksH2];
-    int kbc[kMaxTasksH2];       // k-blocks (32 rows of K) per LDS chunk
-    int lockstep[kMaxTasksH2];  // 0: K and the MLP resident together, tiles by ticket; 1: lock-step rounds
-    int together[kMaxTasksH2];  // lock-step: MLP layers and projection matrix staged together
-    int lock_tiles[kMaxTasksH2];  // lock-step: tiles (= working wavefronts) per workgroup and round, <= wavefronts per workgroup
+    tspgnn_cell_mlp_task task[kMaxTasks];
+    int blk_end[kMaxTasks];
+    int kbc[kMaxTasks];       // k-blocks (32 rows of K) per LDS chunk
+    int lockstep[kMaxTasks];  // 0: K and the MLP resident together, tiles by ticket; 1: lock-step rounds
+    int together[kMaxTasks];  // lock-step: MLP layers and projection matrix staged together
+    int lock_tiles[kMaxTasks];  // lock-step: tiles (= working wavefronts) per workgroup and round, <= wavefronts per workgroup
     int n;
 };
 
@@ -551,21 +550,6 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTa
     h2_range_report(tk.range_flag, wit, vmin);
 }
 
-static int split_blocks_h2(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
-}
-
 template <int D>
 static int launch_mlp_h2(const tspgnn_mlp_task* tasks, int n, hipStream_t st, const float* head_w = nullptr,
                          const float* head_b = nullptr, float* head_y = nullptr) {
@@ -573,21 +557,18 @@ static int launch_mlp_h2(const tspgnn_mlp_task* tasks, int n, hipStream_t st, co
     tt.head_w = head_w;
     tt.head_b = head_b;
     tt.head_y = head_y;
-    long long cost[kMaxTasksH2];
+    long long cost[kMaxTasks];
     long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        if (tt.task[k].acts && tt.task[k].acts_stride == 0) tt.task[k].acts_stride = (long long)tasks[k].rows * D;
-        cost[k] = ((long long)tasks[k].rows + 15) / 16 * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += ((long long)tasks[k].rows + 15) / 16;
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
     }
     tt.n = n;
     int grid = n_cus();
     int nw = 16;
     if (tiles_all <= (long long)grid * 16) nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_h2(cost, n, grid, tt.blk_end);
+    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
     mlp_fwd_h2_kernel<D><<<grid, nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_fwd_multi_h2");
 }
@@ -611,7 +592,7 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
     const size_t budget = 160 * 1024 - head;
     const size_t layer_all = 2 * D * D * 2 + D * 4, proj_bytes = (size_t)2 * D * 4 * D * 2;
     CellTaskTableH2 tt;
-    long long cost[kMaxTasksH2];
+    long long cost[kMaxTasks];
     long long tiles_all = 0;
     size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
@@ -646,7 +627,7 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
             if (second > need) need = second;
         }
         if (need > lds_w) lds_w = need;
-        const long long tiles = ((long long)c.rows + 15) / 16;
+        const long long tiles = tiles16(c.rows);
         cost[k] = tiles * (KBT * 4 + 2 * L + (tasks[k].proj_w ? 8 : 0) + 8);
         tiles_all += tiles;
     }
@@ -655,8 +636,7 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
     int grid = n_cus();
     const int nw_max = 12;
     const int nw = tiles_all <= (long long)grid * 4 ? 4 : (tiles_all <= (long long)grid * 8 ? 8 : nw_max);
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
+    grid = clamp_grid(grid, tiles_all, nw);
     {
         // A lock-step task is a latency chain (two LDS stagings per round) that the resident tasks of the launch hide.
         // It gets the workgroups of a whole number of rounds -- ONE round while that stays within about twice its share
@@ -665,12 +645,11 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
         // workgroups instead of starving the edge task of 99); the resident tasks share the rest by cost.
         long long total_cost = 0;
         for (int k = 0; k < n; ++k) total_cost += cost[k] > 0 ? cost[k] : 1;
-        int fixed[kMaxTasksH2], fixed_sum = 0, n_res = 0;
-        long long res_cost[kMaxTasksH2];
+        int fixed[kMaxTasks];
         for (int k = 0; k < n; ++k) {
             fixed[k] = 0;
             if (tt.lockstep[k]) {
-                const long long tiles = ((long long)tasks[k].cell.rows + 15) / 16;
+                const long long tiles = tiles16(tasks[k].cell.rows);
                 const int lw = nw < h2_lock_tiles() ? nw : h2_lock_tiles();
                 tt.lock_tiles[k] = lw;
                 const long long per_round = (tiles + lw - 1) / lw;
@@ -678,27 +657,9 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
                 if (share < 1) share = 1;
                 const long long n_rounds = (per_round + share - 1) / share;
                 fixed[k] = (int)((per_round + n_rounds - 1) / n_rounds);
-            } else {
-                ++n_res;
             }
-            fixed_sum += fixed[k];
         }
-        if (n_res == 0 || fixed_sum == 0 || fixed_sum > grid / 2) {
-            grid = split_blocks_h2(cost, n, grid, tt.blk_end);
-        } else {
-            int res_end[kMaxTasksH2], j = 0;
-            for (int k = 0; k < n; ++k)
-                if (!fixed[k]) res_cost[j++] = cost[k];
-            split_blocks_h2(res_cost, n_res, grid - fixed_sum, res_end);
-            int used = 0;
-            j = 0;
-            for (int k = 0; k < n; ++k) {
-                used += fixed[k] ? fixed[k] : res_end[j] - (j ? res_end[j - 1] : 0);
-                if (!fixed[k]) ++j;
-                tt.blk_end[k] = used;
-            }
-            grid = used;
-        }
+        grid = split_blocks_fixed(cost, fixed, n, grid, tt.blk_end);
     }
     bool centered = true, loop_buffers = false;
     long long out_bytes = 0;   // h', c' of every task and its messages: what the launch stores (and the next ones re-read)
@@ -719,9 +680,8 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
     void (*fn)(const CellTaskTableH2) =
         centered ? (wt ? &lnlstm_mlp_fwd_h2_kernel<D, true, true> : &lnlstm_mlp_fwd_h2_kernel<D, true, false>)
                  : (wt ? &lnlstm_mlp_fwd_h2_kernel<D, false, true> : &lnlstm_mlp_fwd_h2_kernel<D, false, false>);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "%s: hipFuncSetAttribute(%d B): %s", what, (int)lds_bytes, hipGetErrorString(e));
+    const int rc = set_dynamic_lds(fn, lds_bytes, what, true);
+    if (rc) return rc;
     fn<<<grid, nw * 64, lds_bytes, st>>>(tt);
     return launched(what);
 }
@@ -758,20 +718,12 @@ extern "C" int tspgnn_pack_mlp_h2(const float* wb, void* out, int d, int n_layer
 }
 
 extern "C" int tspgnn_mlp_fwd_multi_h2(const tspgnn_mlp_task* tasks, int n_tasks, int d, void* stream) {
-    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasksH2, "mlp_fwd_multi_h2: 1..%d tasks", kMaxTasksH2);
+    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "mlp_fwd_multi_h2: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64, "mlp_fwd_h2: d=%d must be 32 or 64", d);
-    tspgnn_mlp_task live[kMaxTasksH2];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_mlp_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "mlp_fwd_h2: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_fwd_h2: n_layers=%d must be in 1..4", t.n_layers);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.X && t.wb && t.Y, "mlp_fwd_h2: null pointer");
-        TSPGNN_REQUIRE(!t.proj_w || t.proj_out, "mlp_fwd_h2: projection needs proj_out");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+    tspgnn_mlp_task live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](tspgnn_mlp_task& t) { return check_mlp_task(t, d, "mlp_fwd_h2"); });
+    if (rc || n == 0) return rc;
     return d == 32 ? launch_mlp_h2<32>(live, n, as_stream(stream)) : launch_mlp_h2<64>(live, n, as_stream(stream));
 }
 
@@ -779,45 +731,32 @@ extern "C" int tspgnn_mlp_head_fwd_h2(const tspgnn_mlp_task* task, const float* 
                                       int d, void* stream) {
     TSPGNN_REQUIRE(task, "mlp_head_fwd_h2: null task");
     TSPGNN_REQUIRE(d == 32 || d == 64, "mlp_head_fwd_h2: d=%d must be 32 or 64", d);
-    const tspgnn_mlp_task& t = *task;
-    TSPGNN_REQUIRE(t.rows >= 0, "mlp_head_fwd_h2: rows=%d", t.rows);
-    TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_head_fwd_h2: n_layers=%d must be in 1..4", t.n_layers);
+    tspgnn_mlp_task t = *task;
+    const int rc = check_mlp_shape(t, "mlp_head_fwd_h2");
+    if (rc) return rc;
     TSPGNN_REQUIRE(!t.proj_w, "mlp_head_fwd_h2: a head task has no projection");
     if (t.rows == 0) return TSPGNN_OK;
-    TSPGNN_REQUIRE(t.X && t.wb && head_w && head_b && y, "mlp_head_fwd_h2: null pointer");
-    return d == 32 ? launch_mlp_h2<32>(task, 1, as_stream(stream), head_w, head_b, y)
-                   : launch_mlp_h2<64>(task, 1, as_stream(stream), head_w, head_b, y);
+    TSPGNN_REQUIRE(t.X && t.wb && head_w && head_b && y, "mlp_head_fwd_h2: null pointer");   // (Y may be NULL: MlpTaskTableH2)
+    default_stride(t.acts, &t.acts_stride, t.rows, d);
+    return d == 32 ? launch_mlp_h2<32>(&t, 1, as_stream(stream), head_w, head_b, y)
+                   : launch_mlp_h2<64>(&t, 1, as_stream(stream), head_w, head_b, y);
 }
 
 static int cell_mlp_h2(const tspgnn_cell_mlp_task* tasks, int n_tasks, int d, void* stream, const char* what) {
-    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasksH2, "%s: 1..%d tasks", what, kMaxTasksH2);
+    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64, "%s: d=%d must be 32 or 64", what, d);
-    tspgnn_cell_mlp_task live[kMaxTasksH2];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_lstm_task& t = tasks[k].cell;
-        TSPGNN_REQUIRE(t.rows >= 0, "%s: rows=%d", what, t.rows);
-        TSPGNN_REQUIRE((long long)t.rows * (4 * d > t.dx ? 4 * d : t.dx) < (1ll << 30), "%s: rows=%d too large for 32-bit offsets",
-                       what, t.rows);
-        TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "%s: dx=%d must be a non-negative multiple of 32", what, t.dx);
-        TSPGNN_REQUIRE(tasks[k].mlp_layers >= 0 && tasks[k].mlp_layers <= 4, "%s: mlp_layers=%d must be in 0..4", what,
-                       tasks[k].mlp_layers);
-        if (t.rows == 0) continue;
-        // (c == NULL: the zero cell state of a run's first step, nothing is read)
-        TSPGNN_REQUIRE(t.h && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x), "%s: null pointer", what);
-        // (h_out == h and c_out == c are fine: a tile reads its own rows of h and c, and only those, before it writes
-        // them -- the in-place update keeps the states' footprint at one copy, inside the Infinity Cache)
-        TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "%s: gather-init mode needs dx == 0 and Zx", what);
-        TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "%s: zbias needs zscale and excludes gather-init mode", what);
-        TSPGNN_REQUIRE(tasks[k].mlp_layers == 0 || tasks[k].mlp_wb, "%s: mlp_layers > 0 needs mlp_wb", what);
-        TSPGNN_REQUIRE(!tasks[k].proj_w || (tasks[k].proj_out && tasks[k].mlp_layers > 0),
-                       "%s: a projection needs proj_out and at least one MLP layer", what);
-        TSPGNN_REQUIRE(tasks[k].mlp_acts_stride >= 0, "%s: mlp_acts_stride=%lld", what, tasks[k].mlp_acts_stride);
-        live[n] = tasks[k];
-        if (live[n].mlp_acts && live[n].mlp_acts_stride == 0) live[n].mlp_acts_stride = (long long)t.rows * d;
-        ++n;
-    }
-    if (n == 0) return TSPGNN_OK;
+    tspgnn_cell_mlp_task live[kMaxTasks];
+    int n;
+    // (h_out == h and c_out == c are fine: a tile reads its own rows of h and c, and only those, before it writes them --
+    // the in-place update keeps the states' footprint at one copy, inside the Infinity Cache)
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d, what](tspgnn_cell_mlp_task& t) {
+        const int rc = check_cell_mlp_task(t, d, what);
+        if (rc || t.cell.rows == 0) return rc;
+        TSPGNN_REQUIRE(t.mlp_acts_stride >= 0, "%s: mlp_acts_stride=%lld", what, t.mlp_acts_stride);
+        default_stride(t.mlp_acts, &t.mlp_acts_stride, t.cell.rows, d);
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     return d == 32 ? launch_cell_h2<32>(live, n, as_stream(stream), what) : launch_cell_h2<64>(live, n, as_stream(stream), what);
 }
 
@@ -826,8 +765,8 @@ extern "C" int tspgnn_lnlstm_mlp_fwd_multi_h2(const tspgnn_cell_mlp_task* tasks,
 }
 
 extern "C" int tspgnn_lnlstm_fwd_multi_h2(const tspgnn_lstm_task* tasks, int n_tasks, int d, void* stream) {
-    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasksH2, "lnlstm_fwd_multi_h2: 1..%d tasks", kMaxTasksH2);
-    tspgnn_cell_mlp_task wrapped[kMaxTasksH2];
+    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_fwd_multi_h2: 1..%d tasks", kMaxTasks);
+    tspgnn_cell_mlp_task wrapped[kMaxTasks];
     for (int k = 0; k < n_tasks; ++k) {
         wrapped[k] = tspgnn_cell_mlp_task{};
         wrapped[k].cell = tasks[k];

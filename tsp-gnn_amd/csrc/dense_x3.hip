@@ -15,6 +15,7 @@
 // MFMA covers 32 features: lane (rl, g) supplies the 8 features  16*(2kb + (j>>2)) + 4g + (j&3), j = 0..7,
 // i.e. its registers of tiles 2kb and 2kb+1; the packed weights use the same permutation.
 #include "common.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 
 namespace tspgnn {
@@ -145,8 +146,6 @@ __device__ __forceinline__ void copy_bytes_to_lds(void* dst, const void* __restr
     }
 }
 __device__ __forceinline__ void stage_wait() { __builtin_amdgcn_s_waitcnt(0); }
-
-constexpr int kMaxTasks = 4;
 
 // ---------------------------------------------------------------------------------- MLP (x3)
 // Task fields as tspgnn_mlp_task; wb points at n_layers blocks of { bf16 packed[3*D*D] , float bias[D] };
@@ -504,21 +503,6 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_x3_kernel(const CellTaskTa
     }
 }
 
-static int split_blocks_x3(const long long* cost, int n, int grid, int* blk_end) {
-    long long total = 0;
-    for (int k = 0; k < n; ++k) total += cost[k] > 0 ? cost[k] : 1;
-    if (grid < n) grid = n;
-    int used = 0;
-    for (int k = 0; k < n; ++k) {
-        const long long ck = cost[k] > 0 ? cost[k] : 1;
-        int bk = (int)((ck * grid + total / 2) / total);
-        if (bk < 1) bk = 1;
-        used += bk;
-        blk_end[k] = used;
-    }
-    return used;
-}
-
 template <int D>
 static int launch_mlp_x3(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
     MlpTaskTableX3 tt;
@@ -526,17 +510,14 @@ static int launch_mlp_x3(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
     long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        if (tt.task[k].acts && tt.task[k].acts_stride == 0) tt.task[k].acts_stride = (long long)tasks[k].rows * D;
-        cost[k] = ((long long)tasks[k].rows + 15) / 16 * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += ((long long)tasks[k].rows + 15) / 16;
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
     }
     tt.n = n;
     int grid = n_cus();
     int nw = 16;
     if (tiles_all <= (long long)grid * 16) nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
-    grid = split_blocks_x3(cost, n, grid, tt.blk_end);
+    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
     mlp_fwd_x3_kernel<D><<<grid, nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_fwd_multi_x3");
 }
@@ -577,7 +558,7 @@ static int launch_cell_x3(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
             if (tasks[k].proj_w && (size_t)3 * D * 4 * D * 2 > need) need = (size_t)3 * D * 4 * D * 2;
         }
         if (need > lds_w) lds_w = need;
-        const long long tiles = ((long long)c.rows + 15) / 16;
+        const long long tiles = tiles16(c.rows);
         cost[k] = tiles * (KBT * 4 + 2 * L + (tasks[k].proj_w ? 8 : 0) + 6);
         tiles_all += tiles;
     }
@@ -585,41 +566,20 @@ static int launch_cell_x3(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
     const size_t lds_bytes = lds_w + head;
     int grid = n_cus();
     const int nw = tiles_all <= (long long)grid * 4 ? 4 : (tiles_all <= (long long)grid * 8 ? 8 : 12);
-    const long long max_grid = (tiles_all + nw - 1) / nw;
-    if (grid > max_grid) grid = (int)max_grid;
+    grid = clamp_grid(grid, tiles_all, nw);
     {
         // A lock-step task is a latency chain (several LDS re-stagings per round) that the resident tasks of the
         // launch hide: it gets exactly the workgroups of ONE round (more would idle, fewer would double the chain),
         // capped at half the grid; the resident tasks share the rest in proportion to their cost.
-        int fixed[kMaxTasks], fixed_sum = 0, n_res = 0;
-        long long res_cost[kMaxTasks];
+        int fixed[kMaxTasks];
         for (int k = 0; k < n; ++k) {
             const bool lock = tt.kbc[k] < (tasks[k].cell.dx + D) / 32;
-            const long long tiles = ((long long)tasks[k].cell.rows + 15) / 16;
-            fixed[k] = lock ? (int)((tiles + nw - 1) / nw) : 0;
-            fixed_sum += fixed[k];
-            if (!lock) ++n_res;
+            fixed[k] = lock ? (int)((tiles16(tasks[k].cell.rows) + nw - 1) / nw) : 0;
         }
-        if (n_res == 0 || fixed_sum == 0 || fixed_sum > grid / 2) {
-            grid = split_blocks_x3(cost, n, grid, tt.blk_end);
-        } else {
-            int res_end[kMaxTasks], j = 0;
-            for (int k = 0; k < n; ++k)
-                if (!fixed[k]) res_cost[j++] = cost[k];
-            split_blocks_x3(res_cost, n_res, grid - fixed_sum, res_end);
-            int used = 0;
-            j = 0;
-            for (int k = 0; k < n; ++k) {
-                used += fixed[k] ? fixed[k] : res_end[j] - (j ? res_end[j - 1] : 0);
-                if (!fixed[k]) ++j;
-                tt.blk_end[k] = used;
-            }
-            grid = used;
-        }
+        grid = split_blocks_fixed(cost, fixed, n, grid, tt.blk_end);
     }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lnlstm_mlp_fwd_x3_kernel<D>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "%s: hipFuncSetAttribute(%d B): %s", what, (int)lds_bytes, hipGetErrorString(e));
+    const int rc = set_dynamic_lds(&lnlstm_mlp_fwd_x3_kernel<D>, lds_bytes, what, true);
+    if (rc) return rc;
     lnlstm_mlp_fwd_x3_kernel<D><<<grid, nw * 64, lds_bytes, st>>>(tt);
     return launched(what);
 }
@@ -643,17 +603,9 @@ extern "C" int tspgnn_mlp_fwd_multi_x3(const tspgnn_mlp_task* tasks, int n_tasks
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "mlp_fwd_multi_x3: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64, "mlp_fwd_x3: d=%d must be 32 or 64", d);
     tspgnn_mlp_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_mlp_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0, "mlp_fwd_x3: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_fwd_x3: n_layers=%d must be in 1..4", t.n_layers);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.X && t.wb && t.Y, "mlp_fwd_x3: null pointer");
-        TSPGNN_REQUIRE(!t.proj_w || t.proj_out, "mlp_fwd_x3: projection needs proj_out");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d](tspgnn_mlp_task& t) { return check_mlp_task(t, d, "mlp_fwd_x3"); });
+    if (rc || n == 0) return rc;
     return d == 32 ? launch_mlp_x3<32>(live, n, as_stream(stream)) : launch_mlp_x3<64>(live, n, as_stream(stream));
 }
 
@@ -661,28 +613,18 @@ static int cell_mlp_x3(const tspgnn_cell_mlp_task* tasks, int n_tasks, int d, vo
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64, "%s: d=%d must be 32 or 64", what, d);
     tspgnn_cell_mlp_task live[kMaxTasks];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_lstm_task& t = tasks[k].cell;
-        TSPGNN_REQUIRE(t.rows >= 0, "%s: rows=%d", what, t.rows);
-        TSPGNN_REQUIRE((long long)t.rows * (4 * d > t.dx ? 4 * d : t.dx) < (1ll << 30), "%s: rows=%d too large for 32-bit offsets",
-                       what, t.rows);
-        TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "%s: dx=%d must be a non-negative multiple of 32", what, t.dx);
-        TSPGNN_REQUIRE(tasks[k].mlp_layers >= 0 && tasks[k].mlp_layers <= 4, "%s: mlp_layers=%d must be in 0..4", what,
-                       tasks[k].mlp_layers);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE(t.h && t.c && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x), "%s: null pointer", what);
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d, what](const tspgnn_cell_mlp_task& ct) {
+        const tspgnn_lstm_task& t = ct.cell;
+        const int rc = check_cell_mlp_task(ct, d, what);
+        if (rc || t.rows == 0) return rc;
+        TSPGNN_REQUIRE(t.c, "%s: null pointer", what);
         TSPGNN_REQUIRE(t.h_out != t.h && t.c_out != t.c, "%s: outputs may not alias inputs", what);
-        TSPGNN_REQUIRE(!tasks[k].state_in_blocked && !tasks[k].state_out_blocked, "%s: blocked states are an f16x2 feature", what);
-        TSPGNN_REQUIRE(!tasks[k].mlp_acts, "%s: saving the MLP's hidden activations is an f16x2 feature", what);
-        TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "%s: gather-init mode needs dx == 0 and Zx", what);
-        TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "%s: zbias needs zscale and excludes gather-init mode", what);
-        TSPGNN_REQUIRE(tasks[k].mlp_layers == 0 || tasks[k].mlp_wb, "%s: mlp_layers > 0 needs mlp_wb", what);
-        TSPGNN_REQUIRE(!tasks[k].proj_w || (tasks[k].proj_out && tasks[k].mlp_layers > 0),
-                       "%s: a projection needs proj_out and at least one MLP layer", what);
-        live[n++] = tasks[k];
-    }
-    if (n == 0) return TSPGNN_OK;
+        TSPGNN_REQUIRE(!ct.state_in_blocked && !ct.state_out_blocked, "%s: blocked states are an f16x2 feature", what);
+        TSPGNN_REQUIRE(!ct.mlp_acts, "%s: saving the MLP's hidden activations is an f16x2 feature", what);
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     return d == 32 ? launch_cell_x3<32>(live, n, as_stream(stream), what) : launch_cell_x3<64>(live, n, as_stream(stream), what);
 }
 

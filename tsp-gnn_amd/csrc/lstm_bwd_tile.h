@@ -195,7 +195,6 @@ __device__ __forceinline__ void lstm_tile_load(const float* c_row, const float* 
 }
 
 // LDS: [K chunk or all of K] [K^T (optional)] [ln 10*D] [NW slabs of 10*D].
-constexpr int kMaxTasks = 4;
 
 struct LstmBwdTaskTable {
     tspgnn_lstm_bwd_task task[kMaxTasks];

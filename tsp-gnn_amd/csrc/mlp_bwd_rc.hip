@@ -15,6 +15,7 @@
 #include "common.h"
 #include "bf16_tile.h"
 #include "h2_tile.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 
 namespace tspgnn {
@@ -63,10 +64,9 @@ __device__ __forceinline__ void dense_layer_h2_np(f32x4 (&out)[NP][4], const f32
 // per layer and tile: tspgnn_mlp_bwd_multi_h2.  Same task structure (several MLPs per launch, gather-init mode, bf16
 // tapes); wt = n_layers blocks tspgnn_pack_weights_h2(W_l^T).  d = 64 with up to four layers (64 KB of LDS), d = 128 with
 // up to two (128 KB) -- the chunking of tspgnn_mlp_bwd_multi_f32.
-constexpr int kMaxTasksBwdH2 = 4;
 struct MlpBwdTaskTableH2 {
-    tspgnn_mlp_bwd_task task[kMaxTasksBwdH2];
-    int blk_end[kMaxTasksBwdH2];
+    tspgnn_mlp_bwd_task task[kMaxTasks];
+    int blk_end[kMaxTasks];
     int n;
 };
 
@@ -221,12 +221,10 @@ __global__ __launch_bounds__(1024) void mlp_bwd_h2_kernel(const MlpBwdTaskTableH
 template <int D, int MAXL>
 static int launch_mlp_bwd_h2(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_t st) {
     MlpBwdTaskTableH2 tt;
-    long long cost[kMaxTasksBwdH2], total = 0, tiles_all = 0;
+    long long cost[kMaxTasks], total = 0, tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        if (tt.task[k].acts && tt.task[k].acts_stride == 0) tt.task[k].acts_stride = (long long)tasks[k].rows * D;
-        if (tt.task[k].dpre && tt.task[k].dpre_stride == 0) tt.task[k].dpre_stride = (long long)tasks[k].rows * D;
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         cost[k] = tiles * (tasks[k].n_layers + (tasks[k].pre_X ? (tasks[k].pre_k + 63) / 64 : 0));
         total += cost[k];
         tiles_all += tiles;
@@ -239,10 +237,10 @@ static int launch_mlp_bwd_h2(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_
     if (grid < n) grid = n;
     // workgroups in proportion to tiles x layers, at least one each -- and never more than one wavefront per tile can use (a
     // small task with a long chain, e.g. the vertex side with its projection head: the surplus goes to the largest task)
-    int bks[kMaxTasksBwdH2], used = 0, big = 0;
+    int bks[kMaxTasks], used = 0, big = 0;
     for (int k = 0; k < n; ++k) {
         int bk = (int)((cost[k] * grid + total / 2) / (total > 0 ? total : 1));
-        const long long tiles = ((long long)tasks[k].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[k].rows);
         const int useful = (int)((tiles + threads / 64 - 1) / (threads / 64));
         if (bk > useful) bk = useful;
         if (bk < 1) bk = 1;
@@ -251,7 +249,7 @@ static int launch_mlp_bwd_h2(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_
         if (cost[k] > cost[big]) big = k;
     }
     if (used < grid) {
-        const long long tiles = ((long long)tasks[big].rows + 15) / 16;
+        const long long tiles = tiles16(tasks[big].rows);
         const int useful = (int)((tiles + threads / 64 - 1) / (threads / 64));
         int add = grid - used;
         if (bks[big] + add > useful) add = useful > bks[big] ? useful - bks[big] : 0;
@@ -269,8 +267,8 @@ static int launch_mlp_bwd_h2(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_
     const bool abf = tasks[0].acts_bf16 != 0;
     const void* fn = abf ? reinterpret_cast<const void*>(&mlp_bwd_h2_kernel<D, MAXL, true>)
                          : reinterpret_cast<const void*>(&mlp_bwd_h2_kernel<D, MAXL, false>);
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "mlp_bwd_h2: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const int rc = set_dynamic_lds(fn, lds_bytes, "mlp_bwd_h2");
+    if (rc) return rc;
     if (abf) mlp_bwd_h2_kernel<D, MAXL, true><<<used, threads, lds_bytes, st>>>(tt);
     else mlp_bwd_h2_kernel<D, MAXL, false><<<used, threads, lds_bytes, st>>>(tt);
     return launched("tspgnn_mlp_bwd_multi_h2");
@@ -488,9 +486,8 @@ static int launch_mlp_bwd_rcw(const tspgnn_mlp_bwd_rc_task& tk, hipStream_t st) 
     constexpr int D = 64;
     const size_t lds_bytes = (size_t)(L - 1) * (2 * D * D * 2 + D * 4) + (size_t)L * 2 * D * D * 2 + (size_t)kRcwWaves * kRcwUnit;
     if (lds_bytes > 160 * 1024) return fail(TSPGNN_EUNSUPPORTED, "mlp_bwd_rc_h2: %d layers do not fit LDS", L);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_bwd_rcw_kernel<L>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return fail((int)e, "mlp_bwd_rc_h2: hipFuncSetAttribute: %s", hipGetErrorString(e));
+    const int rc = set_dynamic_lds(&mlp_bwd_rcw_kernel<L>, lds_bytes, "mlp_bwd_rc_h2");
+    if (rc) return rc;
     const long long tiles = ((long long)tk.rows + 15) / 16;
     int grid = n_cus();
     const long long max_grid = (tiles + kRcwWaves - 1) / kRcwWaves;
@@ -538,26 +535,18 @@ extern "C" int tspgnn_mlp_bwd_rc_finish_f32(const float* partial, float* grad_wb
 }
 
 extern "C" int tspgnn_mlp_bwd_multi_h2(const tspgnn_mlp_bwd_task* tasks, int n_tasks, int d, void* stream) {
-    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasksBwdH2, "mlp_bwd_multi_h2: 1..%d tasks", kMaxTasksBwdH2);
+    TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "mlp_bwd_multi_h2: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 64 || d == 128, "mlp_bwd_h2: d=%d must be 64 or 128", d);
-    tspgnn_mlp_bwd_task live[kMaxTasksBwdH2];
-    int n = 0;
-    for (int k = 0; k < n_tasks; ++k) {
-        const tspgnn_mlp_bwd_task& t = tasks[k];
-        TSPGNN_REQUIRE(t.rows >= 0 && (long long)t.rows * d < (1ll << 31), "mlp_bwd_h2: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.n_layers >= 1 && t.n_layers <= 4, "mlp_bwd_h2: n_layers=%d must be in 1..4", t.n_layers);
-        if (d == 128 && t.n_layers > 2)
-            return fail(TSPGNN_EUNSUPPORTED, "mlp_bwd_h2: d=128 holds at most 2 layers in LDS (got %d)", t.n_layers);
-        if (t.rows == 0) continue;
-        TSPGNN_REQUIRE((t.dY || t.pre_X) && t.wt, "mlp_bwd_h2: null pointer");
+    tspgnn_mlp_bwd_task live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [&](tspgnn_mlp_bwd_task& t) {
+        TSPGNN_REQUIRE((long long)t.rows * d < (1ll << 31), "mlp_bwd_h2: rows=%d", t.rows);
+        const int rc = check_mlp_bwd_task(t, d, n ? live : nullptr, "mlp_bwd_h2");
+        if (rc || t.rows == 0) return rc;
         TSPGNN_REQUIRE(!t.pre_X || (d == 64 && t.pre_wt && !t.uv && t.pre_k >= 32 && t.pre_k <= 256 && t.pre_k % 32 == 0),
                        "mlp_bwd_h2: pre_X needs d == 64, pre_wt, no uv and pre_k in 32..256 (a multiple of 32), got %d", t.pre_k);
-        const unsigned inner = t.relu_mask & ((1u << (t.n_layers - 1)) - 1u);
-        TSPGNN_REQUIRE(!inner || t.acts, "mlp_bwd_h2: relu layers need the saved activations");
-        TSPGNN_REQUIRE(!((t.relu_mask >> (t.n_layers - 1)) & 1u) || t.Yout, "mlp_bwd_h2: relu on the last layer needs Yout");
-        TSPGNN_REQUIRE(n == 0 || (t.acts_bf16 != 0) == (live[0].acts_bf16 != 0), "mlp_bwd_h2: the tasks of a launch share acts_bf16");
-        live[n++] = t;
-    }
-    if (n == 0) return TSPGNN_OK;
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
     return d == 64 ? launch_mlp_bwd_h2<64, 4>(live, n, as_stream(stream)) : launch_mlp_bwd_h2<128, 2>(live, n, as_stream(stream));
 }

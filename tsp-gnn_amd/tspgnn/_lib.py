@@ -293,9 +293,14 @@ def task_array(tasks):
     return (type(tasks[0]) * len(tasks))(*tasks)
 
 
+MAX_TASKS = 4   # tasks per tspgnn_*_multi_* launch: kMaxTasks (csrc/common.h)
+
+
 def launches(by_width):
-    """{width: [tasks]} -> [(task_array, width)] in dict order, then list order.  The ABI takes at most 4 tasks per launch."""
-    return [(task_array(tasks[k:k + 4]), d) for d, tasks in by_width.items() for k in range(0, len(tasks), 4)]
+    """{width: [tasks]} -> [(task_array, width)] in dict order, then list order.  The ABI takes at most MAX_TASKS tasks per
+    launch."""
+    return [(task_array(tasks[k:k + MAX_TASKS]), d) for d, tasks in by_width.items()
+            for k in range(0, len(tasks), MAX_TASKS)]
 
 
 def call_multi(name, tasks, d):
