@@ -95,6 +95,11 @@ def _center_gates(K, d):
     return (k64 - k64.mean(dim=2, keepdim=True)).reshape(K.shape[0], 4 * d).to(torch.float32).contiguous()
 
 
+def _check_cell_input(shape, rows, dx):
+    if shape[0] != rows or shape[1] != dx:
+        raise ValueError("cell input must be [%d,%d], got %s" % (rows, dx, tuple(shape)))
+
+
 def _dev_i32(a, device):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(device)
 
@@ -375,8 +380,7 @@ class LayerNormBasicLSTMCell(object):
         lets the caller own the output buffers (training keeps every step's state)."""
         c, h = state.c, state.h
         rows = h.shape[0]
-        if inputs.shape[0] != rows or inputs.shape[1] != self.dx:
-            raise ValueError("cell input must be [%d,%d], got %s" % (rows, self.dx, tuple(inputs.shape)))
+        _check_cell_input(inputs.shape, rows, self.dx)
         x = inputs if inputs.is_contiguous() else inputs.contiguous()
         h_out, c_out = out if out is not None else (torch.empty_like(h), torch.empty_like(c))
         _lib.call("tspgnn_lnlstm_fwd_f32", _lib.ptr(x), self.dx, _lib.ptr(h), _lib.ptr(c), _lib.ptr(self.packed("K", "f32")),
@@ -790,17 +794,136 @@ class GraphNN(object):
             return False
         return cell.d == 64 and cell.dx == 64 and mlp.sizes[-1] == cell.dx
 
-    def _folded(self, v, mats):
+    def _folded(self, v, mats, bf16_inference=False):
         """The loop entry of v if its cell input is a single gather over a two-ones-per-row matrix
-        (then the adjacency product is folded through the cell's GEMM), else None."""
+        (then the adjacency product is folded through the cell's GEMM), else None.  The fp32-storage forward and every
+        training forward fold at d == dx == 64 (can_fold), with or without a message MLP; ``bf16_inference``: the
+        bf16-storage inference forward folds at every width, but only behind a message MLP of the cell's own width, whose
+        launch then projects Zx = msg(y) Kx on the source rows."""
         if not self.fold_adjacency or len(self.loop[v]) != 1:
             return None
         u = self.loop[v][0]
-        if "var" not in u or "fun" in u or "mat" not in u or u.get("transpose?", False):
+        if "var" not in u or "fun" in u or "mat" not in u or u.get("transpose?", False) or mats[u["mat"]].uv is None:
             return None
-        if mats[u["mat"]].uv is None or not self._RNN_cells[v].can_fold():
-            return None
-        return u
+        cell = self._RNN_cells[v]
+        if bf16_inference:
+            return u if "msg" in u and cell.dx == self._msg_MLPs[u["msg"]].sizes[-1] == self.var[v] else None
+        return u if cell.can_fold() else None
+
+    def _pushed_degrees(self, v, mats):
+        """Stored entries per row of the adjacency product behind a pushed cell (the factor of its bias b Kx)."""
+        u0 = self.loop[v][0]
+        return mats[u0["mat"]].row_degrees(bool(u0.get("transpose?", False)))
+
+    def _matrices(self, adjacency_matrices, device):
+        """-> ({name: DeviceAdjacency} of the matrices that multiply an embedding, {name: dense fp32 tensor} of those a
+        loop entry without 'var' appends to the cell input as they are), each converted once per call."""
+        mats, dense = {}, {}
+        for v in self.var:
+            for update in self.loop[v]:
+                m = update.get("mat")
+                if m is None:
+                    continue
+                if "var" in update and m not in mats:
+                    mats[m] = DeviceAdjacency.wrap(adjacency_matrices[m], device)
+                elif "var" not in update and m not in dense:
+                    # graphnn.py:163-165: the matrix itself joins the cell input -- a constant of the step (a placeholder:
+                    # tf.gradients stops there); its columns only meet the cell kernel's rows
+                    a = adjacency_matrices[m]
+                    if isinstance(a, (SparseEV, DeviceAdjacency)):
+                        raise NotImplementedError("a matrix appended as a cell input must be dense")
+                    dense[m] = torch.as_tensor(a, dtype=torch.float32).to(device).contiguous()
+        return mats, dense
+
+    def _cell_input(self, v, msg_out, mats, rows, dtype, out=None):
+        """The input of v's unfolded cell from msg_out = {(v, i): rows of loop entry i after 'fun' / the message MLP, or the
+        appended matrix}: per entry with a matrix the adjacency product, several entries concatenated on axis 1.
+        -> (x [rows, dx], ops): ``ops`` is the list of (fn, args) that fills x -- a plan replays it every step, an eager
+        driver runs it on the spot.  ``out`` (training: the tape's slot of the step) becomes x: a single product writes
+        straight into it, the concatenation writes into it, a single entry that lives elsewhere is copied."""
+        single = len(self.loop[v]) == 1
+        new = dict(dtype=dtype, device=self.store.theta.device)
+        inputs, ops = [], []
+        for i, u in enumerate(self.loop[v]):
+            y = msg_out[(v, i)]
+            if "var" in u and "mat" in u:
+                adj, tr = mats[u["mat"]], u.get("transpose?", False)
+                o = out if single and out is not None else torch.empty((adj.shape[1] if tr else adj.shape[0], y.shape[1]), **new)
+                ops.append((adj.matmul, (y, tr, o)))
+                y = o
+            inputs.append(y)
+        dx = self._RNN_cells[v].dx
+        for y in inputs:    # every entry on the cell's rows, the widths adding up to the cell's input width
+            _check_cell_input((y.shape[0], sum(z.shape[1] for z in inputs)), rows, dx)
+        if not single:
+            x = out if out is not None else torch.empty((rows, dx), **new)
+            ops.append((lambda ins, o: torch.cat(ins, dim=1, out=o), (inputs, x)))
+        elif out is not None and inputs[0].data_ptr() != out.data_ptr():
+            x = out
+            ops.append((out.copy_, (inputs[0],)))
+        else:
+            x = inputs[0]
+        return x, ops
+
+    def _cell_forward_task(self, v, x, st, out, folded, pushed, mats, arith=None, centered=False):
+        """v's cell task in the form its selectors name: folded (x = the projected messages Zx of the source rows, gathered
+        by the cell kernel), pushed (x = the row-sum of the message MLP's last hidden activation, K' = [W Kx ; Kh]) or plain."""
+        cell = self._RNN_cells[v]
+        if folded[v] is not None:
+            return cell.gather_task(mats[folded[v]["mat"]], x, st, out, arith=arith, centered=centered)
+        if pushed[v]:
+            kp, zb = cell.pushed_bias_pack(self._msg_MLPs[self.loop[v][0]["msg"]], arith=arith, centered=centered)
+            return cell.pushed_task(x, st, out, kp, zb, self._pushed_degrees(v, mats), arith=arith, centered=centered)
+        return cell.task(x, st, out, arith=arith, centered=centered)
+
+    def _prepack_cells(self, folded, pushed, arith, centered, with_kx_and_mlps=False):
+        """The packings _cell_forward_task will take, made up front: the caller vets their range (check_h2_weights) before
+        any kernel multiplies with them.  A folded cell multiplies with Kh, a pushed one with the PRODUCT [W Kx ; Kh] --
+        which can leave the range on its own --, the others with the whole kernel.  ``with_kx_and_mlps`` (the training
+        forward, whose message launches are not built yet): also the Kx a folded cell's message MLP projects with and the
+        single-kernel message MLPs."""
+        for v, cell in self._RNN_cells.items():
+            if folded[v] is not None:
+                cell.packed("Kh", arith, centered)
+                if with_kx_and_mlps and "msg" in folded[v]:
+                    cell.packed("Kx", arith, centered)
+            elif pushed[v]:
+                cell.pushed_bias_pack(self._msg_MLPs[self.loop[v][0]["msg"]], arith=arith, centered=centered)
+            else:
+                cell.packed("K", arith, centered)
+        if with_kx_and_mlps:
+            for mlp in self._msg_MLPs.values():
+                if len(mlp._chunks()) == 1:
+                    mlp.wb_packed(0, mlp.n_square - 1, mlp.sizes[-1], arith)
+
+    def _check_bf16_wiring(self, folded=None):
+        """What the bf16-storage kernels cover; ``folded`` (training, which folds by the fp32 rule): its folded cells must
+        also be the ones the bf16 gather cell takes."""
+        for v in self.var:
+            cell = self._RNN_cells[v]
+            if self.var[v] not in (32, 64, 128) or cell.dx % 32 != 0:
+                raise NotImplementedError("bf16 storage needs widths 32/64/128 and cell inputs in multiples of 32")
+            if folded is not None and folded[v] is not None and (
+                    "msg" not in folded[v] or cell.dx != self._msg_MLPs[folded[v]["msg"]].sizes[-1] or cell.dx != self.var[v]):
+                raise NotImplementedError("bf16 storage: a folded cell input needs a message MLP of the cell's width")
+            for u in self.loop[v]:
+                if "var" not in u or "fun" in u:
+                    raise NotImplementedError("bf16 storage supports loop entries made of var / msg / mat only")
+                if "msg" in u:
+                    m = self._msg_MLPs[u["msg"]]
+                    if m._plan[0] != "square" or m._plan[3] or not (1 <= m.n_square <= 4) or m.input_size != m.sizes[-1]:
+                        raise NotImplementedError("bf16 storage needs square message MLPs of at most 4 layers")
+
+    def _bf16_message_task(self, mlp, y, rows, out, proj, interleave=False, blocked=False, acts=None):
+        """tspgnn_mlp_task_bf16 of ``mlp`` over ``rows`` rows of y (``blocked``: a state buffer blocked by 16 rows);
+        proj = (bf16 Kx, Zx) of a folded receiver or (None, None); ``interleave``: the last layer's columns interleaved
+        (y_interleaved); ``acts``: the tape's [layers-1, rows, d] slice for the hidden activations."""
+        n, d = mlp.n_square, mlp.sizes[-1]
+        return _lib.MlpTaskB(X=_lib.ptr(y), wb=_lib.ptr(mlp.wb_packed_bf16(0, n - 1, d, interleave_last=interleave)),
+                             Y=_lib.ptr(out), rows=rows, n_layers=n, relu_mask=mlp.relu_mask(0, n), proj_w=_lib.ptr(proj[0]),
+                             proj_out=_lib.ptr(proj[1]), acts=_lib.ptr(acts) if n > 1 else None,
+                             acts_stride=0 if acts is None else acts.stride(0), x_blocked=int(blocked),
+                             y_interleaved=int(interleave))
 
     # ---------------------------------------------------------------- forward
     def __call__(self, adjacency_matrices, initial_embeddings, time_steps, LSTM_initial_states={}):
@@ -811,19 +934,7 @@ class GraphNN(object):
         self._launched_loop = None
         some = next(iter(initial_embeddings.values()))
         device = some.device
-        mats, dense_mats = {}, {}
-        for v in self.var:
-            for update in self.loop[v]:
-                m = update.get("mat")
-                if m is None:
-                    continue
-                if "var" in update and m not in mats:
-                    mats[m] = DeviceAdjacency.wrap(adjacency_matrices[m], device)
-                elif "var" not in update and m not in dense_mats:
-                    a = adjacency_matrices[m]
-                    if isinstance(a, (SparseEV, DeviceAdjacency)):
-                        raise NotImplementedError("a matrix appended as a cell input must be dense")
-                    dense_mats[m] = torch.as_tensor(a, dtype=torch.float32).to(device).contiguous()
+        mats, dense_mats = self._matrices(adjacency_matrices, device)
         T = int(time_steps)
         h0 = {v: to_storage(init, self.float_dtype) for v, init in initial_embeddings.items()}   # storage type
         c0 = {v: LSTM_initial_states[v].to(torch.float32).contiguous() if v in LSTM_initial_states else None for v in h0}
@@ -860,16 +971,7 @@ class GraphNN(object):
         if dense_mats:
             raise NotImplementedError("bf16 storage: dense matrices appended as cell inputs")
         bf = dict(dtype=torch.bfloat16, device=self.store.theta.device)
-        for v in self.var:
-            if self.var[v] not in (32, 64, 128) or self._RNN_cells[v].dx % 32 != 0:
-                raise NotImplementedError("bf16 storage needs widths 32/64/128 and cell inputs in multiples of 32")
-            for u in self.loop[v]:
-                if "var" not in u or "fun" in u:
-                    raise NotImplementedError("bf16 storage supports loop entries made of var / msg / mat only")
-                if "msg" in u:
-                    m = self._msg_MLPs[u["msg"]]
-                    if m._plan[0] != "square" or m._plan[3] or not (1 <= m.n_square <= 4) or m.input_size != m.sizes[-1]:
-                        raise NotImplementedError("bf16 storage needs square message MLPs of at most 4 layers")
+        self._check_bf16_wiring()
         if T == 0:
             return {v: LSTMStateTuple(c=st.c if st.c is not None else torch.zeros(st.h.shape, dtype=torch.float32,
                                                                                     device=st.h.device), h=st.h)
@@ -887,15 +989,7 @@ class GraphNN(object):
                                     dtype=dtype, device=st.h.device) for v, st in states.items()} for _ in (0, 1)]
         hbuf, cbuf = buffers(torch.bfloat16), buffers(torch.float32)
         last = {v: LSTMStateTuple(c=torch.empty(st.h.shape, **f32), h=torch.empty_like(st.h)) for v, st in states.items()}
-
-        def folds(v):   # single gather over a two-ones-per-row matrix behind a message MLP: Zx = msg(y) Kx on source rows
-            if not self.fold_adjacency or len(self.loop[v]) != 1:
-                return None
-            u = self.loop[v][0]
-            if "mat" not in u or "msg" not in u or u.get("transpose?", False) or mats[u["mat"]].uv is None:
-                return None
-            return u if self._RNN_cells[v].dx == self._msg_MLPs[u["msg"]].sizes[-1] == self.var[v] else None
-        folded = {v: folds(v) for v in self.var}
+        folded = {v: self._folded(v, mats, bf16_inference=True) for v in self.var}
         keep = [hbuf, cbuf, last, states]
         built = {}
 
@@ -920,19 +1014,15 @@ class GraphNN(object):
                         d = mlp.sizes[-1]
                         rows = states[src].h.shape[0]
                         out = torch.empty((rows, d), **bf)
-                        pw = po = None
+                        proj = (None, None)
                         if folded[v] is not None:
-                            cv = self._RNN_cells[v]
                             zxs[v] = torch.empty((_pad16(rows), 4 * self.var[v]), **bf)
-                            pw, po = cv.packed("Kx", "bf16"), zxs[v]
-                        n = mlp.n_square
+                            proj = (self._RNN_cells[v].packed("Kx", "bf16"), zxs[v])
                         # a plain message (no projection rides behind it): the last layer's columns interleaved in the
                         # packing, 16-byte stores of Y (tspgnn_mlp_task_bf16.y_interleaved)
-                        il = pw is None and d % 32 == 0 and os.environ.get("TSPGNN_BF16_INTERLEAVE", "1") != "0"
-                        mlp_tasks.setdefault(d, []).append(_lib.MlpTaskB(
-                            X=_lib.ptr(y), wb=_lib.ptr(mlp.wb_packed_bf16(0, n - 1, d, interleave_last=il)), Y=_lib.ptr(out),
-                            rows=rows, n_layers=n, relu_mask=mlp.relu_mask(0, n), proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po),
-                            x_blocked=int(blk_in[src]), y_interleaved=int(il)))
+                        il = proj[0] is None and d % 32 == 0 and os.environ.get("TSPGNN_BF16_INTERLEAVE", "1") != "0"
+                        mlp_tasks.setdefault(d, []).append(
+                            self._bf16_message_task(mlp, y, rows, out, proj, interleave=il, blocked=blk_in[src]))
                         y = out
                     msg_out[(v, i)] = y
             for v, d in self.var.items():
@@ -941,22 +1031,8 @@ class GraphNN(object):
                 if folded[v] is not None:
                     adj, x = mats[folded[v]["mat"]], zxs[v]
                 else:
-                    inputs = []
-                    for i, u in enumerate(self.loop[v]):
-                        y = msg_out[(v, i)]
-                        if "mat" in u:
-                            adj_, tr = mats[u["mat"]], u.get("transpose?", False)
-                            o = torch.empty((adj_.shape[1] if tr else adj_.shape[0], y.shape[1]), **bf)
-                            mid.append((adj_.matmul, (y, tr, o)))
-                            y = o
-                        inputs.append(y)
-                    if len(inputs) == 1:
-                        x = inputs[0]
-                    else:
-                        x = torch.empty((rows, cell.dx), **bf)
-                        mid.append((lambda ins, o: torch.cat(ins, dim=1, out=o), (inputs, x)))
-                    if x.shape[0] != rows or x.shape[1] != cell.dx:
-                        raise ValueError("cell input must be [%d,%d], got %s" % (rows, cell.dx, tuple(x.shape)))
+                    x, ops = self._cell_input(v, msg_out, mats, rows, torch.bfloat16)
+                    mid += ops
                     adj = None
                     keep.append(x)
                 cell_tasks.setdefault(d, []).append(cell.task_bf16(
@@ -1064,18 +1140,20 @@ class GraphNN(object):
                 return False
         return True
 
-    def _single_consumers(self):
+    def _single_consumers(self, own_width=False):
         """{source variable: (v, i)} when every variable's h feeds exactly one loop entry and that entry has a
-        single-kernel square message MLP of the variable's own width (the wiring the fused cell + message launch
-        covers), else None."""
+        single-kernel message MLP (the wiring the fused cell + message launch covers), else None.  ``own_width`` (the
+        training forward, whose tape keeps the hidden activations per SOURCE row): the MLP must also be square and of the
+        source variable's own width."""
         consumers = {u: [] for u in self.var}
         for v in self.var:
             for i, u in enumerate(self.loop[v]):
                 if "var" not in u or "fun" in u or "msg" not in u:
                     return None
                 mlp = self._msg_MLPs[u["msg"]]
-                if mlp._plan[0] != "square" or len(mlp._chunks()) != 1 or mlp.n_square < 1 or mlp._plan[3] \
-                        or mlp.sizes[-1] != self.var[u["var"]]:
+                if len(mlp._chunks()) != 1 or mlp.n_square < 1 or mlp._plan[3]:
+                    return None
+                if own_width and (mlp._plan[0] != "square" or mlp.sizes[-1] != self.var[u["var"]]):
                     return None
                 consumers[u["var"]].append((v, i))
         if any(len(c) != 1 for c in consumers.values()):
@@ -1092,16 +1170,8 @@ class GraphNN(object):
         arith = self._split_arith({v: st.h.shape[0] for v, st in states.items()})
         if arith is None:
             return None
-        consumers = {u: [] for u in self.var}
-        for v in self.var:
-            for i, u in enumerate(self.loop[v]):
-                if "var" not in u or "fun" in u or "msg" not in u:
-                    return None
-                mlp = self._msg_MLPs[u["msg"]]
-                if len(mlp._chunks()) != 1 or mlp.n_square < 1 or mlp._plan[3]:
-                    return None
-                consumers[u["var"]].append((v, i))
-        if any(len(c) != 1 for c in consumers.values()):
+        consumers = self._single_consumers()
+        if consumers is None:
             return None
         f32 = dict(dtype=torch.float32, device=self.store.theta.device)
         # f16x2: the states of a folded (edge-side) variable live BLOCKED by 16 rows between the steps (include/tspgnn.h,
@@ -1158,41 +1228,20 @@ class GraphNN(object):
             src, dst = buf[p], buf[1 - p]
             mid, tasks = [], {}
             for v, d in self.var.items():
-                cell = self._RNN_cells[v]
                 n_v = rows_of[v]
                 st = first_state[v] if first else LSTMStateTuple(c=src[v].c[:n_v], h=src[v].h[:n_v])
                 out = (dst[v].h, dst[v].c)
                 if folded[v] is not None:
-                    t = cell.gather_task(mats[folded[v]["mat"]], zxs[p][v], st, out, arith=arith, centered=cen)
+                    x = zxs[p][v]
                 else:
-                    inputs = []
-                    for i, u in enumerate(self.loop[v]):
-                        y = mo[p][(v, i)]
-                        if "mat" in u:
-                            adj, tr = mats[u["mat"]], u.get("transpose?", False)
-                            o = torch.empty((adj.shape[1] if tr else adj.shape[0], y.shape[1]), **f32)
-                            mid.append((adj.matmul, (y, tr, o)))
-                            y = o
-                        inputs.append(y)
-                    if len(inputs) == 1:
-                        x = inputs[0]
-                    else:
-                        x = torch.empty((st.h.shape[0], cell.dx), **f32)
-                        mid.append((lambda ins, o: torch.cat(ins, dim=1, out=o), (inputs, x)))
-                    if x.shape[0] != st.h.shape[0] or x.shape[1] != cell.dx:
-                        raise ValueError("cell input must be [%d,%d], got %s" % (st.h.shape[0], cell.dx, tuple(x.shape)))
+                    x, ops = self._cell_input(v, mo[p], mats, n_v, torch.float32)
+                    mid += ops
                     keep.append(x)
-                    if pushed[v]:
-                        u0 = self.loop[v][0]
-                        kp, zb = cell.pushed_bias_pack(self._msg_MLPs[u0["msg"]], arith=arith, centered=cen)
-                        deg = mats[u0["mat"]].row_degrees(bool(u0.get("transpose?", False)))
-                        t = cell.pushed_task(x, st, out, kp, zb, deg, arith=arith, centered=cen)
-                    else:
-                        t = cell.task(x, st, out, arith=arith, centered=cen)
+                t = self._cell_forward_task(v, x, st, out, folded, pushed, mats, arith, cen)
                 s_in = 1 if blocked[v] and not first else 0
                 s_out = 1 if blocked[v] and with_messages else 0
                 if with_messages:   # the message MLP that reads this variable's new h in the next step
-                    (cv, ci), = consumers[v]
+                    cv, ci = consumers[v]
                     wb, n, mask, mout, pw, po = message(cv, ci, 1 - p)
                     ct = _lib.CellMlpTask(t, mlp_wb=_lib.ptr(wb), mlp_layers=n, relu_mask=mask, mlp_out=_lib.ptr(mout),
                                           proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po), state_in_blocked=s_in,
@@ -1221,14 +1270,7 @@ class GraphNN(object):
         self._plan_keep = keep
         # the cells' packings are made here, not at the first step: the caller vets their range (check_h2_weights) between
         # the construction of the plan and its first launch
-        for v in self.var:
-            cell = self._RNN_cells[v]
-            if folded[v] is not None:
-                cell.packed("Kh", arith, cen)
-            elif pushed[v]:
-                cell.pushed_bias_pack(self._msg_MLPs[self.loop[v][0]["msg"]], arith=arith, centered=cen)
-            else:
-                cell.packed("K", arith, cen)
+        self._prepack_cells(folded, pushed, arith, cen)
 
         loop_launch = self._loop_launch(states, mats, folded, pushed, consumers, message, first_state, arith, cen, keep) \
             if arith == "h2" else None
@@ -1400,38 +1442,15 @@ class GraphNN(object):
             for v, d in self.var.items():
                 cell, st = self._RNN_cells[v], src_states[v]
                 out = (dst_states[v].h, dst_states[v].c)
-                if folded[v] is not None:
-                    if v in zxs:
-                        zx = zxs[v]
-                    else:
-                        zx = torch.empty((_pad16(msg_out[(v, 0)].shape[0]), 4 * d), **f32)
-                        mid.append((cell.premultiply, (msg_out[(v, 0)], zx, zx_scale)))
-                    lstm_tasks.setdefault(d, []).append(cell.gather_task(mats[folded[v]["mat"]], zx, st, out, arith=arith))
-                    keep.append(zx)
-                    continue
-                inputs = []
-                for i, u in enumerate(self.loop[v]):
-                    y = msg_out[(v, i)]
-                    if "mat" in u:
-                        adj, tr = mats[u["mat"]], u.get("transpose?", False)
-                        o = torch.empty((adj.shape[1] if tr else adj.shape[0], y.shape[1]), **f32)
-                        mid.append((adj.matmul, (y, tr, o)))
-                        y = o
-                    inputs.append(y)
-                if len(inputs) == 1:
-                    x = inputs[0]
-                else:
-                    x = torch.empty((st.h.shape[0], cell.dx), **f32)
-                    mid.append((lambda ins, o: torch.cat(ins, dim=1, out=o), (inputs, x)))
-                if x.shape[0] != st.h.shape[0] or x.shape[1] != cell.dx:
-                    raise ValueError("cell input must be [%d,%d], got %s" % (st.h.shape[0], cell.dx, tuple(x.shape)))
-                if pushed[v]:
-                    u0 = self.loop[v][0]
-                    kp, zb = cell.pushed_bias_pack(self._msg_MLPs[u0["msg"]], arith=arith)
-                    deg = mats[u0["mat"]].row_degrees(bool(u0.get("transpose?", False)))
-                    lstm_tasks.setdefault(d, []).append(cell.pushed_task(x, st, out, kp, zb, deg, arith=arith))
-                else:
-                    lstm_tasks.setdefault(d, []).append(cell.task(x, st, out, arith=arith))
+                if folded[v] is None:
+                    x, ops = self._cell_input(v, msg_out, mats, st.h.shape[0], torch.float32)
+                    mid += ops
+                elif v in zxs:
+                    x = zxs[v]
+                else:   # no message MLP to project behind: Zx = y Kx by a launch of its own
+                    x = torch.empty((_pad16(msg_out[(v, 0)].shape[0]), 4 * d), **f32)
+                    mid.append((cell.premultiply, (msg_out[(v, 0)], x, zx_scale)))
+                lstm_tasks.setdefault(d, []).append(self._cell_forward_task(v, x, st, out, folded, pushed, mats, arith))
                 keep.append(x)
             keep.append(msg_out)
 
@@ -1461,7 +1480,8 @@ class GraphNN(object):
         msg_out, tasks, keep = {}, {}, []
         for v in self.var:
             for i, u in enumerate(self.loop[v]):
-                if "var" not in u:
+                if "var" not in u:          # an appended matrix: joins the cell input in B
+                    msg_out[(v, i)] = dense_mats[u["mat"]]
                     continue
                 y = states[u["var"]].h
                 if "fun" in u:
@@ -1485,32 +1505,18 @@ class GraphNN(object):
             if folded[v] is not None:
                 cell_in[v] = self._RNN_cells[v].premultiply(msg_out[(v, 0)])
                 continue
-            inputs = []
-            for i, u in enumerate(self.loop[v]):
-                if "var" in u:
-                    y = msg_out[(v, i)]
-                    if "mat" in u:
-                        y = mats[u["mat"]].matmul(y, transpose=u.get("transpose?", False))
-                    inputs.append(y)
-                else:
-                    inputs.append(dense_mats[u["mat"]])
-            cell_in[v] = inputs[0] if len(inputs) == 1 else torch.cat(inputs, dim=1)
+            x, ops = self._cell_input(v, msg_out, mats, states[v].h.shape[0], torch.float32)
+            for fn, args in ops:
+                fn(*args)
+            cell_in[v] = x if x.is_contiguous() else x.contiguous()
         # ---- C: all cells
         new_states, tasks = {}, {}
+        unpushed = {v: False for v in self.var}
         for v, d in self.var.items():
-            cell, st = self._RNN_cells[v], states[v]
+            st = states[v]
             out = (torch.empty_like(st.h), torch.empty_like(st.c))
             new_states[v] = LSTMStateTuple(c=out[1], h=out[0])
-            if folded[v] is not None:
-                t = cell.gather_task(mats[folded[v]["mat"]], cell_in[v], st, out)
-            else:
-                x = cell_in[v]
-                if x.shape[0] != st.h.shape[0] or x.shape[1] != cell.dx:
-                    raise ValueError("cell input must be [%d,%d], got %s" % (st.h.shape[0], cell.dx, tuple(x.shape)))
-                x = x if x.is_contiguous() else x.contiguous()
-                keep.append(x)
-                t = cell.task(x, st, out)
-            tasks.setdefault(d, []).append(t)
+            tasks.setdefault(d, []).append(self._cell_forward_task(v, cell_in[v], st, out, folded, unpushed, mats))
         _lib.call_by_width("tspgnn_lnlstm_fwd_multi_f32", tasks)
         return new_states
 
@@ -1532,21 +1538,9 @@ class GraphNN(object):
         device = next(iter(initial_embeddings.values())).device
         f32 = dict(dtype=torch.float32, device=device)
         stored = dict(dtype=self.float_dtype, device=device)   # what the tape keeps of h, messages, activations
-        mats, dense = {}, {}
-        for v in self.var:
-            for u in self.loop[v]:
-                if ("fun" in u or "var" not in u) and bf16:
-                    raise NotImplementedError("bf16-storage training supports loop entries made of var / msg / mat only")
-                if "var" not in u:
-                    # graphnn.py:163-165: the matrix itself joins the cell input -- a constant of the step (a placeholder:
-                    # tf.gradients stops there); its columns only meet the cell kernel's rows
-                    if u["mat"] not in dense:
-                        a = adjacency_matrices[u["mat"]]
-                        a = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-                        dense[u["mat"]] = a.to(device=device, dtype=torch.float32).contiguous()
-                    continue
-                if "mat" in u and u["mat"] not in mats:
-                    mats[u["mat"]] = DeviceAdjacency.wrap(adjacency_matrices[u["mat"]], device)
+        if bf16 and any("fun" in u or "var" not in u for v in self.var for u in self.loop[v]):
+            raise NotImplementedError("bf16-storage training supports loop entries made of var / msg / mat only")
+        mats, dense = self._matrices(adjacency_matrices, device)
         tape = Tape()
         tape.T, tape.mats, tape.dense = T, mats, dense
         tape.folded = {v: self._folded(v, mats) for v in self.var}
@@ -1591,20 +1585,7 @@ class GraphNN(object):
         if arith == "h2":
             # the step's f16x2 packings up front (they are cached for the tasks below), so that the guard can veto them
             # before any kernel multiplies with them
-            # (exactly the packings the tasks below take: a folded cell multiplies with Kh and projects with Kx, a pushed
-            # one with the PRODUCT [W Kx ; Kh] -- which can leave the range on its own --, the others with the whole kernel)
-            for v, cell in self._RNN_cells.items():
-                if tape.folded[v] is not None:
-                    cell.packed("Kh", "h2")
-                    if "msg" in tape.folded[v]:
-                        cell.packed("Kx", "h2")
-                elif pushable[v]:
-                    cell.pushed_bias_pack(self._msg_MLPs[self.loop[v][0]["msg"]], arith="h2")
-                else:
-                    cell.packed("K", "h2")
-            for mlp in self._msg_MLPs.values():
-                if len(mlp._chunks()) == 1:
-                    mlp.wb_packed(0, mlp.n_square - 1, mlp.sizes[-1], "h2")
+            self._prepack_cells(tape.folded, pushable, "h2", False, with_kx_and_mlps=True)
             if not self.check_h2_weights():
                 arith = self._split_arith({v: initial_embeddings[v].shape[0] for v in self.var})
         tape.arith = arith
@@ -1685,40 +1666,19 @@ class GraphNN(object):
                         self._RNN_cells[v].premultiply(tape.X[v][t], out=tape.ZX[v][t],
                                                        scale=_lib.lib.tspgnn_h2_weight_scale() if arith == "h2" else None)
                     continue
-                single = len(self.loop[v]) == 1
-                inputs = []
-                for i, u in enumerate(self.loop[v]):
-                    y = msg_out[(v, i)]
-                    if "var" not in u:
-                        if single:
-                            tape.X[v][t].copy_(y)
-                    elif "mat" in u:
-                        y = mats[u["mat"]].matmul(y, transpose=u.get("transpose?", False),
-                                                  out=tape.X[v][t] if single else None)
-                    elif single and ("msg" not in u or "fun" in u):
-                        tape.X[v][t].copy_(y)
-                    inputs.append(y)
-                if not single:
-                    torch.cat(inputs, dim=1, out=tape.X[v][t])
+                for fn, args in self._cell_input(v, msg_out, mats, n[v], torch.float32, out=tape.X[v][t])[1]:
+                    fn(*args)
 
         def cell_task(v, t):
-            cell = self._RNN_cells[v]
-            st = LSTMStateTuple(c=tape.C[v][t], h=tape.H[v][t])
-            out = (tape.H[v][t + 1], tape.C[v][t + 1])
-            if tape.folded[v] is not None:
-                return cell.gather_task(mats[tape.folded[v]["mat"]], tape.ZX[v][t], st, out, arith=arith)
-            if tape.pushed[v]:
-                u0 = self.loop[v][0]
-                kp, zb = cell.pushed_bias_pack(self._msg_MLPs[u0["msg"]], arith=arith)
-                return cell.pushed_task(tape.X[v][t], st, out, kp, zb,
-                                        mats[u0["mat"]].row_degrees(bool(u0.get("transpose?", False))), arith=arith)
-            return cell.task(tape.X[v][t], st, out, arith=arith)
+            x = (tape.X if tape.folded[v] is None else tape.ZX)[v][t]
+            return self._cell_forward_task(v, x, LSTMStateTuple(c=tape.C[v][t], h=tape.H[v][t]),
+                                           (tape.H[v][t + 1], tape.C[v][t + 1]), tape.folded, tape.pushed, mats, arith)
 
         # f16x2, opt-in (fuse_training_messages): the message MLPs of step t+1 ride in the cell launch of step t, on the
         # rows of h' it still holds in registers (tspgnn_lnlstm_mlp_fwd_multi_h2 as in the inference plan, here writing
         # the tape: states, hidden activations, messages and projected messages of every step)
-        consumers = self._single_consumers() if arith == "h2" and (self.fuse_training_messages or any(tape.rc.values())) \
-            else None
+        consumers = self._single_consumers(own_width=True) \
+            if arith == "h2" and (self.fuse_training_messages or any(tape.rc.values())) else None
         tape.fused = consumers is not None
         if consumers is not None:
             msg_out = messages(0) if T > 0 else {}
@@ -1766,18 +1726,7 @@ class GraphNN(object):
         task with its Kx projection --, adjacency products, cells), every output written into the tape."""
         mats = tape.mats
         bf = dict(dtype=torch.bfloat16, device=self.store.theta.device)
-        for v in self.var:
-            if self.var[v] not in (32, 64, 128) or self._RNN_cells[v].dx % 32 != 0:
-                raise NotImplementedError("bf16 storage needs widths 32/64/128 and cell inputs in multiples of 32")
-            if tape.folded[v] is not None and ("msg" not in tape.folded[v]
-                                               or self._RNN_cells[v].dx != self._msg_MLPs[tape.folded[v]["msg"]].sizes[-1]
-                                               or self._RNN_cells[v].dx != self.var[v]):
-                raise NotImplementedError("bf16 storage: a folded cell input needs a message MLP of the cell's width")
-            for u in self.loop[v]:
-                if "msg" in u:
-                    m = self._msg_MLPs[u["msg"]]
-                    if m._plan[0] != "square" or m._plan[3] or not (1 <= m.n_square <= 4) or m.input_size != m.sizes[-1]:
-                        raise NotImplementedError("bf16 storage needs square message MLPs of at most 4 layers")
+        self._check_bf16_wiring(tape.folded)
         for t in range(T):
             msg_out, plain, with_proj = {}, {}, {}
             for v in self.var:
@@ -1786,19 +1735,13 @@ class GraphNN(object):
                     if "msg" in u:
                         mlp = self._msg_MLPs[u["msg"]]
                         d = mlp.sizes[-1]
-                        acts = tape.acts[(v, i)]
                         to_tape = tape.folded[v] is not None or (len(self.loop[v]) == 1 and "mat" not in u)
                         out = tape.X[v][t] if to_tape else torch.empty((y.shape[0], d), **bf)
-                        pw = po = None
+                        proj = (None, None)
                         if tape.folded[v] is not None:
-                            cv = self._RNN_cells[v]
-                            pw, po = cv.packed("Kx", "bf16"), tape.ZX[v][t]
-                        k = mlp.n_square
-                        task = _lib.MlpTaskB(X=_lib.ptr(y), wb=_lib.ptr(mlp.wb_packed_bf16(0, k - 1, d)), Y=_lib.ptr(out),
-                                             rows=y.shape[0], n_layers=k, relu_mask=mlp.relu_mask(0, k), proj_w=_lib.ptr(pw),
-                                             proj_out=_lib.ptr(po), acts=_lib.ptr(acts[:, t]) if k > 1 else None,
-                                             acts_stride=acts.stride(0))
-                        (with_proj if pw is not None else plain).setdefault(d, []).append(task)
+                            proj = (self._RNN_cells[v].packed("Kx", "bf16"), tape.ZX[v][t])
+                        task = self._bf16_message_task(mlp, y, y.shape[0], out, proj, acts=tape.acts[(v, i)][:, t])
+                        (plain if proj[0] is None else with_proj).setdefault(d, []).append(task)
                         y = out
                     msg_out[(v, i)] = y
             for group in (plain, with_proj):   # (projections in their own launch: see _run_bf16)
@@ -1807,23 +1750,13 @@ class GraphNN(object):
             for v, d in self.var.items():
                 cell = self._RNN_cells[v]
                 if tape.folded[v] is not None:
-                    task = cell.task_bf16(tape.ZX[v][t], tape.H[v][t], tape.C[v][t], tape.H[v][t + 1], tape.C[v][t + 1], n[v],
-                                          adj=mats[tape.folded[v]["mat"]])
+                    x, adj = tape.ZX[v][t], mats[tape.folded[v]["mat"]]
                 else:
-                    single = len(self.loop[v]) == 1
-                    inputs = []
-                    for i, u in enumerate(self.loop[v]):
-                        y = msg_out[(v, i)]
-                        if "mat" in u:
-                            y = mats[u["mat"]].matmul(y, transpose=u.get("transpose?", False),
-                                                      out=tape.X[v][t] if single else None)
-                        elif single and "msg" not in u:
-                            tape.X[v][t].copy_(y)
-                        inputs.append(y)
-                    if not single:
-                        torch.cat(inputs, dim=1, out=tape.X[v][t])
-                    task = cell.task_bf16(tape.X[v][t], tape.H[v][t], tape.C[v][t], tape.H[v][t + 1], tape.C[v][t + 1], n[v])
-                cells.setdefault(d, []).append(task)
+                    x, adj = tape.X[v][t], None
+                    for fn, args in self._cell_input(v, msg_out, mats, n[v], torch.bfloat16, out=x)[1]:
+                        fn(*args)
+                cells.setdefault(d, []).append(cell.task_bf16(x, tape.H[v][t], tape.C[v][t], tape.H[v][t + 1],
+                                                              tape.C[v][t + 1], n[v], adj=adj))
             _lib.call_by_width("tspgnn_lnlstm_fwd_multi_bf16", cells)
 
     def backward(self, tape, dstates):
@@ -1928,9 +1861,8 @@ class GraphNN(object):
         push = {}
         for v, d in self.var.items():
             if pushed[v]:
-                u0 = self.loop[v][0]
-                deg = mats[u0["mat"]].row_degrees(bool(u0.get("transpose?", False)))
-                push[v] = dict(mlp=self._msg_MLPs[u0["msg"]], deg=deg, deg_steps=deg.repeat(CH),
+                deg = self._pushed_degrees(v, mats)
+                push[v] = dict(mlp=self._msg_MLPs[self.loop[v][0]["msg"]], deg=deg, deg_steps=deg.repeat(CH),
                                g_wkx=torch.zeros((self._RNN_cells[v].dx, 4 * d), **f32), g_zb=torch.zeros((1, 4 * d), **f32))
 
         def weight_gradients(t0, t1):
