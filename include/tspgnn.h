@@ -506,6 +506,64 @@ int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n,
 int tspgnn_tour_lower_bound_tri(const float* W, const long long* w_off, const int* n, const float* upper, int n_inst,
                                 int n_max, int iters, double* lb, void* stream);
 
+/* ------------------------------------------------------------------ decision-TSP baselines (tspgnn/baselines.py) */
+
+/*
+ * Nearest-neighbour tours, one workgroup per instance, W / w_off / n / t_off as tspgnn_tour_search (dense matrices,
+ * 4 <= n[i] <= n_max <= 128; n_max > 128: TSPGNN_EUNSUPPORTED).  From the start vertex the tour moves repeatedly to the
+ * unvisited vertex v of smallest W(cur, v), ties to the smaller vertex id.  start >= 0: the one tour from vertex
+ * start % n[i].  start == -1: the tour from every start vertex, the waves of the workgroup striding over the starts, and
+ * of those the tour of smallest fp32 cost, ties to the smaller start.  start < -1: TSPGNN_EINVAL.
+ * Out: tours + t_off[i] in canonical form (tour[0] = 0, tour[1] < tour[n-1]); costs[i] = its fp32 cost under W.
+ * n_inst == 0 is a no-op.
+ */
+int tspgnn_tour_nearest_neighbor(const float* W, const long long* w_off, const int* n, const long long* t_off, int n_inst,
+                                 int n_max, int start, int32_t* tours, float* costs, void* stream);
+
+/*
+ * tspgnn_tour_nearest_neighbor on the packed strict upper triangle of tspgnn_tour_search_tri, n_max <= 256 (above:
+ * TSPGNN_EUNSUPPORTED).  For n <= 128 the tours and costs equal tspgnn_tour_nearest_neighbor's bit for bit.
+ */
+int tspgnn_tour_nearest_neighbor_tri(const float* W, const long long* w_off, const int* n, const long long* t_off,
+                                     int n_inst, int n_max, int start, int32_t* tours, float* costs, void* stream);
+
+/*
+ * Metropolis annealing over 2-exchange moves: one workgroup per instance, one wave64 per chain, `chains` in [1, 16] and
+ * at most what fits in LDS beside the weights (the rule of tspgnn_tour_search's restarts; TSPGNN_EINVAL names the limit).
+ * W / w_off / n / init_tours / t_off / index as tspgnn_tour_search.  inv_temp:[n_inst, levels] fp32 on the device holds
+ * 1 / T per level (+inf: T = 0); per_level:[n_inst] int on the device; levels >= 0.  Instance i runs
+ * levels * per_level[i] proposals per chain, which must be at most 2^31 - 1: the arrays live on the device, so this entry
+ * point cannot see them, and an instance that breaks the rule (or has per_level[i] < 0) gets costs[i] = NaN and no tour.
+ * Chain 0 starts from init_tours + t_off[i] when that is given and a permutation, otherwise from the nearest-neighbour
+ * tour from vertex 0; chain c > 0 from the nearest-neighbour tour from vertex c % n[i].
+ * A chain is this sequential process over proposal numbers p = 0, 1, ...:
+ *   r = the generator's draw for (seed, index[i], chain, p, 0);  i = (r & 0xffff) % n, j = ((r >> 16) & 0xffff) % n,
+ *   swapped if i > j;  u = (((r >> 40) & 0x7fffff) + 0.5) * 2^-23;
+ *   the proposal is void (a rejection) unless j > i + 1 and not (i == 0 and j == n - 1);
+ *   d = (W(a,c) + W(b,e)) - (W(a,b) + W(c,e)) in fp32, a = t[i], b = t[i+1], c = t[j], e = t[(j+1) % n];
+ *   accepted iff d <= 0 or u < expf(-(d * inv_temp[i][p / per_level[i]]));  acceptance reverses positions i+1..j;
+ *   rel, the fp32 running sum of the accepted d, starts at 0, and the tour is kept as the chain's best whenever rel falls
+ *   below its smallest value so far.
+ * The wave evaluates 64 consecutive proposals against the current tour at once and applies the first that accepts, which
+ * is the same process.  Out: of the chains' best tours the one of smallest fp32 cost (recomputed from the tour), ties to
+ * the lower chain, in canonical form; costs[i] = that cost.  Results depend on (seed, index[i], chains, the schedule)
+ * only.  n_inst == 0 is a no-op; n_max > 128: TSPGNN_EUNSUPPORTED.
+ */
+int tspgnn_tour_anneal(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                       const long long* t_off, const long long* index, const float* inv_temp, const int* per_level,
+                       int n_inst, int n_max, int chains, int levels, unsigned long long seed, int32_t* tours,
+                       float* costs, void* stream);
+
+/*
+ * tspgnn_tour_anneal on the packed strict upper triangle of tspgnn_tour_search_tri, n_max <= 256 (above:
+ * TSPGNN_EUNSUPPORTED); at n_max = 256 chains <= 10.  For n <= 128 the tours and costs equal tspgnn_tour_anneal's bit
+ * for bit.
+ */
+int tspgnn_tour_anneal_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                           const long long* t_off, const long long* index, const float* inv_temp, const int* per_level,
+                           int n_inst, int n_max, int chains, int levels, unsigned long long seed, int32_t* tours,
+                           float* costs, void* stream);
+
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 
 /*

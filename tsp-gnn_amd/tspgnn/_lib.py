@@ -92,6 +92,14 @@ SIGNATURES = {
     "tspgnn_tour_search_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_lower_bound_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "tspgnn_tour_nearest_neighbor": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p],
+    "tspgnn_tour_nearest_neighbor_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p],
+    "tspgnn_tour_anneal": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                           c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_anneal_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                               c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
 }
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",
