@@ -11,6 +11,11 @@ incidences (E<-V gather of M rows + V<-E row-sum over 2M incidences) and updates
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run does what ``value`` needs and nothing else: set-up, warm-up, the timed steps, ``--dump-outputs``, the line.
+``--full`` adds, after the timed steps, every side measurement (fresh-batch serve leg, training leg, other GEMM
+arithmetics, per-kernel durations, SpMM micro-loop and rooflines, CPU baseline); without it their fields are null.  At
+N>1 the training leg is the headline and runs either way.
+
 The forward pass needs no collective (EV is block diagonal: instances never exchange messages), so
 N>1 is weak scaling over independent shards of the global batch: "sharded by instance".
 """
@@ -174,8 +179,14 @@ def main():
     ap.add_argument("--mode", default="forward", choices=["forward", "train"],
                     help="what one timed step is: a forward pass (default, the metric's definition) or a full "
                          "training step (forward + backward + gradient all-reduce + L2/clip/Adam)")
-    ap.add_argument("--train-steps", type=int, default=3, help="extra (untimed-by-the-driver) training steps reported "
-                                                               "under 'train' when --mode forward")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement and put it on the result line: the "
+                         "fresh-batch 'serve' leg, the training leg, the other GEMM arithmetics ('gemm'), per-kernel "
+                         "durations ('kernels_us'), the SpMM micro-loop and the rooflines, the CPU baseline.  Off by default: "
+                         "a plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line with "
+                         "those fields null (--serve-*, --train-steps, --cpu-seconds and --no-cpu-baseline shape --full only)")
+    ap.add_argument("--train-steps", type=int, default=3, help="with --full: extra (untimed-by-the-driver) training steps "
+                                                               "reported under 'train' when --mode forward")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from the host instead of replaying "
                                                             "the captured HIP graph of the forward pass")
     ap.add_argument("--serve-batches", type=int, default=64,
@@ -319,7 +330,7 @@ def main():
     # batch -> copied into the buffers of the captured graph -> replay.  Every rank packs its own shard concurrently, so at
     # N > 1 this is where host contention between the ranks' packers would show; the resident-batch `value` cannot see it.
     serve = None
-    if args.mode == "forward" and use_graph and args.serve_batches > 0:
+    if args.full and args.mode == "forward" and use_graph and args.serve_batches > 0:
         try:
             rng = np.random.RandomState(99 + rank)
             uniq = sorted(set(int(n) for n in sizes))
@@ -419,7 +430,8 @@ def main():
     # a collective (one RCCL all-reduce of the gradient bucket per step) -- timed over exactly --steps steps
     # after --warmup, barrier-bracketed, max over ranks; the collective-free forward moves to `forward_value`.
     n_train, w_train = (args.steps, max(1, args.warmup)) if world > 1 else (args.train_steps, 1)
-    if args.mode == "forward" and n_train > 0:
+    # (N = 1: a side measurement, --full only; N > 1: the headline itself, every run)
+    if args.mode == "forward" and n_train > 0 and (args.full or world > 1):
         # the training step (backward + RCCL all-reduce of the 462 KB gradient bucket + fused optimiser), reported
         # next to the forward number; a failure here (e.g. the collective) must not lose the forward measurement
         try:
@@ -460,10 +472,12 @@ def main():
             train = {"error": "%s: %s" % (type(exc).__name__, exc)}
         sess.run(tspgnn.global_variables_initializer(seed=0))   # restore the benchmark weights
 
-    result = None
-    if rank == 0:
-        ms_per_step = 1e3 * elapsed / args.steps
-        mp_steps_per_s = world * args.steps * T / elapsed
+    SIDE_KEYS = ("roofline", "roofline_cell", "roofline_dense", "cpu_baseline", "gemm", "kernels_us")
+
+    def side_measurements():
+        """--full, rank 0, after every timed leg: the result line's SIDE_KEYS -- measurements next to the headline (other
+        GEMM arithmetics, per-kernel durations, the SpMM micro-loop, the rooflines, the CPU baseline), each a run of its
+        own on the benchmark batch.  A plain run reports them as null."""
         gather_b, rowsum_b = spmm_bytes(N, M, d, eb=2 if bf16 else 4)
 
         # ---- the same forward with the other GEMM arithmetics, next to the headline: their time, and how far their
@@ -765,7 +779,16 @@ def main():
         cpu_baseline = None
         if not args.no_cpu_baseline and world == 1 and float(M) * N * 4 < 16e9:   # rank 0, N=1 only; dense EV must fit
             cpu_baseline = run_cpu_baseline(d, batch, T, args.cpu_seconds, M)
+        return {"roofline": roofline, "roofline_cell": roofline_cell, "roofline_dense": roofline_dense,
+                "cpu_baseline": cpu_baseline, "gemm": gemm,
+                "kernels_us": {k: {"n": v["n"], "avg_us": round(v["avg_us"], 2)} for k, v in kernels_us.items()}}
 
+    # ---- the line
+    result = None
+    if rank == 0:
+        ms_per_step = 1e3 * elapsed / args.steps
+        mp_steps_per_s = world * args.steps * T / elapsed
+        side = side_measurements() if args.full else dict.fromkeys(SIDE_KEYS)
         # which step the headline fields describe: the forward pass at N = 1 (BASELINE's metric as the reference runs it),
         # the training step -- with its all-reduce -- at N > 1
         train_ok = world > 1 and isinstance(train, dict) and "error" not in train
@@ -792,11 +815,12 @@ def main():
                        "parallelism": "shard-by-instance x%d, no data-path collective" % world},
             "edges_per_s": round(mp_steps_per_s * M, 1),
             "incidences_per_s": round(mp_steps_per_s * 4 * M, 1),
-            "roofline": roofline,
-            "roofline_cell": roofline_cell,
-            "roofline_dense": roofline_dense,
-            "cpu_baseline": cpu_baseline,
-            "gemm": gemm,
+            "full": bool(args.full),   # False: the side measurements (SIDE_KEYS; `train` at N = 1; `serve`) were not run
+            "roofline": side["roofline"],
+            "roofline_cell": side["roofline_cell"],
+            "roofline_dense": side["roofline_dense"],
+            "cpu_baseline": side["cpu_baseline"],
+            "gemm": side["gemm"],
             "mode": args.mode, "hip_graph": bool(use_graph),
             # N > 1: the forward-only `value` has no collective and scales by construction; the curve north_star asks for
             # is the TRAINING step's (one RCCL all-reduce per step) -- lifted to the top level so that it cannot be missed
@@ -811,7 +835,7 @@ def main():
             "range_guard_bits": guard_bits,
             "train": train,
             "serve": serve,
-            "kernels_us": {k: {"n": v["n"], "avg_us": round(v["avg_us"], 2)} for k, v in kernels_us.items()},
+            "kernels_us": side["kernels_us"],
             "host_pack_s": round(t_pack, 4),
             "loss": loss,
         }

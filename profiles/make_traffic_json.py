@@ -47,7 +47,7 @@ for w in ("c2", "c4", "c5"):
     F, Wr = parse(p("pmc_FETCH_SIZE")), parse(p("pmc_WRITE_SIZE"))
     FF, WF = parse(p("forward_pmc_FETCH_SIZE")), parse(p("forward_pmc_WRITE_SIZE"))
     ent = {"how": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python bench.py "
-                  "--workload %s --steps 2 --warmup 1 --no-cpu-baseline --train-steps 0 --no-graph (kernels) and -- python "
+                  "--full --workload %s --steps 2 --warmup 1 --no-cpu-baseline --train-steps 0 --no-graph (kernels) and -- python "
                   "tools/forward_only.py %s 3 (in_forward); per dispatch means; FETCH_SIZE doubled (gfx950 reports half of "
                   "a wide coalesced read); L2<->fabric side, Infinity-Cache hits included" % (w, w),
            "kernels": {}, "in_forward": {}}

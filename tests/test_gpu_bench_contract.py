@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,8 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract(cuda_device):
+    """`--full`: the line carries every side measurement (roofline, CPU baseline, training leg) next to the headline."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--cpu-seconds", "2", "--train-steps", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--cpu-seconds", "2", "--train-steps", "1"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines            # exactly ONE line on stdout
@@ -32,15 +35,34 @@ def test_bench_json_contract(cuda_device):
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in cpu, key
     assert cpu["kind"] == "port" and cpu["cores"] >= 1
-    assert "error" not in (r.get("train") or {})
+    assert r["full"] is True and "error" not in r["train"] and "error" not in r["serve"]
+    assert r["train"]["steps"] == 1 and r["serve"]["batches"] == 64 and r["kernels_us"] and r["gemm"]["alternatives"]
     # N = 1: the headline is the forward pass (BASELINE's metric as the reference runs it), no guard bit was raised
     assert r["value_is"] == "forward pass" and r["forward_value"] == r["value"] and r["range_guard_bits"] == 0
+
+
+def test_bench_plain_run_is_lean(cuda_device):
+    """Without `--full` the run is set-up, warm-up, the timed steps and the line: the headline fields say what they say
+    under `--full`, every side measurement is null -- also when its own options are given."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--train-steps", "2", "--serve-batches", "8"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    r = json.loads(lines[0])
+    assert r["full"] is False and r["n_gpus"] == 1 and r["steps"] == 3 and r["warmup"] == 1
+    assert r["unit"] == "mp-steps/s" and r["higher_is_better"] is True and r["dtype"] == "f32" and "n=40" in r["metric"]
+    assert r["value"] > 0 and abs(r["value"] - 32 * 1e3 / r["ms_per_step"]) / r["value"] < 1e-3
+    assert r["value_is"] == "forward pass" and r["forward_value"] == r["value"] and r["range_guard_bits"] == 0
+    for key in ("roofline", "roofline_cell", "roofline_dense", "cpu_baseline", "gemm", "kernels_us", "train", "serve",
+                "train_value", "train_ms_per_step"):
+        assert key in r and r[key] is None, key
+    assert np.isfinite(r["loss"])
 
 
 def test_bench_dump_outputs(cuda_device, tmp_path):
     """--dump-outputs DIR: after exactly --steps timed steps, the last step's outputs as float32 .npy files (at most
     64 MB), the same arrays the result line's loss and guard describe."""
-    import numpy as np
     d = tmp_path / "out"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
                           "--no-cpu-baseline", "--serve-batches", "0", "--train-steps", "0", "--dump-outputs", str(d)],

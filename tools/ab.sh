@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 for i in $(seq $N); do
   for side in A B; do
     if [ $side = A ]; then unset TSPGNN_LIB; else export TSPGNN_LIB=$R/tools/variants/$V.so; fi
-    python $R/bench.py --workload $W --steps 30 --warmup 5 --no-cpu-baseline --train-steps ${TRAIN:-0} 2>/dev/null | python -c "
+    python $R/bench.py --full --workload $W --steps 30 --warmup 5 --no-cpu-baseline --train-steps ${TRAIN:-0} 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readlines()[-1])
 k = j.get('kernels_us', {})

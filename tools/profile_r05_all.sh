@@ -13,7 +13,7 @@ stats() {  # db, title, out
 }
 for w in ${WORKLOADS:-c2 c4 c5 c1}; do
   steps=20; [ $w != c2 ] && [ $w != c1 ] && steps=6
-  python $R/bench.py --workload $w --steps $steps --warmup 3 --train-steps $([ $w = c5 ] && echo 0 || echo 2) > $O/${w}_bench.json 2> $O/${w}_bench.err
+  python $R/bench.py --full --workload $w --steps $steps --warmup 3 --train-steps $([ $w = c5 ] && echo 0 || echo 2) > $O/${w}_bench.json 2> $O/${w}_bench.err
   rm -rf $O/kt_$w
   rocprofv3 --kernel-trace --stats -d $O/kt_$w -o k -- python $R/tools/forward_graph.py $w 20 > $O/kt_$w.log 2>&1
   f=$(find $O/kt_$w -name "*.db" | head -1)
@@ -22,7 +22,7 @@ for w in ${WORKLOADS:-c2 c4 c5 c1}; do
   if [ $w != c1 ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/pmc_${w}_$c
-    rocprofv3 --kernel-trace --pmc $c -d $O/pmc_${w}_$c -o p -- python $R/bench.py --workload $w --steps 2 --warmup 1 --no-cpu-baseline --train-steps 0 --no-graph > $O/pmc_${w}_$c.log 2>&1
+    rocprofv3 --kernel-trace --pmc $c -d $O/pmc_${w}_$c -o p -- python $R/bench.py --full --workload $w --steps 2 --warmup 1 --no-cpu-baseline --train-steps 0 --no-graph > $O/pmc_${w}_$c.log 2>&1
     f=$(find $O/pmc_${w}_$c -name "*.db" | head -1)
     python $R/profiles/summarize_pmc.py $f > $O/${w}_pmc_$c.txt
     rm -rf $O/pmcf_${w}_$c
@@ -43,12 +43,12 @@ for spec in "c1 0" "c2 4"; do
   find $O -name "*.db" -delete
 done
 # training steps
-python $R/bench.py --mode train --steps 5 --warmup 2 --no-cpu-baseline > $O/c2_train_bench.json 2> $O/c2_train_bench.err
+python $R/bench.py --full --mode train --steps 5 --warmup 2 --no-cpu-baseline > $O/c2_train_bench.json 2> $O/c2_train_bench.err
 rm -rf $O/kt_c2t
 rocprofv3 --kernel-trace --stats -d $O/kt_c2t -o k -- python $R/bench.py --mode train --steps 5 --warmup 2 --no-cpu-baseline > $O/kt_c2t.log 2>&1
 f=$(find $O/kt_c2t -name "*.db" | head -1)
 stats $f "round 5: python bench.py --mode train --steps 5 --warmup 2 --no-cpu-baseline (C2 training step, HIP-graph replay)" $O/c2_train_kernel_stats.txt
-python $R/bench.py --workload c5 --mode train --steps 3 --warmup 2 --no-cpu-baseline --no-graph > $O/c5_train_bench.json 2> $O/c5_train_bench.err
+python $R/bench.py --full --workload c5 --mode train --steps 3 --warmup 2 --no-cpu-baseline --no-graph > $O/c5_train_bench.json 2> $O/c5_train_bench.err
 rm -rf $O/kt_c5t
 rocprofv3 --kernel-trace --stats -d $O/kt_c5t -o k -- python $R/bench.py --workload c5 --mode train --steps 1 --warmup 1 --no-cpu-baseline --no-graph > $O/kt_c5t.log 2>&1
 f=$(find $O/kt_c5t -name "*.db" | head -1)
