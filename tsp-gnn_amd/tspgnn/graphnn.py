@@ -11,6 +11,7 @@ aggregation kernels; a 0/1 matrix with exactly two ones per row (the TSP EV matr
 gather path.
 """
 from collections import namedtuple
+from types import SimpleNamespace
 
 import ctypes
 import os
@@ -486,7 +487,7 @@ class LayerNormBasicLSTMCell(object):
 
     def fuses_pushed_data_gradient(self):
         """The pushed cell's data gradient can ride in its backward launch (f16x2, d == dx == 64)."""
-        return self.d == 64 and self.dx == 64 and os.environ.get("TSPGNN_FUSE_DATA_GRADIENTS", "1") != "0"
+        return self.d == 64 and self.dx == 64
 
     def pushed_backward_data(self, mlp, dz, dx_out, dh_in):
         """[d(aggregate) | dh] = dz K'^T."""
@@ -573,44 +574,34 @@ class LayerNormBasicLSTMCell(object):
         return self._backward_task(h, c, self.packed("K" if adj is None else "Kh", "bf16"), dh_out, dc_out, dz, dc_in, ws,
                                    defer_reduce=1, **form)
 
-    def backward_data_bf16(self, dz, dx_out, dh_in):
-        """[dx | dh] = dz K^T on the bf16 matrix cores (the weights are bf16-exact in this mode)."""
-        W = self.packed("K", "bf16T")
-        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(W), _lib.ptr(dx_out), self.dx,
-                  _lib.ptr(dh_in), self.d, 0, dz.shape[0], _lib.current_stream())
-
-    def gather_backward_data_bf16(self, adj, dz, dh_in, dzx, dy):
-        """dh = dz Kh^T, dZx = EV^T dz, dy = dZx Kx^T (gather_backward_data with bf16-exact weights)."""
-        st = _lib.current_stream()
-        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("Kh", "bf16T")),
-                  None, 0, _lib.ptr(dh_in), self.d, 0, dz.shape[0], st)
-        adj.matmul(dz, transpose=True, out=dzx)
-        _lib.call("tspgnn_linear_bf16w_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.packed("Kx", "bf16T")),
-                  None, 0, _lib.ptr(dy), self.dx, 0, dzx.shape[0], st)
-
     def backward_finish(self, ws):
         """Fold the LayerNorm-gradient partials that the deferred backward launches of all time steps left in ws."""
         _lib.call("tspgnn_lnlstm_bwd_finish_f32", _lib.ptr(ws), _lib.ptr(self.ln_grad()), self.d, _lib.current_stream())
 
-    def backward_data(self, dz, dx_out, dh_in):
-        """[dx | dh] = dz K^T."""
-        if (self.dx + self.d) not in (64, 128, 256):
+    # data-gradient GEMMs by ``form``: the fp32 kernel, or on a bf16 tape read as it is the bf16-exact weights of that mode
+    DATA_GEMM = {"f32": "tspgnn_linear_f32", "bf16": "tspgnn_linear_bf16w_f32"}
+
+    def check_backward_data(self, form):
+        if form == "f32" and (self.dx + self.d) not in (64, 128, 256):
             raise NotImplementedError("LSTM backward needs dx+d in {64,128,256} (got %d)" % (self.dx + self.d))
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("K", "f32T")), _lib.ptr(dx_out),
+
+    def backward_data(self, dz, dx_out, dh_in, form="f32"):
+        """[dx | dh] = dz K^T."""
+        self.check_backward_data(form)
+        _lib.call(self.DATA_GEMM[form], _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("K", form + "T")), _lib.ptr(dx_out),
                   self.dx, _lib.ptr(dh_in), self.d, 0, dz.shape[0], _lib.current_stream())
 
-    def gather_backward_data(self, adj, dz, dh_in, dzx, dy):
+    def gather_backward_data(self, adj, dz, dh_in, dzx, dy, form="f32"):
         """dh = dz Kh^T (unless the cell launch already formed it: dh_in None), dZx = EV^T dz, dy = dZx Kx^T (``dy`` None:
         left to the source MLP's backward launch)."""
         st = _lib.current_stream()
         if dh_in is not None:
-            _lib.call("tspgnn_linear_f32", _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("Kh", "f32T")), None, 0, _lib.ptr(dh_in),
-                      self.d, 0, dz.shape[0], st)
+            _lib.call(self.DATA_GEMM[form], _lib.ptr(dz), 4 * self.d, _lib.ptr(self.packed("Kh", form + "T")), None, 0,
+                      _lib.ptr(dh_in), self.d, 0, dz.shape[0], st)
         adj.matmul(dz, transpose=True, out=dzx)
-        if dy is None:
-            return
-        _lib.call("tspgnn_linear_f32", _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.packed("Kx", "f32T")), None, 0, _lib.ptr(dy),
-                  self.dx, 0, dzx.shape[0], st)
+        if dy is not None:
+            _lib.call(self.DATA_GEMM[form], _lib.ptr(dzx), 4 * self.d, _lib.ptr(self.packed("Kx", form + "T")), None, 0,
+                      _lib.ptr(dy), self.dx, 0, dzx.shape[0], st)
 
     def backward_weights_folded(self, y_all, dzx_all, rows_src, h_all, dz_all, rows):
         """dKx += y^T dZx over T*n_src rows (instead of T*M), dKh += h^T dz over T*M rows."""
@@ -1791,31 +1782,65 @@ class GraphNN(object):
             (g_in,) = torch.autograd.grad(y, x, grad_outputs=g_out.to(y.dtype))
         return g_in
 
-    def _backward(self, tape, dstates):
-        T, mats = tape.T, tape.mats
-        device = self.store.theta.device
-        f32 = dict(dtype=torch.float32, device=device)
+    def _vet_native_mlp_h2(self, tape):
+        """bf16-native pass: -> the message MLPs' data gradient runs on tspgnn_mlp_bwd_multi_h2.  That kernel packs 2^s W^T
+        into fp16 pieces, which the bf16 forward never vetted: pack up front and look at the guard's weight word (one
+        4-byte read per backward pass) -- beyond half the fp16 range the pass uses tspgnn_mlp_bwd_multi_f32.  A pass being
+        CAPTURED (or one without a device) cannot look: it follows the eager pass before it (Session.capture_train_step
+        warms up eagerly) and its replays watch the word at the f16x2 guard's lag."""
+        store = self.store
+        can_look = store.theta.is_cuda and not torch.cuda.is_current_stream_capturing()
+        if not self.mlp_backward_h2 or not (can_look or self._mlp_h2_native_ok):
+            return False
+        for (v, i), acts in tape.acts.items():      # the packs the pass will use
+            mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
+            if mlp.backward_h2_ok(acts):
+                for l0, nl in mlp._chunks():
+                    mlp.wt_packed(l0, l0 + nl - 1, mlp.sizes[-1], h2=True)
+        if can_look:
+            guard = store.h2_guard()
+            bits = int(guard[1].item())
+            guard[1:2].zero_()
+            store.h2_packs_pending = 0
+            self._mlp_h2_native_ok = bits < store.H2_WEIGHT_LIMIT_BITS
+        return self._mlp_h2_native_ok
+
+    def _backward_plan(self, tape):
+        """Every decision of a backward pass over ``tape``, taken before its first launch (the only reader of
+        TSPGNN_BF16_BACKWARD and TSPGNN_FUSE_DATA_GRADIENTS); fills tape.native and last_backward.  -> a namespace of
+          native: a bf16 tape read as it is by the bf16 kernels (widths 64 / 128; narrow widths widen slices of the tape for
+          the fp32 kernels); cells: the cell kernels' arithmetic "bf16" / "h2" / "f32" (it follows the forward); form {var:
+          "folded" | "pushed" | "plain"}; mlp_h2: the message MLPs' data gradient is f16x2 where the kernel covers the chain;
+          fused_data / projected {var: its data-gradient GEMM rides in one of the step's launches -- a pushed cell's
+          [d(aggregate) | dh] = dz K'^T as a second phase of its task, a folded cell's dy = dZx Kx^T as the head of its
+          source MLP's chain}; n {var: rows}; per_step, CH: bytes of chunk buffers per step, steps per chunk."""
+        T, rc, folded, device = tape.T, tape.rc, tape.folded, self.store.theta.device
         n = {v: tape.H[v].shape[1] for v in self.var}
-        folded = tape.folded
-        bwd_arith = "h2" if tape.arith == "h2" else None   # the cells' backward follows the forward
-        # bf16-storage tape: the bf16-reading backward kernels take the tape's arrays as they are (widths 64 / 128; the
-        # narrow widths widen slices of the tape for the fp32 kernels instead)
         native = tape.arith == "bf16" and all(d in (64, 128) for d in self.var.values()) \
             and all(c.dx % 64 == 0 for c in self._RNN_cells.values()) \
             and os.environ.get("TSPGNN_BF16_BACKWARD", "native") == "native"
         tape.native = native
-        # Weight gradients are one reduction per variable over a CHUNK of time steps: all T when the gradients w.r.t.
-        # the pre-activations of the chunk (4d + the MLP layers' d floats per row and step) fit the budget -- the C2
-        # case, ~6 GB -- else the largest chunk that does (a C5 shard: 84 GB for all 64 steps)
-        pushed = tape.pushed
-        rc = tape.rc                              # entries whose backward recomputes the hidden activations and forms the
-                                                  # weight gradients in the same launch (no chunk buffers)
+        cells = "bf16" if native else ("h2" if tape.arith == "h2" else "f32")
+        form = {v: "folded" if folded[v] is not None else ("pushed" if tape.pushed[v] else "plain") for v in self.var}
+        for v, cell in self._RNN_cells.items():
+            if form[v] == "plain" and T > 0:
+                cell.check_backward_data("bf16" if native else "f32")
+        fuse_data = cells == "h2" and os.environ.get("TSPGNN_FUSE_DATA_GRADIENTS", "1") != "0"
+        fused_data = {v: bool(fuse_data and form[v] == "pushed" and self._RNN_cells[v].fuses_pushed_data_gradient())
+                      for v in self.var}
+        projected = {}
+        for v in self.var:
+            u0 = self.loop[v][0]
+            projected[v] = bool(
+                fuse_data and form[v] == "folded" and "msg" in u0 and not rc.get((v, 0)) and self.mlp_backward_h2 and T > 0
+                and self._msg_MLPs[u0["msg"]].backward_task_takes_projection(tape.acts_at((v, 0), 0)[0],
+                                                                              4 * self._RNN_cells[v].d))
         per_step = sum(n[v] * 4 * d * 4 for v, d in self.var.items())
         per_step += sum(self._msg_MLPs[self.loop[v][i]["msg"]].n_square * n[self.loop[v][i]["var"]]
                         * self.var[self.loop[v][i]["var"]] * 4 * (0 if rc.get((v, i)) else 1)
                         for (v, i) in tape.acts)
-        per_step += sum(tape.X[v].shape[1] * 4 * self.var[v] * 4 for v in self.var if folded[v] is not None)   # DZX
-        per_step += sum(n[v] * 4 for v in self.var if pushed[v])          # degrees
+        per_step += sum(tape.X[v].shape[1] * 4 * self.var[v] * 4 for v in self.var if form[v] == "folded")   # DZX
+        per_step += sum(n[v] * 4 for v in self.var if form[v] == "pushed")          # degrees
         if tape.arith == "bf16" and not native:
             # widened fp32 copies of the chunk's tape slices (h, cell inputs, hidden activations) for the fp32 reductions
             per_step += sum(n[v] * d * 4 + tape.X[v].shape[1] * tape.X[v].shape[2] * 4 for v, d in self.var.items())
@@ -1826,243 +1851,218 @@ class GraphNN(object):
             # allocator holds but has not handed out counts as free
             avail = torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
             budget = min(budget, avail // 2)
+        # Weight gradients are one reduction per variable over a CHUNK of time steps: all T when the gradients w.r.t. the
+        # pre-activations fit the budget (the C2 case, ~6 GB), else the largest chunk that does (a C5 shard: 84 GB for 64 steps)
         CH = max(1, min(T, int(budget // max(per_step, 1)))) if T > 0 else 1
-        DZ = {v: torch.empty((CH, n[v], 4 * d), **f32) for v, d in self.var.items()}
-        # bf16-storage tape: the f16x2 data gradient of the message MLPs packs 2^s W^T into fp16 pieces, which the bf16 forward
-        # never vetted -- pack now and look at the guard's weight word (one 4-byte read per backward pass): beyond half the fp16
-        # range the pass uses tspgnn_mlp_bwd_multi_f32.  A pass being CAPTURED cannot look: it follows the eager pass before it
-        # (Session.capture_train_step warms up eagerly) and its replays watch the word at the f16x2 guard's lag
-        mlp_h2_native = bool(native and self.mlp_backward_h2 and self._mlp_h2_native_ok)
-        if native and self.mlp_backward_h2 and device.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-            store = self.store
-            for (v, i), acts in tape.acts.items():
-                mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
-                if mlp.backward_h2_ok(acts):
-                    for l0, nl in mlp._chunks():
-                        mlp.wt_packed(l0, l0 + nl - 1, mlp.sizes[-1], h2=True)
-            guard = store.h2_guard()
-            bits = int(guard[1].item())
-            guard[1:2].zero_()
-            store.h2_packs_pending = 0
-            mlp_h2_native = self._mlp_h2_native_ok = bits < store.H2_WEIGHT_LIMIT_BITS
-        DPRE, RCP = {}, {}
-        for (v, i), acts in tape.acts.items():
+        mlp_h2 = bool(self.mlp_backward_h2 and cells == "h2") or bool(native and self._vet_native_mlp_h2(tape))
+        self._last_backward = {
+            "forward": tape.arith or "f32", "backward": ("bf16-native" if native else "bf16-widened") if tape.arith == "bf16" else cells,
+            "folded": {v: form[v] == "folded" for v in self.var}, "pushed": {v: form[v] == "pushed" for v in self.var},
+            "fused_data": dict(fused_data), "projected": dict(projected), "chunk_steps": CH, "chunks": -(-T // CH)}
+        return SimpleNamespace(n=n, native=native, cells=cells, form=form, mlp_h2=mlp_h2, fused_data=fused_data,
+                               projected=projected, per_step=per_step, CH=CH)
+
+    def _backward_buffers(self, tape, plan):
+        """What a pass allocates once, from the plan -> a namespace of the chunk buffers DZ {var: dz [CH, rows, 4d]}, DZX
+        (folded cells: dZx per source row), DPRE {(var, i): the message MLP's dpre [layers, CH, rows, d]}; RCP (recomputed
+        entries: workgroup partials of {dW, db} over all T steps); ws (LayerNorm-gradient partials of all T steps, zeroed);
+        push (pushed cells: message MLP, degrees, gradients w.r.t. W Kx [dx, 4d] and b Kx [4d]) -- folded after the loop."""
+        n, CH = plan.n, plan.CH
+        f32 = dict(dtype=torch.float32, device=self.store.theta.device)
+        b = SimpleNamespace(DZX={}, DPRE={}, RCP={}, push={})
+        b.DZ = {v: torch.empty((CH, n[v], 4 * d), **f32) for v, d in self.var.items()}
+        for (v, i) in tape.acts:
             u = self.loop[v][i]
             mlp = self._msg_MLPs[u["msg"]]
-            if rc.get((v, i)):
-                RCP[(v, i)] = mlp.backward_rc_partial(mlp.n_square - 1)   # workgroup partials of {dW, db}, all T steps
-                continue
-            DPRE[(v, i)] = torch.empty((mlp.n_square - (1 if pushed[v] else 0), CH, n[u["var"]], self.var[u["var"]]), **f32)
-        # LayerNorm-gradient partials of all T steps accumulate here (zeroed); one fold per cell after the loop
-        ws = {v: _lib.workspace("tspgnn_lnlstm_bwd_workspace_floats", d, device=device).zero_() for v, d in self.var.items()}
-        DZX = {v: torch.empty((CH, tape.X[v].shape[1], 4 * self.var[v]), **f32) for v in self.var if folded[v] is not None}
-
-        # pushed cells: gradients w.r.t. the products W Kx [dx, 4d] and b Kx [4d], split into dW, db, dKx after the loop
-        push = {}
+            if tape.rc.get((v, i)):
+                b.RCP[(v, i)] = mlp.backward_rc_partial(mlp.n_square - 1)
+            else:       # (a pushed entry's last layer has its gradient formed on the receiving side)
+                b.DPRE[(v, i)] = torch.empty((mlp.n_square - (plan.form[v] == "pushed"), CH, n[u["var"]], self.var[u["var"]]), **f32)
+        b.ws = {v: _lib.workspace("tspgnn_lnlstm_bwd_workspace_floats", d, device=f32["device"]).zero_() for v, d in self.var.items()}
         for v, d in self.var.items():
-            if pushed[v]:
-                deg = self._pushed_degrees(v, mats)
-                push[v] = dict(mlp=self._msg_MLPs[self.loop[v][0]["msg"]], deg=deg, deg_steps=deg.repeat(CH),
-                               g_wkx=torch.zeros((self._RNN_cells[v].dx, 4 * d), **f32), g_zb=torch.zeros((1, 4 * d), **f32))
+            if plan.form[v] == "folded":
+                b.DZX[v] = torch.empty((CH, tape.X[v].shape[1], 4 * d), **f32)
+            if plan.form[v] == "pushed":
+                deg = self._pushed_degrees(v, tape.mats)
+                b.push[v] = dict(mlp=self._msg_MLPs[self.loop[v][0]["msg"]], deg=deg, deg_steps=deg.repeat(CH),
+                                 g_wkx=torch.zeros((self._RNN_cells[v].dx, 4 * d), **f32), g_zb=torch.zeros((1, 4 * d), **f32))
+        return b
 
-        def weight_gradients(t0, t1):
-            """Steps [t0, t1): their dz / dpre sit in slots 0 .. t1-t0-1 of the chunk buffers."""
-            steps = t1 - t0
-            for v, d in self.var.items():
-                cell = self._RNN_cells[v]
-                if pushed[v]:
-                    cell.pushed_backward_weights(tape.x_steps(v, t0, t1), tape.h_steps(v, t0, t1), DZ[v][:steps].view(-1, 4 * d),
-                                                 steps * n[v], push[v]["deg_steps"], push[v]["g_wkx"], push[v]["g_zb"])
-                elif folded[v] is not None:
-                    rows_src = steps * tape.X[v].shape[1]
-                    cell.backward_weights_folded(tape.x_steps(v, t0, t1), DZX[v][:steps].view(-1, 4 * d), rows_src,
-                                                 tape.h_steps(v, t0, t1), DZ[v][:steps].view(-1, 4 * d), steps * n[v])
-                else:
-                    cell.backward_weights(tape.x_steps(v, t0, t1), tape.h_steps(v, t0, t1), DZ[v][:steps].view(-1, 4 * d),
-                                          steps * n[v])
-            for (v, i), dpre in DPRE.items():
-                u = self.loop[v][i]
-                mlp = self._msg_MLPs[u["msg"]]
-                src, dsrc = u["var"], self.var[u["var"]]
-                layers = dpre.shape[0]      # (a pushed entry's last layer has its gradient formed on the receiving side)
-                first = tape.h_steps(src, t0, t1)
-                if "fun" in u:      # the MLP's input rows are fun(h), step by step as the forward formed them
-                    with torch.no_grad():
-                        first = torch.cat([u["fun"](tape.h(src, t)).to(torch.float32) for t in range(t0, t1)], dim=0).contiguous()
-                inputs = [first] + [tape.acts_steps((v, i), l, t0, t1) for l in range(layers - 1)]
-                mlp.backward_weights(inputs, [dpre[l, :steps].reshape(-1, dsrc) for l in range(layers)], steps * n[src],
-                                     n_layers=layers)
+    def _backward_weights(self, tape, plan, buf, t0, t1):
+        """Weight gradients of steps [t0, t1): their dz / dpre sit in slots 0 .. t1-t0-1 of the chunk buffers."""
+        steps, n = t1 - t0, plan.n
+        for v, d in self.var.items():
+            cell, push = self._RNN_cells[v], buf.push.get(v)
+            x, h, dz = tape.x_steps(v, t0, t1), tape.h_steps(v, t0, t1), buf.DZ[v][:steps].view(-1, 4 * d)
+            if plan.form[v] == "pushed":
+                cell.pushed_backward_weights(x, h, dz, steps * n[v], push["deg_steps"], push["g_wkx"], push["g_zb"])
+            elif plan.form[v] == "folded":
+                cell.backward_weights_folded(x, buf.DZX[v][:steps].view(-1, 4 * d), steps * tape.X[v].shape[1], h, dz, steps * n[v])
+            else:
+                cell.backward_weights(x, h, dz, steps * n[v])
+        for (v, i), dpre in buf.DPRE.items():
+            u = self.loop[v][i]
+            src, dsrc = u["var"], self.var[u["var"]]
+            layers = dpre.shape[0]
+            first = tape.h_steps(src, t0, t1)
+            if "fun" in u:      # the MLP's input rows are fun(h), step by step as the forward formed them
+                with torch.no_grad():
+                    first = torch.cat([u["fun"](tape.h(src, t)).to(torch.float32) for t in range(t0, t1)], dim=0).contiguous()
+            inputs = [first] + [tape.acts_steps((v, i), l, t0, t1) for l in range(layers - 1)]
+            self._msg_MLPs[u["msg"]].backward_weights(inputs, [dpre[l, :steps].reshape(-1, dsrc) for l in range(layers)],
+                                                      steps * n[src], n_layers=layers)
 
+    def _cell_backward_task(self, v, t, tape, plan, buf, s):
+        """v's task of step t's cell launch (recompute z, LayerNorm / gate gradients), in the plan's form."""
+        cell, form = self._RNN_cells[v], plan.form[v]
+        h_t, c_t = tape.h(v, t), tape.C[v][t]
+        grads = (s.dH[v], s.dC[v], buf.DZ[v][s.k], s.ndC[v], buf.ws[v])
+        if form == "folded":
+            adj, zx_t = tape.mats[tape.folded[v]["mat"]], tape.zx(v, t)
+            if plan.native:
+                return cell.backward_task_bf16(None, h_t, c_t, *grads, adj=adj, zx=zx_t)
+            s.keep += [h_t, zx_t]
+            return cell.gather_backward_task(adj, zx_t, h_t, c_t, *grads, dh_in=s.ndH[v], defer=True, arith=plan.cells)
+        if form == "pushed":
+            push = buf.push[v]
+            kp, zb = cell.pushed_bias_pack(push["mlp"], arith="h2")
+            # (fused_data: [d(aggregate) | dh] = dz K'^T as a second phase of the task's workgroups, one launch less a step)
+            data = (cell.packed("K", "h2T", pushed=push["mlp"]), s.dX[v], s.ndH[v]) if plan.fused_data[v] else None
+            return cell.pushed_backward_task(tape.x(v, t), h_t, c_t, *grads, kp, zb, push["deg"], defer=True, data=data)
+        x_t = tape.x(v, t)
+        if plan.native:
+            return cell.backward_task_bf16(x_t, h_t, c_t, *grads)
+        s.keep += [h_t, x_t]
+        return cell.backward_task(x_t, h_t, c_t, *grads, defer=True, arith=plan.cells)
+
+    def _cell_backward_data(self, v, tape, plan, buf, s):
+        """Data gradients of v's cell GEMMs: these WRITE dh (s.ndH[v]), the message paths ACCUMULATE into it.  s.dX[v] becomes
+        the gradient w.r.t. the cell input -- folded: w.r.t. the message y (source rows); pushed: w.r.t. the aggregated last
+        hidden activation."""
+        cell, dz, gemm = self._RNN_cells[v], buf.DZ[v][s.k], "bf16" if plan.native else "f32"
+        if plan.form[v] == "folded":
+            # (fp32, d == 64: dh was formed by the cell launch; projected: dy = dZx Kx^T is left to the message MLP's launch)
+            cell.gather_backward_data(tape.mats[tape.folded[v]["mat"]], dz, s.ndH[v] if plan.native or cell.d != 64 else None,
+                                      buf.DZX[v][s.k], None if plan.projected[v] else s.dX[v], gemm)
+        elif plan.form[v] == "plain":
+            cell.backward_data(dz, s.dX[v], s.ndH[v], gemm)
+        elif not plan.fused_data[v]:
+            cell.pushed_backward_data(buf.push[v]["mlp"], dz, s.dX[v], s.ndH[v])
+
+    def _message_backward(self, v, i, t, tape, plan, buf, s):
+        """Loop entry (v, i) at step t, from the gradient w.r.t. its columns of v's cell input: the adjoint adjacency product
+        (or its gather inside the MLP launch), the pull-back through 'fun', and the message MLP's data gradient -- as a task
+        of the step's launch (s.mlp_tasks: plain, pushed prefix, or starting from the projection; s.rc_tasks: recomputed),
+        else in launches of its own."""
+        u = self.loop[v][i]
+        if "var" not in u:      # an appended matrix is a constant of the graph: its columns' gradient ends here
+            return
+        off, w = sum(self._update_width(x) for x in self.loop[v][:i]), self._update_width(u)
+        dy = s.dX[v] if len(self.loop[v]) == 1 else s.dX[v][:, off:off + w].contiguous()
+        src, k, ndh = u["var"], s.k, s.ndH[u["var"]]
+        mlp = self._msg_MLPs[u["msg"]] if "msg" in u else None
+        adjoint = dict(transpose=not u.get("transpose?", False))    # of mat (x) y: mat^T (x) dy, and vice versa
+        if mlp is not None and not tape.rc.get((v, i)):
+            (acts_t, acts_stride), dpre = tape.acts_at((v, i), t), buf.DPRE[(v, i)]
+            chain = (acts_t, acts_stride, None, dpre[:, k], dpre.stride(0))
+        if "fun" in u:
+            # graphnn.py:149-151: y = fun(h) ahead of the message MLP.  The gradient w.r.t. fun's OUTPUT is formed apart
+            # (adjoint product, the MLP's backward on its own, never fused with another writer of dh), then pulled back
+            # through fun (_fun_vjp) and added to dh of the source
+            if "mat" in u:
+                dy = tape.mats[u["mat"]].matmul(dy, **adjoint)
+            if mlp is not None:
+                g_out = torch.empty_like(ndh)
+                mlp.backward_data(dy, *chain, g_out, accumulate=False, h2=False)
+                dy = g_out
+            ndh.add_(self._fun_vjp(u["fun"], tape.h(src, t), dy))
+            return
+        # The tasks of the step's launch accumulate into dh side by side: one per source.  A second writer of dh[src] runs
+        # in launches of its own, ahead of it (a recomputed or pushed entry has no such form)
+        first = src not in s.targets
+        gather_uv = None
+        if "mat" in u and plan.form[v] != "folded":
+            adj = tape.mats[u["mat"]]
+            if first and u.get("transpose?", False) and adj.uv is not None and mlp is not None \
+                    and mlp.backward_task_fuses_gather(dy):
+                gather_uv = adj.uv     # the adjoint of the row-sum is a two-row gather: the MLP launch forms it
+            else:
+                dy = adj.matmul(dy, **adjoint)
+        if mlp is None:
+            ndh.add_(dy)
+            return
+        if tape.rc.get((v, i)):     # the chain is recomputed from its input rows; data and weight gradients in one launch
+            if not first:
+                raise NotImplementedError("recomputed message MLP: a second writer of the source's gradient")
+            h_src = tape.h(src, t)
+            s.keep += [dy, h_src]
+            s.rc_tasks.append((mlp, mlp.backward_rc_task(mlp.n_square - 1, h_src, tape.acts[(v, i)][0, t], dy, ndh, True,
+                                                         gather_uv=gather_uv, partial=buf.RCP[(v, i)])))
+            s.targets.append(src)
+            return
+        s.keep += [dy, acts_t]
+        h2 = bool(plan.mlp_h2 and mlp.backward_h2_ok(acts_t))
+        cell, task = self._RNN_cells[v], None
+        if plan.form[v] == "pushed":   # the chain ends at the last hidden activation (a relu layer: masked by its output)
+            if first:
+                task = mlp.backward_prefix_task(dpre.shape[0], dy, acts_t, acts_stride, acts_t[dpre.shape[0] - 1], *chain[3:],
+                                                ndh, True, gather_uv=gather_uv, h2=h2)
+            if task is None:
+                raise NotImplementedError("pushed training needs the message MLP's backward in one launch")
+        elif plan.projected[v] and first:   # the chain starts from dZx Kx^T, formed inside the launch
+            task = mlp.backward_task(None, *chain, ndh, True, h2=True, pre=(buf.DZX[v][k], cell.packed("Kx", "h2T")))
+        else:
+            if plan.projected[v]:
+                _lib.call("tspgnn_linear_f32", _lib.ptr(buf.DZX[v][k]), 4 * cell.d, _lib.ptr(cell.packed("Kx", "f32T")), None, 0,
+                          _lib.ptr(dy), cell.dx, 0, buf.DZX[v][k].shape[0], _lib.current_stream())
+            if first:
+                task = mlp.backward_task(dy, *chain, ndh, True, gather_uv=gather_uv, h2=h2)
+        if task is None:    # several kernels, or a second writer
+            mlp.backward_data(dy, *chain, ndh, accumulate=True, h2=h2)
+        else:
+            s.mlp_tasks.setdefault((self.var[src], h2), []).append(task)
+            s.targets.append(src)
+
+    def _backward(self, tape, dstates):
+        """What _backward_plan decided, on _backward_buffers' arrays: per step, in reverse, the three launches (per width) of
+        the builders above, the weight gradients flushed chunk by chunk, then the deferred reductions."""
+        T, plan = tape.T, self._backward_plan(tape)
+        buf = self._backward_buffers(tape, plan)
+        f32 = dict(dtype=torch.float32, device=self.store.theta.device)
         dH = {v: (dstates.get(v, (None, None))[0]) for v in self.var}
         dC = {v: (dstates.get(v, (None, None))[1]) for v in self.var}
-        # The vertex side's two data-gradient GEMMs ride in the step's two backward launches (TSPGNN_FUSE_DATA_GRADIENTS=0: as
-        # launches of their own): a pushed cell's [d(aggregate) | dh] = dz K'^T as a second phase of its backward task,
-        # a folded cell's dy = dZx Kx^T as the head of its source MLP's chain
-        fuse_data = bwd_arith == "h2" and not native and os.environ.get("TSPGNN_FUSE_DATA_GRADIENTS", "1") != "0"
-        fused_data = {v: bool(fuse_data and pushed[v] and self._RNN_cells[v].fuses_pushed_data_gradient()) for v in self.var}
-        projected = {}
-        for v in self.var:
-            u0 = self.loop[v][0]
-            projected[v] = bool(
-                fuse_data and folded[v] is not None and len(self.loop[v]) == 1 and "msg" in u0 and "fun" not in u0
-                and not rc.get((v, 0)) and not pushed[v] and self.mlp_backward_h2 and T > 0
-                and self._msg_MLPs[u0["msg"]].backward_task_takes_projection(tape.acts_at((v, 0), 0)[0],
-                                                                              4 * self._RNN_cells[v].d))
-        arith = tape.arith
-        self._last_backward = {
-            "forward": arith or "f32",
-            "backward": ("bf16-native" if native else "bf16-widened") if arith == "bf16" else (bwd_arith or "f32"),
-            "folded": {v: folded[v] is not None for v in self.var}, "pushed": {v: bool(pushed[v]) for v in self.var},
-            "fused_data": dict(fused_data), "projected": dict(projected), "chunk_steps": CH, "chunks": -(-T // CH)}
         for t in range(T - 1, -1, -1):
-            k = t % CH      # slot of step t in the chunk buffers (chunks start at multiples of CH)
-            ndH = {v: torch.empty((n[v], d), **f32) for v, d in self.var.items()}
-            ndC = {v: torch.empty((n[v], d), **f32) for v, d in self.var.items()}
-            dX = {v: torch.empty((tape.X[v].shape[1], self._RNN_cells[v].dx), **f32) for v in self.var}
-            keep = []       # widened tape slices stay alive until the step's launches are enqueued
-            # ---- 1: every cell's backward (recompute z, LayerNorm / gate gradients) in one launch per width
+            # the step's own -- k: its slot in the chunk buffers (chunks start at multiples of CH); keep: what has to stay
+            # alive until the step's launches are enqueued; targets: the sources whose dh a task of the message launch writes
+            s = SimpleNamespace(k=t % plan.CH, dH=dH, dC=dC, keep=[], mlp_tasks={}, rc_tasks=[], targets=[])
+            s.ndH = {v: torch.empty((plan.n[v], d), **f32) for v, d in self.var.items()}
+            s.ndC = {v: torch.empty((plan.n[v], d), **f32) for v, d in self.var.items()}
+            s.dX = {v: torch.empty((tape.X[v].shape[1], self._RNN_cells[v].dx), **f32) for v in self.var}
+            # ---- 1: every cell's backward in one launch per width
             tasks = {}
             for v, d in self.var.items():
-                cell = self._RNN_cells[v]
-                h_t, c_t = tape.h(v, t), tape.C[v][t]
-                if native:
-                    if folded[v] is not None:
-                        task = cell.backward_task_bf16(None, h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v], ws[v],
-                                                       adj=mats[folded[v]["mat"]], zx=tape.zx(v, t))
-                    else:
-                        task = cell.backward_task_bf16(tape.x(v, t), h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v], ws[v])
-                elif folded[v] is not None:
-                    zx_t = tape.zx(v, t)
-                    keep += [h_t, zx_t]
-                    task = cell.gather_backward_task(mats[folded[v]["mat"]], zx_t, h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v],
-                                                     ws[v], dh_in=ndH[v], defer=True, arith=bwd_arith)
-                elif pushed[v]:
-                    kp, zb = cell.pushed_bias_pack(push[v]["mlp"], arith="h2")
-                    # (d == dx == 64: [d(aggregate) | dh] = dz K'^T rides in this launch as a second phase of the task's
-                    # workgroups -- one launch less per step)
-                    data = (cell.packed("K", "h2T", pushed=push[v]["mlp"]), dX[v], ndH[v]) if fused_data[v] else None
-                    task = cell.pushed_backward_task(tape.x(v, t), h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v], ws[v], kp, zb,
-                                                     push[v]["deg"], defer=True, data=data)
-                else:
-                    x_t = tape.x(v, t)
-                    keep += [h_t, x_t]
-                    task = cell.backward_task(x_t, h_t, c_t, dH[v], dC[v], DZ[v][k], ndC[v], ws[v], defer=True,
-                                              arith=bwd_arith)
-                tasks.setdefault(d, []).append(task)
-            _lib.call_by_width("tspgnn_lnlstm_bwd_multi_" + ("bf16" if native else (bwd_arith or "f32")), tasks)
-            # ---- 2: data gradients of the cell GEMMs; these WRITE dh, the message paths below ACCUMULATE into it
+                tasks.setdefault(d, []).append(self._cell_backward_task(v, t, tape, plan, buf, s))
+            _lib.call_by_width("tspgnn_lnlstm_bwd_multi_" + plan.cells, tasks)
+            # ---- 2: data gradients of the cell GEMMs
             for v in self.var:
-                cell = self._RNN_cells[v]
-                if native and folded[v] is not None:
-                    cell.gather_backward_data_bf16(mats[folded[v]["mat"]], DZ[v][k], ndH[v], DZX[v][k], dX[v])
-                elif native:
-                    cell.backward_data_bf16(DZ[v][k], dX[v], ndH[v])
-                elif folded[v] is not None:   # dX[v] becomes the gradient w.r.t. the message y (source rows)
-                    cell.gather_backward_data(mats[folded[v]["mat"]], DZ[v][k], None if cell.d == 64 else ndH[v],
-                                              DZX[v][k], None if projected[v] else dX[v])
-                    # (d == 64: dh was formed by the cell launch; projected: dy = dZx Kx^T is left to the message MLP's launch)
-                elif pushed[v]:             # dX[v] becomes the gradient w.r.t. the aggregated last hidden activation
-                    if not fused_data[v]:
-                        cell.pushed_backward_data(push[v]["mlp"], DZ[v][k], dX[v], ndH[v])
-                else:
-                    cell.backward_data(DZ[v][k], dX[v], ndH[v])
+                self._cell_backward_data(v, tape, plan, buf, s)
             # ---- 3: adjoint adjacency products, then every message MLP's data gradient in one launch
-            mlp_tasks, rc_tasks, targets = [], [], []
             for v in self.var:
-                off = 0
-                for i, u in enumerate(self.loop[v]):
-                    w = self._update_width(u)
-                    if "var" not in u:      # an appended matrix is a constant of the graph: its columns' gradient ends here
-                        off += w
-                        continue
-                    dy = dX[v] if len(self.loop[v]) == 1 else dX[v][:, off:off + w].contiguous()
-                    off += w
-                    src = u["var"]
-                    gather_uv = None
-                    if "fun" in u:
-                        # graphnn.py:149-151: y = fun(h) ahead of the message MLP.  The gradient w.r.t. fun's OUTPUT is formed
-                        # apart (adjoint product, the MLP's backward on its own, never fused with another writer of dh), then
-                        # pulled back through fun (_fun_vjp) and added to dh of the source
-                        if "mat" in u:
-                            dy = mats[u["mat"]].matmul(dy, transpose=not u.get("transpose?", False))
-                        if "msg" in u:
-                            mlp = self._msg_MLPs[u["msg"]]
-                            (acts_t, acts_stride), dpre = tape.acts_at((v, i), t), DPRE[(v, i)]
-                            g_out = torch.empty((n[src], self.var[src]), **f32)
-                            mlp.backward_data(dy, acts_t, acts_stride, None, dpre[:, k], dpre.stride(0), g_out, accumulate=False,
-                                              h2=False)
-                        else:
-                            g_out = dy
-                        ndH[src].add_(self._fun_vjp(u["fun"], tape.h(src, t), g_out))
-                        continue
-                    if "mat" in u and folded[v] is None:   # adjoint of mat (x) y is mat^T (x) dy and vice versa
-                        adj = mats[u["mat"]]
-                        if u.get("transpose?", False) and adj.uv is not None and "msg" in u and src not in targets \
-                                and self._msg_MLPs[u["msg"]].backward_task_fuses_gather(dy):
-                            gather_uv = adj.uv     # the adjoint of the row-sum is a two-row gather: the MLP launch forms it
-                        else:
-                            dy = adj.matmul(dy, transpose=not u.get("transpose?", False))
-                    if "msg" in u and rc.get((v, i)):
-                        # the chain is recomputed from its input rows; data and weight gradients in one launch
-                        mlp = self._msg_MLPs[u["msg"]]
-                        if src in targets:
-                            raise NotImplementedError("recomputed message MLP: a second writer of the source's gradient")
-                        h_src = tape.h(src, t)
-                        keep.append(h_src)
-                        task = mlp.backward_rc_task(mlp.n_square - 1, h_src, tape.acts[(v, i)][0, t], dy, ndH[src], True,
-                                                    gather_uv=gather_uv, partial=RCP[(v, i)])
-                        rc_tasks.append((mlp, task, dy))
-                        targets.append(src)
-                        continue
-                    if "msg" in u:
-                        mlp = self._msg_MLPs[u["msg"]]
-                        (acts_t, acts_stride), dpre = tape.acts_at((v, i), t), DPRE[(v, i)]
-                        keep.append(acts_t)
-                        h2 = bool((bwd_arith == "h2" or mlp_h2_native) and self.mlp_backward_h2 and mlp.backward_h2_ok(acts_t))
-                        if projected[v]:   # the chain starts from dZx Kx^T, formed inside the launch
-                            cell = self._RNN_cells[v]
-                            if src not in targets:
-                                task = mlp.backward_task(None, acts_t, acts_stride, None, dpre[:, k], dpre.stride(0), ndH[src],
-                                                         True, h2=True, pre=(DZX[v][k], cell.packed("Kx", "h2T")))
-                                mlp_tasks.append(((self.var[src], True), task, None))
-                                targets.append(src)
-                                continue
-                            _lib.call("tspgnn_linear_f32", _lib.ptr(DZX[v][k]), 4 * cell.d, _lib.ptr(cell.packed("Kx", "f32T")), None, 0,
-                                      _lib.ptr(dy), cell.dx, 0, DZX[v][k].shape[0], _lib.current_stream())
-                        if pushed[v]:   # the chain ends at the last hidden activation (a relu layer: masked by its output)
-                            task = mlp.backward_prefix_task(dpre.shape[0], dy, acts_t, acts_stride, acts_t[dpre.shape[0] - 1],
-                                                            dpre[:, k], dpre.stride(0), ndH[src], True, gather_uv=gather_uv, h2=h2)
-                            if task is None or src in targets:
-                                raise NotImplementedError("pushed training needs the message MLP's backward in one launch")
-                            mlp_tasks.append(((self.var[src], h2), task, dy))
-                            targets.append(src)
-                            continue
-                        task = mlp.backward_task(dy, acts_t, acts_stride, None, dpre[:, k], dpre.stride(0),
-                                                 ndH[src], True, gather_uv=gather_uv, h2=h2)
-                        if task is None or src in targets:   # several kernels, or a second writer of ndH[src]
-                            mlp.backward_data(dy, acts_t, acts_stride, None, dpre[:, k], dpre.stride(0), ndH[src],
-                                              accumulate=True, h2=h2)
-                        else:
-                            mlp_tasks.append(((self.var[src], h2), task, dy))
-                            targets.append(src)
-                    else:
-                        ndH[src].add_(dy)
-            by_d = {}
-            for key, task, _ in mlp_tasks:
-                by_d.setdefault(key, []).append(task)
-            for (d, h2), ts in by_d.items():
+                for i in range(len(self.loop[v])):
+                    self._message_backward(v, i, t, tape, plan, buf, s)
+            for (d, h2), ts in s.mlp_tasks.items():
                 _lib.call_by_width("tspgnn_mlp_bwd_multi_" + ("h2" if h2 else "f32"), {d: ts})
-            for mlp, task, _ in rc_tasks:
+            for mlp, task in s.rc_tasks:
                 _lib.call("tspgnn_mlp_bwd_rc_h2", ctypes.cast(ctypes.pointer(task), ctypes.c_void_p), mlp.sizes[-1],
                           _lib.current_stream())
-            dH, dC = ndH, ndC
-            if k == 0:      # the chunk [t, t + CH) is complete
-                weight_gradients(t, min(t + CH, T))
-        for (v, i), part in RCP.items():
+            dH, dC = s.ndH, s.ndC
+            if s.k == 0:      # the chunk [t, t + CH) is complete
+                self._backward_weights(tape, plan, buf, t, min(t + plan.CH, T))
+        for (v, i), part in buf.RCP.items():
             mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
             mlp.backward_rc_finish(mlp.n_square - 1, part)
         for v in self.var:
-            self._RNN_cells[v].backward_finish(ws[v])      # LayerNorm parameters: the deferred per-step partials
-            if pushed[v]:
-                self._RNN_cells[v].pushed_backward_finish(push[v]["mlp"], push[v]["g_wkx"], push[v]["g_zb"])
+            self._RNN_cells[v].backward_finish(buf.ws[v])      # LayerNorm parameters: the deferred per-step partials
+            if plan.form[v] == "pushed":
+                self._RNN_cells[v].pushed_backward_finish(buf.push[v]["mlp"], buf.push[v]["g_wkx"], buf.push[v]["g_zb"])
         return {v: (dH[v], dC[v]) for v in self.var}
