@@ -9,155 +9,33 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import h2_zx_pack, rel_err
-from oracle import torch_oracle as TO
+import lstm_bwd_cases
+from conftest import rel_err
+from lstm_bwd_cases import dev, empty, k_chunked, packed_bf16, rb, release, workspace
 from tspgnn import _lib
 
 pytestmark = pytest.mark.gpu
 
-_KEEP = []
 TOL = 5e-6          # the fp32 backward kernels' bar (test_gpu_backward_kernels.py)
-GATES = ("input", "transform", "forget", "output", "state")
-
-
-def dev(a, device, dtype=np.float32):
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device)
-    _KEEP.append(t)
-    return t
-
-
-def dev_bf16(a, device):
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16).to(device)
-    _KEEP.append(t)
-    return t
-
-
-def empty(shape, device, fill=None):
-    t = torch.empty(shape, dtype=torch.float32, device=device) if fill is None else \
-        torch.full(shape, fill, dtype=torch.float32, device=device)
-    _KEEP.append(t)
-    return t
-
-
-def rb(x):
-    """Round to bf16 (nearest even), back in float32."""
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(torch.bfloat16).to(torch.float32).numpy()
 
 
 @pytest.fixture(autouse=True)
 def _release():
     yield
-    torch.cuda.synchronize()
-    del _KEEP[:]
+    release()
 
 
-def packed_bf16(W, device):
-    """Piece 0 of tspgnn_pack_weights_x3 = W rounded to bf16 in MFMA fragment order (bytes)."""
-    src = dev(W, device)
-    out = torch.empty(3 * W.size * 2, dtype=torch.uint8, device=device)
-    _KEEP.append(out)
-    _lib.call("tspgnn_pack_weights_x3", _lib.ptr(src), _lib.ptr(out), W.shape[0], W.shape[1], None)
-    return out[:W.size * 2]
-
-
-def workspace(d, device):
-    return empty((int(_lib.lib.tspgnn_lnlstm_bwd_workspace_floats(d)),), device, 0.0)
-
-
-def k_chunked(d, dx):
-    """launch_lnlstm_bwd_bf16's LDS arithmetic: is K streamed through LDS in chunks (rather than resident)?  A copy of the
-    launcher's NWMAX, tail and 160 KB budget (csrc/dense_bwd_bf16.hip): a change there must be made here too, or the tests
-    that assert the chunked path stop knowing whether they reach it."""
-    nwmax = 4 if d >= 128 else 8
-    tail = (10 * d + nwmax * 10 * d + 4) * 4
-    per_kb = 32 * 4 * d * 2
-    return (dx + d) // 32 * per_kb > 160 * 1024 - tail
-
-
-class Cell(object):
-    """One backward task's inputs: bf16-exact x, h, K (or the gather-init Zx, uv, Kh), fp32 c, dh', dc', LayerNorm."""
+class Cell(lstm_bwd_cases.Cell):
+    """One backward task's inputs (lstm_bwd_cases.Cell in the bf16 arithmetic): bf16-exact x, h, K (or the gather-init Zx,
+    uv, Kh), fp32 c, dh', dc', LayerNorm."""
 
     def __init__(self, d, dx, rows, seed, gather=False, null_grads=False, n_src=257):
-        rng = np.random.RandomState(seed)
-        self.d, self.dx, self.rows, self.gather = d, dx, rows, gather
-        f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-        self.h, self.c = rb(rng.randn(rows, d)), f32(rng.randn(rows, d))
-        if gather:
-            self.n_src = n_src
-            self.uv = np.stack([rng.randint(0, n_src, rows), rng.randint(0, n_src, rows)], 1).astype(np.int32)
-            self.Zx = rb(rng.randn(n_src, 4 * d))
-            self.K = rb(rng.randn(d, 4 * d) / np.sqrt(d))
-        else:
-            self.x = rb(rng.randn(rows, dx))
-            self.K = rb(rng.randn(dx + d, 4 * d) / np.sqrt(dx + d))
-        self.ln = f32(np.stack([np.stack([1 + 0.2 * rng.randn(d), 0.2 * rng.randn(d)]) for _ in range(5)]))
-        self.dh, self.dc = (None, None) if null_grads else (f32(rng.randn(rows, d)), f32(rng.randn(rows, d)))
-
-    def z64(self, device):
-        """z = [x | h] K (gather-init: Zx[u] + Zx[v] + h Kh) in float64: exact operands, so the z the kernel recomputes."""
-        t64 = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=device)
-        if self.gather:
-            uv = torch.as_tensor(self.uv, dtype=torch.long, device=device)
-            Zx = t64(self.Zx)
-            return Zx[uv[:, 0]] + Zx[uv[:, 1]] + t64(self.h) @ t64(self.K)
-        return torch.cat([t64(self.x), t64(self.h)], dim=1) @ t64(self.K)
-
-    def quiet_kinks(self, device):
-        """Rows where a relu input -- the normalised transform gate j or the normalised cell state c' -- lies within 2^-16 of
-        zero are a rounding away from the other side of the kink: the fp32 kernel and the float64 reference may take
-        different derivatives there, and legitimately (measured: one row of 70 001 with |c'| = 3.7e-8 moved dz by 1e-2).
-        Such rows get no incoming gradient (dh' = dc' = 0): they still pass through the kernel, and contribute exactly zero
-        on both sides.  -> the number of rows quietened."""
-        if self.dh is None:
-            return 0
-        d = self.d
-        ln = torch.tensor(self.ln, dtype=torch.float64, device=device)
-        i, j, f, o = torch.chunk(self.z64(device), 4, dim=1)
-        i, j, f = (TO.layer_norm(g, ln[k, 0], ln[k, 1]) for k, g in enumerate((i, j, f)))
-        c = torch.tensor(self.c, dtype=torch.float64, device=device)
-        cn = TO.layer_norm(c * torch.sigmoid(f + TO.FORGET_BIAS) + torch.sigmoid(i) * torch.relu(j), ln[4, 0], ln[4, 1])
-        kink = ((j.abs().min(dim=1).values < 2.0 ** -16) | (cn.abs().min(dim=1).values < 2.0 ** -16)).cpu().numpy()
-        self.dh[kink] = 0.0
-        self.dc[kink] = 0.0
-        assert kink.sum() <= max(2, 1e-2 * self.rows), (d, int(kink.sum()))
-        return int(kink.sum())
-
-    def task(self, device, ws=None, defer=False, ln_grad=None):
-        d, rows = self.d, self.rows
-        if not hasattr(self, "quietened"):
-            self.quietened = self.quiet_kinks(device)
-        self.dz, self.dc_in = empty((rows, 4 * d), device), empty((rows, d), device)
-        self.ln_grad = empty((10 * d,), device, 0.0) if ln_grad is None else ln_grad
-        self.ws = workspace(d, device) if ws is None else ws
-        K = packed_bf16(self.K, device)
-        common = (_lib.ptr(dev_bf16(self.h, device)), _lib.ptr(dev(self.c, device)), _lib.ptr(K), _lib.ptr(dev(self.ln, device)),
-                  _lib.ptr(None if self.dh is None else dev(self.dh, device)),
-                  _lib.ptr(None if self.dc is None else dev(self.dc, device)),
-                  _lib.ptr(self.dz), _lib.ptr(self.dc_in), _lib.ptr(self.ln_grad), _lib.ptr(self.ws), rows)
-        if self.gather:   # the projected messages as Tape.ZX holds them: bf16, blocked by 16 rows
-            return _lib.LstmBwdTask(None, 0, *common, _lib.ptr(dev(self.uv, device, np.int32)),
-                                    _lib.ptr(dev_bf16(h2_zx_pack(self.Zx, 1.0), device)), None, None, int(defer))
-        return _lib.LstmBwdTask(_lib.ptr(dev_bf16(self.x, device)), self.dx, *common, None, None, None, None, int(defer))
-
-    def outputs(self):
-        return [t.cpu().numpy().astype(np.float64) for t in (self.dz, self.dc_in, self.ln_grad)]
+        super().__init__("bf16", d, dx, rows, seed, gather=gather, null_grads=null_grads, n_src=n_src)
 
     def reference(self, device):
         """float64 autograd of TO.lnlstm_cell with respect to z (z64) -> (dz, dc_in, ln_grad [10d])."""
-        d = self.d
-        t64 = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=device)
-        z = self.z64(device)
-        z.requires_grad_(True)
-        c, ln = t64(self.c).requires_grad_(True), t64(self.ln).requires_grad_(True)
-        base = "TSP/Q_cell/layer_norm_basic_lstm_cell"
-        params = {base + "/kernel": torch.eye(4 * d, dtype=torch.float64, device=device)}   # the cell's GEMM: z itself
-        for i, g in enumerate(GATES):
-            params[base + "/%s/gamma" % g] = ln[i, 0]
-            params[base + "/%s/beta" % g] = ln[i, 1]
-        nh, nc = TO.lnlstm_cell(z, torch.zeros((self.rows, 0), dtype=torch.float64, device=device), c, params, "Q")
-        loss = (nh * t64(self.dh)).sum() + (nc * t64(self.dc)).sum()
-        gz, gc, gln = torch.autograd.grad(loss, [z, c, ln])
-        return [gz.cpu().numpy(), gc.cpu().numpy(), gln.cpu().numpy().reshape(-1)]
+        ref = super().reference(device)
+        return [ref["dz"], ref["dc_in"], ref["ln_grad"]]
 
 
 def launch(tasks, d):
