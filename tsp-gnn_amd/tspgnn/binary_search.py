@@ -133,6 +133,7 @@ def get_costs(sess, model, instances, time_steps, threshold=0.5, stopping_delta=
 def _search_chunk(sess, model, chunk, time_steps, threshold, stopping_delta, k, max_rounds, trace):
     import torch
     from . import _lib
+    from .range_guard import decode
 
     n = len(chunk)
     bounds, route_costs = [], []
@@ -153,21 +154,22 @@ def _search_chunk(sess, model, chunk, time_steps, threshold, stopping_delta, k, 
     iters = torch.zeros(n, dtype=torch.int32, device=dev)
     pred_out = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
     n_active = torch.zeros(1, dtype=torch.int32, device=dev)
-    guard = sess.store.h2_guard()
-    host = torch.zeros(4, dtype=torch.int32).pin_memory()
+    guard = sess.store.guard
+    host = torch.zeros(5, dtype=torch.int32).pin_memory()
     seg_h = np.concatenate([[0], np.cumsum(n_edges)]).astype(np.int64)
 
     def launch(mode, pred):
         _lib.call("tspgnn_cost_search_step", _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(iters), _lib.ptr(pred_out),
-                  _lib.ptr(n_active), _lib.ptr(pred), _lib.ptr(b.WC), _lib.ptr(b.seg), _lib.ptr(guard), n, k, threshold,
-                  stopping_delta, mode, _lib.current_stream())
+                  _lib.ptr(n_active), _lib.ptr(pred), _lib.ptr(b.WC), _lib.ptr(b.seg), _lib.ptr(guard.words), n, k,
+                  threshold, stopping_delta, mode, _lib.current_stream())
 
     def read_status():
-        """[active instances, guard[0], guard[1], guard[2]] with one synchronisation."""
+        """(active instances, the guard's words decoded) with one synchronisation."""
         host[0:1].copy_(n_active, non_blocking=True)
-        host[1:4].copy_(guard[0:3], non_blocking=True)
+        host[1:].copy_(guard.words, non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        return host.tolist()
+        status = host.tolist()
+        return status[0], decode(status[1:])
 
     sess.range_exceeded()               # a flag left by an earlier, unchecked forward must not skip this search's rounds
     launch(0, None)
@@ -183,11 +185,11 @@ def _search_chunk(sess, model, chunk, time_steps, threshold, stopping_delta, k, 
             probes = b.WC[:, 1].cpu().numpy()[seg_h[:-1]].reshape(n, k)   # (every graph has at least one edge)
             it0 = iters.cpu().numpy()
         out = replay()
-        status = read_status()
-        if status[3] or status[1] & 3:
+        still_active, words = read_status()
+        if words.status or words.activation:
             sess.range_exceeded()       # raises on a loop timeout; clears the range bits, records sess.last_range_bits
             if forced:
-                raise RuntimeError("get_costs: the range guard flagged a bf16x3 round (bits %d)" % (status[1] & 3))
+                raise RuntimeError("get_costs: the range guard flagged a bf16x3 round (bits %d)" % words.activation)
             # the search kernel left this round's brackets alone: repeat it, and the rest of the chunk, on bf16x3
             del replay, out
             forced = True
@@ -195,7 +197,7 @@ def _search_chunk(sess, model, chunk, time_steps, threshold, stopping_delta, k, 
                 replay = sess.capture_forward(b, epilogue=lambda out: launch(1, out["predictions"]))
             continue
         rounds += 1
-        active = status[0]
+        active = still_active
         if trace:
             preds = out["predictions"].cpu().numpy().reshape(n, k)
             it1, lo_h, hi_h = iters.cpu().numpy(), lo.cpu().numpy(), hi.cpu().numpy()

@@ -81,9 +81,9 @@ def to_f32(x):
 
 def _pack_split(store, arith, W, out, krows, ncols):
     """tspgnn_pack_weights_x3 / _h2 of W [krows, ncols] into the byte tensor ``out``; an f16x2 packing also raises the
-    store's range guard word to max |2^s W| (VariableStore.h2_guard)."""
+    store's range guard's weight word to max |2^s W| (range_guard.py)."""
     if arith == "h2":
-        _lib.call("tspgnn_pack_weights_h2", _lib.ptr(W), _lib.ptr(out), krows, ncols, store.h2_absmax_ptr(),
+        _lib.call("tspgnn_pack_weights_h2", _lib.ptr(W), _lib.ptr(out), krows, ncols, store.guard.weight_ptr(),
                   _lib.current_stream())
     else:
         _lib.call("tspgnn_pack_weights_" + arith, _lib.ptr(W), _lib.ptr(out), krows, ncols, _lib.current_stream())
@@ -430,8 +430,8 @@ class LayerNormBasicLSTMCell(object):
                                   range_flag=self._flag(arith), z_centered=int(centered))
 
     def _flag(self, arith):
-        """The range_flag of an f16x2 task (include/tspgnn.h): the store's guard word."""
-        return self.store.h2_flag_ptr() if arith == "h2" else None
+        """The range_flag of an f16x2 task (include/tspgnn.h): the store's guard's flags word."""
+        return self.store.guard.flag_ptr() if arith == "h2" else None
 
     def pushed_kernel(self, mlp):
         """(K' = [W Kx ; Kh] as fp32 [dx+d, 4d], b Kx as [1, 4d], pack(K'^T) for the data gradient) of the message MLP's
@@ -677,8 +677,6 @@ class GraphNN(object):
         self.gemm = os.environ.get("TSPGNN_GEMM", "f16x2")
         if self.gemm not in GEMM_ARITH:
             raise ValueError("TSPGNN_GEMM must be one of %s, got %r" % (sorted(GEMM_ARITH), self.gemm))
-        self._h2_off_at = None       # store.assignments at which the weights were found outside the f16x2 range
-        self._h2_force_off = False
         self._mlp_h2_native_ok = False   # bf16-storage backward: the last eager pass found the MLP weights inside the f16x2 range
         self.check_model()
         self._init_parameters()
@@ -1063,16 +1061,13 @@ class GraphNN(object):
         return None
 
     # ---- f16x2 range guard.  fp16 pieces cannot hold what fp32 -- the reference's type, graphnn.py:18 -- can: a weight
-    # with 2^6 |w| >= 65504 or an activation >= 65504 overflows to inf.  Weights are checked where they are packed (a
-    # device word raised by tspgnn_pack_weights_h2, read here when packings were refreshed); activations where the
-    # kernels split them (the tasks' range_flag, read by Session.run next to the statistics it fetches anyway).  Either
-    # way the network falls back to bf16x3, whose pieces have fp32's exponent range.
+    # with 2^6 |w| >= 65504 or an activation >= 65504 overflows to inf.  Weights are checked where they are packed,
+    # activations where the kernels split them; either way the network falls back to bf16x3, whose pieces have fp32's
+    # exponent range.  The device words and the latches behind these methods are range_guard.RangeGuard's (store.guard).
     def active_arith(self):
         """Suffix of the split-operand entry points in force: "h2" / "x3" / None, after the range guard's say."""
         arith = GEMM_ARITH[self.gemm]
-        if arith == "h2" and (self._h2_force_off or self._h2_off_at == self.store.assignments):
-            return "x3"
-        return arith
+        return "x3" if arith == "h2" and self.store.guard.h2_off() else arith
 
     @property
     def launched_loop(self):
@@ -1101,34 +1096,23 @@ class GraphNN(object):
 
     def forced_off_h2(self):
         """Context manager: f16x2 disabled inside (Session's re-run of a batch whose activations overflowed)."""
-        import contextlib
+        return self.store.guard.forced_off()
 
-        @contextlib.contextmanager
-        def cm():
-            prev, self._h2_force_off = self._h2_force_off, True
-            try:
-                yield self
-            finally:
-                self._h2_force_off = prev
-        return cm()
+    def leave_h2(self):
+        """f16x2 is off for these variables, the bf16-native backward's message MLPs included, until they are assigned
+        anew (a captured training step whose guard fired)."""
+        self.store.guard.veto()
+        self._mlp_h2_native_ok = False
 
     def check_h2_weights(self):
         """False if the weights just packed veto f16x2 (the caller rebuilds its launch plan: _split_arith now answers
-        "x3"), True otherwise.  Reads the guard's weight word when packings were enqueued
-        since the last look (one 4-byte device read; skipped while a HIP graph is being captured -- a captured
-        sequence is checked by its replay closure); past HALF the fp16 range the network is latched to bf16x3 until
-        the variables are assigned anew."""
-        store = self.store
-        if GEMM_ARITH[self.gemm] != "h2" or self._h2_force_off or self._h2_off_at == store.assignments:
+        "x3"), True otherwise.  Takes the guard's weight word when packings were enqueued since the last look and the guard
+        can look; past HALF the fp16 range the network is latched to bf16x3 until the variables are assigned anew."""
+        guard = self.store.guard
+        if GEMM_ARITH[self.gemm] != "h2" or guard.h2_off():
             return True    # (not in use, or already vetoed for these variables: the caller's plan stands)
-        if store.h2_packs_pending and store.theta.is_cuda and not torch.cuda.is_current_stream_capturing():
-            guard = store.h2_guard()
-            bits = int(guard[1].item())
-            guard[1:2].zero_()
-            store.h2_packs_pending = 0
-            if bits >= store.H2_WEIGHT_LIMIT_BITS:
-                self._h2_off_at = store.assignments
-                return False
+        if guard.packs_pending and guard.can_look():
+            return guard.vet_weights()
         return True
 
     def _single_consumers(self, own_width=False):
@@ -1255,7 +1239,7 @@ class GraphNN(object):
                 pre.setdefault(self._msg_MLPs[u["msg"]].sizes[-1], []).append(
                     _lib.MlpTask(X=_lib.ptr(y), wb=_lib.ptr(wb), Y=_lib.ptr(mout), rows=y.shape[0], n_layers=n, relu_mask=mask,
                                  proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po),
-                                 range_flag=self.store.h2_flag_ptr() if arith == "h2" else None))
+                                 range_flag=self.store.guard.flag_ptr() if arith == "h2" else None))
         pre_calls = _lib.launches(pre)
         built = {}
         self._plan_keep = keep
@@ -1335,7 +1319,7 @@ class GraphNN(object):
         out_v = LSTMStateTuple(c=torch.empty((N, 64), **f32), h=torch.empty((N, 64), **f32))
         vagg = [torch.empty((N, 64), **f32), torch.empty((N, 64), **f32)]
         counters = torch.zeros(4 * 32 * n_groups + 32, dtype=torch.int32, device=f32["device"])
-        guard = self.store.h2_guard()
+        guard = self.store.guard
         fs_e, fs_v = first_state[ve], first_state[vv]
         resident = kind == "resident"
         a = _lib.MpResidentArgs() if resident else _lib.MpLoopArgs()
@@ -1359,7 +1343,7 @@ class GraphNN(object):
         a.vagg[0], a.vagg[1] = _lib.ptr(vagg[0]), _lib.ptr(vagg[1])
         a.plan, a.counters, a.n_groups, a.grid = _lib.ptr(plan_t), _lib.ptr(counters), n_groups, grid
         a.M, a.N, a.z_centered = M, N, int(cen)
-        a.range_flag, a.status = guard.data_ptr(), guard.data_ptr() + 8
+        a.range_flag, a.status = guard.flag_ptr(), guard.status_ptr()
         trace = None
         if os.environ.get("TSPGNN_LOOP_TRACE"):   # development: per-wavefront phase times (tools/loop_trace.py)
             trace = self.loop_trace = torch.zeros((grid, resident_plan.WAVES if resident else loop_plan.WAVES, 32 if resident else 16),
@@ -1788,8 +1772,8 @@ class GraphNN(object):
         4-byte read per backward pass) -- beyond half the fp16 range the pass uses tspgnn_mlp_bwd_multi_f32.  A pass being
         CAPTURED (or one without a device) cannot look: it follows the eager pass before it (Session.capture_train_step
         warms up eagerly) and its replays watch the word at the f16x2 guard's lag."""
-        store = self.store
-        can_look = store.theta.is_cuda and not torch.cuda.is_current_stream_capturing()
+        guard = self.store.guard
+        can_look = guard.can_look()
         if not self.mlp_backward_h2 or not (can_look or self._mlp_h2_native_ok):
             return False
         for (v, i), acts in tape.acts.items():      # the packs the pass will use
@@ -1798,11 +1782,7 @@ class GraphNN(object):
                 for l0, nl in mlp._chunks():
                     mlp.wt_packed(l0, l0 + nl - 1, mlp.sizes[-1], h2=True)
         if can_look:
-            guard = store.h2_guard()
-            bits = int(guard[1].item())
-            guard[1:2].zero_()
-            store.h2_packs_pending = 0
-            self._mlp_h2_native_ok = bits < store.H2_WEIGHT_LIMIT_BITS
+            self._mlp_h2_native_ok = guard.vet_weights(latch=False)
         return self._mlp_h2_native_ok
 
     def _backward_plan(self, tape):

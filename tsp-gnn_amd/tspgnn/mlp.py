@@ -130,7 +130,7 @@ class Mlp(object):
         def fill(out):
             src, st = self.wb(first, last), _lib.current_stream()
             if arith == "h2":
-                _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(src), _lib.ptr(out), d, n, 0, self.store.h2_absmax_ptr(), st)
+                _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(src), _lib.ptr(out), d, n, 0, self.store.guard.weight_ptr(), st)
                 return
             for j in range(n):
                 W, bias = src[j * per_src:j * per_src + d * d], src[j * per_src + d * d:(j + 1) * per_src]
@@ -179,7 +179,7 @@ class Mlp(object):
             st = _lib.current_stream()
             if h2:
                 _lib.call("tspgnn_pack_mlp_h2", _lib.ptr(self.wb(first, last)), _lib.ptr(out), d, n, 1,
-                          self.store.h2_absmax_ptr(), st)
+                          self.store.guard.weight_ptr(), st)
                 return
             for j in range(n):
                 W = self.store.view(self.layer_names[first + j] + "/kernel")
@@ -242,7 +242,7 @@ class Mlp(object):
         return _lib.MlpTask(X=_lib.ptr(x), wb=_lib.ptr(self.wb_packed(0, n_layers - 1, self._plan[1], arith)), Y=_lib.ptr(out),
                             acts=_lib.ptr(acts), acts_stride=acts_stride, rows=x.shape[0], n_layers=n_layers,
                             relu_mask=self.relu_mask(0, n_layers), proj_w=_lib.ptr(proj[0]), proj_out=_lib.ptr(proj[1]),
-                            range_flag=self.store.h2_flag_ptr() if arith == "h2" else None)
+                            range_flag=self.store.guard.flag_ptr() if arith == "h2" else None)
 
     def prefix_task(self, x, out, n_layers, arith=None, acts=None, acts_stride=0):
         """Task running only the first ``n_layers`` square layers (the rest is folded elsewhere); ``acts``: the hidden

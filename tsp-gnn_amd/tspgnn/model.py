@@ -26,6 +26,7 @@ from . import variables as V
 from .graphnn import GEMM_ARITH, GraphNN, LSTMStateTuple, to_f32
 from .instance_loader import SparseEV
 from .mlp import Mlp
+from .range_guard import decode, flag_bits
 
 LEARNING_RATE = 2e-5          # model.py:13
 L2NORM_SCALING = 1e-10        # model.py:14
@@ -323,18 +324,26 @@ class Session(object):
         """True if an f16x2 launch since the last call flagged an operand outside the fp16 range (synchronises)."""
         if self.device.type != "cuda":
             return False
-        guard = self.store.h2_guard()
-        words = guard[:3].tolist()
-        if words[2]:                        # tspgnn_mp_loop_h2 gave up waiting: its workgroups were not all resident
-            guard[2:3].zero_()
+        guard = self.store.guard
+        words = guard.peek()
+        if words.status:                    # tspgnn_mp_loop_h2 gave up waiting: its workgroups were not all resident
+            guard.clear_status()
             raise RuntimeError("tspgnn_mp_loop_h2: a wait inside the one-launch loop timed out (status %d); the launch's "
-                               "outputs are invalid -- set TSPGNN_LOOP=0 to run the stepwise launches" % words[2])
-        bits = words[0] & 3                 # bit 0: an operand beyond fp16's largest value; bit 1: a gate row whose spread
-        if bits:                            # is below the absolute error of its operands' fp16 pieces (h2_tile.h)
-            self.last_range_bits = bits
+                               "outputs are invalid -- set TSPGNN_LOOP=0 to run the stepwise launches" % words.status)
+        if words.activation:                # bit 0: an operand beyond fp16's largest value; bit 1: a gate row whose spread
+            self.last_range_bits = words.activation   # is below the absolute error of its operands' fp16 pieces (h2_tile.h)
             if clear:
-                guard[0:1].zero_()
-        return bool(bits)
+                guard.clear_flags()
+        return bool(words.activation)
+
+    def _on_bf16x3_if_flagged(self, do, then=lambda out: out):
+        """``then(do())``; if do() raised the range flags (one look: range_exceeded), do() again and then() with f16x2 forced
+        off -- this batch on bf16x3, which has fp32's range."""
+        out = do()
+        if not self.range_exceeded():
+            return then(out)
+        with self.model["gnn"].forced_off_h2():
+            return then(do())
 
     def capture_forward(self, batch, epilogue=None):
         """Captures one forward pass over a resident batch into a HIP graph (hipStreamBeginCapture via
@@ -345,10 +354,11 @@ class Session(object):
         ``epilogue(outputs)``, if given, enqueues more work on the current stream after the forward: it is
         captured into the same graph (the warm-up passes do not run it) -- get_costs' bracket update."""
         b = batch if isinstance(batch, DeviceBatch) else self.prepare(batch)
-        self.forward_device(b)          # warm-up: builds packed-weight caches (and vets their range) outside the capture
-        if self.range_exceeded():       # this batch's activations leave the f16x2 range: capture it on bf16x3
-            with self.model["gnn"].forced_off_h2():
-                return self.capture_forward(b, epilogue)
+        # warm-up: builds packed-weight caches (and vets their range) outside the capture; a batch whose activations leave
+        # the f16x2 range is warmed up again and captured on bf16x3
+        return self._on_bf16x3_if_flagged(lambda: self.forward_device(b), lambda _: self._capture_forward(b, epilogue))
+
+    def _capture_forward(self, b, epilogue):
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         side = torch.cuda.Stream(device=self.device)
@@ -395,10 +405,7 @@ class Session(object):
                 # a statistic of the batch is a statistic of the GLOBAL batch in a data-parallel session (collective:
                 # every rank fetches it, as run_batch does); predictions / last_states alone stay rank-local
                 gs = any(n in STAT_FETCHES for n in names)
-                out = self.forward(feed_dict, global_stats=gs)
-                if self.range_exceeded():   # an activation left the fp16 range: this batch again on bf16x3 (fp32's range)
-                    with self.model["gnn"].forced_off_h2():
-                        out = self.forward(feed_dict, global_stats=gs)
+                out = self._on_bf16x3_if_flagged(lambda: self.forward(feed_dict, global_stats=gs))
         results = []
         stats = None
         for f in flist:
@@ -497,7 +504,7 @@ class Session(object):
         tail = store.bucket[n:]
         if self.device.type == "cuda":     # one launch (tspgnn_bucket_pack_f32): no at::native node in the captured step
             _lib.call("tspgnn_bucket_pack_f32", _lib.ptr(store.bucket), n, 1 if with_grad else 0, nb, _lib.ptr(stats),
-                      store.h2_flag_ptr(), _lib.current_stream())
+                      store.guard.flag_ptr(), _lib.current_stream())
             return tail
         # device="cpu" (plumbing: the gloo tests): the same arithmetic as tensor ops
         if with_grad:
@@ -508,9 +515,7 @@ class Session(object):
             tail[1:3].copy_(stats[0:2])
             tail[1:3].mul_(nb)
             tail[3:7].copy_(stats[2:6])
-        word = store.h2_guard()[0:1]             # guard bits, one slot each: every rank must skip / repeat the step together
-        for k in range(3):
-            tail[7 + k:8 + k].copy_((word >> k) & 1)
+        store.guard.flags_to_bucket(tail)   # one slot per bit
         return tail
 
     def _unpack_bucket(self, stats, with_grad):
@@ -518,7 +523,7 @@ class Session(object):
         n = store.theta.numel()
         if self.device.type == "cuda":
             _lib.call("tspgnn_bucket_unpack_f32", _lib.ptr(store.bucket), n, 1 if with_grad else 0, _lib.ptr(stats),
-                      store.h2_flag_ptr(), _lib.current_stream())
+                      store.guard.flag_ptr(), _lib.current_stream())
             return
         tail = store.bucket[n:]
         inv = torch.reciprocal(tail[0:1])
@@ -527,8 +532,7 @@ class Session(object):
         if stats is not None:
             stats[0:2].copy_(tail[1:3] * inv)
             stats[2:6].copy_(tail[3:7])
-        store.h2_guard()[0:1].copy_((tail[7:8] != 0).to(torch.int32) + 2 * (tail[8:9] != 0).to(torch.int32)
-                                    + 4 * (tail[9:10] != 0).to(torch.int32))
+        store.guard.flags_from_bucket(tail)
 
     def allreduce_grads(self, local_batch, stats=None):
         """One all-reduce of [gradient | batch size, statistics]; afterwards ``store.grad`` holds the gradient of
@@ -602,7 +606,7 @@ class Session(object):
         _lib.call("tspgnn_adam_clip_step_f32", _lib.ptr(store.theta), _lib.ptr(store.grad), _lib.ptr(a["m"]),
                   _lib.ptr(a["v"]), store.theta.numel(), L2NORM_SCALING, GLOBAL_NORM_CLIP, LEARNING_RATE, b1, b2, eps,
                   _lib.ptr(a["gnorm"]), _lib.ptr(a["ws"]), _lib.ptr(a["t"]),
-                  store.h2_flag_ptr() if self.device.type == "cuda" else None, _lib.current_stream())
+                  store.guard.flag_ptr() if self.device.type == "cuda" else None, _lib.current_stream())
         store.touch()
         return a["gnorm"]
 
@@ -642,29 +646,22 @@ class Session(object):
             self._ever_synced = True
         need = dp and (not self._replicas_synced or self._synced_assignments != self.store.assignments)
         h2 = on_gpu and self.model["gnn"].active_arith() == "h2"   # (only f16x2 launches raise bits 0 / 1)
+        guard = self.store.guard
         if on_gpu:
-            self.store.h2_guard()[0:1].fill_(4 if need else 0)     # always: the optimiser kernel skips on a non-zero word
+            guard.arm(need)     # always: the optimiser kernel skips on a non-zero word
         out = self._train_step_once(feed)
-        bits = self._guard_word() if on_gpu and (h2 or dp) else 0
-        if bits & 4:   # skipped everywhere: some replica had been assigned to.  Make them identical, then take the step.
+        act, resync = flag_bits(guard.take_flags()) if on_gpu and (h2 or dp) else (0, False)
+        if resync:   # skipped everywhere: some replica had been assigned to.  Make them identical, then take the step.
             self._adam["step"] -= 1
             self.broadcast_variables(0)
             out = self._train_step_once(feed)
-            bits = self._guard_word() if h2 else 0
-        if bits & 3:
-            self.last_range_bits = bits & 3
+            act = flag_bits(guard.take_flags())[0] if h2 else 0
+        if act:
+            self.last_range_bits = act
             self._adam["step"] -= 1     # (Adam skipped the update on the device: theta, m, v and t are untouched)
             with self.model["gnn"].forced_off_h2():
                 out = self._train_step_once(feed)
         return out
-
-    def _guard_word(self):
-        """The guard word (VariableStore.h2_guard()[0]) after a step, cleared if set: one blocking 4-byte read."""
-        guard = self.store.h2_guard()
-        w = int(guard[0].item())
-        if w:
-            guard[0:1].zero_()
-        return w
 
     def _train_step_once(self, feed):
         out = self.loss_and_grads(feed)
@@ -680,13 +677,13 @@ class Session(object):
         b = batch if isinstance(batch, DeviceBatch) else self.prepare(batch)
         self._ensure_adam()
         self._sync_replicas_once()
-        gnn, store = self.model["gnn"], self.store
-        store.h2_guard()[0:1].zero_()         # (a flag left by an earlier unchecked forward() is not this capture's)
+        gnn, store, guard = self.model["gnn"], self.store, self.store.guard
+        guard.clear_flags()                   # (a flag left by an earlier unchecked forward() is not this capture's)
         self.loss_and_grads(b)                # warm-up outside the capture (allocator, caches)
         torch.cuda.synchronize()
         # did the warm-up leave the f16x2 range?  Then the step is captured on bf16x3 (and stays there for these
         # variables).  Decided together in a data-parallel session: the ranks' batches differ, their graphs must not.
-        bits = int(store.h2_guard()[0].item()) & 3
+        bits = guard.peek().activation
         if self.world_size > 1:
             import torch.distributed as dist
             agreed = torch.tensor([bits], dtype=torch.int32, device=self.device)
@@ -694,8 +691,8 @@ class Session(object):
             bits = int(agreed.item())
         if bits and gnn.active_arith() == "h2":
             self.last_range_bits = bits
-            store.h2_guard()[0:1].zero_()
-            gnn._h2_off_at = store.assignments
+            guard.clear_flags()
+            gnn.leave_h2()
             return self.capture_train_step(b)
         side = torch.cuda.Stream(device=self.device)
         ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
@@ -727,13 +724,13 @@ class Session(object):
             if len(inflight) >= LAG:
                 ev, words = inflight.pop(0)
                 ev.synchronize()
-                act, weight = int(words[0]) & 3, int(words[1]) >= store.H2_WEIGHT_LIMIT_BITS
-                if act or weight:
+                seen = decode(words)
+                act = seen.activation
+                if act or seen.weight_over:
                     torch.cuda.synchronize()
                     self.last_range_bits = act
-                    gnn._h2_off_at = store.assignments
-                    gnn._mlp_h2_native_ok = False
-                    store.h2_guard().zero_()
+                    gnn.leave_h2()
+                    guard.clear()
                     del inflight[:]
                     self._adam["step"] = int(self._adam["t"].item())   # the device counter did not count the skipped steps
                     if act:
@@ -753,7 +750,7 @@ class Session(object):
             if gnn.training_packs_h2():
                 words = ring[count[0] % (LAG + 1)]
                 count[0] += 1
-                words.copy_(store.h2_guard(), non_blocking=True)
+                words.copy_(guard.words, non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
                 inflight.append((ev, words))

@@ -14,6 +14,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from .range_guard import RangeGuard
+
 
 def xavier_uniform(shape, gen):
     """tf.contrib.layers.xavier_initializer(): U(-l, l), l = sqrt(6/(fan_in+fan_out)); a 1-D
@@ -50,26 +52,11 @@ class VariableStore(object):
                               # Session re-broadcasts from rank 0 before its next training step
         self._packed = {}
         self.grad = None      # flat gradient buffer, same layout as theta (allocated on first use)
-        self._h2_guard = None
-        self.h2_packs_pending = 0   # f16x2 weight packings enqueued since the guard's weight word was last read
-
-    # -- f16x2 range guard (include/tspgnn.h, tspgnn_pack_weights_h2) ------------------------------------
-    # int32[4] on the device: [0] bit 0 set by an f16x2 launch whose operand left the fp16 range (the tasks' range_flag,
-    # also Adam's skip_flag); [1] IEEE bits of max |2^s W| over every f16x2 weight packing since it was last zeroed.
-    H2_WEIGHT_LIMIT_BITS = 0x46ffe000   # 32752.0f: HALF of fp16's largest finite value -- margin for the steps a
-                                        # training run takes between two looks at the word (Adam moves a weight by ~lr)
+        self.guard = None     # the f16x2 range guard's device words and host latches (range_guard.py): made by finalize()
 
     def h2_guard(self):
-        if self._h2_guard is None:
-            self._h2_guard = torch.zeros(4, dtype=torch.int32, device=self.theta.device)
-        return self._h2_guard
-
-    def h2_flag_ptr(self):
-        return self.h2_guard().data_ptr()
-
-    def h2_absmax_ptr(self):
-        self.h2_packs_pending += 1
-        return self.h2_guard().data_ptr() + 4
+        """The range guard's live int32[4] device words (range_guard.py states their layout)."""
+        return self.guard.words
 
     # -- declaration phase -------------------------------------------------------------
     def declare(self, name, shape, initializer):
@@ -101,7 +88,7 @@ class VariableStore(object):
         self._offsets = offsets
         self.device = torch.device(device)
         self.theta = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.h2_guard()   # allocated (and zeroed) NOW: a first use inside a HIP-graph capture would capture the memset
+        self.guard = RangeGuard(self)   # allocated (and zeroed) NOW: a first use inside a HIP-graph capture would capture the memset
         return self
 
     @property
