@@ -1,11 +1,13 @@
 """Create a labelled dataset of .graph files on the GPU: the reference's dataset.py command line (dataset.py:189-214).
 
     python examples/create_dataset.py -path instances/train -samples 32768 -nmin 20 -nmax 40 [-seed 42]
-        [-distances euc_2D|random] [--metric] [-cmin 1] [-cmax 1] [--require-certified DEV]
+        [-distances euc_2D|random] [--metric] [-cmin 1] [-cmax 1] [--require-certified DEV] [-exact]
 
 Unlike the reference's __main__, -seed is applied: random and np.random are seeded with it before the first draw, so
 the instance stream is the one the reference's train.py gets after its own seeding (train.py seeds both the same way).
 Instances of up to 256 vertices are labelled (tspgnn.label_tours).
+-exact proves every tour of up to 128 vertices optimal by branch and bound (tspgnn.prove_tours), or improves it first,
+and reports how many it proved within its node budget.
 --metric, as in the reference, turns the metric closure OFF for random distances.
 """
 import argparse
@@ -33,16 +35,22 @@ def main():
     p.add_argument("-cmax", default=1, type=float, help="Max. connectivity")
     p.add_argument("--require-certified", type=float, default=None, metavar="DEV",
                    help="redraw instances whose labels cannot be certified at this dev (biases the distribution)")
+    p.add_argument("-exact", action="store_true",
+                   help="prove the tours optimal by branch and bound (n <= 128), as Concorde does for the reference")
     a = p.parse_args()
     random.seed(a.seed)
     np.random.seed(a.seed)
     print("Creating {} instances".format(a.samples), flush=True)
     s = dataset.create_dataset(a.path, a.nmin, a.nmax, a.cmin, a.cmax, samples=a.samples, distances=a.distances,
-                               metric=a.metric, require_certified=a.require_certified, verbose=True)
+                               metric=a.metric, require_certified=a.require_certified, verbose=True, exact=a.exact)
     t = s["times"]
     print("search %.2f s, bound %.2f s, write %.2f s; certified fraction %.4f; gap median %.5f max %.5f; redrawn %d"
-          % (t["search"], t["bound"], t["write"], s["certified_fraction"], float(np.median(s["gap"])),
+          % (t["search"], t.get("bound", 0.0), t["write"], s["certified_fraction"], float(np.median(s["gap"])),
              float(s["gap"].max()), s["redrawn"]), flush=True)
+    if a.exact:
+        print("exact %.2f s; proved optimal %d of %d; nodes median %d max %d"
+              % (t.get("exact", 0.0), int(s["proved"].sum()), a.samples, int(np.median(s["nodes"])),
+                 int(s["nodes"].max())), flush=True)
 
 
 if __name__ == "__main__":

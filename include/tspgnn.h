@@ -506,6 +506,52 @@ int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n,
 int tspgnn_tour_lower_bound_tri(const float* W, const long long* w_off, const int* n, const float* upper, int n_inst,
                                 int n_max, int iters, double* lb, void* stream);
 
+/* ------------------------------------------------------------------ exact tour labels (dataset.py:9-50, Concorde's role) */
+
+#define TSPGNN_BB_PROVED 0   /* the search finished: no tour is cheaper than the one returned, up to opt_tol */
+#define TSPGNN_BB_BUDGET 1   /* max_nodes or the depth limit left nodes open: lb is valid, the tour is the best found */
+#define TSPGNN_BB_BAD 2      /* n[i] outside [4, n_max], or the incumbent is no permutation: lb = NaN, tour untouched */
+#define TSPGNN_BB_MAX_DEPTH 128   /* stack levels of the depth-first search (sizes the workspace) */
+
+/*
+ * Depth-first branch and bound on the Held-Karp 1-tree bound (tspgnn/dataset.py prove_tours): what Concorde does for the
+ * reference's labels (dataset.py:9-50).  One wave64 per instance; W / w_off / n / t_off as tspgnn_tour_search (dense
+ * matrices, 4 <= n[i] <= n_max <= 128; n_max > 128: TSPGNN_EUNSUPPORTED).  The workgroup keeps the weights and an int8
+ * edge-class matrix (free / forced / forbidden) in LDS.
+ * In/out: tours + t_off[i] holds an incumbent tour on entry and the best tour found on exit, in canonical form.
+ * upper: NULL, or float[n_inst], the fp32 cost that steers the root's Polyak step; NULL takes the incumbent's cost.
+ * Out: lb[i], a lower bound on every tour's cost under W, rounding included; nodes[i], the nodes whose ascent ran;
+ * status[i], TSPGNN_BB_*.  workspace: tspgnn_tour_branch_bound_ws(n_inst, n_max) bytes on the device, the stack's
+ * multipliers (n_max floats per level and instance; the decisions and bounds of the levels sit in LDS).
+ * Root: tspgnn_tour_lower_bound's ascent (pi = 0, lambda = 2, root_iters steps) and fp64 rebuild; with max_nodes = 1 and
+ * the same upper, lb[i] equals that kernel's bit for bit.  With inc = the incumbent's fp64 cost under the fp32 weights,
+ * summed in tour order, a node is:
+ *   infeasible  when a vertex has more than two forced edges or fewer than two edges that are not forbidden (a vertex
+ *               with two forced edges forbids its others first), or when the allowed edges hold no 1-tree;
+ *   bounded     by node_iters fp32 ascent steps from its parent's best multipliers (lambda = 2 again), the best
+ *               multipliers' 1-tree rebuilt in fp64 less 8 n DBL_EPSILON times its magnitude, and not below the parent's
+ *               bound: Lr.  The constrained 1-tree picks by (class, cost), a forced edge before any free one, a forbidden
+ *               one never; its value is summed from the true W + pi_u + pi_v;
+ *   pruned      when Lr >= inc (1 - opt_tol);
+ *   a tour      when all fp64 1-tree degrees are 2: it becomes the incumbent when its cost is below inc;
+ *   branched    otherwise, at the vertex v of largest degree (ties: smaller id) on its free tree edges e1, e2 of smallest
+ *               and second smallest W(v, .) (ties: smaller id).  No forced edge at v: children force e1 and e2 / force
+ *               e1, forbid e2 / forbid e1, visited in this order; one forced edge at v: force e1 / forbid e1.
+ * A node that would be branched after max_nodes ascents or at depth TSPGNN_BB_MAX_DEPTH stays open, as does a node whose
+ * children were not all visited; each counts with its own Lr.  lb[i] = min(inc, Lr of every pruned, tour and open
+ * node): valid whether or not the search finished.  status[i] = TSPGNN_BB_PROVED exactly when nothing stayed open.
+ * 1 <= max_nodes <= 65 536, node_iters >= 1, root_iters >= 1, opt_tol finite and >= 0 (relative), else TSPGNN_EINVAL
+ * before any launch; n_inst == 0 is a no-op.  At most max_nodes * (node_iters + 1) + root_iters 1-trees per instance.
+ */
+int tspgnn_tour_branch_bound(const float* W, const long long* w_off, const int* n, const long long* t_off,
+                             const float* upper, int n_inst, int n_max, int root_iters, int node_iters, int max_nodes,
+                             double opt_tol, void* workspace, int32_t* tours, double* lb, int32_t* nodes, int32_t* status,
+                             void* stream);
+
+/* Bytes of workspace tspgnn_tour_branch_bound needs for n_inst instances at n_max (dataset.py:9-50): n_inst *
+ * TSPGNN_BB_MAX_DEPTH * n_max floats; 0 for an empty or unsupported request. */
+long long tspgnn_tour_branch_bound_ws(int n_inst, int n_max);
+
 /* ------------------------------------------------------------------ decision-TSP baselines (tspgnn/baselines.py) */
 
 /*

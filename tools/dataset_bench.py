@@ -3,8 +3,11 @@ the test set (2^10), n = 80, and n = 200 and 256 (label_tours on the triangle ke
 at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per shape.
 
     python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
+        [--exact [--max-nodes N]]
 
 Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
+--exact labels with the branch and bound (label_tours(exact=True), n <= 128) and adds the proved fraction, the nodes per
+instance (p50 / p90 / max) and the seconds of that launch; bound_s is then 0.
 """
 import argparse
 import json
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--restarts", type=int, default=None)
     ap.add_argument("--kicks", type=int, default=None)
     ap.add_argument("--lb-iters", type=int, default=None)
+    ap.add_argument("--exact", action="store_true", help="label with the branch and bound (n <= 128)")
+    ap.add_argument("--max-nodes", type=int, default=None, help="--exact: nodes per instance")
     ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
@@ -41,6 +46,9 @@ def main():
     # warm-up: load the code objects outside the timed runs
     for n in (20, 130):
         dataset.label_tours([(np.triu(np.ones((n, n)), 1), np.random.RandomState(0).rand(n, n))], kicks=1, lb_iters=1)
+    if a.exact:
+        dataset.label_tours([(np.triu(np.ones((20, 20)), 1), np.random.RandomState(0).rand(20, 20))], kicks=1, lb_iters=1,
+                            exact=True, max_nodes=1)
     for name in a.shapes.split(","):
         samples, nmin, nmax = SHAPES[name]
         samples = a.samples or samples
@@ -49,9 +57,10 @@ def main():
         t0 = time.perf_counter()
         graphs = dataset.draw_instances(nmin, nmax, samples=samples)
         t_draw = time.perf_counter() - t0
-        tm = {}
+        tm, stats = {}, {}
         res = dataset.label_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs],
-                                  restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, timings=tm)
+                                  restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, timings=tm,
+                                  exact=a.exact, max_nodes=a.max_nodes, stats=stats)
         large = nmax > dataset.MAX_N
         restarts = a.restarts or (dataset.DEFAULT_RESTARTS_LARGE if large else dataset.DEFAULT_RESTARTS)
         kicks = a.kicks if a.kicks is not None else (dataset.DEFAULT_KICKS_LARGE if large else dataset.DEFAULT_KICKS)
@@ -68,10 +77,18 @@ def main():
                 shutil.rmtree(out)
         c = dataset.certify(res, 0.02)
         gap = np.array([(r.cost - r.lb) / r.cost for r in res])
+        exact = {}
+        if a.exact:
+            nd = stats["nodes"]
+            exact = {"exact_s": round(tm.get("exact", 0.0), 3),
+                     "max_nodes": a.max_nodes or dataset.DEFAULT_BB_NODES, "node_iters": dataset.DEFAULT_BB_ITERS,
+                     "proved": round(float(np.mean(stats["status"] == "proved")), 4),
+                     "nodes": {"p50": int(np.percentile(nd, 50)), "p90": int(np.percentile(nd, 90)), "max": int(nd.max())},
+                     "proved_gap_max": float(gap[stats["status"] == "proved"].max(initial=0.0))}
         print(json.dumps({
             "shape": name, "samples": samples, "n": [nmin, nmax], "restarts": restarts, "kicks": kicks,
             "lb_iters": lb_iters, "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
-            "search_s": round(tm["search"], 3), "bound_s": round(tm["bound"], 3),
+            "search_s": round(tm["search"], 3), "bound_s": round(tm.get("bound", 0.0), 3), **exact,
             "write_s": None if t_write is None else round(t_write, 3),
             "feasible": float(np.mean([r.feasible for r in res])),
             "certified_0.02": round(c["fraction"], 4), "label0": round(float(c["label0"].mean()), 4),

@@ -1,5 +1,6 @@
-// Device and host helpers shared by the tour kernels (tour_search.hip, tour_baselines.hip): the two LDS layouts of an
-// instance's weights, the counter-based generator, the wave reductions, the canonical write-out and the LDS budget.
+// Device and host helpers shared by the tour kernels (tour_search.hip, tour_baselines.hip, tour_exact.hip): the two LDS
+// layouts of an instance's weights, the counter-based generator, the wave reductions, the canonical write-out, the LDS
+// budget, and the Held-Karp 1-tree with its subgradient ascent (the bound kernel and the branch and bound).
 #pragma once
 #include "common.h"
 
@@ -113,6 +114,284 @@ __device__ __forceinline__ void write_canonical(const int* t, int n, int32_t* ou
         if (q < 0) q += n;
         out[k] = t[q];
     }
+}
+
+// Wave-wide minimum of an int; every lane gets it.
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------- Held-Karp 1-tree
+// Edge classes of a branch-and-bound node (tour_exact.hip).  A 1-tree picks its edges by (rank, cost): rank 0 = forced,
+// before any free edge (rank 1); a forbidden edge (rank 2) is never picked.  The classes never touch the costs.
+constexpr int kEdgeFree = 0, kEdgeForced = 1, kEdgeForbidden = 2;
+
+// No constraints (the bound kernel, the root node): every edge is free and the class code compiles away.
+struct NoCons {
+    static constexpr bool kActive = false;
+    __device__ __forceinline__ int rank(int, int) const { return 1; }
+};
+
+// The n x n int8 class matrix of a node in LDS, row stride s bytes, symmetric.
+struct LdsCons {
+    static constexpr bool kActive = true;
+    int8_t* c;
+    int s;
+    __device__ __forceinline__ int operator()(int a, int b) const { return c[a * s + b]; }
+    __device__ __forceinline__ int rank(int a, int b) const {
+        const int x = c[a * s + b];
+        return x == kEdgeForced ? 0 : x == kEdgeFree ? 1 : 2;
+    }
+};
+
+// Minimum 1-tree under the costs c(u,v) = W(u,v) + pi_u + pi_v, evaluated in T: Prim's tree on vertices 1..n-1 plus the two
+// cheapest edges at vertex 0, both by (rank, cost) under the classes C.  Lane l owns the K vertices l, l+64, ... (pi[j] is
+// vertex l + 64 j's).  Returns sum c(edges) - 2 sum pi; deg[] (LDS) gets the 1-tree degrees; *mag gets sum |c(edges)| +
+// 2 sum |pi| (the scale of the rounding error).  Vertices past n take no part and add nothing to a lane's sums, so the
+// result does not depend on K.  tp (LDS, optional) gets the tree's edges: (u, tp[u]) for u >= 2, (0, tp[0]) and (0, tp[1]).
+// When the allowed edges hold no 1-tree (constraints only) the result is not below FLT_MAX; deg and tp are then partial.
+template <typename T, int K, class WA, class CA>
+__device__ T one_tree(const WA& W, const CA& C, int n, const T (&pi)[K], int lane, int* deg, T* mag, int* tp = nullptr) {
+    const T inf = (T)FLT_MAX * (T)4;
+    int v[K];
+    bool ok[K], in[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        v[j] = lane + j * kWave;
+        ok[j] = v[j] < n;
+        if (ok[j]) deg[v[j]] = 0;
+        in[j] = !ok[j] || v[j] <= 1;
+    }
+    wave_sync();
+    const T pir = __shfl(pi[0], 1);
+    T key[K];
+    int par[K], rk[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        key[j] = in[j] ? inf : (T)W(1, v[j]) + pir + pi[j];
+        par[j] = 1;
+        rk[j] = 1;
+        if constexpr (CA::kActive) {
+            rk[j] = in[j] ? 2 : C.rank(1, v[j]);
+            if (rk[j] == 2) key[j] = inf;
+        }
+    }
+    T tree = 0, amag = 0;
+    for (int step = 0; step < n - 2; ++step) {
+        T k = inf;
+        int who = INT_MAX;
+        if constexpr (!CA::kActive) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                if (!in[j] && (j == 0 || key[j] < k)) {
+                    k = key[j];
+                    who = v[j];
+                }
+            }
+        } else {
+            int r = 2;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                if (!in[j] && (rk[j] < r || (rk[j] == r && key[j] < k))) {
+                    r = rk[j];
+                    k = key[j];
+                    who = v[j];
+                }
+            }
+            const int rmin = wave_min(r);
+            if (rmin == 2) {   // wave-uniform: the allowed edges do not connect 1..n-1
+                *mag = 0;
+                return inf;
+            }
+            if (r != rmin) {
+                k = inf;
+                who = INT_MAX;
+            }
+        }
+        wave_argmin(k, who);
+        const int u = who;
+        tree += k;
+        amag += k < 0 ? -k : k;
+        T pu = __shfl(pi[0], u & (kWave - 1));
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (v[j] == u) {
+                in[j] = true;
+                atomicAdd(&deg[par[j]], 1);
+                atomicAdd(&deg[u], 1);
+                if (tp) tp[u] = par[j];
+            }
+            if (j > 0) {
+                const T x = __shfl(pi[j], u & (kWave - 1));
+                if (u / kWave == j) pu = x;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (!in[j]) {
+                if constexpr (!CA::kActive) {
+                    const T c = (T)W(u, v[j]) + pu + pi[j];
+                    if (c < key[j]) {
+                        key[j] = c;
+                        par[j] = u;
+                    }
+                } else {
+                    const int r = C.rank(u, v[j]);
+                    const T c = (T)W(u, v[j]) + pu + pi[j];
+                    if (r < 2 && (r < rk[j] || (r == rk[j] && c < key[j]))) {
+                        rk[j] = r;
+                        key[j] = c;
+                        par[j] = u;
+                    }
+                }
+            }
+        }
+    }
+    // the two cheapest edges at vertex 0 (pi_0 is lane 0's pi[0]); per lane the smallest, ties to the smaller vertex
+    const T piz = __shfl(pi[0], 0);
+    T c[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) c[j] = (ok[j] && v[j] >= 1) ? (T)W(0, v[j]) + piz + pi[j] : inf;
+    T m1, m2;
+    int e1, e2;
+    if constexpr (!CA::kActive) {
+        m1 = c[0];
+        e1 = v[0];
+#pragma unroll
+        for (int j = 1; j < K; ++j) {
+            if (c[j] < m1) {
+                m1 = c[j];
+                e1 = v[j];
+            }
+        }
+        wave_argmin(m1, e1);
+        m2 = inf;
+        e2 = INT_MAX;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (v[j] != e1 && c[j] < m2) {
+                m2 = c[j];
+                e2 = v[j];
+            }
+        }
+        if (m2 == inf) e2 = INT_MAX;
+        wave_argmin(m2, e2);
+    } else {
+        int r0[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) r0[j] = (ok[j] && v[j] >= 1) ? C.rank(0, v[j]) : 2;
+        e1 = INT_MAX;
+#pragma unroll
+        for (int pick = 0; pick < 2; ++pick) {   // the first edge, then the second among the rest
+            int r = 2, e = INT_MAX;
+            T m = inf;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                if (v[j] != e1 && (r0[j] < r || (r0[j] == r && c[j] < m))) {
+                    r = r0[j];
+                    m = c[j];
+                    e = v[j];
+                }
+            }
+            const int rmin = wave_min(r);
+            if (rmin == 2) {   // wave-uniform: vertex 0 has fewer than two allowed edges
+                *mag = 0;
+                return inf;
+            }
+            if (r != rmin) {
+                m = inf;
+                e = INT_MAX;
+            }
+            wave_argmin(m, e);
+            if (pick == 0) {
+                m1 = m;
+                e1 = e;
+            } else {
+                m2 = m;
+                e2 = e;
+            }
+        }
+    }
+    wave_sync();
+    if (lane == 0) {
+        deg[0] = 2;
+        atomicAdd(&deg[e1], 1);
+        atomicAdd(&deg[e2], 1);
+        if (tp) {
+            tp[0] = e1;
+            tp[1] = e2;
+        }
+    }
+    T psum = (ok[0] ? pi[0] : (T)0) + (ok[1] ? pi[1] : (T)0);
+    T pmag = (ok[0] ? (pi[0] < 0 ? -pi[0] : pi[0]) : (T)0) + (ok[1] ? (pi[1] < 0 ? -pi[1] : pi[1]) : (T)0);
+#pragma unroll
+    for (int j = 2; j < K; ++j) {
+        if (ok[j]) {
+            psum += pi[j];
+            pmag += pi[j] < 0 ? -pi[j] : pi[j];
+        }
+    }
+    psum = wave_sum(psum);
+    pmag = wave_sum(pmag);
+    wave_sync();
+    *mag = amag + (m1 < 0 ? -m1 : m1) + (m2 < 0 ? -m2 : m2) + 2 * pmag;
+    return tree + m1 + m2 - 2 * psum;
+}
+
+// Subgradient ascent on the 1-tree bound from the multipliers pi: at most `iters` steps, each a 1-tree under pi and a
+// Polyak step lambda * (ub - L) / |g|^2 along g = degree - 2, lambda = 2 halved after 8 steps without a new best.  Returns
+// the best fp32 value and leaves its multipliers in bp; a value not below FLT_MAX says that the classes allow no 1-tree.
+template <int K, class WA, class CA>
+__device__ float ascend(const WA& W, const CA& C, int n, float ub, int iters, int lane, int* deg, float (&pi)[K],
+                        float (&bp)[K]) {
+    float best = -FLT_MAX, lambda = 2.f, mag;
+#pragma unroll
+    for (int j = 0; j < K; ++j) bp[j] = pi[j];
+    int stall = 0;
+    for (int it = 0; it < iters; ++it) {
+        const float L = one_tree<float>(W, C, n, pi, lane, deg, &mag);
+        if constexpr (CA::kActive) {
+            if (!(L < FLT_MAX)) return L;
+        }
+        if (L > best) {
+            best = L;
+#pragma unroll
+            for (int j = 0; j < K; ++j) bp[j] = pi[j];
+            stall = 0;
+        } else if (++stall >= 8) {   // halving schedule: no improvement in 8 steps
+            lambda *= 0.5f;
+            stall = 0;
+        }
+        int g[K], g2 = 0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            g[j] = lane + j * kWave < n ? deg[lane + j * kWave] - 2 : 0;
+            g2 += g[j] * g[j];
+        }
+        const int gg = wave_sum(g2);
+        if (gg == 0 || lambda < 1e-6f) break;   // the 1-tree is a tour (optimal), or the step has vanished
+        const float gap = fmaxf(ub - L, 1e-4f * fabsf(L) + 1e-30f);
+        const float t = lambda * gap / (float)gg;   // Polyak step towards the upper bound
+#pragma unroll
+        for (int j = 0; j < K; ++j) pi[j] += t * (float)g[j];
+        wave_sync();
+    }
+    return best;
+}
+
+// The 1-tree of the multipliers bp again from scratch in fp64 (the fp32 Prim of the ascent may pick a non-minimal tree
+// under rounding), less a margin for the fp64 rounding of the c(u,v) sums and the accumulation: a lower bound on every
+// tour that the classes allow, rounding included.  deg and tp as one_tree; not below FLT_MAX when there is no 1-tree.
+template <int K, class WA, class CA>
+__device__ double rebuilt_bound(const WA& W, const CA& C, int n, const float (&bp)[K], int lane, int* deg,
+                                int* tp = nullptr) {
+    double dpi[K], dmag;
+#pragma unroll
+    for (int j = 0; j < K; ++j) dpi[j] = (double)bp[j];
+    const double L = one_tree<double>(W, C, n, dpi, lane, deg, &dmag, tp);
+    return L - 8.0 * (double)n * DBL_EPSILON * dmag;
 }
 
 template <class K>

@@ -218,118 +218,6 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
 
 // ---------------------------------------------------------------------------------------------------------- lower bound
 
-// Minimum 1-tree under the costs c(u,v) = W(u,v) + pi_u + pi_v, evaluated in T: Prim's tree on vertices 1..n-1 plus the two
-// cheapest edges at vertex 0.  Lane l owns the K vertices l, l+64, ... (pi[j] is vertex l + 64 j's).  Returns sum c(edges)
-// - 2 sum pi; deg[] (LDS) gets the 1-tree degrees; *mag gets sum |c(edges)| + 2 sum |pi| (the scale of the rounding
-// error).  Vertices past n take no part and add nothing to a lane's sums, so the result does not depend on K.
-template <typename T, int K, class WA>
-__device__ T one_tree(const WA& W, int n, const T (&pi)[K], int lane, int* deg, T* mag) {
-    const T inf = (T)FLT_MAX * (T)4;
-    int v[K];
-    bool ok[K], in[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        v[j] = lane + j * kWave;
-        ok[j] = v[j] < n;
-        if (ok[j]) deg[v[j]] = 0;
-        in[j] = !ok[j] || v[j] <= 1;
-    }
-    wave_sync();
-    const T pir = __shfl(pi[0], 1);
-    T key[K];
-    int par[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        key[j] = in[j] ? inf : (T)W(1, v[j]) + pir + pi[j];
-        par[j] = 1;
-    }
-    T tree = 0, amag = 0;
-    for (int step = 0; step < n - 2; ++step) {
-        T k = inf;
-        int who = INT_MAX;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            if (!in[j] && (j == 0 || key[j] < k)) {
-                k = key[j];
-                who = v[j];
-            }
-        }
-        wave_argmin(k, who);
-        const int u = who;
-        tree += k;
-        amag += k < 0 ? -k : k;
-        T pu = __shfl(pi[0], u & (kWave - 1));
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            if (v[j] == u) {
-                in[j] = true;
-                atomicAdd(&deg[par[j]], 1);
-                atomicAdd(&deg[u], 1);
-            }
-            if (j > 0) {
-                const T x = __shfl(pi[j], u & (kWave - 1));
-                if (u / kWave == j) pu = x;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            if (!in[j]) {
-                const T c = (T)W(u, v[j]) + pu + pi[j];
-                if (c < key[j]) {
-                    key[j] = c;
-                    par[j] = u;
-                }
-            }
-        }
-    }
-    // the two cheapest edges at vertex 0 (pi_0 is lane 0's pi[0]); per lane the smallest, ties to the smaller vertex
-    const T piz = __shfl(pi[0], 0);
-    T c[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) c[j] = (ok[j] && v[j] >= 1) ? (T)W(0, v[j]) + piz + pi[j] : inf;
-    T m1 = c[0];
-    int e1 = v[0];
-#pragma unroll
-    for (int j = 1; j < K; ++j) {
-        if (c[j] < m1) {
-            m1 = c[j];
-            e1 = v[j];
-        }
-    }
-    wave_argmin(m1, e1);
-    T m2 = inf;
-    int e2 = INT_MAX;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        if (v[j] != e1 && c[j] < m2) {
-            m2 = c[j];
-            e2 = v[j];
-        }
-    }
-    if (m2 == inf) e2 = INT_MAX;
-    wave_argmin(m2, e2);
-    wave_sync();
-    if (lane == 0) {
-        deg[0] = 2;
-        atomicAdd(&deg[e1], 1);
-        atomicAdd(&deg[e2], 1);
-    }
-    T psum = (ok[0] ? pi[0] : (T)0) + (ok[1] ? pi[1] : (T)0);
-    T pmag = (ok[0] ? (pi[0] < 0 ? -pi[0] : pi[0]) : (T)0) + (ok[1] ? (pi[1] < 0 ? -pi[1] : pi[1]) : (T)0);
-#pragma unroll
-    for (int j = 2; j < K; ++j) {
-        if (ok[j]) {
-            psum += pi[j];
-            pmag += pi[j] < 0 ? -pi[j] : pi[j];
-        }
-    }
-    psum = wave_sum(psum);
-    pmag = wave_sum(pmag);
-    wave_sync();
-    *mag = amag + (m1 < 0 ? -m1 : m1) + (m2 < 0 ? -m2 : m2) + 2 * pmag;
-    return tree + m1 + m2 - 2 * psum;
-}
-
 template <class WA>
 __global__ __launch_bounds__(kWave) void tour_lower_bound_kernel(const float* __restrict__ Wg,
                                                                  const long long* __restrict__ w_off,
@@ -347,43 +235,12 @@ __global__ __launch_bounds__(kWave) void tour_lower_bound_kernel(const float* __
     }
     const WA W = WA::stage(lds, Wg + w_off[inst], n, lane, kWave);
     __syncthreads();
-    const float ub = upper[inst];
-    float pi[K], bp[K], best = -FLT_MAX, lambda = 2.f, mag;
+    float pi[K], bp[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) pi[j] = bp[j] = 0.f;
-    int stall = 0;
-    for (int it = 0; it < iters; ++it) {
-        const float L = one_tree<float>(W, n, pi, lane, deg, &mag);
-        if (L > best) {
-            best = L;
-#pragma unroll
-            for (int j = 0; j < K; ++j) bp[j] = pi[j];
-            stall = 0;
-        } else if (++stall >= 8) {   // halving schedule: no improvement in 8 steps
-            lambda *= 0.5f;
-            stall = 0;
-        }
-        int g[K], g2 = 0;
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-            g[j] = lane + j * kWave < n ? deg[lane + j * kWave] - 2 : 0;
-            g2 += g[j] * g[j];
-        }
-        const int gg = wave_sum(g2);
-        if (gg == 0 || lambda < 1e-6f) break;   // the 1-tree is a tour (optimal), or the step has vanished
-        const float gap = fmaxf(ub - L, 1e-4f * fabsf(L) + 1e-30f);
-        const float t = lambda * gap / (float)gg;   // Polyak step towards the tour-search upper bound
-#pragma unroll
-        for (int j = 0; j < K; ++j) pi[j] += t * (float)g[j];
-        wave_sync();
-    }
-    // the best multipliers' 1-tree, again from scratch in fp64 (the fp32 Prim above may pick a non-minimal tree under
-    // rounding), less a margin for the fp64 rounding of the c(u,v) sums and the accumulation
-    double dpi[K], dmag;
-#pragma unroll
-    for (int j = 0; j < K; ++j) dpi[j] = (double)bp[j];
-    const double L = one_tree<double>(W, n, dpi, lane, deg, &dmag);
-    if (lane == 0) lb[inst] = L - 8.0 * (double)n * DBL_EPSILON * dmag;
+    for (int j = 0; j < K; ++j) pi[j] = 0.f;
+    ascend(W, NoCons{}, n, upper[inst], iters, lane, deg, pi, bp);
+    const double L = rebuilt_bound(W, NoCons{}, n, bp, lane, deg);
+    if (lane == 0) lb[inst] = L;
 }
 
 template <class WA>

@@ -92,6 +92,8 @@ SIGNATURES = {
     "tspgnn_tour_search_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_lower_bound_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "tspgnn_tour_branch_bound": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_nearest_neighbor": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p],
     "tspgnn_tour_nearest_neighbor_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
@@ -105,7 +107,7 @@ SIGNATURES = {
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",
                   "tspgnn_host_read_graph", "tspgnn_host_count_edges", "tspgnn_host_pack_batch", "tspgnn_host_stage_batch")
 
-# size queries: name -> argtypes; these return long long (floats of workspace)
+# size queries: name -> argtypes; these return long long (floats of workspace; tspgnn_tour_branch_bound_ws: bytes)
 SIZE_QUERIES = {
     "tspgnn_lnlstm_bwd_workspace_floats": [c_int],
     "tspgnn_wgrad_workspace_floats": [c_longlong, c_int, c_int],
@@ -113,6 +115,7 @@ SIZE_QUERIES = {
     "tspgnn_wcolsum_workspace_floats": [c_longlong, c_int],
     "tspgnn_einit_bwd_workspace_floats": [c_int, c_int],
     "tspgnn_adam_workspace_floats": [],
+    "tspgnn_tour_branch_bound_ws": [c_int, c_int],
 }
 
 

@@ -1,10 +1,13 @@
 """Labelled TSP instances: the counterpart of the reference's ``dataset.py`` (create_graph, create_dataset, solve).
 
-The reference labels every instance with Concorde (dataset.py:9-50).  Here the label comes from two HIP kernels
-(csrc/tour_search.hip): ``tspgnn_tour_search``, a batched multi-start iterated local search that returns a short tour,
-and ``tspgnn_tour_lower_bound``, the Held-Karp 1-tree bound that certifies how far that tour can be from the optimum.
-Neither is an exact solver; a label is trusted when ``certify`` says the bound and the tour settle it for the target
-cost ``create_batch`` will feed.
+The reference labels every instance with Concorde (dataset.py:9-50).  Here the label comes from HIP kernels:
+``tspgnn_tour_search`` (csrc/tour_search.hip), a batched multi-start iterated local search that returns a short tour;
+``tspgnn_tour_lower_bound``, the Held-Karp 1-tree bound that certifies how far that tour can be from the optimum; and
+``tspgnn_tour_branch_bound`` (csrc/tour_exact.hip), a branch and bound on that bound which starts from the search's tour
+and either proves it optimal, replaces it by a better one and proves that, or runs out of its node budget and says so
+(``prove_tours``, ``label_tours(exact=True)``, ``create_dataset(exact=True)``; n <= 128).  Without ``exact`` a label is
+trusted when ``certify`` says the bound and the tour settle it for the target cost ``create_batch`` will feed
+(DESIGN.md §12).
 
 Instance generation (create_graph, create_dataset) draws from the global ``random`` / ``np.random`` in exactly the
 reference's order, so a script that seeds them as the reference's train.py does gets the reference's instances.
@@ -37,6 +40,12 @@ DEFAULT_RESTARTS_LARGE = 8
 DEFAULT_KICKS_LARGE = 384
 DEFAULT_LB_ITERS_LARGE = 400
 DEFAULT_CHUNK = 8192
+# Branch and bound (prove_tours; DESIGN.md §12 has the measured table): nodes per instance and ascent steps per node.
+# One launch runs at most max_nodes * (node_iters + 1) + root_iters 1-trees per instance.
+DEFAULT_BB_NODES = 2048
+DEFAULT_BB_ITERS = 30
+BB_WORKSPACE_BYTES = 1 << 30   # most workspace of one branch-and-bound launch; larger chunks are split
+BB_STATUS = ("proved", "budget", "skipped")   # TSPGNN_BB_PROVED, TSPGNN_BB_BUDGET; 'skipped': no launch for it
 
 TourResult = collections.namedtuple("TourResult", ["tour", "cost", "lb", "feasible", "target"])
 TourResult.__doc__ = """One solved instance.
@@ -172,11 +181,19 @@ def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, ma
     return checked, index
 
 
-def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0, tri):
+def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0, tri,
+           exact=None, incumbents=None):
     """solve_tours on checked instances, n < 4 on the host and the rest on the square kernels (tri=False, n <= 128) or
-    the triangle kernels (tri=True, n <= 256)."""
+    the triangle kernels (tri=True, n <= 256).
+    exact = (max_nodes, node_iters, opt_tol, status, nodes): the branch and bound takes the place of the bound launch
+    (tri=False only) and fills the int arrays status / nodes at this call's positions (n < 4: proved, 0 nodes).
+    incumbents: one tour per instance; the search is skipped and the branch and bound starts from these."""
     B = len(checked)
     out = [None] * B
+    if exact is not None:
+        for k in range(B):
+            if checked[k][2] < 4:
+                exact[3][k], exact[4][k] = 0, 0
     big = [k for k in range(B) if checked[k][2] >= 4]
     for k in range(B):
         if checked[k][2] < 4:
@@ -205,7 +222,9 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
         W32 = (_penalised_tri if tri else _penalised)(A, Mw)
         for g, p in enumerate(poss):
             Wflat[w_off[p]:w_off[p] + sq[p]] = W32[g].reshape(-1)
-            if init_tours is not None and init_tours[big[p]] is not None:
+            if incumbents is not None:
+                init[t_off[p]:t_off[p] + n] = incumbents[big[p]]
+            elif init_tours is not None and init_tours[big[p]] is not None:
                 it = np.asarray(init_tours[big[p]], dtype=np.int64).reshape(-1)
                 if it.shape[0] != n or not np.array_equal(np.sort(it), np.arange(n)):
                     raise ValueError("init_tours[%d] is not a permutation of 0..%d" % (big[p], n - 1))
@@ -226,10 +245,13 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
         d_tours = torch.empty(int(ns.sum()), dtype=torch.int32, device=dev)
         d_cost = torch.empty(G, dtype=torch.float32, device=dev)
         d_lb = torch.empty(G, dtype=torch.float64, device=dev)
+        if incumbents is not None:
+            d_tours.copy_(torch.from_numpy(init))
+            d_cost = None   # the root's step then aims at the incumbent's own cost
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         st = _lib.current_stream()
-        for c0 in range(0, G, chunk):
+        for c0 in range(0, G if incumbents is None else 0, chunk):
             c1 = min(G, c0 + chunk)
             _lib.call(search, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                       _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
@@ -237,7 +259,23 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
                       st)
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
-        if lower_bound:
+        if exact is not None:
+            # results do not depend on the launch size, so a chunk whose stack would not fit BB_WORKSPACE_BYTES is split
+            per = int(_lib.lib.tspgnn_tour_branch_bound_ws(1, int(ns.max())))
+            step = max(1, min(chunk, G, BB_WORKSPACE_BYTES // per))
+            d_ws = torch.empty(per * step, dtype=torch.uint8, device=dev)
+            d_nodes = torch.empty(G, dtype=torch.int32, device=dev)
+            d_stat = torch.empty(G, dtype=torch.int32, device=dev)
+            for c0 in range(0, G, step):
+                c1 = min(G, c0 + step)
+                _lib.call("tspgnn_tour_branch_bound", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                          _lib.ptr(d_toff[c0:c1]), _lib.ptr(None if d_cost is None else d_cost[c0:c1]), c1 - c0,
+                          int(ns[c0:c1].max()), int(lb_iters), int(exact[1]), int(exact[0]), float(exact[2]),
+                          _lib.ptr(d_ws), _lib.ptr(d_tours), _lib.ptr(d_lb[c0:c1]), _lib.ptr(d_nodes[c0:c1]),
+                          _lib.ptr(d_stat[c0:c1]), st)
+            exact[3][big] = d_stat.cpu().numpy()
+            exact[4][big] = d_nodes.cpu().numpy()
+        elif lower_bound:
             for c0 in range(0, G, chunk):
                 c1 = min(G, c0 + chunk)
                 _lib.call(bound, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
@@ -246,7 +284,7 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
         torch.cuda.synchronize(dev)
         t3 = time.perf_counter()
         tours = d_tours.cpu().numpy().astype(np.int64)
-        lbs = d_lb.cpu().numpy() if lower_bound else np.full(G, np.nan)
+        lbs = d_lb.cpu().numpy() if lower_bound or exact is not None else np.full(G, np.nan)
     for n, poss in groups.items():
         A, Mw = stacked[n]
         T = np.stack([tours[t_off[p]:t_off[p] + n] for p in poss])
@@ -261,7 +299,8 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
     if timings is not None:
         timings["pack"] = timings.get("pack", 0.0) + (t1 - t0)
         timings["search"] = timings.get("search", 0.0) + (t2 - t1)
-        timings["bound"] = timings.get("bound", 0.0) + (t3 - t2)
+        leg = "bound" if exact is None else "exact"
+        timings[leg] = timings.get(leg, 0.0) + (t3 - t2)
     return out
 
 
@@ -271,8 +310,74 @@ def tri_chains_fit(n):
     return min(16, (163712 - 2 * n * (n - 1)) // (12 * n))
 
 
+def _bb_stats(stats, status, nodes, seconds):
+    if stats is not None:
+        stats["status"] = np.array([BB_STATUS[s] for s in status])
+        stats["nodes"] = np.asarray(nodes, dtype=np.int64)
+        stats["seconds"] = float(seconds)
+
+
+def _check_bb(max_nodes, node_iters, opt_tol):
+    if not 1 <= max_nodes <= 65536:
+        raise ValueError("max_nodes=%d must be in [1, 65536]" % max_nodes)
+    if node_iters < 1:
+        raise ValueError("node_iters=%d must be positive" % node_iters)
+    if not (np.isfinite(opt_tol) and opt_tol >= 0):
+        raise ValueError("opt_tol=%r must be finite and non-negative" % (opt_tol,))
+
+
+def prove_tours(instances, results, max_nodes=DEFAULT_BB_NODES, node_iters=DEFAULT_BB_ITERS, root_iters=DEFAULT_LB_ITERS,
+                opt_tol=1e-9, device=None, chunk=DEFAULT_CHUNK, stats=None):
+    """Exact labels: prove the tours of solve_tours / label_tours optimal, or improve them, by branch and bound on the
+    Held-Karp 1-tree bound (tspgnn_tour_branch_bound, csrc/tour_exact.hip) -- Concorde's role in the reference
+    (dataset.py:9-50).
+
+    instances: as solve_tours; results: one TourResult per instance, whose tour is the incumbent.
+    max_nodes: nodes per instance (1..65536); node_iters / root_iters: ascent steps per node / at the root; opt_tol: a
+    node is pruned when its bound reaches (1 - opt_tol) times the incumbent's cost.  chunk: instances per launch.
+    stats: optional dict that receives 'status' (array of 'proved' / 'budget' / 'skipped'), 'nodes' (per instance) and
+    'seconds' (of the launches, device-synchronised).
+
+    Returns a list of TourResult: lb is the branch and bound's, and tour, cost, feasible and target are those of the best
+    tour it holds at the end (the incumbent, or a cheaper one it met).  'proved' means: under the fp64 weights no tour is
+    cheaper than ``cost`` by more than (opt_tol + n * 2**-24) * cost -- the kernel sees fp32 weights, each rounded down by
+    at most one ulp.  (Concorde in the reference sees int(10**6 * w), exact only to 10**-6 per edge, which is coarser.)
+    'budget' means max_nodes ran out: lb is still a valid bound and the tour the best found.  Instances with n < 4 (their
+    host bound is already exact: 'proved'), with n > 128, or whose incumbent is infeasible ('skipped') pass through
+    unchanged.  Results never depend on chunk or on which other instances share the call.
+    """
+    if len(instances) != len(results):
+        raise ValueError("prove_tours: %d instances but %d results" % (len(instances), len(results)))
+    _check_counts(1, 0, root_iters, chunk)
+    _check_bb(max_nodes, node_iters, opt_tol)
+    checked = [_check(k, Ma, Mw, MAX_N_TRI) for k, (Ma, Mw) in enumerate(instances)]
+    B = len(checked)
+    status = np.full(B, 2, dtype=np.int64)
+    nodes = np.zeros(B, dtype=np.int64)
+    sel = []
+    for k, ((_, _, n), r) in enumerate(zip(checked, results)):
+        if sorted(r.tour) != list(range(n)):
+            raise ValueError("prove_tours: results[%d].tour is not a permutation of 0..%d" % (k, n - 1))
+        if n < 4:
+            status[k] = 0
+        elif n <= MAX_N and r.feasible:
+            sel.append(k)
+    out = list(results)
+    times = {}
+    if sel:
+        st, nd = np.zeros(len(sel), dtype=np.int64), np.zeros(len(sel), dtype=np.int64)
+        res = _solve([checked[k] for k in sel], np.arange(len(sel), dtype=np.int64), None, 1, 0, 0, True, device,
+                     root_iters, chunk, times, time.perf_counter(), False,
+                     exact=(max_nodes, node_iters, opt_tol, st, nd), incumbents=[results[k].tour for k in sel])
+        for j, k in enumerate(sel):
+            out[k] = res[j]
+        status[sel], nodes[sel] = st, nd
+    _bb_stats(stats, status, nodes, times.get("exact", 0.0))
+    return out
+
+
 def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, init_tours=None, lower_bound=True,
-                device=None, chunk=DEFAULT_CHUNK, index=None, timings=None):
+                device=None, chunk=DEFAULT_CHUNK, index=None, timings=None, exact=False, max_nodes=None, stats=None):
     """solve_tours for instances of up to MAX_N_TRI = 256 vertices, split by n: n < 4 on the host, 4-128 on the square
     kernels (exactly solve_tours), 129-256 on the packed-triangle kernels (tspgnn_tour_search_tri /
     tspgnn_tour_lower_bound_tri); n > 256 raises ValueError before anything is launched.
@@ -281,8 +386,19 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
     For n > 128 restarts may not exceed tri_chains_fit(largest n) (10 at n = 256).  The other arguments are solve_tours'.
     Results come back in input order; each depends on (seed, its index, restarts, kicks) only, never on chunk or on which
     other instances share the call.
+    exact=True: for n <= 128 the branch and bound (prove_tours, with max_nodes or DEFAULT_BB_NODES, DEFAULT_BB_ITERS
+    steps per node and lb_iters at the root) takes the place of the bound launch: lb is its bound and the tour the best it
+    holds.  stats then receives prove_tours' 'status', 'nodes' and 'seconds'; n > 128 is 'skipped' and keeps the plain
+    bound.  timings gets the launch under 'exact'.
     """
     t0 = time.perf_counter()
+    bb = None
+    if exact:
+        bb = (DEFAULT_BB_NODES if max_nodes is None else max_nodes, DEFAULT_BB_ITERS, 1e-9,
+              np.full(len(instances), 2, dtype=np.int64), np.zeros(len(instances), dtype=np.int64))
+        _check_bb(*bb[:3])
+        timings = {} if timings is None else timings
+        before = timings.get("exact", 0.0)
     small = (DEFAULT_RESTARTS if restarts is None else restarts, DEFAULT_KICKS if kicks is None else kicks,
              DEFAULT_LB_ITERS if lb_iters is None else lb_iters)
     large = (DEFAULT_RESTARTS_LARGE if restarts is None else restarts,
@@ -298,10 +414,15 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
         if not sel:
             continue
         inits = None if init_tours is None else [init_tours[i] for i in sel]
+        sub = None if bb is None or tri else bb[:3] + (np.zeros(len(sel), dtype=np.int64), np.zeros(len(sel), dtype=np.int64))
         res = _solve([checked[i] for i in sel], index[sel], inits, r, k, seed, lower_bound, device, it, chunk, timings,
-                     t0 if not tri else time.perf_counter(), tri)
+                     t0 if not tri else time.perf_counter(), tri, exact=sub)
         for i, x in zip(sel, res):
             out[i] = x
+        if sub is not None:
+            bb[3][sel], bb[4][sel] = sub[3], sub[4]
+    if bb is not None:
+        _bb_stats(stats, bb[3], bb[4], timings.get("exact", 0.0) - before)
     return out
 
 
@@ -396,7 +517,7 @@ def draw_instances(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="
 
 
 def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True,
-                   require_certified=None, max_redraw_rounds=20, verbose=False, **solve_kw):
+                   require_certified=None, max_redraw_rounds=20, verbose=False, exact=False, **solve_kw):
     """dataset.py:118-143: draw ``samples`` instances (the reference's stream), label them on the GPU in batches with
     the planted cycle as a starting tour, and write ``{path}/{i}.graph`` with write_graph.
 
@@ -404,19 +525,28 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     ``certify(.., dev)`` cannot prove, for at most max_redraw_rounds rounds, then raise RuntimeError if any remain.
     Redrawing BIASES the distribution: it drops the instances whose optimum sits close to the quirk target, which are the
     hardest ones, and the set no longer matches the reference's stream from the first redrawn index on.
-    solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device); n up to 256.
+    exact=True: label with label_tours(exact=True), the branch and bound for n <= 128 (prove_tours).
+    solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device, max_nodes); n up to 256.
 
     Returns a summary dict: samples, n (per instance), cost, lb, target, feasible, gap = (cost - lb) / cost,
-    certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'}.
+    certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'};
+    with exact=True also proved (per instance: the written tour is proved optimal), nodes (per instance) and
+    times['exact'].
     """
     os.makedirs(path, exist_ok=True)
     graphs = draw_instances(nmin, nmax, conn_min, conn_max, samples, distances, metric)
     times = {}
     solve_kw.setdefault("lower_bound", True)
+    proved, nodes = np.zeros(samples, dtype=bool), np.zeros(samples, dtype=np.int64)
 
     def label(idx, keys):
+        if exact:
+            stats = {}
+            solve_kw.update(exact=True, stats=stats)
         res = label_tours([(graphs[i][0], graphs[i][1]) for i in idx], init_tours=[graphs[i][2] for i in idx],
                           index=keys, timings=times, **solve_kw)
+        if exact:
+            proved[idx], nodes[idx] = stats["status"] == "proved", stats["nodes"]
         for r in res:
             if not r.feasible:
                 raise Exception("Unsolvable")
@@ -455,6 +585,8 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
         "redrawn": redrawn,
         "times": times,
     }
+    if exact:
+        summary["proved"], summary["nodes"] = proved, nodes
     summary["gap"] = (summary["cost"] - summary["lb"]) / np.where(summary["cost"] > 0, summary["cost"], 1.0)
     summary["certified_fraction"] = certify(summary, 0.02 if require_certified is None else require_certified)["fraction"]
     return summary
