@@ -1,13 +1,14 @@
 """Create a labelled dataset of .graph files on the GPU: the reference's dataset.py command line (dataset.py:189-214).
 
     python examples/create_dataset.py -path instances/train -samples 32768 -nmin 20 -nmax 40 [-seed 42]
-        [-distances euc_2D|random] [--metric] [-cmin 1] [-cmax 1] [--require-certified DEV] [-exact]
+        [-distances euc_2D|random] [--metric] [-cmin 1] [-cmax 1] [--require-certified DEV] [-exact] [-neighbors K]
 
 Unlike the reference's __main__, -seed is applied: random and np.random are seeded with it before the first draw, so
 the instance stream is the one the reference's train.py gets after its own seeding (train.py seeds both the same way).
 Instances of up to 256 vertices are labelled (tspgnn.label_tours).
 -exact proves every tour of up to 128 vertices optimal by branch and bound (tspgnn.prove_tours), or improves it first,
 and reports how many it proved within its node budget.
+-neighbors K restricts the search's descent to moves between K nearest neighbours (1..32; tspgnn.label_tours).
 --metric, as in the reference, turns the metric closure OFF for random distances.
 """
 import argparse
@@ -37,12 +38,15 @@ def main():
                    help="redraw instances whose labels cannot be certified at this dev (biases the distribution)")
     p.add_argument("-exact", action="store_true",
                    help="prove the tours optimal by branch and bound (n <= 128), as Concorde does for the reference")
+    p.add_argument("-neighbors", type=int, default=None, metavar="K",
+                   help="candidate-list descent over the K nearest neighbours (1..32; default: the full scan)")
     a = p.parse_args()
     random.seed(a.seed)
     np.random.seed(a.seed)
     print("Creating {} instances".format(a.samples), flush=True)
     s = dataset.create_dataset(a.path, a.nmin, a.nmax, a.cmin, a.cmax, samples=a.samples, distances=a.distances,
-                               metric=a.metric, require_certified=a.require_certified, verbose=True, exact=a.exact)
+                               metric=a.metric, require_certified=a.require_certified, verbose=True, exact=a.exact,
+                               neighbors=a.neighbors)
     t = s["times"]
     print("search %.2f s, bound %.2f s, write %.2f s; certified fraction %.4f; gap median %.5f max %.5f; redrawn %d"
           % (t["search"], t.get("bound", 0.0), t["write"], s["certified_fraction"], float(np.median(s["gap"])),

@@ -499,6 +499,34 @@ int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n,
                            unsigned long long seed, int32_t* tours, float* costs, void* stream);
 
 /*
+ * tspgnn_tour_search with a candidate-list descent (dataset.py:9-50): same starts, kicks, keys, acceptance and canonical
+ * output, but a descent step looks only at the moves that add an edge between near neighbours.  With kk = min(neighbors,
+ * n[i] - 1), N(x) = the kk vertices y != x smallest by (W[x][y], y) and S = the pairs {x, y} with y in N(x) or x in N(y).
+ * The moves, their fp32 deltas and their order are tspgnn_tour_search's, the two orientations of an Or-opt move counted
+ * as two moves.  A 2-opt move (reverse positions i+1..j) is a candidate iff {t[i], t[j]} or {t[i+1], t[j+1]} is in S; an
+ * Or-opt move (segment s0..sl between a and b) iff {a, s0} or {sl, b} is (reversed: {a, sl} or {s0, b}); the edge that
+ * closes the gap the segment leaves does not count.  A step applies the best candidate when it gains more than
+ * 1e-6 * cost / n.  The result is defined by that set, not by an enumeration order.  neighbors in 1..32, else
+ * TSPGNN_EINVAL before any launch; neighbors >= n[i] - 1 gives tspgnn_tour_search's tours and costs bit for bit.  LDS holds
+ * n_max * neighbors bytes of neighbour table and n_max more bytes per chain; at n_max <= 128 all 16 chains still fit.
+ * n_inst == 0 is a no-op; n_max > 128: TSPGNN_EUNSUPPORTED.
+ */
+int tspgnn_tour_search_knn(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                           const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks,
+                           int neighbors, unsigned long long seed, int32_t* tours, float* costs, void* stream);
+
+/*
+ * tspgnn_tour_search_knn on the packed strict upper triangle of tspgnn_tour_search_tri, n_max <= 256 (above:
+ * TSPGNN_EUNSUPPORTED) (dataset.py:9-50).  LDS: 2 n_max (n_max - 1) + n_max * neighbors + 13 restarts n_max bytes must
+ * fit 163 712: at n_max = 256 and neighbors = 8 restarts <= 9.  A larger restarts is TSPGNN_EINVAL, and the message names
+ * the limit.  For n <= 128 the tours and costs equal tspgnn_tour_search_knn's bit for bit.
+ */
+int tspgnn_tour_search_knn_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                               const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
+                               int kicks, int neighbors, unsigned long long seed, int32_t* tours, float* costs,
+                               void* stream);
+
+/*
  * tspgnn_tour_lower_bound on the packed triangle of tspgnn_tour_search_tri (dataset.py:9-50): the same subgradient
  * ascent, fp64 re-evaluation and margin; a lane owns the vertices l, l+64, l+128 and l+192.  n_max <= 256
  * (above: TSPGNN_EUNSUPPORTED).  For n <= 128, lb[i] equals tspgnn_tour_lower_bound's bit for bit.

@@ -3,11 +3,12 @@ the test set (2^10), n = 80, and n = 200 and 256 (label_tours on the triangle ke
 at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per shape.
 
     python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
-        [--exact [--max-nodes N]]
+        [--exact [--max-nodes N]] [--neighbors K]
 
 Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
 --exact labels with the branch and bound (label_tours(exact=True), n <= 128) and adds the proved fraction, the nodes per
 instance (p50 / p90 / max) and the seconds of that launch; bound_s is then 0.
+--neighbors K runs the candidate-list descent (label_tours(neighbors=K)); the JSON line then carries "neighbors".
 """
 import argparse
 import json
@@ -38,6 +39,7 @@ def main():
     ap.add_argument("--lb-iters", type=int, default=None)
     ap.add_argument("--exact", action="store_true", help="label with the branch and bound (n <= 128)")
     ap.add_argument("--max-nodes", type=int, default=None, help="--exact: nodes per instance")
+    ap.add_argument("--neighbors", type=int, default=None, help="candidate-list descent over K nearest neighbours")
     ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
@@ -45,7 +47,8 @@ def main():
     assert torch.cuda.is_available(), "dataset_bench needs an MI355X"
     # warm-up: load the code objects outside the timed runs
     for n in (20, 130):
-        dataset.label_tours([(np.triu(np.ones((n, n)), 1), np.random.RandomState(0).rand(n, n))], kicks=1, lb_iters=1)
+        dataset.label_tours([(np.triu(np.ones((n, n)), 1), np.random.RandomState(0).rand(n, n))], kicks=1, lb_iters=1,
+                            neighbors=a.neighbors)
     if a.exact:
         dataset.label_tours([(np.triu(np.ones((20, 20)), 1), np.random.RandomState(0).rand(20, 20))], kicks=1, lb_iters=1,
                             exact=True, max_nodes=1)
@@ -60,7 +63,7 @@ def main():
         tm, stats = {}, {}
         res = dataset.label_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs],
                                   restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, timings=tm,
-                                  exact=a.exact, max_nodes=a.max_nodes, stats=stats)
+                                  exact=a.exact, max_nodes=a.max_nodes, stats=stats, neighbors=a.neighbors)
         large = nmax > dataset.MAX_N
         restarts = a.restarts or (dataset.DEFAULT_RESTARTS_LARGE if large else dataset.DEFAULT_RESTARTS)
         kicks = a.kicks if a.kicks is not None else (dataset.DEFAULT_KICKS_LARGE if large else dataset.DEFAULT_KICKS)
@@ -87,7 +90,7 @@ def main():
                      "proved_gap_max": float(gap[stats["status"] == "proved"].max(initial=0.0))}
         print(json.dumps({
             "shape": name, "samples": samples, "n": [nmin, nmax], "restarts": restarts, "kicks": kicks,
-            "lb_iters": lb_iters, "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
+            "lb_iters": lb_iters, **({} if a.neighbors is None else {"neighbors": a.neighbors}), "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
             "search_s": round(tm["search"], 3), "bound_s": round(tm.get("bound", 0.0), 3), **exact,
             "write_s": None if t_write is None else round(t_write, 3),
             "feasible": float(np.mean([r.feasible for r in res])),

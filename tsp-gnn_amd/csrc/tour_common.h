@@ -414,5 +414,16 @@ int chains_fit(int n_max) {
     return c < (size_t)kMaxChains ? (int)c : kMaxChains;
 }
 
+// The _knn search (tour_search.hip) adds bytes: one neighbour table of n_max x neighbors ids for the workgroup and one
+// position array of n_max per chain.
+constexpr int kMaxNeighbors = 32;
+template <class WA>
+int knn_chains_fit(int n_max, int neighbors) {
+    const size_t free_bytes =
+        kLdsBytes - kSearchStaticLds - WA::floats(n_max) * sizeof(float) - (size_t)n_max * (size_t)neighbors;
+    const size_t c = free_bytes / ((size_t)3 * n_max * sizeof(int) + (size_t)n_max);
+    return c < (size_t)kMaxChains ? (int)c : kMaxChains;
+}
+
 }  // namespace
 }  // namespace tspgnn

@@ -3,7 +3,9 @@
 //                            instance, one wave64 per chain, the instance's weight matrix resident in LDS;
 //   tspgnn_tour_lower_bound  the Held-Karp 1-tree bound by subgradient ascent, one wave64 per instance, the final 1-tree
 //                            re-evaluated in fp64 so that the reported value is a lower bound under rounding.
-// Both are issue-bound on LDS reads and VALU work: an instance reads its n*n weights from memory once.
+//   tspgnn_tour_search_knn   the same search with its descent restricted to the moves that add an edge between near
+//                            neighbours (descend_knn below): about 13 n K evaluations per applied move, not 5.3 n^2.
+// All are issue-bound on LDS reads and VALU work: an instance reads its n*n weights from memory once.
 // Each has two layouts of the weights, one device body: the dense matrix (tspgnn_tour_search / _lower_bound, n <= 128)
 // and the packed strict upper triangle (the _tri entry points, n <= 256, 130 560 B at n = 256).  The bodies read a weight
 // only through the layout's W(a, b), and both layouts hold the same fp32 value for w(a, b), so for n <= 128 the two give
@@ -36,6 +38,30 @@ struct Strider {
         }
     }
 };
+
+// u = tour t after the move `code`; then the two are swapped, so that t is the new tour.
+__device__ __forceinline__ void apply_move(int*& t, int*& u, int n, int code, int lane) {
+    const int i = (code >> 8) & 0xff, j = code & 0xff;
+    if (!(code & kOrOpt)) {
+        for (int k = lane; k < n; k += kWave) u[k] = (k <= i || k > j) ? t[k] : t[i + 1 + j - k];
+    } else {
+        const int L = (code >> 26) & 3, rv = (code >> 29) & 1;
+        int rel = j - i;
+        if (rel < 0) rel += n;
+        const int A = rel - L + 1;   // t[i+L .. p] come first, then the segment, then t[p+1 .. i-1]
+        for (int k = lane; k < n; k += kWave) {
+            int src;
+            if (k < A) src = i + L + k;
+            else if (k < A + L) src = i + (rv ? L - 1 - (k - A) : k - A);
+            else src = i + k;
+            u[k] = t[src % n];
+        }
+    }
+    wave_sync();
+    int* x = t;
+    t = u;
+    u = x;
+}
 
 // Best-improvement descent on tour *t (scratch *u; the two are swapped per applied move).  Returns the tour's cost.
 template <class WA>
@@ -86,26 +112,148 @@ __device__ float descend(const WA& W, int*& t, int*& u, int n, int lane) {
         }
         wave_argmin(best, code);
         if (!(best < -kEpsRel * cost / (float)n)) break;   // wave-uniform: every lane holds the same pair
-        const int i = (code >> 8) & 0xff, j = code & 0xff;
-        if (!(code & kOrOpt)) {
-            for (int k = lane; k < n; k += kWave) u[k] = (k <= i || k > j) ? t[k] : t[i + 1 + j - k];
-        } else {
-            const int L = (code >> 26) & 3, rv = (code >> 29) & 1;
-            int rel = j - i;
-            if (rel < 0) rel += n;
-            const int A = rel - L + 1;   // t[i+L .. p] come first, then the segment, then t[p+1 .. i-1]
-            for (int k = lane; k < n; k += kWave) {
-                int src;
-                if (k < A) src = i + L + k;
-                else if (k < A + L) src = i + (rv ? L - 1 - (k - A) : k - A);
-                else src = i + k;
-                u[k] = t[src % n];
+        apply_move(t, u, n, code, lane);
+        cost = tour_cost(W, t, n, lane);
+    }
+    return cost;
+}
+
+// ------------------------------------------------------------------------------------- candidate-list descent (_knn)
+// N(x) = the kk = min(K, n-1) vertices y != x smallest by (w(x, y), y); S = the pairs {x, y} with y in N(x) or x in N(y).
+// A move of descend() is a candidate iff one of the edges it adds -- 2-opt: {t[i], t[j]}, {t[i+1], t[j+1]}; Or-opt: the
+// two insertion edges of its orientation, not the closing edge {prev, nx} -- is in S.  A step takes the argmin of
+// (delta, code) over the candidates, with descend()'s deltas, codes, threshold and cap, where the two orientations of an
+// Or-opt (L, i, q) are two moves (descend()'s "reverse iff rev < fwd" is that argmin: the forward code is the smaller).
+// The result is a function of the candidate SET, so the enumeration below may meet a move more than once.
+struct Knn {
+    uint8_t* tab;   // [n][kk] vertex ids: row x = N(x), less the entries (x, y) with y < x and x in N(y), which hold x
+                    // itself ("skip"): every pair of S is then met once, from its smaller vertex when both rows have it
+    uint8_t* pos;   // this chain's pos[v] = position of vertex v in the tour being descended
+    int kk;
+};
+
+// The workgroup builds the table: wave `wave` of `waves` selects rows wave, wave + waves, ... by kk rounds of argmin
+// over (w, y), a lane holding vertices lane, lane + 64, ...; then every thread drops the second copy of a mutual pair.
+// A thread meets at most n kk / 64 <= 128 entries, whose verdicts wait in two 64-bit masks for the barrier between the
+// reading and the writing of the table.  Ends with a barrier.
+template <class WA>
+__device__ void build_neighbors(const WA& W, uint8_t* tab, int n, int kk, int wave, int waves, int lane) {
+    constexpr int V = WA::kMaxN / kWave;
+    static_assert(WA::kMaxN * 32 / kWave <= 128, "the two dedup masks hold a thread's entries");
+    for (int x = wave; x < n; x += waves) {
+        float key[V];
+        bool avail[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const int y = lane + j * kWave;
+            avail[j] = y < n && y != x;
+            key[j] = avail[j] ? W(x, y) : FLT_MAX;
+        }
+        for (int s = 0; s < kk; ++s) {
+            float bv = FLT_MAX;
+            int bc = INT_MAX;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {   // ascending y: a strict < keeps the smaller id on a tie
+                if (avail[j] && (bc == INT_MAX || key[j] < bv)) {
+                    bv = key[j];
+                    bc = lane + j * kWave;
+                }
+            }
+            wave_argmin(bv, bc);
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (lane + j * kWave == bc) avail[j] = false;
+            if (lane == 0) tab[x * kk + s] = (uint8_t)(bc == INT_MAX ? x : bc);   // kk <= n - 1: bc is a vertex
+        }
+    }
+    __syncthreads();
+    const int tid = wave * kWave + lane, nt = waves * kWave, m = n * kk;
+    uint64_t dup0 = 0, dup1 = 0;
+    int it = 0;
+    for (int e = tid; e < m; e += nt, ++it) {
+        const int x = e / kk, y = tab[e];
+        bool dup = false;
+        if (y < x)
+            for (int s = 0; s < kk; ++s) dup |= tab[y * kk + s] == x;
+        if (dup) {
+            if (it < 64) dup0 |= 1ull << it;
+            else dup1 |= 1ull << (it - 64);
+        }
+    }
+    __syncthreads();
+    it = 0;
+    for (int e = tid; e < m; e += nt, ++it)
+        if ((it < 64 ? dup0 >> it : dup1 >> (it - 64)) & 1) tab[e] = (uint8_t)(e / kk);
+    __syncthreads();
+}
+
+// One lane's running best over the candidates it generates.
+template <class WA>
+struct KnnScan {
+    const WA& W;
+    const int* t;
+    int n;
+    float best = FLT_MAX;
+    int code = INT_MAX;
+    __device__ __forceinline__ void take(float d, int cd) {
+        if (d < best || (d == best && cd < code)) {
+            best = d;
+            code = cd;
+        }
+    }
+    __device__ __forceinline__ int wrap(int p) const { return p < 0 ? p + n : p >= n ? p - n : p; }
+    // descend()'s 2-opt move (i, j), when it is one
+    __device__ __forceinline__ void two_opt(int i, int j) {
+        if (i < 0 || !(j > i + 1) || (i == 0 && j == n - 1)) return;
+        const int a = t[i], b = t[i + 1], c = t[j], e = t[j + 1 < n ? j + 1 : 0];
+        take((W(a, c) + W(b, e)) - (W(a, b) + W(c, e)), (i << 8) | j);
+    }
+    // descend()'s Or-opt move (L, i, q) in the orientation rv, when it is one; i and q in [0, n)
+    __device__ __forceinline__ void or_opt(int L, int i, int q, int rv) {
+        const int rel = wrap(q - i);
+        if (rel < L || rel > n - 2) return;
+        const int prev = t[wrap(i - 1)], s0 = t[i], sl = t[wrap(i + L - 1)], nx = t[wrap(i + L)], a = t[q],
+                  b = t[wrap(q + 1)];
+        const float gain = W(prev, nx) - (W(prev, s0) + W(sl, nx));
+        const float ab = W(a, b);
+        const float ins = rv ? (W(a, sl) + W(s0, b)) - ab : (W(a, s0) + W(sl, b)) - ab;
+        take(gain + ins, kOrOpt | (rv << 29) | (L << 26) | (i << 8) | q);
+    }
+};
+
+// descend() over the candidates.  Work item 2 e + h: table entry e = (x, y), h = which of the two is u in the ordered
+// roles below; eleven moves per item.  Lanes 2 k and 2 k + 1 read one table byte, a wave 32 consecutive ones.
+template <class WA>
+__device__ float descend_knn(const WA& W, const Knn& K, int*& t, int*& u, int n, int lane) {
+    float cost = tour_cost(W, t, n, lane);
+    const int cap = 4 * n * n, items = 2 * n * K.kk;
+    for (int mv = 0; mv < cap; ++mv) {
+        for (int k = lane; k < n; k += kWave) K.pos[t[k]] = (uint8_t)k;
+        wave_sync();
+        KnnScan<WA> sc{W, t, n};
+        for (int item = lane; item < items; item += kWave) {
+            const int e = item >> 1, h = item & 1;
+            const int x = e / K.kk, y = K.tab[e];
+            if (y == x) continue;
+            const int pu = K.pos[h ? y : x], pv = K.pos[h ? x : y];
+            const int lo = min(pu, pv), hi = max(pu, pv);
+            if (!h) sc.two_opt(lo, hi);                      // {t[i], t[j]} = {x, y}
+            else if (lo >= 1) sc.two_opt(lo - 1, hi - 1);    // {t[i+1], t[j+1]} = {x, y}
+            else sc.two_opt(hi - 1, n - 1);                  // ... with j + 1 = n, which is position 0
+            for (int L = 1; L <= 3 && L <= n - 3; ++L) {
+                sc.or_opt(L, pv, pu, 0);                                   // a = u, s0 = v
+                sc.or_opt(L, sc.wrap(pu - L + 1), sc.wrap(pv - 1), 0);     // sl = u, b = v
+                if (L > 1) {
+                    sc.or_opt(L, sc.wrap(pv - L + 1), pu, 1);              // a = u, sl = v
+                    sc.or_opt(L, pu, sc.wrap(pv - 1), 1);                  // s0 = u, b = v
+                }
             }
         }
-        wave_sync();
-        int* x = t;
-        t = u;
-        u = x;
+        float best = sc.best;
+        int code = sc.code;
+        wave_argmin(best, code);
+        if (!(best < -kEpsRel * cost / (float)n)) break;   // wave-uniform: every lane holds the same pair
+        apply_move(t, u, n, code, lane);
         cost = tour_cost(W, t, n, lane);
     }
     return cost;
@@ -132,11 +280,12 @@ __device__ void double_bridge(const int* src, int* dst, int n, uint64_t r, int l
     wave_sync();
 }
 
-template <class WA>
+// kKnn: the chains descend by descend_knn over the neighbour table of `neighbors` columns; otherwise by descend().
+template <class WA, bool kKnn>
 __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     const float* __restrict__ Wg, const long long* __restrict__ w_off, const int* __restrict__ n_arr,
     const int32_t* __restrict__ init, const long long* __restrict__ t_off, const long long* __restrict__ index, int n_max,
-    int kicks, unsigned long long seed, int32_t* __restrict__ tours, float* __restrict__ costs) {
+    int kicks, int neighbors, unsigned long long seed, int32_t* __restrict__ tours, float* __restrict__ costs) {
     extern __shared__ float lds[];
     __shared__ float s_cost[kMaxChains];
     __shared__ int s_tour[kMaxChains];
@@ -156,6 +305,14 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     int* work = base + n_max;
     int* scr = base + 2 * n_max;
     __syncthreads();
+    // _knn: after every chain's tours the neighbour table [n_max][neighbors], then one pos[n_max] per chain, all bytes
+    Knn nb{};
+    if constexpr (kKnn) {
+        nb.tab = reinterpret_cast<uint8_t*>(reinterpret_cast<int*>(lds + WA::floats(n_max)) + chains * 3 * n_max);
+        nb.pos = nb.tab + n_max * neighbors + wave * n_max;
+        nb.kk = min(neighbors, n - 1);
+        build_neighbors(W, nb.tab, n, nb.kk, wave, chains, lane);
+    }
 
     // starting tour: chain 0 takes init_tours when given and a permutation of 0..n-1; otherwise Fisher-Yates
     bool have = false;
@@ -187,10 +344,14 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
         }
         wave_sync();
     }
-    float best = descend(W, cur, scr, n, lane);
+    float best;
+    if constexpr (kKnn) best = descend_knn(W, nb, cur, scr, n, lane);
+    else best = descend(W, cur, scr, n, lane);
     for (int kick = 0; kick < kicks; ++kick) {
         double_bridge(cur, work, n, draw(seed, gi, wave, kick, 0), lane);
-        const float c = descend(W, work, scr, n, lane);
+        float c;
+        if constexpr (kKnn) c = descend_knn(W, nb, work, scr, n, lane);
+        else c = descend(W, work, scr, n, lane);
         if (c <= best) {   // no worse: accept (the chain's current tour is always its best)
             int* x = cur;
             cur = work;
@@ -243,25 +404,30 @@ __global__ __launch_bounds__(kWave) void tour_lower_bound_kernel(const float* __
     if (lane == 0) lb[inst] = L;
 }
 
-template <class WA>
+// neighbors: 0 = the full-scan kernel (kKnn false); the _knn entry points pass their 1..32.
+template <class WA, bool kKnn>
 int search(const char* entry, const char* what, const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
-           const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks,
+           const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks, int neighbors,
            unsigned long long seed, int32_t* tours, float* costs, void* stream) {
     TSPGNN_REQUIRE(n_inst >= 0, "%s: n_inst=%d", what, n_inst);
     if (n_inst == 0) return TSPGNN_OK;
+    if constexpr (kKnn)
+        TSPGNN_REQUIRE(neighbors >= 1 && neighbors <= kMaxNeighbors, "%s: neighbors=%d not in [1, %d]", what, neighbors,
+                       kMaxNeighbors);
     if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
     TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
     TSPGNN_REQUIRE(restarts >= 1 && restarts <= kMaxChains, "%s: restarts=%d not in [1, %d]", what, restarts,
                    kMaxChains);
-    TSPGNN_REQUIRE(restarts <= chains_fit<WA>(n_max), "%s: restarts=%d: at n_max=%d at most %d chains fit in LDS", what,
-                   restarts, n_max, chains_fit<WA>(n_max));
+    const int fit = kKnn ? knn_chains_fit<WA>(n_max, neighbors) : chains_fit<WA>(n_max);
+    TSPGNN_REQUIRE(restarts <= fit, "%s: restarts=%d: at n_max=%d at most %d chains fit in LDS", what, restarts, n_max, fit);
     TSPGNN_REQUIRE(kicks >= 0, "%s: kicks=%d", what, kicks);
     TSPGNN_REQUIRE(W && w_off && n && t_off && tours && costs, "%s: null pointer", what);
-    const size_t lds = (WA::floats(n_max) + (size_t)3 * restarts * n_max) * sizeof(float);
-    int rc = allow_lds(tour_search_kernel<WA>, lds);
+    size_t lds = (WA::floats(n_max) + (size_t)3 * restarts * n_max) * sizeof(float);
+    if (kKnn) lds += (size_t)n_max * neighbors + (size_t)restarts * n_max;
+    int rc = allow_lds(tour_search_kernel<WA, kKnn>, lds);
     if (rc) return rc;
-    tour_search_kernel<WA><<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
-        W, w_off, n, init_tours, t_off, index, n_max, kicks, seed, tours, costs);
+    tour_search_kernel<WA, kKnn><<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
+        W, w_off, n, init_tours, t_off, index, n_max, kicks, neighbors, seed, tours, costs);
     return launched(entry);
 }
 
@@ -289,8 +455,8 @@ using namespace tspgnn;
 extern "C" int tspgnn_tour_search(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                   const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
                                   int kicks, unsigned long long seed, int32_t* tours, float* costs, void* stream) {
-    return search<SquareW>("tspgnn_tour_search", "tour_search", W, w_off, n, init_tours, t_off, index, n_inst, n_max,
-                           restarts, kicks, seed, tours, costs, stream);
+    return search<SquareW, false>("tspgnn_tour_search", "tour_search", W, w_off, n, init_tours, t_off, index, n_inst,
+                                  n_max, restarts, kicks, 0, seed, tours, costs, stream);
 }
 
 extern "C" int tspgnn_tour_lower_bound(const float* W, const long long* w_off, const int* n, const float* upper,
@@ -302,12 +468,28 @@ extern "C" int tspgnn_tour_lower_bound(const float* W, const long long* w_off, c
 extern "C" int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                       const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
                                       int kicks, unsigned long long seed, int32_t* tours, float* costs, void* stream) {
-    return search<TriW>("tspgnn_tour_search_tri", "tour_search_tri", W, w_off, n, init_tours, t_off, index, n_inst, n_max,
-                        restarts, kicks, seed, tours, costs, stream);
+    return search<TriW, false>("tspgnn_tour_search_tri", "tour_search_tri", W, w_off, n, init_tours, t_off, index, n_inst,
+                               n_max, restarts, kicks, 0, seed, tours, costs, stream);
 }
 
 extern "C" int tspgnn_tour_lower_bound_tri(const float* W, const long long* w_off, const int* n, const float* upper,
                                            int n_inst, int n_max, int iters, double* lb, void* stream) {
     return lower_bound<TriW>("tspgnn_tour_lower_bound_tri", "tour_lower_bound_tri", W, w_off, n, upper, n_inst, n_max,
                              iters, lb, stream);
+}
+
+extern "C" int tspgnn_tour_search_knn(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                                      const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
+                                      int kicks, int neighbors, unsigned long long seed, int32_t* tours, float* costs,
+                                      void* stream) {
+    return search<SquareW, true>("tspgnn_tour_search_knn", "tour_search_knn", W, w_off, n, init_tours, t_off, index, n_inst,
+                                 n_max, restarts, kicks, neighbors, seed, tours, costs, stream);
+}
+
+extern "C" int tspgnn_tour_search_knn_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                                          const long long* t_off, const long long* index, int n_inst, int n_max,
+                                          int restarts, int kicks, int neighbors, unsigned long long seed, int32_t* tours,
+                                          float* costs, void* stream) {
+    return search<TriW, true>("tspgnn_tour_search_knn_tri", "tour_search_knn_tri", W, w_off, n, init_tours, t_off, index,
+                              n_inst, n_max, restarts, kicks, neighbors, seed, tours, costs, stream);
 }

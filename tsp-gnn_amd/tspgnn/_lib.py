@@ -91,6 +91,10 @@ SIGNATURES = {
     "tspgnn_tour_lower_bound": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "tspgnn_tour_search_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_search_knn": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                               c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_search_knn_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_lower_bound_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "tspgnn_tour_branch_bound": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -25,6 +25,7 @@ from .instance_loader import route_cost, write_graph
 
 MAX_N = 128
 MAX_N_TRI = 256   # label_tours: the triangle kernels (n 129-256)
+MAX_NEIGHBORS = 32   # neighbors=K: the widest neighbour table of tspgnn_tour_search_knn
 
 # Defaults measured on the MI355X at the reference's training shape (n 20-40): 8 chains of 96 kicks label
 # 2^15 instances in a few seconds, and on n 5-13 they match exact optima; 400 subgradient steps bring the median
@@ -140,7 +141,7 @@ def _target(Ma, Mw, tour):
 
 
 def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=0, init_tours=None, lower_bound=True,
-                device=None, lb_iters=DEFAULT_LB_ITERS, chunk=DEFAULT_CHUNK, index=None, timings=None):
+                device=None, lb_iters=DEFAULT_LB_ITERS, chunk=DEFAULT_CHUNK, index=None, timings=None, neighbors=None):
     """Solve symmetric TSP instances on the GPU, many at once.
 
     instances: list of (Ma, Mw); Ma upper-triangular or symmetric (nonzero = edge), Mw [n,n] with w(i,j) = Mw[min, max].
@@ -150,16 +151,20 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
     cycle, so a planted graph always gets a feasible tour.
     lower_bound: also run the Held-Karp bound (lb_iters subgradient steps).  chunk: instances per launch.
     index: the key of each instance in the generator (default: its position in ``instances``); results depend on
-    (seed, index, restarts, kicks) only, never on ``chunk``.
+    (seed, index, restarts, kicks, neighbors) only, never on ``chunk``.
+    neighbors: None = every descent step scans the whole 2-opt + Or-opt neighbourhood (tspgnn_tour_search).  K in 1..32 =
+    it scans only the moves that add an edge {x, y} with y among the K nearest vertices of x or x among y's
+    (tspgnn_tour_search_knn): many times fewer evaluations per step, so more kicks in the same time.
     timings: optional dict that receives the seconds spent in 'pack', 'search' and 'bound' (device-synchronised).
     n < 4 is solved on the host; n > 128 raises ValueError before anything is launched.
 
     Returns a list of TourResult (tour, cost, lb, feasible, target).
     """
     t0 = time.perf_counter()
+    _check_neighbors(neighbors)
     checked, index = _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, MAX_N)
     return _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0,
-                  tri=False)
+                  tri=False, neighbors=neighbors)
 
 
 def _check_counts(restarts, kicks, lb_iters, chunk):
@@ -167,6 +172,13 @@ def _check_counts(restarts, kicks, lb_iters, chunk):
         raise ValueError("restarts=%d must be in [1, 16]" % restarts)
     if kicks < 0 or lb_iters < 1 or chunk < 1:
         raise ValueError("kicks, lb_iters and chunk must be non-negative / positive")
+
+
+def _check_neighbors(neighbors):
+    if neighbors is None:
+        return
+    if isinstance(neighbors, bool) or not isinstance(neighbors, (int, np.integer)) or not 1 <= neighbors <= MAX_NEIGHBORS:
+        raise ValueError("neighbors=%r must be None or an int in [1, %d]" % (neighbors, MAX_NEIGHBORS))
 
 
 def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, max_n):
@@ -182,9 +194,9 @@ def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, ma
 
 
 def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0, tri,
-           exact=None, incumbents=None):
+           exact=None, incumbents=None, neighbors=None):
     """solve_tours on checked instances, n < 4 on the host and the rest on the square kernels (tri=False, n <= 128) or
-    the triangle kernels (tri=True, n <= 256).
+    the triangle kernels (tri=True, n <= 256); neighbors=K: the search is the _knn entry point of that layout.
     exact = (max_nodes, node_iters, opt_tol, status, nodes): the branch and bound takes the place of the bound launch
     (tri=False only) and fills the int arrays status / nodes at this call's positions (n < 4: proved, 0 nodes).
     incumbents: one tour per instance; the search is skipped and the branch and bound starts from these."""
@@ -233,6 +245,9 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
     has_init = init_tours is not None and any(t is not None for t in init_tours)
     search, bound = ("tspgnn_tour_search_tri", "tspgnn_tour_lower_bound_tri") if tri else \
         ("tspgnn_tour_search", "tspgnn_tour_lower_bound")
+    knn = ()
+    if neighbors is not None:
+        search, knn = search.replace("_search", "_search_knn"), (int(neighbors),)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     G = len(big)
     with torch.cuda.device(dev):
@@ -255,8 +270,8 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
             c1 = min(G, c0 + chunk)
             _lib.call(search, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                       _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
-                      int(restarts), int(kicks), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours), _lib.ptr(d_cost[c0:c1]),
-                      st)
+                      int(restarts), int(kicks), *knn, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours),
+                      _lib.ptr(d_cost[c0:c1]), st)
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
         if exact is not None:
@@ -304,10 +319,14 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
     return out
 
 
-def tri_chains_fit(n):
+def tri_chains_fit(n, neighbors=None):
     """The most restarts tspgnn_tour_search_tri takes at n_max = n: its LDS holds the n (n-1) / 2 fp32 triangle and
-    three tours of n int32 ids per chain in 163 712 bytes (160 KiB less its 128 static bytes): 10 at n = 256."""
-    return min(16, (163712 - 2 * n * (n - 1)) // (12 * n))
+    three tours of n int32 ids per chain in 163 712 bytes (160 KiB less its 128 static bytes): 10 at n = 256.
+    neighbors=K: tspgnn_tour_search_knn_tri's, which also holds n K bytes of neighbour table and n bytes of positions
+    per chain: 9 at n = 256 with K = 8."""
+    if neighbors is None:
+        return min(16, (163712 - 2 * n * (n - 1)) // (12 * n))
+    return min(16, (163712 - 2 * n * (n - 1) - n * neighbors) // (13 * n))
 
 
 def _bb_stats(stats, status, nodes, seconds):
@@ -377,21 +396,23 @@ def prove_tours(instances, results, max_nodes=DEFAULT_BB_NODES, node_iters=DEFAU
 
 
 def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, init_tours=None, lower_bound=True,
-                device=None, chunk=DEFAULT_CHUNK, index=None, timings=None, exact=False, max_nodes=None, stats=None):
+                device=None, chunk=DEFAULT_CHUNK, index=None, timings=None, exact=False, max_nodes=None, stats=None,
+                neighbors=None):
     """solve_tours for instances of up to MAX_N_TRI = 256 vertices, split by n: n < 4 on the host, 4-128 on the square
     kernels (exactly solve_tours), 129-256 on the packed-triangle kernels (tspgnn_tour_search_tri /
     tspgnn_tour_lower_bound_tri); n > 256 raises ValueError before anything is launched.
 
     restarts, kicks, lb_iters: None takes DEFAULT_* for n <= 128 and DEFAULT_*_LARGE for n > 128; a value applies to both.
-    For n > 128 restarts may not exceed tri_chains_fit(largest n) (10 at n = 256).  The other arguments are solve_tours'.
-    Results come back in input order; each depends on (seed, its index, restarts, kicks) only, never on chunk or on which
-    other instances share the call.
+    For n > 128 restarts may not exceed tri_chains_fit(largest n, neighbors) (10 at n = 256; 9 with neighbors=8).  The
+    other arguments are solve_tours'.  Results come back in input order; each depends on (seed, its index, restarts, kicks,
+    neighbors) only, never on chunk or on which other instances share the call.
     exact=True: for n <= 128 the branch and bound (prove_tours, with max_nodes or DEFAULT_BB_NODES, DEFAULT_BB_ITERS
     steps per node and lb_iters at the root) takes the place of the bound launch: lb is its bound and the tour the best it
     holds.  stats then receives prove_tours' 'status', 'nodes' and 'seconds'; n > 128 is 'skipped' and keeps the plain
     bound.  timings gets the launch under 'exact'.
     """
     t0 = time.perf_counter()
+    _check_neighbors(neighbors)
     bb = None
     if exact:
         bb = (DEFAULT_BB_NODES if max_nodes is None else max_nodes, DEFAULT_BB_ITERS, 1e-9,
@@ -406,8 +427,9 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
     _check_counts(*large, chunk)
     checked, index = _validate(instances, *small, chunk, index, init_tours, MAX_N_TRI)
     n_big = max([c[2] for c in checked if c[2] > MAX_N], default=0)
-    if n_big and large[0] > tri_chains_fit(n_big):
-        raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS" % (large[0], n_big, tri_chains_fit(n_big)))
+    if n_big and large[0] > tri_chains_fit(n_big, neighbors):
+        raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS"
+                         % (large[0], n_big, tri_chains_fit(n_big, neighbors)))
     out = [None] * len(checked)
     for tri, (r, k, it) in ((False, small), (True, large)):
         sel = [i for i, c in enumerate(checked) if (c[2] > MAX_N) == tri]
@@ -416,7 +438,7 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
         inits = None if init_tours is None else [init_tours[i] for i in sel]
         sub = None if bb is None or tri else bb[:3] + (np.zeros(len(sel), dtype=np.int64), np.zeros(len(sel), dtype=np.int64))
         res = _solve([checked[i] for i in sel], index[sel], inits, r, k, seed, lower_bound, device, it, chunk, timings,
-                     t0 if not tri else time.perf_counter(), tri, exact=sub)
+                     t0 if not tri else time.perf_counter(), tri, exact=sub, neighbors=neighbors)
         for i, x in zip(sel, res):
             out[i] = x
         if sub is not None:
@@ -428,7 +450,7 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
 
 def solve(Ma, Mw, **kw):
     """The reference's contract (dataset.py:9-50): the tour as a list, or None when the best tour found needs an edge
-    absent from Ma.  Keyword arguments go to label_tours."""
+    absent from Ma.  Keyword arguments (restarts, kicks, seed, neighbors, ...) go to label_tours."""
     r = label_tours([(Ma, Mw)], lower_bound=False, **kw)[0]
     return r.tour if r.feasible else None
 
@@ -526,7 +548,7 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     Redrawing BIASES the distribution: it drops the instances whose optimum sits close to the quirk target, which are the
     hardest ones, and the set no longer matches the reference's stream from the first redrawn index on.
     exact=True: label with label_tours(exact=True), the branch and bound for n <= 128 (prove_tours).
-    solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device, max_nodes); n up to 256.
+    solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device, max_nodes, neighbors); n up to 256.
 
     Returns a summary dict: samples, n (per instance), cost, lb, target, feasible, gap = (cost - lb) / cost,
     certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'};
