@@ -580,6 +580,20 @@ int tspgnn_tour_branch_bound(const float* W, const long long* w_off, const int* 
  * TSPGNN_BB_MAX_DEPTH * n_max floats; 0 for an empty or unsupported request. */
 long long tspgnn_tour_branch_bound_ws(int n_inst, int n_max);
 
+/*
+ * Metric closure of `count` weight matrices, in place: batched Floyd-Warshall in fp64, one workgroup per instance.
+ * Replaces the networkx closure of the reference's 'random' distances (dataset.py:85-101).  Instance b is a row-major
+ * fp64 n[b] x n[b] matrix at D + off[b] (off in doubles, in any order, gaps allowed; nothing outside the matrices is
+ * written); 1 <= n[b] <= n_max <= 256.  Entries are finite and >= 0; the matrix need not be symmetric.
+ * The result is exactly this process: the diagonal is set to 0; for k = 0 .. n-1 in ascending order
+ * D[i][j] = min(D[i][j], D[i][k] + D[k][j]), the sum rounded once in fp64; the diagonal is set to 0.  It depends on the
+ * instance alone, never on n_max, on the other instances or on the launch.
+ * n_max <= 143 (8 n_max^2 bytes fit the 160 KiB of LDS): the matrix is closed in LDS; above, in place in global memory.
+ * n_max > 256, n_max < 1, count < 0 or a null pointer with count > 0: TSPGNN_EINVAL before any launch.  count == 0 is a
+ * no-op.
+ */
+int tspgnn_metric_closure(double* D, const long long* off, const int* n, int count, int n_max, void* stream);
+
 /* ------------------------------------------------------------------ decision-TSP baselines (tspgnn/baselines.py) */
 
 /*

@@ -1,14 +1,17 @@
 """Times GPU labelling (tspgnn.dataset) at the reference's dataset shapes: the training set (2^15 instances, n 20-40),
-the test set (2^10), n = 80, and n = 200 and 256 (label_tours on the triangle kernels).  Reports the search, bound and file-writing seconds separately, the certified fraction
+the test set (2^10), n = 80, and n = 200 and 256 (label_tours on the triangle kernels).  Reports the closure, search, bound and file-writing seconds separately, the certified fraction
 at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per shape.
 
     python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
-        [--exact [--max-nodes N]] [--neighbors K]
+        [--exact [--max-nodes N]] [--neighbors K] [--distances euc_2D|random] [--closure host|device]
 
 Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
 --exact labels with the branch and bound (label_tours(exact=True), n <= 128) and adds the proved fraction, the nodes per
 instance (p50 / p90 / max) and the seconds of that launch; bound_s is then 0.
 --neighbors K runs the candidate-list descent (label_tours(neighbors=K)); the JSON line then carries "neighbors".
+--distances random draws the reference's random metric instances; --closure says where their metric closure is taken
+(draw_instances(closure=...)): "closure_s" is its wall seconds (for device: synchronised, transfers included) and
+"draw_s" the rest of the drawing.
 """
 import argparse
 import json
@@ -40,6 +43,9 @@ def main():
     ap.add_argument("--exact", action="store_true", help="label with the branch and bound (n <= 128)")
     ap.add_argument("--max-nodes", type=int, default=None, help="--exact: nodes per instance")
     ap.add_argument("--neighbors", type=int, default=None, help="candidate-list descent over K nearest neighbours")
+    ap.add_argument("--distances", default="euc_2D", choices=("euc_2D", "random"))
+    ap.add_argument("--closure", default="host", choices=("host", "device"),
+                    help="--distances random: where the metric closure is taken")
     ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
@@ -49,6 +55,9 @@ def main():
     for n in (20, 130):
         dataset.label_tours([(np.triu(np.ones((n, n)), 1), np.random.RandomState(0).rand(n, n))], kicks=1, lb_iters=1,
                             neighbors=a.neighbors)
+    if a.closure == "device" and a.distances != "euc_2D":
+        for n in (20, 40, 80, 140, 200):   # one launch per kernel instantiation
+            dataset.metric_closure([np.ones((n, n))])
     if a.exact:
         dataset.label_tours([(np.triu(np.ones((20, 20)), 1), np.random.RandomState(0).rand(20, 20))], kicks=1, lb_iters=1,
                             exact=True, max_nodes=1)
@@ -58,8 +67,10 @@ def main():
         random.seed(1)
         np.random.seed(1)
         t0 = time.perf_counter()
-        graphs = dataset.draw_instances(nmin, nmax, samples=samples)
-        t_draw = time.perf_counter() - t0
+        tc = {}
+        graphs = dataset.draw_instances(nmin, nmax, samples=samples, distances=a.distances, closure=a.closure, timings=tc)
+        t_draw = time.perf_counter() - t0 - tc.get("closure", 0.0)
+        closure = {} if "closure" not in tc else {"closure": a.closure, "closure_s": round(tc["closure"], 3)}
         tm, stats = {}, {}
         res = dataset.label_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs],
                                   restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, timings=tm,
@@ -90,7 +101,7 @@ def main():
                      "proved_gap_max": float(gap[stats["status"] == "proved"].max(initial=0.0))}
         print(json.dumps({
             "shape": name, "samples": samples, "n": [nmin, nmax], "restarts": restarts, "kicks": kicks,
-            "lb_iters": lb_iters, **({} if a.neighbors is None else {"neighbors": a.neighbors}), "draw_s": round(t_draw, 3), "pack_s": round(tm["pack"], 3),
+            "lb_iters": lb_iters, **({} if a.neighbors is None else {"neighbors": a.neighbors}), "distances": a.distances, "draw_s": round(t_draw, 3), **closure, "pack_s": round(tm["pack"], 3),
             "search_s": round(tm["search"], 3), "bound_s": round(tm.get("bound", 0.0), 3), **exact,
             "write_s": None if t_write is None else round(t_write, 3),
             "feasible": float(np.mean([r.feasible for r in res])),

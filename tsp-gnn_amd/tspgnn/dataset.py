@@ -26,6 +26,8 @@ from .instance_loader import route_cost, write_graph
 MAX_N = 128
 MAX_N_TRI = 256   # label_tours: the triangle kernels (n 129-256)
 MAX_NEIGHBORS = 32   # neighbors=K: the widest neighbour table of tspgnn_tour_search_knn
+CLOSURE_MAX_N = 256       # metric_closure: the largest matrix tspgnn_metric_closure takes
+CLOSURE_LDS_MAX_N = 143   # ... and the largest it closes in LDS: 8 n^2 <= 160 KiB (kClosureLdsMaxN, csrc/tour_closure.hip)
 
 # Defaults measured on the MI355X at the reference's training shape (n 20-40): 8 chains of 96 kicks label
 # 2^15 instances in a few seconds, and on n 5-13 they match exact optima; 400 subgradient steps bring the median
@@ -488,9 +490,95 @@ def floyd_warshall(Mw):
     return D
 
 
-def _draw_graph(n, connectivity, distances="euc_2D", metric=True):
+def metric_closure(matrices, device=None, chunk_bytes=1 << 30):
+    """floyd_warshall on the GPU, many matrices at once (tspgnn_metric_closure, csrc/tour_closure.hip): the closure the
+    reference takes with networkx for 'random' distances (dataset.py:85-101).
+
+    matrices: a list of square arrays, 1 <= n <= CLOSURE_MAX_N = 256, entries finite and >= 0, not necessarily symmetric.
+    Everything is checked on the host before the first launch; a failure raises ValueError naming the instance.
+    The instances are sorted by n; those of n <= CLOSURE_LDS_MAX_N and the larger ones go to separate launches, so a small
+    instance is closed in LDS whatever its neighbours, and a launch holds at most chunk_bytes of matrices (and at least
+    one).  Each result equals floyd_warshall of its matrix bit for bit; it never depends on the other instances, on
+    chunk_bytes or on the kernel's tier.
+
+    Returns a list of fp64 [n, n] arrays in input order.
+    """
+    if chunk_bytes < 1:
+        raise ValueError("chunk_bytes=%r must be positive" % (chunk_bytes,))
+    mats = []
+    for k, m in enumerate(matrices):
+        a = np.asarray(m, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("instance %d: a weight matrix must be square, not %s" % (k, a.shape))
+        n = a.shape[0]
+        if not 1 <= n <= CLOSURE_MAX_N:
+            raise ValueError("instance %d: n=%d is outside the closure kernel's range [1, %d]" % (k, n, CLOSURE_MAX_N))
+        if not np.all(np.isfinite(a)) or a.min() < 0:
+            raise ValueError("instance %d: weights must be finite and non-negative" % k)
+        mats.append(a)
+    out = [None] * len(mats)
+    if not mats:
+        return out
+    ns = np.array([a.shape[0] for a in mats], dtype=np.int32)
+    order = np.argsort(ns, kind="stable")
+    launches = []   # lists of positions in `mats`: one tier each, ascending n, at most chunk_bytes
+    for tier in (order[ns[order] <= CLOSURE_LDS_MAX_N], order[ns[order] > CLOSURE_LDS_MAX_N]):
+        cur, size = [], 0
+        for p in tier:
+            b = 8 * int(ns[p]) ** 2
+            if cur and size + b > chunk_bytes:
+                launches.append(cur)
+                cur, size = [], 0
+            cur.append(int(p))
+            size += b
+        if cur:
+            launches.append(cur)
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        st = _lib.current_stream()
+        for sel in launches:
+            n_sel = ns[sel]
+            sq = n_sel.astype(np.int64) ** 2
+            off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
+            d_D = torch.from_numpy(np.concatenate([mats[p].reshape(-1) for p in sel])).to(dev)
+            d_off = torch.from_numpy(off).to(dev)
+            d_n = torch.from_numpy(np.ascontiguousarray(n_sel)).to(dev)
+            _lib.call("tspgnn_metric_closure", _lib.ptr(d_D), _lib.ptr(d_off), _lib.ptr(d_n), len(sel),
+                      int(n_sel.max()), st)
+            flat = d_D.cpu().numpy()
+            for p, o, n in zip(sel, off, n_sel):
+                out[p] = flat[o:o + int(n) * int(n)].reshape(int(n), int(n)).copy()
+    return out
+
+
+def _check_closure(closure):
+    if closure not in ("host", "device"):
+        raise ValueError("closure=%r must be 'host' or 'device'" % (closure,))
+
+
+def _closes(distances, metric):
+    """Whether create_graph takes the metric closure of these weights (dataset.py:85)."""
+    return bool(metric) and distances != "euc_2D"
+
+
+def _close_on_device(graphs, idx, device, timings):
+    """closure='device': close the weights of graphs[i], i in idx, which _draw_graph left open, in one metric_closure
+    call; its wall seconds (transfers included, device-synchronised) are added to timings['closure']."""
+    if not len(idx):
+        return
+    t0 = time.perf_counter()
+    closed = metric_closure([graphs[i][1] for i in idx], device=device)
+    for i, Mw in zip(idx, closed):
+        graphs[i] = (graphs[i][0], Mw) + tuple(graphs[i][2:])
+    if timings is not None:
+        timings["closure"] = timings.get("closure", 0.0) + (time.perf_counter() - t0)
+
+
+def _draw_graph(n, connectivity, distances="euc_2D", metric=True, close=True, timings=None):
     """create_graph's draws (dataset.py:52-108) in the reference's order on the global np.random: the adjacency pairs,
-    then the points or the weights, then the planted permutation.  Returns (symmetric Ma, Mw, permutation, nodes)."""
+    then the points or the weights, then the planted permutation.  Returns (symmetric Ma, Mw, permutation, nodes).
+    close=False leaves the metric closure of Mw to the caller (closure='device'); it draws no random numbers, so the
+    stream is the same.  timings: optional dict; the closure's seconds are added to its 'closure'."""
     Ma = np.zeros((n, n))
     Mw = np.zeros((n, n))
     iu = np.triu_indices(n, 1)   # the (i, j > i) loop order of dataset.py:60-64 and :77-81
@@ -508,19 +596,28 @@ def _draw_graph(n, connectivity, distances="euc_2D", metric=True):
         w = np.random.rand(iu[0].size)
         Mw[iu] = w
         Mw[iu[1], iu[0]] = w
-    if metric and distances != "euc_2D":
+    if close and _closes(distances, metric):
+        t0 = time.perf_counter()
         Mw = floyd_warshall(Mw)
+        if timings is not None:
+            timings["closure"] = timings.get("closure", 0.0) + (time.perf_counter() - t0)
     permutation = [int(x) for x in np.random.permutation(n)]
     for i, j in zip(permutation, permutation[1:] + permutation[:1]):
         Ma[i, j] = Ma[j, i] = 1
     return Ma, Mw, permutation, nodes
 
 
-def create_graph(n, connectivity, distances="euc_2D", metric=True, **solve_kw):
+def create_graph(n, connectivity, distances="euc_2D", metric=True, closure="host", **solve_kw):
     """dataset.py:52-116: a random graph with a planted Hamiltonian cycle, labelled with the best tour found.
     Returns (np.triu(Ma), Mw, route, nodes); raises Exception('Unsolvable') as the reference does when that tour needs an
-    absent edge (it cannot here: the planted cycle is the search's first start).  solve_kw go to label_tours."""
-    Ma, Mw, perm, nodes = _draw_graph(n, connectivity, distances, metric)
+    absent edge (it cannot here: the planted cycle is the search's first start).  closure: 'host' takes the metric
+    closure of non-Euclidean weights with floyd_warshall, 'device' with metric_closure -- the same draws and the same
+    bits.  solve_kw go to label_tours."""
+    _check_closure(closure)
+    graphs = [_draw_graph(n, connectivity, distances, metric, close=closure == "host")]
+    if closure == "device" and _closes(distances, metric):
+        _close_on_device(graphs, [0], solve_kw.get("device"), None)
+    Ma, Mw, perm, nodes = graphs[0]
     solve_kw.setdefault("lower_bound", False)
     r = label_tours([(Ma, Mw)], init_tours=[perm], **solve_kw)[0]
     if not r.feasible:
@@ -528,18 +625,28 @@ def create_graph(n, connectivity, distances="euc_2D", metric=True, **solve_kw):
     return np.triu(Ma), Mw, r.tour, nodes
 
 
-def draw_instances(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True):
+def draw_instances(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True, closure="host",
+                   timings=None, device=None):
     """The instance stream of create_dataset (dataset.py:126-133): per sample random.randint(nmin, nmax), then
-    np.random.uniform(conn_min, conn_max), then create_graph's draws.  Returns a list of (Ma, Mw, permutation, nodes)."""
+    np.random.uniform(conn_min, conn_max), then create_graph's draws.  Returns a list of (Ma, Mw, permutation, nodes).
+    closure: where the metric closure of non-Euclidean weights is taken.  'host': floyd_warshall inside each draw.
+    'device': the draws run as before with the closure left out -- it consumes no random numbers -- and one
+    metric_closure call on ``device`` closes them all afterwards: the same instances bit for bit, the global generators
+    in the same state.  With euc_2D or metric=False nothing is closed and the argument changes nothing.
+    timings: optional dict; when a closure ran, its wall seconds are added to timings['closure']."""
+    _check_closure(closure)
     out = []
     for _ in range(samples):
         n = random.randint(nmin, nmax)
-        out.append(_draw_graph(n, np.random.uniform(conn_min, conn_max), distances=distances, metric=metric))
+        out.append(_draw_graph(n, np.random.uniform(conn_min, conn_max), distances=distances, metric=metric,
+                               close=closure == "host", timings=timings))
+    if closure == "device" and _closes(distances, metric):
+        _close_on_device(out, range(samples), device, timings)
     return out
 
 
 def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True,
-                   require_certified=None, max_redraw_rounds=20, verbose=False, exact=False, **solve_kw):
+                   require_certified=None, max_redraw_rounds=20, verbose=False, exact=False, closure="host", **solve_kw):
     """dataset.py:118-143: draw ``samples`` instances (the reference's stream), label them on the GPU in batches with
     the planted cycle as a starting tour, and write ``{path}/{i}.graph`` with write_graph.
 
@@ -548,16 +655,21 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     Redrawing BIASES the distribution: it drops the instances whose optimum sits close to the quirk target, which are the
     hardest ones, and the set no longer matches the reference's stream from the first redrawn index on.
     exact=True: label with label_tours(exact=True), the branch and bound for n <= 128 (prove_tours).
+    closure: 'host' | 'device', as draw_instances: where the metric closure of non-Euclidean weights is taken, for the
+    stream and for every redraw round (one metric_closure call each); the files are the same bytes either way.
     solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device, max_nodes, neighbors); n up to 256.
 
     Returns a summary dict: samples, n (per instance), cost, lb, target, feasible, gap = (cost - lb) / cost,
-    certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'};
+    certified_fraction (at require_certified, else 0.02), redrawn (count) and times {'pack', 'search', 'bound', 'write'},
+    plus times['closure'] when a metric closure ran (wall seconds; for 'device' synchronised, transfers included);
     with exact=True also proved (per instance: the written tour is proved optimal), nodes (per instance) and
     times['exact'].
     """
+    _check_closure(closure)
     os.makedirs(path, exist_ok=True)
-    graphs = draw_instances(nmin, nmax, conn_min, conn_max, samples, distances, metric)
     times = {}
+    graphs = draw_instances(nmin, nmax, conn_min, conn_max, samples, distances, metric, closure=closure, timings=times,
+                            device=solve_kw.get("device"))
     solve_kw.setdefault("lower_bound", True)
     proved, nodes = np.zeros(samples, dtype=bool), np.zeros(samples, dtype=np.int64)
 
@@ -583,7 +695,10 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
                 break
             for i in bad:
                 n = graphs[i][0].shape[0]
-                graphs[i] = _draw_graph(n, np.random.uniform(conn_min, conn_max), distances=distances, metric=metric)
+                graphs[i] = _draw_graph(n, np.random.uniform(conn_min, conn_max), distances=distances, metric=metric,
+                                        close=closure == "host", timings=times)
+            if closure == "device" and _closes(distances, metric):
+                _close_on_device(graphs, [int(i) for i in bad], solve_kw.get("device"), times)
             redrawn += int(bad.size)
             new = label(list(bad), rnd * samples + bad)
             for i, r in zip(bad, new):
