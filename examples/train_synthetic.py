@@ -18,7 +18,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tsp-gnn_amd"))
-from tspgnn import (InstanceLoader, Session, build_network, global_variables_initializer, load_weights,  # noqa: E402
+from tspgnn import (DeviceDataset, InstanceLoader, Session, build_network, global_variables_initializer, load_weights,  # noqa: E402
                     random_instance, save_weights, write_graph)
 from tspgnn.train import run_batch, summarize_epoch  # noqa: E402
 
@@ -36,6 +36,9 @@ if __name__ == '__main__':
                                                      'missing); batches then come from InstanceLoader.get_batches like train.py:178')
     p.add_argument('--checkpoints', default=None, help='directory for TensorFlow-format checkpoints: resumes from the '
                                                        'newest epoch=N found there and saves after every epoch (train.py:205)')
+    p.add_argument('-device_dataset', action='store_true',
+                   help='upload the instances once (tspgnn.DeviceDataset) and assemble every batch on the GPU from instance '
+                        'ids: epochs through DeviceDataset.get_batches instead of InstanceLoader / create_batch')
     a = p.parse_args()
     rng = np.random.RandomState(a.seed)
     loader = None
@@ -46,6 +49,10 @@ if __name__ == '__main__':
                 Ma, Mw, route = random_instance(int(rng.randint(20, 41)), rng)
                 write_graph(Ma, Mw, os.path.join(a.instances, '{}.graph'.format(i)), route=route)
         loader = InstanceLoader(a.instances)
+    dataset = None
+    if a.device_dataset:   # the same instances every epoch, shuffled per epoch like InstanceLoader.reset()
+        dataset = DeviceDataset.from_directory(a.instances) if a.instances is not None else DeviceDataset(
+            [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize * a.batches)])
     GNN = build_network(a.d)
     with Session() as sess:
         sess.run(global_variables_initializer(seed=a.seed))
@@ -56,7 +63,9 @@ if __name__ == '__main__':
                 first = load_weights(sess, '{}/epoch={}'.format(a.checkpoints, saved[-1])) + 1
         for epoch in range(first, first + a.epochs):
             stats = []
-            if loader is not None:
+            if dataset is not None:
+                batches = dataset.get_batches(a.batchsize, a.dev, a.timesteps, rng=rng)
+            elif loader is not None:
                 loader.reset()
                 batches = loader.get_batches(a.batchsize, a.dev)
             else:

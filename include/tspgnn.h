@@ -861,6 +861,34 @@ int tspgnn_adam_clip_step_f32(float* theta, float* g, float* m, float* v, int n,
                               float* gnorm_out, float* workspace, int* step_counter, const unsigned* skip_flag,
                               void* stream);
 
+/* ------------------------------------------------------------------ batches from a device-resident dataset */
+
+/*
+ * One batch, assembled on the device from a dataset that was uploaded once (tspgnn/device_dataset.py): writes exactly
+ * the bytes tspgnn_host_stage_batch (below) writes for the instance list ids[0..B), in ONE launch.
+ * The dataset, all DEVICE arrays, instance i of I:
+ *   inst   int32[I][4]        n, m, first edge e0, first vertex v0 of the instance in the arrays below (prefix sums)
+ *   uv     int32[sum m][2]    LOCAL endpoint ids of its edges in np.nonzero(Ma) order, at e0
+ *   w      float[sum m]       (float)Mw[i,j] of those edges, at e0
+ *   rowptr int32[sum (n+1)]   its local CSR by vertex, n + 1 entries at v0 + i
+ *   eid    int32[2 sum m]     ... and its 2 m local edge ids, ascending inside a vertex, at 2 e0
+ *   cost   double[I]          tspgnn_host_route_cost of its tour (may be NULL with use_target)
+ * The batch: ids int32[B] on the DEVICE, each in [0, I) -- checked by the caller, not here; e_start / v_start
+ * int32[B+1] on the DEVICE, the prefix sums of m[ids[b]] / n[ids[b]]; M = e_start[B], N = v_start[B].
+ * Out, at dst + off[k] (dst on the DEVICE, off[7] a HOST array, the order of parallel.stage_layout):
+ *   uv int32[M][2] local endpoint + v_start[b] | eid int32[2M] local edge id + e_start[b] | rowptr int32[N+1] local row
+ *   pointer + 2 e_start[b], rowptr[N] = 2M | wc float[M][2] (weight, (float)c_b) | labels float[B] b mod 2 |
+ *   seg int32[B+1] = e_start | n_edges int32[B].
+ * c_b = target_cost if use_target, else (1.0 - dev) * cost for even b and (1.0 + dev) * cost for odd b, in fp64 with
+ * two roundings like the host code.  Nothing outside the seven arrays is written.
+ * B, M or N < 0, a null pointer with B > 0, dst or an offset not 8-byte aligned: TSPGNN_EINVAL before any launch.
+ * B == 0 or M == 0 launches nothing and returns 0 (a batch without edges is all offsets: the caller fills it).
+ */
+int tspgnn_gather_batch(const int32_t* inst, const int32_t* uv, const float* w, const int32_t* rowptr,
+                        const int32_t* eid, const double* cost, const int32_t* ids, const int32_t* e_start,
+                        const int32_t* v_start, int B, int M, int N, double dev, int use_target, double target_cost,
+                        unsigned char* dst, const long long* off, void* stream);
+
 /* ------------------------------------------------------------------ host-side batch packing (no GPU work) */
 
 /*

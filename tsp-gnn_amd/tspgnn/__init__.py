@@ -14,6 +14,7 @@ from .dataset import solve_tours, label_tours, prove_tours, solve, certify, crea
 from .baselines import nearest_neighbor_tours, anneal_tours, decide
 from .mlp import Mlp
 from .parallel import BatchPrefetcher, BatchStager, shard_instances
+from .device_dataset import DeviceDataset
 from .model import build_network, Session, global_variables_initializer
 from .variables import VariableStore, get_default_store, reset_default_store
 from . import tf_checkpoint
@@ -27,5 +28,5 @@ __all__ = [
     "Session", "global_variables_initializer", "get_cost", "get_costs", "BatchPrefetcher", "BatchStager", "shard_instances", "VariableStore", "get_default_store", "reset_default_store",
     "load_weights", "save_weights", "run_batch", "summarize_epoch", "solve_tours", "label_tours", "prove_tours", "solve", "certify", "create_graph",
     "create_dataset", "TourResult", "nearest_neighbor_tours", "anneal_tours", "decide",
-    "metric_closure",
+    "metric_closure", "DeviceDataset",
 ]

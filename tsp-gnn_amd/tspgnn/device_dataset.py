@@ -1,0 +1,273 @@
+"""Device-resident datasets: the instances are uploaded once, a batch is a list of instance ids and one launch.
+
+What a batch needs from an instance does not depend on the batch, apart from two offsets and one factor: the edge list in
+np.nonzero order, the fp32 weights, the CSR by vertex and the tour cost are properties of the INSTANCE; the vertex offset,
+the edge offset and (1 -/+ dev) are properties of the BATCH.  ``DeviceDataset`` packs every instance once on the host with
+the native packers (tspgnn_host_stage_batch / tspgnn_host_route_cost: edge order and arithmetic are the ones
+tests/test_packer.py pins), keeps the concatenation in HBM, and ``batch(indices)`` runs tspgnn_gather_batch
+(csrc/batch_gather.hip) over it: the bytes tspgnn_host_stage_batch would write for the same instance list, without a host
+pass over the matrices and without the upload.
+
+Layout (device, int32 offsets -- ``MAX_CSR_ENTRIES``):
+    inst   int32[I][4]       n, m, first edge, first vertex of instance i (prefix sums)
+    uv     int32[sum m][2]   local endpoint ids          w    float[sum m]     (float)Mw[i, j]
+    rowptr int32[sum (n+1)]  local CSR by vertex         eid  int32[2 sum m]   ascending edge ids inside a vertex
+    cost   double[I]         route_cost, closing-pair quirk included
+The host keeps ``n`` and ``m`` (int64): a batch's e_start / v_start are their prefix sums over the index list
+(``plan_batch``), uploaded with the ids as one small pinned buffer.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from .instance_loader import read_graph, route_cost
+from .parallel import stage_instances, stage_layout
+
+MAX_CSR_ENTRIES = 2 ** 31   # 2 * sum(m) must stay below: CSR positions and edge ids are int32 on the device
+_CHUNK = 1024               # instances per host packing call (bounds the scratch of the one-off preprocessing)
+_PLAN_CACHE = 64            # work plans kept per dataset (an epoch of fixed-size batches needs one)
+_RING = 4                   # pinned (ids, e_start, v_start) buffers in flight
+
+
+def check_size(total_edges):
+    """Raises ValueError when a dataset of ``total_edges`` edges does not fit the int32 offsets of the device layout."""
+    if 2 * int(total_edges) >= MAX_CSR_ENTRIES:
+        raise ValueError("DeviceDataset: %d edges: 2 * sum(m) must stay below 2^31 (int32 CSR offsets); split the dataset"
+                         % int(total_edges))
+
+
+def preprocess(instances):
+    """Packs every (Ma, Mw, route) once: -> dict of NumPy arrays ``n``, ``m`` (int64), ``e0``, ``v0`` (int64 prefix sums,
+    I + 1 entries), ``uv`` int32[sum m, 2] (local ids), ``w`` float32[sum m], ``rowptr`` int32[sum (n + 1)], ``eid``
+    int32[2 sum m] (local ids), ``cost`` float64[I].  Raises like create_batch: ValueError for a non-square adjacency or a
+    weight matrix of another shape, IndexError for a route that leaves its graph."""
+    instances = list(instances)
+    I = len(instances)
+    for k, (Ma, Mw, _) in enumerate(instances):
+        sa, sw = np.shape(Ma), np.shape(Mw)
+        if len(sa) != 2 or sa[0] != sa[1]:
+            raise ValueError("DeviceDataset: instance %d: the adjacency matrix must be square, got %s" % (k, sa))
+        if sw != sa:
+            raise ValueError("DeviceDataset: instance %d: weight matrix %s does not match adjacency matrix %s" % (k, sw, sa))
+    n = np.array([np.shape(Ma)[0] for Ma, _, _ in instances], dtype=np.int64)
+    m = np.array([int(np.count_nonzero(Ma)) for Ma, _, _ in instances], dtype=np.int64)
+    check_size(m.sum())
+    e0 = np.concatenate([[0], np.cumsum(m)]).astype(np.int64)
+    v0 = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    uv = np.empty((int(e0[-1]), 2), dtype=np.int32)
+    w = np.empty(int(e0[-1]), dtype=np.float32)
+    eid = np.empty(2 * int(e0[-1]), dtype=np.int32)
+    rowptr = np.empty(int(v0[-1]) + I, dtype=np.int32)
+    cost = np.empty(I, dtype=np.float64)
+    for lo in range(0, I, _CHUNK):
+        hi = min(lo + _CHUNK, I)
+        # one tspgnn_host_stage_batch call over the chunk with dev = 0: its endpoints, CSR and (float)Mw are the batch's up
+        # to the chunk-relative offsets taken off below (the cost column is not used: the fp64 cost is kept instead)
+        Mc, Nc, Bc = int(e0[hi] - e0[lo]), int(v0[hi] - v0[lo]), hi - lo
+        off, sizes, total = stage_layout(Mc, Nc, Bc, 0)
+        buf = np.empty(total, dtype=np.uint8)
+        stage_instances(instances[lo:hi], 0.0, None, Mc, Nc, buf.ctypes.data, off)
+        g = lambda k, dt: buf[off[k]:off[k] + sizes[k]].view(dt)
+        el, vl = (e0[lo:hi] - e0[lo]).astype(np.int32), (v0[lo:hi] - v0[lo]).astype(np.int32)   # chunk-relative starts
+        mc, nc = m[lo:hi], n[lo:hi]
+        uv[e0[lo]:e0[hi]] = g(0, np.int32).reshape(Mc, 2) - np.repeat(vl, mc)[:, None]
+        w[e0[lo]:e0[hi]] = g(3, np.float32).reshape(Mc, 2)[:, 0]
+        eid[2 * e0[lo]:2 * e0[hi]] = g(1, np.int32) - np.repeat(el, 2 * mc)
+        # n + 1 row pointers per instance: the chunk's rowptr[v_start[b] .. v_start[b] + n], less 2 * e_start[b]
+        take = np.arange(Nc + Bc) - np.repeat(np.arange(Bc), nc + 1)
+        rowptr[v0[lo] + lo:v0[hi] + hi] = g(2, np.int32)[take] - np.repeat(2 * el, nc + 1)
+        for k in range(lo, hi):
+            cost[k] = route_cost(instances[k][1], instances[k][2])
+    return {"n": n, "m": m, "e0": e0, "v0": v0, "uv": uv, "w": w, "rowptr": rowptr, "eid": eid, "cost": cost}
+
+
+def plan_batch(n, m, indices):
+    """The batch-side half of a gather: -> (e_start int32[B + 1], v_start int32[B + 1], M, N, labels int64[B]) for the
+    instance list ``indices`` -- the prefix sums create_batch returns as EV.blocks, and its route_exists.  IndexError for
+    an id outside the dataset."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= len(n)):
+        raise IndexError("DeviceDataset: instance id outside [0, %d)" % len(n))
+    e_start = np.concatenate([[0], np.cumsum(np.asarray(m, dtype=np.int64)[idx])])
+    v_start = np.concatenate([[0], np.cumsum(np.asarray(n, dtype=np.int64)[idx])])
+    check_size(e_start[-1])
+    return (e_start.astype(np.int32), v_start.astype(np.int32), int(e_start[-1]), int(v_start[-1]),
+            np.arange(idx.size, dtype=np.int64) % 2)
+
+
+def epoch_indices(n_instances, batch_size, shuffle=True, rng=None):
+    """Index lists of one epoch, as InstanceLoader.get_instances / get_batches visit a directory: n_instances //
+    batch_size lists of 2 * batch_size ids, every instance twice in a row (labels 0, 1); with ``shuffle`` the order is
+    drawn from ``rng`` (a numpy.random.RandomState; None: numpy's global one)."""
+    order = np.arange(n_instances, dtype=np.int64)
+    if shuffle:
+        order = (np.random if rng is None else rng).permutation(n_instances).astype(np.int64)
+    bs = int(batch_size)
+    return [np.repeat(order[k * bs:(k + 1) * bs], 2) for k in range(n_instances // bs)]
+
+
+class DeviceDataset(object):
+    """A list of (Ma, Mw, route) -- as read_graph / draw_instances return them -- resident on one GPU.
+
+        ds = DeviceDataset(instances)
+        for batch in ds.get_batches(64, dev=0.02, time_steps=32, rng=np.random.RandomState(0)):
+            run_batch(sess, model, batch, ...)               # or sess.forward(batch) / sess.train_step(batch)
+
+        b = ds.batch(ids, time_steps=32)                     # serving: one buffer, one captured graph
+        replay = sess.capture_forward(b)
+        for ids in stream_of_index_lists_of_that_shape:
+            ds.batch(ids, time_steps=32, out=b); out = replay()
+
+    ``device='cpu'`` is plumbing only (host tests): the arrays stay on the host and batch() raises."""
+
+    def __init__(self, instances, device=None):
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("DeviceDataset needs an MI355X (no HIP device visible)")
+            device = "cuda:%d" % torch.cuda.current_device()
+        self.device = torch.device(device)
+        host = preprocess(instances)
+        self.n, self.m = host["n"], host["m"]
+        I = len(self.n)
+        inst = np.stack([self.n, self.m, host["e0"][:-1], host["v0"][:-1]], axis=1).astype(np.int32).reshape(I, 4)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        self._inst, self._uv, self._w = up(inst), up(host["uv"]), up(host["w"])
+        self._rowptr, self._eid, self._cost = up(host["rowptr"]), up(host["eid"]), up(host["cost"])
+        self._plans = {}     # (e_start bytes, v_start bytes) -> (device int32 plan or None, meta or None)
+        self._ring, self._next = [None] * _RING, 0   # [pinned int32 buffer, its device copy, event of the launch that read it]
+
+    def __len__(self):
+        return len(self.n)
+
+    @classmethod
+    def from_directory(cls, path, device=None):
+        """Every file of a ``.graph`` directory (read_graph), in sorted order."""
+        return cls([read_graph(os.path.join(path, f)) for f in sorted(os.listdir(path))], device=device)
+
+    def _require_gpu(self):
+        if self.device.type != "cuda":
+            raise RuntimeError("DeviceDataset(device=%r) is plumbing only: a batch is assembled by a HIP kernel and needs "
+                               "an MI355X" % str(self.device))
+
+    # ------------------------------------------------------------------ the launch
+    def _small(self, idx, e_start, v_start):
+        """ids, e_start, v_start as one pinned buffer and its (asynchronous) device copy: three int32 device views.  A
+        ring of buffers that grow to the largest batch seen: pinning is the expensive part, and a slot is reused only once
+        the launch that read it has run."""
+        B = idx.size
+        k = self._next
+        self._next = (k + 1) % _RING
+        slot = self._ring[k]
+        if slot is not None and slot[2] is not None:
+            slot[2].synchronize()
+        if slot is None or slot[0].numel() < 3 * B + 2:
+            cap = max(3 * B + 2, 1024)
+            slot = self._ring[k] = [torch.empty(cap, dtype=torch.int32).pin_memory(),
+                                    torch.empty(cap, dtype=torch.int32, device=self.device), None]
+        pinned, dev = slot[0][:3 * B + 2], slot[1][:3 * B + 2]
+        host = pinned.numpy()
+        host[:B], host[B:2 * B + 1], host[2 * B + 1:] = idx, e_start, v_start
+        dev.copy_(pinned, non_blocking=True)
+        return slot, dev[:B], dev[B:2 * B + 1], dev[2 * B + 1:]
+
+    def gather(self, indices, dev, target_cost, buf, offsets):
+        """tspgnn_gather_batch of the instance list ``indices`` into the uint8 device tensor ``buf`` at the byte offsets
+        ``offsets`` (parallel.stage_layout), on the current stream.  -> plan_batch(indices).  Writes the seven arrays and
+        nothing else.  A batch without edges launches nothing: it is all offsets, filled from the host."""
+        self._require_gpu()
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        plan = plan_batch(self.n, self.m, idx)
+        e_start, v_start, M, N, _ = plan
+        B = idx.size
+        if buf.device != self.device or buf.dtype != torch.uint8 or not buf.is_contiguous():
+            raise ValueError("DeviceDataset.gather: the destination is a contiguous uint8 tensor on %s" % self.device)
+        sizes = stage_layout(M, N, B, 0)[1]
+        if any(o < 0 or o + s > buf.numel() for o, s in zip(offsets[:7], sizes[:7])):
+            raise ValueError("DeviceDataset.gather: the destination is too small for %d edges / %d vertices / %d graphs"
+                             % (M, N, B))
+        if B == 0:
+            return plan
+        if M == 0:   # all offsets, no edge anywhere: row pointers, segment offsets and edge counts are zeros
+            part = lambda k, dtype: buf[offsets[k]:offsets[k] + sizes[k]].view(dtype)
+            for k in (2, 5, 6):
+                part(k, torch.int32).zero_()
+            part(4, torch.float32).copy_(torch.arange(B, device=self.device) % 2)
+            return plan
+        slot, ids_d, es_d, vs_d = self._small(idx.astype(np.int32), e_start, v_start)
+        off = (ctypes.c_longlong * 7)(*[int(o) for o in offsets[:7]])
+        _lib.call("tspgnn_gather_batch", _lib.ptr(self._inst), _lib.ptr(self._uv), _lib.ptr(self._w), _lib.ptr(self._rowptr),
+                  _lib.ptr(self._eid), _lib.ptr(self._cost), _lib.ptr(ids_d), _lib.ptr(es_d), _lib.ptr(vs_d), B, M, N,
+                  float(dev), 0 if target_cost is None else 1, 0.0 if target_cost is None else float(target_cost),
+                  buf.data_ptr(), off, _lib.current_stream())
+        ev = torch.cuda.Event()
+        ev.record()
+        slot[2] = ev
+        return plan
+
+    # ------------------------------------------------------------------ batches
+    def _plan_for(self, e_start, v_start, M):
+        """The one-launch loop's work plan for a block structure, built once (device tensor, meta) or (None, None)."""
+        from .graphnn import choose_loop_plan, loop_enabled
+        if not loop_enabled() or M == 0:
+            return None, None
+        key = (e_start.tobytes(), v_start.tobytes())
+        if key not in self._plans:
+            grid = torch.cuda.get_device_properties(self.device).multi_processor_count
+            grid -= grid % 8
+            built = choose_loop_plan(e_start.astype(np.int64), v_start.astype(np.int64), grid)
+            if len(self._plans) >= _PLAN_CACHE:
+                self._plans.clear()
+            self._plans[key] = (None, None) if built is None else (torch.from_numpy(built[0]).to(self.device), built[1])
+        return self._plans[key]
+
+    def batch(self, indices, dev=0.02, target_cost=None, time_steps=32, out=None):
+        """-> DeviceBatch of the instance list ``indices`` (labels 0, 1, 0, 1, ...; target cost (1 -/+ dev) * tour cost, or
+        ``target_cost``), as Session.prepare(feed of create_batch) makes it, plus the host arrays ``route_exists``,
+        ``n_vertices``, ``n_edges`` (int64).  ``out``: a batch this dataset returned earlier for index lists of the same
+        shape (the same instance sizes in the same order): the kernel writes into THAT batch's buffer, so a graph captured
+        on it serves the new batch; ValueError when the shapes differ."""
+        from .graphnn import DeviceAdjacency
+        from .model import DeviceBatch
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        e_start, v_start, M, N, labels = plan_batch(self.n, self.m, idx)
+        B = idx.size
+        if out is not None:
+            if getattr(out, "_dataset", None) is not self:
+                raise ValueError("DeviceDataset.batch: out= takes a batch this dataset returned")
+            if not (np.array_equal(out._blocks[0], e_start) and np.array_equal(out._blocks[1], v_start)):
+                raise ValueError("DeviceDataset.batch: the instance sizes of the index list differ from those of out=")
+            b = out
+        else:
+            self._require_gpu()
+            plan, meta = self._plan_for(e_start, v_start, M)
+            offsets, nbytes, total = stage_layout(M, N, B, 0 if plan is None else plan.numel())
+            buf = torch.empty(total, dtype=torch.uint8, device=self.device)
+
+            def view(k, dtype, shape):
+                o, nb = offsets[k], nbytes[k]
+                return buf[o:o + nb].view(dtype).view(*shape)
+            uv = view(0, torch.int32, (M, 2))
+            csr = (torch.arange(0, 2 * M + 1, 2, dtype=torch.int32, device=self.device), uv.view(-1), None)
+            csr_t = (view(2, torch.int32, (N + 1,)), view(1, torch.int32, (2 * M,)), None)
+            adj = DeviceAdjacency((M, N), self.device, csr, csr_t, uv=uv)
+            if plan is not None:
+                slot = view(7, torch.int32, (plan.numel(),))
+                slot.copy_(plan, non_blocking=True)
+                adj.loop_plan = (slot,) + tuple(meta)
+            b = DeviceBatch()
+            b.adj, b.M, b.N, b.B = adj, M, N, B
+            b.WC, b.labels, b.seg = view(3, torch.float32, (M, 2)), view(4, torch.float32, (B,)), view(5, torch.int32, (B + 1,))
+            b._dataset, b._buf, b._offsets, b._blocks = self, buf, offsets, (e_start, v_start)
+        self.gather(idx, dev, target_cost, b._buf, b._offsets)
+        b.T = int(time_steps)
+        b.route_exists, b.n_vertices, b.n_edges = labels, self.n[idx], self.m[idx]
+        return b
+
+    def get_batches(self, batch_size, dev, time_steps, shuffle=True, rng=None):
+        """One epoch, as InstanceLoader.get_batches: len(self) // batch_size batches of 2 * batch_size graphs, every
+        instance twice in a row; the order is drawn per call (epoch_indices)."""
+        for idx in epoch_indices(len(self), batch_size, shuffle, rng):
+            yield self.batch(idx, dev=dev, time_steps=time_steps)

@@ -41,14 +41,36 @@ def _log(kind, epoch_i, fields):
     sys.stdout.flush()
 
 
-def run_batch(sess, model, batch, batch_i, epoch_i, time_steps, train=False, verbose=True):
-    """One ``sess.run`` over ``batch``; with ``train`` the optimiser step is fetched first (train.py:36-42)."""
-    fetches = [model[key] for key in _STAT_KEYS]
+def _run_device_batch(sess, batch, time_steps, train):
+    """The fetches of run_batch over a batch that is already on the device (DeviceDataset.batch): what Session.run
+    does with a feed -- the training step looks after the f16x2 range flag itself, a flagged forward is repeated on
+    bf16x3, the statistics are those of the global batch -- without a feed to convert."""
+    batch.T = int(time_steps)
     if train:
-        fetches.insert(0, model["train_step"])
-    values = sess.run(fetches, feed_dict=_feed_for(model, batch, time_steps))
-    stats = dict(zip(_STAT_KEYS, values[len(values) - len(_STAT_KEYS):]))
-    labels, n_vertices, n_edges = batch[3], batch[4], batch[5]
+        out = sess.train_step(batch)
+    else:
+        out = sess._on_bf16x3_if_flagged(lambda: sess.forward(batch, global_stats=True))
+    stats = out["stats"].cpu().numpy()
+    values = {key: np.float32(stats[k]) for k, key in enumerate(("loss", "acc", "TP", "FP", "TN", "FN"))}
+    values["predictions"] = out["predictions"].cpu().numpy()
+    return values
+
+
+def run_batch(sess, model, batch, batch_i, epoch_i, time_steps, train=False, verbose=True):
+    """One ``sess.run`` over ``batch``; with ``train`` the optimiser step is fetched first (train.py:36-42).  ``batch``:
+    the create_batch 6-tuple, or a DeviceBatch of DeviceDataset.batch / get_batches (labels and counts from its host
+    arrays)."""
+    from .model import DeviceBatch
+    if isinstance(batch, DeviceBatch):
+        stats = _run_device_batch(sess, batch, time_steps, train)
+        labels, n_vertices, n_edges = batch.route_exists, batch.n_vertices, batch.n_edges
+    else:
+        fetches = [model[key] for key in _STAT_KEYS]
+        if train:
+            fetches.insert(0, model["train_step"])
+        values = sess.run(fetches, feed_dict=_feed_for(model, batch, time_steps))
+        stats = dict(zip(_STAT_KEYS, values[len(values) - len(_STAT_KEYS):]))
+        labels, n_vertices, n_edges = batch[3], batch[4], batch[5]
     mean_label, mean_pred = _batch_means(sess, labels, stats["predictions"])
     if verbose:
         _log("train" if train else "test", epoch_i, (
