@@ -4,14 +4,18 @@ the MI355X path, over synthetic Euclidean instances (no Concorde, no dataset on 
 
     python examples/train_synthetic.py -d 64 -timesteps 32 -batchsize 8 -epochs 2 --batches 8
     python examples/train_synthetic.py --instances /tmp/tsp/instances --checkpoints /tmp/tsp/ckpt   # .graph files + resume
+    python examples/train_synthetic.py -generate 512     # the reference's stream (n 20-40), drawn, labelled, packed on the GPU
 
 The flags keep train.py's names (train.py:107-119).  Every instance appears twice in a batch with target
 cost (1-dev) and (1+dev) times its tour cost and labels 0/1, exactly like InstanceLoader.get_batches
 (instance_loader.py:16-27,82-87).  The "tour" is the planted Hamiltonian cycle, not the optimum, so the
 accuracy printed here says nothing about TSP -- the point is the call sequence and the loss going down.
+With -generate SAMPLES the instances are create_dataset's (seeded with -seed) and the tours are the GPU search's labels:
+DeviceDataset.generate(SAMPLES, 20, 40), no matrix on the host and no file.
 """
 import argparse
 import os
+import random
 import sys
 
 import numpy as np
@@ -39,6 +43,9 @@ if __name__ == '__main__':
     p.add_argument('-device_dataset', action='store_true',
                    help='upload the instances once (tspgnn.DeviceDataset) and assemble every batch on the GPU from instance '
                         'ids: epochs through DeviceDataset.get_batches instead of InstanceLoader / create_batch')
+    p.add_argument('-generate', default=0, type=int, metavar='SAMPLES',
+                   help='train on DeviceDataset.generate(SAMPLES, 20, 40): the instances drawn from the reference\'s stream, '
+                        'labelled and packed on the GPU, instead of a directory or synthetic instances')
     a = p.parse_args()
     rng = np.random.RandomState(a.seed)
     loader = None
@@ -50,7 +57,15 @@ if __name__ == '__main__':
                 write_graph(Ma, Mw, os.path.join(a.instances, '{}.graph'.format(i)), route=route)
         loader = InstanceLoader(a.instances)
     dataset = None
-    if a.device_dataset:   # the same instances every epoch, shuffled per epoch like InstanceLoader.reset()
+    if a.generate:
+        random.seed(a.seed)
+        np.random.seed(a.seed)
+        dataset = DeviceDataset.generate(a.generate, 20, 40)
+        t = dataset.summary['times']
+        print('generated {} instances in {:.2f} s ({}); certified at dev 0.02: {:.3f}'.format(
+            a.generate, t['total'], ', '.join('{} {:.3f}'.format(k, v) for k, v in t.items() if k != 'total'),
+            dataset.summary['certified_fraction']), flush=True)
+    elif a.device_dataset:   # the same instances every epoch, shuffled per epoch like InstanceLoader.reset()
         dataset = DeviceDataset.from_directory(a.instances) if a.instances is not None else DeviceDataset(
             [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize * a.batches)])
     GNN = build_network(a.d)

@@ -889,6 +889,64 @@ int tspgnn_gather_batch(const int32_t* inst, const int32_t* uv, const float* w, 
                         const int32_t* v_start, int B, int M, int N, double dev, int use_target, double target_cost,
                         unsigned char* dst, const long long* off, void* stream);
 
+/* ------------------------------------------------------------------ datasets made on the device (DeviceDataset.generate) */
+
+/*
+ * The three stages between the reference's random draws (dataset.draw_streams, host) and a device-resident dataset
+ * (csrc/dataset_build.hip).  One workgroup per instance, 4 <= n <= n_max <= 256.  An instance is a row of an int64 table
+ * that is passed twice: `tab` on the HOST, checked row by row against the array sizes given, and `d_tab`, the same bytes
+ * on the DEVICE, which the kernels read.  All other arrays are DEVICE arrays.  For each of the three: count < 0, n_max
+ * outside [4, 256], a null pointer, an array not aligned to its element (uv: to 8 bytes), an n outside [4, n_max] or an
+ * offset that leaves its array: TSPGNN_EINVAL before any launch.  count == 0 is a no-op that looks at nothing else.
+ *
+ * tspgnn_build_instances: tab[count][4] = n, first pair p0, first vertex t0, first matrix cell c0.  In: conn
+ * double[count]; adj_u double[n_pairs], the instance's n (n-1) / 2 uniform draws at p0; coord: random_weights == 0:
+ * double[2 n_verts], its points (x, y) at 2 t0, else double[n_pairs], its weights at p0; perm int32[n_verts], the
+ * planted permutation at t0.  Out: Mw double[n_cells] and A uint8[n_cells], row-major n x n at c0; m int32[count].
+ *   Pair k is the k-th (i, j > i) in row-major order.  A[i][j] = A[j][i] = adj_u[k] < conn, or {i, j} is an edge
+ *   perm[t] - perm[t+1 mod n] of the planted cycle.  Points: Mw[i][j] = sqrt((x_i - x_j) (x_i - x_j) + (y_i - y_j)
+ *   (y_i - y_j)), each subtraction, product, sum and the root rounded once to nearest (no FMA); weights: Mw[i][j] =
+ *   Mw[j][i] = coord[p0 + k].  Both diagonals are 0.  m = the number of set pairs i < j.
+ */
+int tspgnn_build_instances(const long long* tab, const long long* d_tab, const double* conn, const double* adj_u,
+                           const double* coord, const int32_t* perm, int random_weights, int count, int n_max,
+                           long long n_pairs, long long n_verts, long long n_cells, double* Mw, unsigned char* A,
+                           int32_t* m, void* stream);
+
+/*
+ * tspgnn_penalise_instances: tab[count][3] = n, first matrix cell c0, first output float f0.  (A, Mw) as above -> the
+ * input of the tour kernels at W + f0: triangle == 0 the row-major n x n matrix of tspgnn_tour_search (n_max <= 128),
+ * else the packed strict upper triangle of tspgnn_tour_search_tri; n_floats is the extent of W.
+ *   w(i, j) = Mw[min][max] + 0.0; mx = the fp64 maximum of 0 and w over the set pairs; pen = n * mx + 1.0 with two
+ *   roundings; the value is 0 on the diagonal, w(i, j) where A is set and pen elsewhere; each is converted to fp32 to
+ *   nearest and then stepped down one ulp when the fp32 value exceeds the fp64 one (dataset._penalised bit for bit).
+ */
+int tspgnn_penalise_instances(const long long* tab, const long long* d_tab, const unsigned char* A, const double* Mw,
+                              int count, int n_max, int triangle, long long n_cells, long long n_floats, float* W,
+                              void* stream);
+
+/*
+ * tspgnn_pack_dataset: tab[count][7] = n, first matrix cell c0, first tour entry t0, m, first edge e0, first vertex v0,
+ * position i of the instance in the dataset.  (A, Mw) as above and its tour tours[t0 .. t0 + n) -> the arrays of
+ * tspgnn_gather_batch's dataset: uv / w at e0, eid at 2 e0, rowptr (n + 1 entries) at v0 + i, and cost[i],
+ * file_cost[i], cycle_cost[i], feasible[i].  n_tour, n_edges, n_rowptr, n_inst are the extents of tours, of uv / w (eid:
+ * twice), of rowptr and of the four per-instance arrays; uv, w and eid may be NULL when n_edges == 0.
+ *   Edges are the set pairs i < j in row-major order (np.nonzero(np.triu(A))); uv holds (i, j), w = (float)Mw[i][j];
+ *   rowptr / eid are the CSR by vertex with ascending edge ids inside a vertex (tspgnn_host_csr_by_vertex).
+ *   cost = tspgnn_host_route_cost of the tour on Mw: one lane sums Mw[min][max] in route order, the closing pair is
+ *   (route[n-1], route[1]), the sum is divided by n; this is the cost array of the dataset, what DeviceDataset keeps for
+ *   an instance (Ma, Mw, route) held in memory.  file_cost = the same on the file form of Mw, which is Mw on the set
+ *   pairs i < j and 0 elsewhere -- what a .graph file of the instance would give (n * file_cost is dataset._target); the
+ *   two differ only when the closing pair or a tour edge is absent from A.  cycle_cost = the fp64 sum of Mw[min][max]
+ *   along the closed tour, in tour order.  feasible = every tour edge is set in A.  A tour entry outside [0, n) makes
+ *   the costs NaN.  An m that is not the mask's count writes the row pointers and the scalars only.
+ */
+int tspgnn_pack_dataset(const long long* tab, const long long* d_tab, const unsigned char* A, const double* Mw,
+                        const int32_t* tours, int count, int n_max, long long n_cells, long long n_tour,
+                        long long n_edges, long long n_rowptr, long long n_inst, int32_t* uv, float* w, int32_t* rowptr,
+                        int32_t* eid, double* cost, double* file_cost, double* cycle_cost, int32_t* feasible,
+                        void* stream);
+
 /* ------------------------------------------------------------------ host-side batch packing (no GPU work) */
 
 /*

@@ -3,7 +3,7 @@ the test set (2^10), n = 80, and n = 200 and 256 (label_tours on the triangle ke
 at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per shape.
 
     python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
-        [--exact [--max-nodes N]] [--neighbors K] [--distances euc_2D|random] [--closure host|device]
+        [--exact [--max-nodes N]] [--neighbors K] [--distances euc_2D|random] [--closure host|device] [--resident]
 
 Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
 --exact labels with the branch and bound (label_tours(exact=True), n <= 128) and adds the proved fraction, the nodes per
@@ -12,6 +12,9 @@ instance (p50 / p90 / max) and the seconds of that launch; bound_s is then 0.
 --distances random draws the reference's random metric instances; --closure says where their metric closure is taken
 (draw_instances(closure=...)): "closure_s" is its wall seconds (for device: synchronised, transfers included) and
 "draw_s" the rest of the drawing.
+--resident times, per shape, the two routes to a device-resident dataset, alternated twice in one process: "host" is
+draw_instances -> label_tours -> DeviceDataset(...), "generate" is DeviceDataset.generate; one JSON line per run with the
+wall seconds from the seeding to the synchronised dataset ("total_s") and the stages each route can name.
 """
 import argparse
 import json
@@ -29,9 +32,46 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from tspgnn import dataset  # noqa: E402
+from tspgnn.device_dataset import DeviceDataset  # noqa: E402
 
 SHAPES = {"train": (2 ** 15, 20, 40), "test": (2 ** 10, 20, 40), "n80": (2 ** 10, 80, 80), "n200": (2 ** 10, 200, 200),
           "n256": (2 ** 10, 256, 256)}
+
+
+def resident(a, name, samples, nmin, nmax):
+    """The two routes to a resident dataset of one shape, alternated twice; one JSON line per run."""
+    kw = dict(restarts=a.restarts, kicks=a.kicks, lb_iters=a.lb_iters, neighbors=a.neighbors)
+    r3 = lambda d: {k + "_s": round(v, 3) for k, v in d.items()}
+    for rep in range(2):
+        for route in ("host", "generate"):
+            random.seed(1)
+            np.random.seed(1)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if route == "host":
+                tc, tm = {}, {}
+                graphs = dataset.draw_instances(nmin, nmax, samples=samples, distances=a.distances, closure=a.closure,
+                                                timings=tc)
+                t_draw = time.perf_counter() - t0 - tc.get("closure", 0.0)
+                res = dataset.label_tours([(g[0], g[1]) for g in graphs], init_tours=[g[2] for g in graphs], timings=tm,
+                                          exact=a.exact, max_nodes=a.max_nodes, **kw)
+                t1 = time.perf_counter()
+                ds = DeviceDataset([(np.triu(g[0]), g[1], r.tour) for g, r in zip(graphs, res)])
+                torch.cuda.synchronize()
+                stages = dict(draw=t_draw, **tc, **tm, resident=time.perf_counter() - t1)
+                certified = dataset.certify(res, 0.02)["fraction"]
+            else:
+                ds = DeviceDataset.generate(samples, nmin, nmax, distances=a.distances, exact=a.exact,
+                                            **({} if a.max_nodes is None else {"max_nodes": a.max_nodes}), **kw)
+                torch.cuda.synchronize()
+                stages = {k: v for k, v in ds.summary["times"].items() if k != "total"}
+                certified = ds.summary["certified_fraction"]
+            total = time.perf_counter() - t0
+            print(json.dumps({"shape": name, "samples": samples, "n": [nmin, nmax], "resident": route, "rep": rep,
+                              "distances": a.distances, **({} if a.neighbors is None else {"neighbors": a.neighbors}),
+                              "total_s": round(total, 3), **r3(stages), "edges": int(ds.m.sum()),
+                              "certified_0.02": round(certified, 4)}), flush=True)
+            del ds
 
 
 def main():
@@ -47,6 +87,8 @@ def main():
     ap.add_argument("--closure", default="host", choices=("host", "device"),
                     help="--distances random: where the metric closure is taken")
     ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
+    ap.add_argument("--resident", action="store_true",
+                    help="time the host route and DeviceDataset.generate to a device-resident dataset, alternated twice")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
     a = ap.parse_args()
@@ -61,9 +103,18 @@ def main():
     if a.exact:
         dataset.label_tours([(np.triu(np.ones((20, 20)), 1), np.random.RandomState(0).rand(20, 20))], kicks=1, lb_iters=1,
                             exact=True, max_nodes=1)
+    if a.resident:   # generate's kernels and the gather-free constructor path, outside the timed runs
+        state = random.getstate(), np.random.get_state()
+        for n in (20, 130):
+            DeviceDataset.generate(2, n, n, distances=a.distances, kicks=1, lb_iters=1, neighbors=a.neighbors)
+        random.setstate(state[0])
+        np.random.set_state(state[1])
     for name in a.shapes.split(","):
         samples, nmin, nmax = SHAPES[name]
         samples = a.samples or samples
+        if a.resident:
+            resident(a, name, samples, nmin, nmax)
+            continue
         random.seed(1)
         np.random.seed(1)
         t0 = time.perf_counter()

@@ -10,7 +10,7 @@ from .graphnn import GraphNN, LSTMStateTuple, DeviceAdjacency, LayerNormBasicLST
 from .instance_loader import InstanceLoader, SparseEV, read_graph, write_graph, synthetic_batch, random_instance
 from .binary_search import get_cost, get_costs
 from .dataset import solve_tours, label_tours, prove_tours, solve, certify, create_graph, create_dataset, TourResult, \
-    metric_closure
+    metric_closure, draw_instances, draw_streams
 from .baselines import nearest_neighbor_tours, anneal_tours, decide
 from .mlp import Mlp
 from .parallel import BatchPrefetcher, BatchStager, shard_instances
@@ -28,5 +28,5 @@ __all__ = [
     "Session", "global_variables_initializer", "get_cost", "get_costs", "BatchPrefetcher", "BatchStager", "shard_instances", "VariableStore", "get_default_store", "reset_default_store",
     "load_weights", "save_weights", "run_batch", "summarize_epoch", "solve_tours", "label_tours", "prove_tours", "solve", "certify", "create_graph",
     "create_dataset", "TourResult", "nearest_neighbor_tours", "anneal_tours", "decide",
-    "metric_closure", "DeviceDataset",
+    "metric_closure", "DeviceDataset", "draw_instances", "draw_streams",
 ]

@@ -109,6 +109,13 @@ SIGNATURES = {
     "tspgnn_metric_closure": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "tspgnn_gather_batch": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p],
+    "tspgnn_build_instances": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                               c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tspgnn_penalise_instances": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_longlong, c_longlong,
+                                  c_void_p, c_void_p],
+    "tspgnn_pack_dataset": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong,
+                            c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p],
 }
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",

@@ -195,6 +195,55 @@ def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, ma
     return checked, index
 
 
+def _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost, d_lb, restarts, kicks, seed,
+                   lb_iters, chunk, tri, neighbors, lower_bound, exact=None, search=True):
+    """The launches of one size class over G instances that are already on ``dev`` (inside torch.cuda.device(dev)): the
+    search, ``chunk`` instances per launch, then the branch and bound (exact = (max_nodes, node_iters, opt_tol, ...),
+    tri=False only) or the bound (lower_bound).  ns: the host copy of d_n.  search=False: d_tours already holds the
+    incumbents.  -> (t1, t2, t3, d_stat, d_nodes): perf_counter before the search, after it and after the bound, each
+    device-synchronised, and the branch and bound's int32 device arrays (None without exact)."""
+    G = len(ns)
+    search_fn, bound_fn = ("tspgnn_tour_search_tri", "tspgnn_tour_lower_bound_tri") if tri else \
+        ("tspgnn_tour_search", "tspgnn_tour_lower_bound")
+    knn = ()
+    if neighbors is not None:
+        search_fn, knn = search_fn.replace("_search", "_search_knn"), (int(neighbors),)
+    d_stat = d_nodes = None
+    torch.cuda.synchronize(dev)
+    t1 = time.perf_counter()
+    st = _lib.current_stream()
+    for c0 in range(0, G if search else 0, chunk):
+        c1 = min(G, c0 + chunk)
+        _lib.call(search_fn, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                  _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
+                  int(restarts), int(kicks), *knn, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours),
+                  _lib.ptr(d_cost[c0:c1]), st)
+    torch.cuda.synchronize(dev)
+    t2 = time.perf_counter()
+    if exact is not None:
+        # results do not depend on the launch size, so a chunk whose stack would not fit BB_WORKSPACE_BYTES is split
+        per = int(_lib.lib.tspgnn_tour_branch_bound_ws(1, int(ns.max())))
+        step = max(1, min(chunk, G, BB_WORKSPACE_BYTES // per))
+        d_ws = torch.empty(per * step, dtype=torch.uint8, device=dev)
+        d_nodes = torch.empty(G, dtype=torch.int32, device=dev)
+        d_stat = torch.empty(G, dtype=torch.int32, device=dev)
+        for c0 in range(0, G, step):
+            c1 = min(G, c0 + step)
+            _lib.call("tspgnn_tour_branch_bound", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                      _lib.ptr(d_toff[c0:c1]), _lib.ptr(None if d_cost is None else d_cost[c0:c1]), c1 - c0,
+                      int(ns[c0:c1].max()), int(lb_iters), int(exact[1]), int(exact[0]), float(exact[2]),
+                      _lib.ptr(d_ws), _lib.ptr(d_tours), _lib.ptr(d_lb[c0:c1]), _lib.ptr(d_nodes[c0:c1]),
+                      _lib.ptr(d_stat[c0:c1]), st)
+    elif lower_bound:
+        for c0 in range(0, G, chunk):
+            c1 = min(G, c0 + chunk)
+            _lib.call(bound_fn, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
+                      _lib.ptr(d_cost[c0:c1]), c1 - c0, int(ns[c0:c1].max()), int(lb_iters), _lib.ptr(d_lb[c0:c1]), st)
+    torch.cuda.synchronize(dev)
+    t3 = time.perf_counter()
+    return t1, t2, t3, d_stat, d_nodes
+
+
 def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0, tri,
            exact=None, incumbents=None, neighbors=None):
     """solve_tours on checked instances, n < 4 on the host and the rest on the square kernels (tri=False, n <= 128) or
@@ -245,11 +294,6 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
                 init[t_off[p]:t_off[p] + n] = it
         stacked[n] = (A, Mw)
     has_init = init_tours is not None and any(t is not None for t in init_tours)
-    search, bound = ("tspgnn_tour_search_tri", "tspgnn_tour_lower_bound_tri") if tri else \
-        ("tspgnn_tour_search", "tspgnn_tour_lower_bound")
-    knn = ()
-    if neighbors is not None:
-        search, knn = search.replace("_search", "_search_knn"), (int(neighbors),)
     dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     G = len(big)
     with torch.cuda.device(dev):
@@ -265,41 +309,12 @@ def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, devic
         if incumbents is not None:
             d_tours.copy_(torch.from_numpy(init))
             d_cost = None   # the root's step then aims at the incumbent's own cost
-        torch.cuda.synchronize(dev)
-        t1 = time.perf_counter()
-        st = _lib.current_stream()
-        for c0 in range(0, G if incumbents is None else 0, chunk):
-            c1 = min(G, c0 + chunk)
-            _lib.call(search, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
-                      _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
-                      int(restarts), int(kicks), *knn, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours),
-                      _lib.ptr(d_cost[c0:c1]), st)
-        torch.cuda.synchronize(dev)
-        t2 = time.perf_counter()
+        t1, t2, t3, d_stat, d_nodes = _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost,
+                                                     d_lb, restarts, kicks, seed, lb_iters, chunk, tri, neighbors,
+                                                     lower_bound, exact, search=incumbents is None)
         if exact is not None:
-            # results do not depend on the launch size, so a chunk whose stack would not fit BB_WORKSPACE_BYTES is split
-            per = int(_lib.lib.tspgnn_tour_branch_bound_ws(1, int(ns.max())))
-            step = max(1, min(chunk, G, BB_WORKSPACE_BYTES // per))
-            d_ws = torch.empty(per * step, dtype=torch.uint8, device=dev)
-            d_nodes = torch.empty(G, dtype=torch.int32, device=dev)
-            d_stat = torch.empty(G, dtype=torch.int32, device=dev)
-            for c0 in range(0, G, step):
-                c1 = min(G, c0 + step)
-                _lib.call("tspgnn_tour_branch_bound", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
-                          _lib.ptr(d_toff[c0:c1]), _lib.ptr(None if d_cost is None else d_cost[c0:c1]), c1 - c0,
-                          int(ns[c0:c1].max()), int(lb_iters), int(exact[1]), int(exact[0]), float(exact[2]),
-                          _lib.ptr(d_ws), _lib.ptr(d_tours), _lib.ptr(d_lb[c0:c1]), _lib.ptr(d_nodes[c0:c1]),
-                          _lib.ptr(d_stat[c0:c1]), st)
             exact[3][big] = d_stat.cpu().numpy()
             exact[4][big] = d_nodes.cpu().numpy()
-        elif lower_bound:
-            for c0 in range(0, G, chunk):
-                c1 = min(G, c0 + chunk)
-                _lib.call(bound, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
-                          _lib.ptr(d_cost[c0:c1]), c1 - c0, int(ns[c0:c1].max()), int(lb_iters), _lib.ptr(d_lb[c0:c1]),
-                          st)
-        torch.cuda.synchronize(dev)
-        t3 = time.perf_counter()
         tours = d_tours.cpu().numpy().astype(np.int64)
         lbs = d_lb.cpu().numpy() if lower_bound or exact is not None else np.full(G, np.nan)
     for n, poss in groups.items():
@@ -643,6 +658,37 @@ def draw_instances(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="
     if closure == "device" and _closes(distances, metric):
         _close_on_device(out, range(samples), device, timings)
     return out
+
+
+def draw_streams(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D"):
+    """draw_instances' random draws without its matrices: per sample random.randint(nmin, nmax), then
+    np.random.uniform(conn_min, conn_max), then rand(n (n-1) / 2) (the adjacency pairs, row-major i < j), then
+    rand(n, 2) (euc_2D: the points) or rand(n (n-1) / 2) (random: the weights of the pairs), then permutation(n) (the
+    planted cycle) -- the same calls in the same order on the same global generators, which it leaves in the state
+    draw_instances leaves them.  Builds no n x n array: DeviceDataset.generate turns the streams into matrices on the GPU
+    (tspgnn_build_instances).
+
+    Returns a dict of flat arrays: 'n' int32[I]; 'conn' float64[I]; 'adj_u' float64[sum pairs]; 'pts' float64[sum 2 n]
+    (x, y interleaved; euc_2D) or 'wts' float64[sum pairs] (random); 'perm' int32[sum n]; and the prefix offsets
+    'pair_off' / 'vert_off' int64[I + 1] of an instance's pairs and vertices; 'distances'."""
+    if distances not in ("euc_2D", "random"):
+        raise ValueError("distances=%r must be 'euc_2D' or 'random'" % (distances,))
+    ns = np.empty(samples, dtype=np.int32)
+    conn = np.empty(samples, dtype=np.float64)
+    adj, second, perm = [], [], []
+    for s in range(samples):
+        n = random.randint(nmin, nmax)
+        ns[s], conn[s] = n, np.random.uniform(conn_min, conn_max)
+        pairs = n * (n - 1) // 2
+        adj.append(np.random.rand(pairs))
+        second.append(np.random.rand(n, 2).reshape(-1) if distances == "euc_2D" else np.random.rand(pairs))
+        perm.append(np.random.permutation(n))
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.empty(0, dtype=dt)
+    n64 = ns.astype(np.int64)
+    return {"n": ns, "conn": conn, "adj_u": cat(adj, np.float64),
+            "pts" if distances == "euc_2D" else "wts": cat(second, np.float64), "perm": cat(perm, np.int32),
+            "pair_off": np.concatenate([[0], np.cumsum(n64 * (n64 - 1) // 2)]).astype(np.int64),
+            "vert_off": np.concatenate([[0], np.cumsum(n64)]).astype(np.int64), "distances": distances}
 
 
 def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True,

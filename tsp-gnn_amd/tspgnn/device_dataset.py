@@ -15,9 +15,14 @@ Layout (device, int32 offsets -- ``MAX_CSR_ENTRIES``):
     cost   double[I]         route_cost, closing-pair quirk included
 The host keeps ``n`` and ``m`` (int64): a batch's e_start / v_start are their prefix sums over the index list
 (``plan_batch``), uploaded with the ids as one small pinned buffer.
+
+``DeviceDataset.generate`` fills the same arrays without the host pass: the reference's random draws stay on the host as
+flat streams (dataset.draw_streams) and csrc/dataset_build.hip builds, penalises and packs the instances around the
+existing closure, search and bound kernels.
 """
 import ctypes
 import os
+import time
 
 import numpy as np
 import torch
@@ -109,10 +114,28 @@ def epoch_indices(n_instances, batch_size, shuffle=True, rng=None):
     return [np.repeat(order[k * bs:(k + 1) * bs], 2) for k in range(n_instances // bs)]
 
 
-class DeviceDataset(object):
-    """A list of (Ma, Mw, route) -- as read_graph / draw_instances return them -- resident on one GPU.
+def _segments(flat, starts, lens):
+    """flat[starts[k]:starts[k] + lens[k]] for every k, concatenated (one fancy-indexing pass over a 1-D stream)."""
+    lens = np.asarray(lens, dtype=np.int64)
+    first = np.cumsum(lens) - lens
+    return flat[np.arange(int(lens.sum()), dtype=np.int64) + np.repeat(np.asarray(starts, dtype=np.int64) - first, lens)]
 
-        ds = DeviceDataset(instances)
+
+def _prefix(lens):
+    """Exclusive prefix sums of ``lens`` (int64, one entry per element) and their total."""
+    lens = np.asarray(lens, dtype=np.int64)
+    ends = np.cumsum(lens)
+    return ends - lens, int(ends[-1]) if len(lens) else 0
+
+
+_GENERATE_KW = ("restarts", "kicks", "lb_iters", "seed", "neighbors", "max_nodes")
+
+
+class DeviceDataset(object):
+    """A list of (Ma, Mw, route) -- as read_graph returns them -- resident on one GPU; ``DeviceDataset.generate`` makes
+    the set draw_instances + label_tours would make without a host pass over the matrices.
+
+        ds = DeviceDataset(instances)                        # or DeviceDataset.generate(2 ** 15, 20, 40)
         for batch in ds.get_batches(64, dev=0.02, time_steps=32, rng=np.random.RandomState(0)):
             run_batch(sess, model, batch, ...)               # or sess.forward(batch) / sess.train_step(batch)
 
@@ -136,8 +159,23 @@ class DeviceDataset(object):
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
         self._inst, self._uv, self._w = up(inst), up(host["uv"]), up(host["w"])
         self._rowptr, self._eid, self._cost = up(host["rowptr"]), up(host["eid"]), up(host["cost"])
+        self._init_batching()
+
+    def _init_batching(self):
         self._plans = {}     # (e_start bytes, v_start bytes) -> (device int32 plan or None, meta or None)
         self._ring, self._next = [None] * _RING, 0   # [pinned int32 buffer, its device copy, event of the launch that read it]
+        self.summary = self.tours = self._matrices = None   # generate() fills these
+
+    @classmethod
+    def _adopt(cls, device, n, m, inst, uv, w, rowptr, eid, cost):
+        """A dataset over arrays that are already on ``device`` in the layout of the module docstring (generate);
+        n, m: the host copies (int64)."""
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+        self.n, self.m = np.asarray(n, dtype=np.int64), np.asarray(m, dtype=np.int64)
+        self._inst, self._uv, self._w, self._rowptr, self._eid, self._cost = inst, uv, w, rowptr, eid, cost
+        self._init_batching()
+        return self
 
     def __len__(self):
         return len(self.n)
@@ -146,6 +184,222 @@ class DeviceDataset(object):
     def from_directory(cls, path, device=None):
         """Every file of a ``.graph`` directory (read_graph), in sorted order."""
         return cls([read_graph(os.path.join(path, f)) for f in sorted(os.listdir(path))], device=device)
+
+    # ------------------------------------------------------------------ made on the device
+    @classmethod
+    def generate(cls, samples, nmin, nmax, conn_min=1, conn_max=1, distances="euc_2D", metric=True, device=None,
+                 exact=False, chunk_bytes=1 << 30, **solve_kw):
+        """The dataset DeviceDataset([(np.triu(Ma), Mw, tour)]) of draw_instances(nmin, nmax, conn_min, conn_max, samples,
+        distances, metric) labelled by label_tours(init_tours=planted cycles, index=arange(samples), exact=exact,
+        **solve_kw) -- byte for byte, the global ``random`` / ``np.random`` consumed exactly alike -- with only the 1-D
+        random draws made on the host (dataset.draw_streams).  The matrices (tspgnn_build_instances), the metric closure
+        of 'random' weights (tspgnn_metric_closure), the search input (tspgnn_penalise_instances), the labels (the tour
+        kernels) and the dataset arrays (tspgnn_pack_dataset) are made on the GPU.
+
+        4 <= nmin <= nmax <= 256.  solve_kw: restarts, kicks, lb_iters, seed, neighbors, max_nodes as label_tours takes
+        them (None: its defaults for n <= 128 and for n 129-256).  exact: the branch and bound for n <= 128.  chunk_bytes:
+        most bytes of fp64 matrices built and labelled together (the search input and the streams of a chunk are dropped
+        after it; its mask and matrix wait on the device for the packing launches, 9 sum n^2 bytes in all); the result does
+        not depend on it.  Every argument is checked before the first launch (ValueError).
+
+        Instance i is the i-th draw.  ``summary`` is create_dataset's dict: samples, n, cost, lb, target, feasible, gap,
+        certified_fraction (at dev 0.02), with ``exact`` proved and nodes, and times {'draw', 'build', 'closure' when one
+        ran, 'search', 'bound' | 'exact', 'pack'} in device-synchronised seconds plus 'total', the call's wall seconds.
+        ``tours`` is (int32 host array of all tours, int64 offsets[samples + 1]).  The device array ``_cost`` is
+        tspgnn_host_route_cost on Mw, as DeviceDataset(instances) keeps it; summary['target'] is n times that cost on the
+        file form of Mw, as create_dataset reports it (they differ only when the closing pair (route[-1], route[1]) is no
+        edge).  The fp64 weight matrices stay on the device (8 sum n^2 bytes) for
+        to_instances()."""
+        from . import dataset as D
+        t_begin = time.perf_counter()
+        unknown = sorted(set(solve_kw) - set(_GENERATE_KW))
+        if unknown:
+            raise TypeError("DeviceDataset.generate: unexpected keyword %s (label_tours' %s)" % (unknown, list(_GENERATE_KW)))
+        restarts, kicks, lb_iters = (solve_kw.get(k) for k in ("restarts", "kicks", "lb_iters"))
+        seed, neighbors, max_nodes = solve_kw.get("seed", 0), solve_kw.get("neighbors"), solve_kw.get("max_nodes")
+        if not 4 <= nmin <= nmax <= D.MAX_N_TRI:
+            raise ValueError("DeviceDataset.generate: 4 <= nmin <= nmax <= %d, got nmin=%r nmax=%r" % (D.MAX_N_TRI, nmin, nmax))
+        if samples < 0 or chunk_bytes < 1:
+            raise ValueError("DeviceDataset.generate: samples=%r must be >= 0 and chunk_bytes=%r positive" % (samples, chunk_bytes))
+        if distances not in ("euc_2D", "random"):
+            raise ValueError("distances=%r must be 'euc_2D' or 'random'" % (distances,))
+        D._check_neighbors(neighbors)
+        small = (D.DEFAULT_RESTARTS if restarts is None else restarts, D.DEFAULT_KICKS if kicks is None else kicks,
+                 D.DEFAULT_LB_ITERS if lb_iters is None else lb_iters)
+        large = (D.DEFAULT_RESTARTS_LARGE if restarts is None else restarts,
+                 D.DEFAULT_KICKS_LARGE if kicks is None else kicks, D.DEFAULT_LB_ITERS_LARGE if lb_iters is None else lb_iters)
+        D._check_counts(*large, 1)
+        D._check_counts(*small, 1)
+        bb = None
+        if exact:
+            bb = (D.DEFAULT_BB_NODES if max_nodes is None else max_nodes, D.DEFAULT_BB_ITERS, 1e-9)
+            D._check_bb(*bb)
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("DeviceDataset needs an MI355X (no HIP device visible)")
+            device = "cuda:%d" % torch.cuda.current_device()
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("DeviceDataset.generate: device=%r: the instances are made by HIP kernels" % str(dev))
+
+        t0 = time.perf_counter()
+        S = D.draw_streams(nmin, nmax, conn_min, conn_max, samples, distances)
+        times = {"draw": time.perf_counter() - t0}
+        ns, I = S["n"], int(samples)
+        n_big = int(ns[ns > D.MAX_N].max(initial=0))
+        if n_big and large[0] > D.tri_chains_fit(n_big, neighbors):
+            raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS"
+                             % (large[0], n_big, D.tri_chains_fit(n_big, neighbors)))
+        random_w = distances == "random"
+        coord = S["wts"] if random_w else S["pts"]
+        closes = D._closes(distances, metric)
+        n64 = ns.astype(np.int64)
+        m = np.zeros(I, dtype=np.int64)
+        lb = np.full(I, np.nan)
+        status, nodes = np.full(I, 2, dtype=np.int64), np.zeros(I, dtype=np.int64)
+        order = np.argsort(ns, kind="stable")   # launch order: by n, the two size classes apart (as label_tours)
+        chunks = []                             # (tri, stream positions) of at most chunk_bytes of fp64 matrices
+        for tri in (False, True):
+            cur, size = [], 0
+            for p in order[(ns[order] > D.MAX_N) == tri]:
+                b = 8 * int(ns[p]) ** 2
+                if cur and size + b > chunk_bytes:
+                    chunks.append((tri, np.array(cur, dtype=np.int64)))
+                    cur, size = [], 0
+                cur.append(int(p))
+                size += b
+            if cur:
+                chunks.append((tri, np.array(cur, dtype=np.int64)))
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        clock = lambda: (torch.cuda.synchronize(dev), time.perf_counter())[1]
+        add = lambda key, dt: times.__setitem__(key, times.get(key, 0.0) + dt)
+        kept = []   # per chunk: positions, n, cell offsets, tour offsets, device A, Mw, tours
+        with torch.cuda.device(dev):
+            st = _lib.current_stream()
+            for tri, pos in chunks:
+                t0 = clock()
+                nc = n64[pos]
+                C, n_max = len(pos), int(nc.max())
+                pairs = nc * (nc - 1) // 2
+                p_off, n_pairs = _prefix(pairs)
+                t_off, n_verts = _prefix(nc)
+                c_off, n_cells = _prefix(nc * nc)
+                w_off, n_floats = _prefix(pairs if tri else nc * nc)
+                d_adj = up(_segments(S["adj_u"], S["pair_off"][pos], pairs))
+                d_coord = up(_segments(coord, S["pair_off"][pos], pairs) if random_w else
+                             _segments(coord, 2 * S["vert_off"][pos], 2 * nc))
+                d_perm = up(_segments(S["perm"], S["vert_off"][pos], nc))
+                d_conn = up(S["conn"][pos])
+                tab = np.ascontiguousarray(np.stack([nc, p_off, t_off, c_off], axis=1))
+                d_tab = up(tab)
+                d_Mw = torch.empty(n_cells, dtype=torch.float64, device=dev)
+                d_A = torch.empty(n_cells, dtype=torch.uint8, device=dev)
+                d_m = torch.empty(C, dtype=torch.int32, device=dev)
+                _lib.call("tspgnn_build_instances", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(d_conn), _lib.ptr(d_adj),
+                          _lib.ptr(d_coord), _lib.ptr(d_perm), int(random_w), C, n_max, n_pairs, n_verts, n_cells,
+                          _lib.ptr(d_Mw), _lib.ptr(d_A), _lib.ptr(d_m), st)
+                d_coff, d_n = up(c_off), up(nc.astype(np.int32))
+                t1 = clock()
+                add("build", t1 - t0)
+                if closes:   # the tiers apart, as metric_closure: a small instance is closed in LDS
+                    cut = int(np.searchsorted(nc, D.CLOSURE_LDS_MAX_N, side="right"))
+                    for lo, hi in ((0, cut), (cut, C)):
+                        if hi > lo:
+                            _lib.call("tspgnn_metric_closure", _lib.ptr(d_Mw), _lib.ptr(d_coff[lo:hi]), _lib.ptr(d_n[lo:hi]),
+                                      hi - lo, int(nc[lo:hi].max()), st)
+                    t0 = clock()
+                    add("closure", t0 - t1)
+                    t1 = t0
+                ptab = np.ascontiguousarray(np.stack([nc, c_off, w_off], axis=1))
+                d_ptab = up(ptab)
+                d_W = torch.empty(n_floats, dtype=torch.float32, device=dev)
+                _lib.call("tspgnn_penalise_instances", ptab.ctypes.data, _lib.ptr(d_ptab), _lib.ptr(d_A), _lib.ptr(d_Mw), C,
+                          n_max, int(tri), n_cells, n_floats, _lib.ptr(d_W), st)
+                d_tours = torch.empty(n_verts, dtype=torch.int32, device=dev)
+                d_cost = torch.empty(C, dtype=torch.float32, device=dev)
+                d_lb = torch.empty(C, dtype=torch.float64, device=dev)
+                r, k, it = large if tri else small
+                sub = None if bb is None or tri else bb
+                t1b, t2, t3, d_stat, d_nodes = D._launch_labels(
+                    dev, nc.astype(np.int32), d_W, up(w_off), up(t_off), d_n, up(pos), d_perm, d_tours, d_cost, d_lb, r, k,
+                    seed, it, D.DEFAULT_CHUNK, tri, neighbors, True, sub)
+                add("build", t1b - t1)
+                add("search", t2 - t1b)
+                add("bound" if sub is None else "exact", t3 - t2)
+                m[pos] = d_m.cpu().numpy()
+                lb[pos] = d_lb.cpu().numpy()
+                if sub is not None:
+                    status[pos], nodes[pos] = d_stat.cpu().numpy(), d_nodes.cpu().numpy()
+                kept.append((pos, nc, c_off, t_off, n_cells, n_verts, n_max, d_A, d_Mw, d_tours))
+                del d_W, d_adj, d_coord
+
+            # every m is known: the dataset's prefix sums, then one packing launch per chunk into the final arrays
+            t0 = clock()
+            check_size(m.sum())
+            e0, M = _prefix(m)
+            v0, N = _prefix(n64)
+            inst = np.stack([n64, m, e0, v0], axis=1).astype(np.int32).reshape(I, 4)
+            d_uv = torch.empty((M, 2), dtype=torch.int32, device=dev)
+            d_w = torch.empty(M, dtype=torch.float32, device=dev)
+            d_eid = torch.empty(2 * M, dtype=torch.int32, device=dev)
+            d_rowptr = torch.empty(N + I, dtype=torch.int32, device=dev)
+            d_rc = torch.empty(I, dtype=torch.float64, device=dev)
+            d_fc = torch.empty(I, dtype=torch.float64, device=dev)
+            d_cyc = torch.empty(I, dtype=torch.float64, device=dev)
+            d_feas = torch.empty(I, dtype=torch.int32, device=dev)
+            tours = np.empty(N, dtype=np.int32)
+            matrices = []
+            for pos, nc, c_off, t_off, n_cells, n_verts, n_max, d_A, d_Mw, d_tours in kept:
+                tab = np.ascontiguousarray(np.stack([nc, c_off, t_off, m[pos], e0[pos], v0[pos], pos], axis=1))
+                d_tab = up(tab)
+                _lib.call("tspgnn_pack_dataset", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(d_A), _lib.ptr(d_Mw),
+                          _lib.ptr(d_tours), len(pos), n_max, n_cells, n_verts, M, N + I, I, _lib.ptr(d_uv), _lib.ptr(d_w),
+                          _lib.ptr(d_rowptr), _lib.ptr(d_eid), _lib.ptr(d_rc), _lib.ptr(d_fc), _lib.ptr(d_cyc),
+                          _lib.ptr(d_feas), st)
+                flat = d_tours.cpu().numpy()
+                tours[np.arange(n_verts, dtype=np.int64) + np.repeat(v0[pos] - t_off, nc)] = flat
+                matrices.append((pos, c_off, d_Mw))
+            kept = None
+            ds = cls._adopt(dev, n64, m, up(inst), d_uv, d_w, d_rowptr, d_eid, d_rc)
+            file_cost, cyc, feas = d_fc.cpu().numpy(), d_cyc.cpu().numpy(), d_feas.cpu().numpy().astype(bool)
+            add("pack", clock() - t0)
+        if not feas.all():
+            raise Exception("Unsolvable")
+        ds.tours = (tours, np.concatenate([v0, [N]]).astype(np.int64))
+        ds._matrices = matrices
+        summary = {"samples": I, "n": n64.copy(), "cost": cyc, "lb": lb, "target": n64 * file_cost, "feasible": feas,
+                   "times": times}
+        if exact:
+            summary["proved"], summary["nodes"] = status == 0, nodes
+        summary["gap"] = (cyc - lb) / np.where(cyc > 0, cyc, 1.0)
+        summary["certified_fraction"] = D.certify(summary, 0.02)["fraction"]
+        times["total"] = time.perf_counter() - t_begin
+        ds.summary = summary
+        return ds
+
+    def to_instances(self):
+        """A generated dataset as the list of (np.triu(Ma), Mw, route) DeviceDataset(...) and write_graph take, downloaded
+        from the device: Ma from the edge list, Mw the fp64 matrices generate kept, route the label."""
+        if self._matrices is None:
+            raise RuntimeError("DeviceDataset.to_instances: only a dataset made by generate() keeps its fp64 matrices")
+        I = len(self.n)
+        uv = self._uv.cpu().numpy()
+        e0 = np.concatenate([[0], np.cumsum(self.m)])
+        tours, t_off = self.tours
+        Mw = [None] * I
+        for pos, c_off, d_Mw in self._matrices:
+            flat = d_Mw.cpu().numpy()
+            for p, o in zip(pos, c_off):
+                n = int(self.n[p])
+                Mw[p] = flat[o:o + n * n].reshape(n, n).copy()
+        out = []
+        for i in range(I):
+            n = int(self.n[i])
+            Ma = np.zeros((n, n))
+            e = uv[e0[i]:e0[i + 1]]
+            Ma[e[:, 0], e[:, 1]] = 1.0
+            out.append((Ma, Mw[i], [int(x) for x in tours[t_off[i]:t_off[i + 1]]]))
+        return out
 
     def _require_gpu(self):
         if self.device.type != "cuda":
