@@ -1,7 +1,8 @@
 """Cases for the LN-LSTM cell backward kernels called directly (tests/test_gpu_h2_backward_kernels.py,
 tests/test_gpu_bf16_backward_kernels.py): one task's inputs, its operands packed for an arithmetic, a float64 autograd
 reference on the device, and a replay of the launchers' planning arithmetic, so that a test that claims to reach a path
-(a second tile per wavefront, the chunked K) asserts that it does.
+(a second tile per wavefront, the chunked K) asserts that it does.  The device-buffer helpers (dev, empty, release, SENTINEL,
+SPARE) and the row-by-row measure row_err also serve tests/test_gpu_fp32_backward_plans.py and tests/test_gpu_batch_kernels.py.
 
 The arithmetic decides the packing of K / K^T, the form of the projected messages Zx, and the entry point:
   "h2"    tspgnn_lnlstm_bwd_multi_h2   (csrc/dense_bwd_h2.hip)    pack_weights_h2 of K and of K^T, Zx scaled and blocked
@@ -44,6 +45,16 @@ def empty(shape, device, fill=None):
         torch.full(shape, fill, dtype=torch.float32, device=device)
     _KEEP.append(t)
     return t
+
+
+def row_err(a, b):
+    """max over the rows of max |a - b| / max |b| (each over the row); a row where b is all zero must be all zero in a."""
+    scale = np.abs(b).max(axis=1)
+    dead = scale == 0
+    assert not a[dead].any(), "rows without a gradient: %d not exactly zero" % int(np.abs(a[dead]).max(axis=1).astype(bool).sum())
+    if dead.all():
+        return 0.0
+    return float((np.abs(a - b).max(axis=1)[~dead] / scale[~dead]).max())
 
 
 def rb(x):

@@ -25,7 +25,8 @@ import pytest
 import torch
 
 from conftest import rel_err
-from lstm_bwd_cases import SENTINEL, Cell, dev, empty, k_resident_f32, plan_of, release, tiles_per_wavefront, workspace
+from lstm_bwd_cases import (SENTINEL, Cell, dev, empty, k_resident_f32, plan_of, release, row_err, tiles_per_wavefront,
+                            workspace)
 from tspgnn import _lib
 
 pytestmark = pytest.mark.gpu
@@ -66,16 +67,6 @@ def assert_deep(cells, d, device, arith):
 def launch(arith, cells, d, device, **kw):
     _lib.call_multi(ENTRY[arith], [c.task(device, **kw) for c in cells], d)
     torch.cuda.synchronize()
-
-
-def row_err(a, b):
-    """max over the rows of max |a - b| / max |b| (each over the row); a row where b is all zero must be all zero in a."""
-    scale = np.abs(b).max(axis=1)
-    dead = scale == 0
-    assert not a[dead].any(), "rows without a gradient: %d not exactly zero" % int(np.abs(a[dead]).max(axis=1).astype(bool).sum())
-    if dead.all():
-        return 0.0
-    return float((np.abs(a - b).max(axis=1)[~dead] / scale[~dead]).max())
 
 
 def check(cell, device, what=""):
