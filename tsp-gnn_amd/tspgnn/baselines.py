@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dataset import (DEFAULT_CHUNK, MAX_N, MAX_N_TRI, TourResult, _cycle_cost, _edge_mask, _host_small, _penalised,
-                      _penalised_tri, _target, _validate, tri_chains_fit)
+from .dataset import (DEFAULT_CHUNK, MAX_N, MAX_N_TRI, _add_time, _device, _finish, _pack, _spans, _split, _upload,
+                      _validate, tri_chains_fit)
 
 # Annealing defaults, chosen from the t_hot x sweeps grid of DESIGN.md §12 (2^10 instances at n 20-40, 80 and 200 on the
 # MI355X).  Temperatures are multiples of the instance's mean real edge weight, and a level runs sweeps * n^2 proposals.
@@ -29,80 +29,6 @@ DEFAULT_SWEEPS = 4
 DEFAULT_T_HOT = 0.1
 DEFAULT_T_COLD = 0.002
 MAX_PROPOSALS = 2 ** 31 - 1
-
-
-def _pack(checked, init_tours, tri):
-    """The instances of n >= 4 packed for one kernel layout, in launch order (by n), and the n < 4 results."""
-    B = len(checked)
-    out = [None] * B
-    for k in range(B):
-        if checked[k][2] < 4:
-            Ma, Mw, n = checked[k]
-            tour, cost, _, feas = _host_small(Ma, Mw, n)
-            out[k] = TourResult(tour, cost, float("nan"), feas, _target(Ma, Mw, tour))
-    big = [k for k in range(B) if checked[k][2] >= 4]
-    ns = np.array([checked[k][2] for k in big], dtype=np.int32)
-    order = np.argsort(ns, kind="stable")
-    big = [big[k] for k in order]
-    ns = ns[order]
-    sq = ns.astype(np.int64) * (ns - 1) // 2 if tri else ns.astype(np.int64) ** 2
-    w_off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
-    t_off = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
-    Wflat = np.empty(int(sq.sum()), dtype=np.float32)
-    init = np.full(int(ns.sum()), -1, dtype=np.int32)
-    mean_w = np.zeros(len(big))
-    groups, stacked = {}, {}
-    for pos in range(len(big)):
-        groups.setdefault(int(ns[pos]), []).append(pos)
-    for n, poss in groups.items():
-        A = np.stack([_edge_mask(checked[big[p]][0]) for p in poss])
-        Mw = np.stack([checked[big[p]][1] for p in poss])
-        W32 = (_penalised_tri if tri else _penalised)(A, Mw)
-        up = np.triu(A, 1)
-        mean_w[poss] = np.where(up, Mw, 0.0).sum(axis=(1, 2)) / np.maximum(up.sum(axis=(1, 2)), 1)
-        for g, p in enumerate(poss):
-            Wflat[w_off[p]:w_off[p] + sq[p]] = W32[g].reshape(-1)
-            if init_tours is not None and init_tours[big[p]] is not None:
-                it = np.asarray(init_tours[big[p]], dtype=np.int64).reshape(-1)
-                if it.shape[0] != n or not np.array_equal(np.sort(it), np.arange(n)):
-                    raise ValueError("init_tours[%d] is not a permutation of 0..%d" % (big[p], n - 1))
-                init[t_off[p]:t_off[p] + n] = it
-        stacked[n] = (A, Mw)
-    return {"out": out, "big": big, "ns": ns, "w_off": w_off, "t_off": t_off, "W": Wflat, "init": init,
-            "mean_w": mean_w, "groups": groups, "stacked": stacked, "checked": checked}
-
-
-def _finish(pk, tours):
-    """TourResults of the packed instances from the kernels' tours (fp64 cycle cost, feasibility, target Q)."""
-    out, big, t_off = pk["out"], pk["big"], pk["t_off"]
-    for n, poss in pk["groups"].items():
-        A, Mw = pk["stacked"][n]
-        T = np.stack([tours[t_off[p]:t_off[p] + n] for p in poss])
-        cost = _cycle_cost(Mw, T)
-        feas = A[np.arange(len(poss))[:, None], T, np.roll(T, -1, axis=1)].all(axis=1)
-        for g, p in enumerate(poss):
-            k = big[p]
-            tour = [int(x) for x in T[g]]
-            out[k] = TourResult(tour, float(cost[g]), float("nan"), bool(feas[g]),
-                                _target(pk["checked"][k][0], pk["checked"][k][1], tour))
-    return out
-
-
-def _device(device):
-    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-
-
-def _split(checked):
-    """[(tri, positions)] of the non-empty halves: n <= 128 on the square kernels, above on the triangle kernels."""
-    halves = [(tri, [i for i, c in enumerate(checked) if (c[2] > MAX_N) == tri]) for tri in (False, True)]
-    return [(tri, sel) for tri, sel in halves if sel]
-
-
-def _upload(pk, dev):
-    d = {k: torch.from_numpy(pk[k]).to(dev) for k in ("W", "w_off", "t_off", "ns")}
-    d["tours"] = torch.empty(int(pk["ns"].sum()), dtype=torch.int32, device=dev)
-    d["cost"] = torch.empty(len(pk["big"]), dtype=torch.float32, device=dev)
-    return d
 
 
 def nearest_neighbor_tours(instances, start=0, device=None, chunk=DEFAULT_CHUNK):
@@ -122,22 +48,20 @@ def nearest_neighbor_tours(instances, start=0, device=None, chunk=DEFAULT_CHUNK)
             raise ValueError("start=%r must be a non-negative vertex id or 'best'" % (start,))
     checked, _ = _validate(instances, 1, 0, 1, chunk, None, None, MAX_N_TRI)
     out = [None] * len(checked)
-    for tri, sel in _split(checked):
-        pk = _pack([checked[i] for i in sel], None, tri)
-        res = pk["out"]
-        if pk["big"]:
+    for tri, sel in _split([c[2] for c in checked]):
+        pk = _pack([checked[i] for i in sel], tri)
+        res = pk.out
+        if pk.big:
             dev = _device(device)
             entry = "tspgnn_tour_nearest_neighbor_tri" if tri else "tspgnn_tour_nearest_neighbor"
-            ns, G = pk["ns"], len(pk["big"])
             with torch.cuda.device(dev):
                 d = _upload(pk, dev)
                 st = _lib.current_stream()
-                for c0 in range(0, G, chunk):
-                    c1 = min(G, c0 + chunk)
-                    _lib.call(entry, _lib.ptr(d["W"]), _lib.ptr(d["w_off"][c0:c1]), _lib.ptr(d["ns"][c0:c1]),
-                              _lib.ptr(d["t_off"][c0:c1]), c1 - c0, int(ns[c0:c1].max()), s, _lib.ptr(d["tours"]),
-                              _lib.ptr(d["cost"][c0:c1]), st)
-                tours = d["tours"].cpu().numpy().astype(np.int64)
+                for c0, c1 in _spans(len(pk.big), chunk):
+                    _lib.call(entry, _lib.ptr(d.W), _lib.ptr(d.w_off[c0:c1]), _lib.ptr(d.n[c0:c1]),
+                              _lib.ptr(d.t_off[c0:c1]), c1 - c0, int(pk.ns[c0:c1].max()), s, _lib.ptr(d.tours),
+                              _lib.ptr(d.cost[c0:c1]), st)
+                tours = d.tours.cpu().numpy().astype(np.int64)
             res = _finish(pk, tours)
         for i, x in zip(sel, res):
             out[i] = x
@@ -209,52 +133,45 @@ def anneal_tours(instances, chains=DEFAULT_CHAINS, levels=DEFAULT_LEVELS, sweeps
         raise ValueError("levels * per_level = %d exceeds the limit of %d proposals per chain"
                          % (int(per.max()) * L, MAX_PROPOSALS))
     out = [None] * B
-    for tri, sel in _split(checked):
+    for tri, sel in _split(ns_all):
         t_pack = time.perf_counter()
-        inits = None if init_tours is None else [init_tours[i] for i in sel]
-        pk = _pack([checked[i] for i in sel], inits, tri)
-        res = pk["out"]
-        if pk["big"]:
-            big = np.array(sel)[pk["big"]]          # positions in `instances`, in launch order
-            ns, G = pk["ns"], len(pk["big"])
+        pk = _pack([checked[i] for i in sel], tri, None if init_tours is None else [init_tours[i] for i in sel],
+                   mean_weight=inv is None)
+        res = pk.out
+        if pk.big:
+            big = np.array(sel)[pk.big]          # positions in `instances`, in launch order
+            G = len(big)
             if inv is None:
                 with np.errstate(divide="ignore"):
-                    inv32 = (1.0 / (pk["mean_w"][:, None] * temps[None, :])).astype(np.float32)
+                    inv32 = (1.0 / (pk.mean_w[:, None] * temps[None, :])).astype(np.float32)
             else:
                 inv32 = inv[big].astype(np.float32)
             inv32 = np.ascontiguousarray(inv32).reshape(G, L)
-            has_init = inits is not None and any(t is not None for t in inits)
             dev = _device(device)
             entry = "tspgnn_tour_anneal_tri" if tri else "tspgnn_tour_anneal"
             with torch.cuda.device(dev):
-                d = _upload(pk, dev)
-                d_idx = torch.from_numpy(np.ascontiguousarray(index[big])).to(dev)
-                d_init = torch.from_numpy(pk["init"]).to(dev) if has_init else None
+                d = _upload(pk, dev, index[sel])
                 d_inv = torch.from_numpy(inv32).to(dev)
                 d_per = torch.from_numpy(per[big].astype(np.int32)).to(dev)
                 torch.cuda.synchronize(dev)
                 t1 = time.perf_counter()
                 st = _lib.current_stream()
-                for c0 in range(0, G, chunk):
-                    c1 = min(G, c0 + chunk)
-                    _lib.call(entry, _lib.ptr(d["W"]), _lib.ptr(d["w_off"][c0:c1]), _lib.ptr(d["ns"][c0:c1]),
-                              _lib.ptr(d_init), _lib.ptr(d["t_off"][c0:c1]), _lib.ptr(d_idx[c0:c1]),
+                for c0, c1 in _spans(G, chunk):
+                    _lib.call(entry, _lib.ptr(d.W), _lib.ptr(d.w_off[c0:c1]), _lib.ptr(d.n[c0:c1]),
+                              _lib.ptr(d.init), _lib.ptr(d.t_off[c0:c1]), _lib.ptr(d.idx[c0:c1]),
                               _lib.ptr(d_inv[c0:c1]) if L else None, _lib.ptr(d_per[c0:c1]), c1 - c0,
-                              int(ns[c0:c1].max()), chains, L, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d["tours"]),
-                              _lib.ptr(d["cost"][c0:c1]), st)
+                              int(pk.ns[c0:c1].max()), chains, L, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d.tours),
+                              _lib.ptr(d.cost[c0:c1]), st)
                 torch.cuda.synchronize(dev)
                 t2 = time.perf_counter()
-                tours = d["tours"].cpu().numpy().astype(np.int64)
+                tours = d.tours.cpu().numpy().astype(np.int64)
             res = _finish(pk, tours)
-            if timings is not None:
-                timings["pack"] = timings.get("pack", 0.0) + (t1 - t_pack)
-                timings["anneal"] = timings.get("anneal", 0.0) + (t2 - t1)
+            _add_time(timings, "pack", t1 - t_pack)
+            _add_time(timings, "anneal", t2 - t1)
         for i, x in zip(sel, res):
             out[i] = x
-    if timings is not None:
-        timings.setdefault("pack", 0.0)
-        timings.setdefault("anneal", 0.0)
-        timings["total"] = timings.get("total", 0.0) + (time.perf_counter() - t0)
+    for key, seconds in (("pack", 0.0), ("anneal", 0.0), ("total", time.perf_counter() - t0)):   # every key, always
+        _add_time(timings, key, seconds)
     return out
 
 

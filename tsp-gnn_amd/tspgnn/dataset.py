@@ -165,8 +165,9 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
     t0 = time.perf_counter()
     _check_neighbors(neighbors)
     checked, index = _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, MAX_N)
-    return _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0,
-                  tri=False, neighbors=neighbors)
+    return _solve(checked, index, tri=False, restarts=restarts, kicks=kicks, seed=seed, init_tours=init_tours,
+                  lower_bound=lower_bound, device=device, lb_iters=lb_iters, chunk=chunk, timings=timings, t0=t0,
+                  neighbors=neighbors)[0]
 
 
 def _check_counts(restarts, kicks, lb_iters, chunk):
@@ -195,13 +196,141 @@ def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, ma
     return checked, index
 
 
-def _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost, d_lb, restarts, kicks, seed,
-                   lb_iters, chunk, tri, neighbors, lower_bound, exact=None, search=True):
-    """The launches of one size class over G instances that are already on ``dev`` (inside torch.cuda.device(dev)): the
-    search, ``chunk`` instances per launch, then the branch and bound (exact = (max_nodes, node_iters, opt_tol, ...),
-    tri=False only) or the bound (lower_bound).  ns: the host copy of d_n.  search=False: d_tours already holds the
-    incumbents.  -> (t1, t2, t3, d_stat, d_nodes): perf_counter before the search, after it and after the bound, each
-    device-synchronised, and the branch and bound's int32 device arrays (None without exact)."""
+def _device(device):
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _to_device(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def _add_time(timings, key, seconds):
+    if timings is not None:
+        timings[key] = timings.get(key, 0.0) + seconds
+
+
+def _spans(count, chunk):
+    """(c0, c1) of every launch over ``count`` instances, ``chunk`` at a time; the last one may be shorter."""
+    for c0 in range(0, count, chunk):
+        yield c0, min(count, c0 + chunk)
+
+
+def _split(ns):
+    """[(tri, positions)] of the non-empty size classes of the vertex counts ``ns``: n <= 128 on the square kernels, above
+    on the triangle kernels."""
+    above = np.asarray(ns) > MAX_N
+    return [(tri, sel) for tri, sel in ((False, np.flatnonzero(~above)), (True, np.flatnonzero(above))) if len(sel)]
+
+
+def _byte_chunks(order, ns, chunk_bytes):
+    """The positions ``order`` (into the vertex counts ``ns``) cut greedily into runs of at most chunk_bytes of fp64
+    n x n matrices, and at least one instance each."""
+    runs, cur, size = [], [], 0
+    for p in order:
+        b = 8 * int(ns[p]) ** 2
+        if cur and size + b > chunk_bytes:
+            runs.append(cur)
+            cur, size = [], 0
+        cur.append(int(p))
+        size += b
+    if cur:
+        runs.append(cur)
+    return runs
+
+
+# The instances of one kernel layout, packed (_pack).  out: per instance the TourResult where n < 4, else None; checked:
+# the (Ma, Mw, n) it was made from; big: the positions of the n >= 4 instances in launch order.  Per launched instance: ns
+# int32, w_off / t_off (its first float in W, its first vertex in init and the kernels' tours), mean_w (None unless asked
+# for).  W: the penalised fp32 matrices, flat; init: the starting tours, -1 where there is none; has_init: some instance
+# came with one.  groups: {n: positions in big}; stacked: {n: (edge masks, fp64 weights)} of a group.
+Packed = collections.namedtuple("Packed", ["out", "checked", "big", "ns", "w_off", "t_off", "W", "init", "has_init",
+                                           "mean_w", "groups", "stacked"])
+# What the tour kernels read and write for G instances of one layout: ns, the host copy of n, then the device arrays (init
+# None: no starting tours; cost None: prove_tours; idx and lb None for the baselines, which take neither).
+LabelArrays = collections.namedtuple("LabelArrays", "ns W w_off t_off n idx init tours cost lb")
+
+
+def _pack(checked, tri, init_tours=None, lower_bound=False, incumbents=None, mean_weight=False):
+    """Checked instances -> Packed: n < 4 solved on the host (lb = nan unless lower_bound), the rest packed for the square
+    (tri=False) or triangle kernels, grouped by n so that the penalties, costs and targets are array operations.
+    incumbents: one tour per instance, taken as its starting tour unchecked (prove_tours has checked them).
+    mean_weight: also the mean real edge weight per instance (annealing's temperature unit)."""
+    out = [None] * len(checked)
+    for k, (Ma, Mw, n) in enumerate(checked):
+        if n < 4:
+            tour, cost, lb, feas = _host_small(Ma, Mw, n)
+            out[k] = TourResult(tour, cost, lb if lower_bound else float("nan"), feas, _target(Ma, Mw, tour))
+    big = [k for k, c in enumerate(checked) if c[2] >= 4]
+    ns = np.array([checked[k][2] for k in big], dtype=np.int32)
+    order = np.argsort(ns, kind="stable")            # launch order: by n (similar work per workgroup)
+    big = [big[k] for k in order]
+    ns = ns[order]
+    sq = ns.astype(np.int64) * (ns - 1) // 2 if tri else ns.astype(np.int64) ** 2   # floats per instance
+    w_off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
+    t_off = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
+    Wflat = np.empty(int(sq.sum()), dtype=np.float32)
+    init = np.full(int(ns.sum()), -1, dtype=np.int32)
+    mean_w = np.zeros(len(big)) if mean_weight else None
+    groups, stacked = {}, {}
+    for pos in range(len(big)):
+        groups.setdefault(int(ns[pos]), []).append(pos)
+    for n, poss in groups.items():
+        A = np.stack([_edge_mask(checked[big[p]][0]) for p in poss])
+        Mw = np.stack([checked[big[p]][1] for p in poss])
+        W32 = (_penalised_tri if tri else _penalised)(A, Mw)
+        if mean_weight:
+            up = np.triu(A, 1)
+            mean_w[poss] = np.where(up, Mw, 0.0).sum(axis=(1, 2)) / np.maximum(up.sum(axis=(1, 2)), 1)
+        for g, p in enumerate(poss):
+            Wflat[w_off[p]:w_off[p] + sq[p]] = W32[g].reshape(-1)
+            if incumbents is not None:
+                init[t_off[p]:t_off[p] + n] = incumbents[big[p]]
+            elif init_tours is not None and init_tours[big[p]] is not None:
+                it = np.asarray(init_tours[big[p]], dtype=np.int64).reshape(-1)
+                if it.shape[0] != n or not np.array_equal(np.sort(it), np.arange(n)):
+                    raise ValueError("init_tours[%d] is not a permutation of 0..%d" % (big[p], n - 1))
+                init[t_off[p]:t_off[p] + n] = it
+        stacked[n] = (A, Mw)
+    has_init = init_tours is not None and any(t is not None for t in init_tours)
+    return Packed(out, checked, big, ns, w_off, t_off, Wflat, init, has_init, mean_w, groups, stacked)
+
+
+def _upload(pk, dev, index=None, bound=False):
+    """Packed -> LabelArrays on ``dev``.  index: the generator key of every packed instance (idx); bound: allocate lb."""
+    G = len(pk.big)
+    return LabelArrays(pk.ns, _to_device(pk.W, dev), _to_device(pk.w_off, dev), _to_device(pk.t_off, dev),
+                       _to_device(pk.ns, dev), None if index is None else _to_device(index[pk.big], dev),
+                       _to_device(pk.init, dev) if pk.has_init else None,
+                       torch.empty(int(pk.ns.sum()), dtype=torch.int32, device=dev),
+                       torch.empty(G, dtype=torch.float32, device=dev),
+                       torch.empty(G, dtype=torch.float64, device=dev) if bound else None)
+
+
+def _finish(pk, tours, lbs=None):
+    """TourResults of the packed instances from the kernels' tours (fp64 cycle cost, feasibility, target Q) and, per
+    launched instance, the bounds ``lbs`` (None: nan)."""
+    out, big, t_off = pk.out, pk.big, pk.t_off
+    for n, poss in pk.groups.items():
+        A, Mw = pk.stacked[n]
+        T = np.stack([tours[t_off[p]:t_off[p] + n] for p in poss])
+        cost = _cycle_cost(Mw, T)
+        feas = A[np.arange(len(poss))[:, None], T, np.roll(T, -1, axis=1)].all(axis=1)
+        for g, p in enumerate(poss):
+            k = big[p]
+            tour = [int(x) for x in T[g]]
+            out[k] = TourResult(tour, float(cost[g]), float("nan") if lbs is None else float(lbs[p]), bool(feas[g]),
+                                _target(pk.checked[k][0], pk.checked[k][1], tour))
+    return out
+
+
+def _launch_labels(dev, a, *, restarts, kicks, seed, lb_iters, chunk, tri, neighbors=None, lower_bound=True, exact=None,
+                   search=True):
+    """The launches of one size class over the LabelArrays ``a``, already on ``dev`` (inside torch.cuda.device(dev)): the
+    search, ``chunk`` instances per launch, then the branch and bound (exact = (max_nodes, node_iters, opt_tol), tri=False
+    only) or the bound (lower_bound).  search=False: a.tours already holds the incumbents (a.cost None: the root's step
+    then aims at the incumbent's own cost).  -> (t1, t2, t3, d_stat, d_nodes): perf_counter before the search, after it
+    and after the bound, each device-synchronised, and the branch and bound's int32 device arrays (None without exact)."""
+    ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost, d_lb = a
     G = len(ns)
     search_fn, bound_fn = ("tspgnn_tour_search_tri", "tspgnn_tour_lower_bound_tri") if tri else \
         ("tspgnn_tour_search", "tspgnn_tour_lower_bound")
@@ -212,8 +341,7 @@ def _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
     st = _lib.current_stream()
-    for c0 in range(0, G if search else 0, chunk):
-        c1 = min(G, c0 + chunk)
+    for c0, c1 in _spans(G if search else 0, chunk):
         _lib.call(search_fn, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                   _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
                   int(restarts), int(kicks), *knn, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours),
@@ -227,16 +355,14 @@ def _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_
         d_ws = torch.empty(per * step, dtype=torch.uint8, device=dev)
         d_nodes = torch.empty(G, dtype=torch.int32, device=dev)
         d_stat = torch.empty(G, dtype=torch.int32, device=dev)
-        for c0 in range(0, G, step):
-            c1 = min(G, c0 + step)
+        for c0, c1 in _spans(G, step):
             _lib.call("tspgnn_tour_branch_bound", _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                       _lib.ptr(d_toff[c0:c1]), _lib.ptr(None if d_cost is None else d_cost[c0:c1]), c1 - c0,
                       int(ns[c0:c1].max()), int(lb_iters), int(exact[1]), int(exact[0]), float(exact[2]),
                       _lib.ptr(d_ws), _lib.ptr(d_tours), _lib.ptr(d_lb[c0:c1]), _lib.ptr(d_nodes[c0:c1]),
                       _lib.ptr(d_stat[c0:c1]), st)
     elif lower_bound:
-        for c0 in range(0, G, chunk):
-            c1 = min(G, c0 + chunk)
+        for c0, c1 in _spans(G, chunk):
             _lib.call(bound_fn, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
                       _lib.ptr(d_cost[c0:c1]), c1 - c0, int(ns[c0:c1].max()), int(lb_iters), _lib.ptr(d_lb[c0:c1]), st)
     torch.cuda.synchronize(dev)
@@ -244,96 +370,62 @@ def _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_
     return t1, t2, t3, d_stat, d_nodes
 
 
-def _solve(checked, index, init_tours, restarts, kicks, seed, lower_bound, device, lb_iters, chunk, timings, t0, tri,
-           exact=None, incumbents=None, neighbors=None):
+def _solve(checked, index, *, tri, lb_iters, chunk, t0, restarts=1, kicks=0, seed=0, init_tours=None, lower_bound=True,
+           device=None, timings=None, exact=None, incumbents=None, neighbors=None):
     """solve_tours on checked instances, n < 4 on the host and the rest on the square kernels (tri=False, n <= 128) or
     the triangle kernels (tri=True, n <= 256); neighbors=K: the search is the _knn entry point of that layout.
-    exact = (max_nodes, node_iters, opt_tol, status, nodes): the branch and bound takes the place of the bound launch
-    (tri=False only) and fills the int arrays status / nodes at this call's positions (n < 4: proved, 0 nodes).
-    incumbents: one tour per instance; the search is skipped and the branch and bound starts from these."""
-    B = len(checked)
-    out = [None] * B
+    exact = (max_nodes, node_iters, opt_tol): the branch and bound takes the place of the bound launch (tri=False only).
+    incumbents: one tour per instance; the search is skipped and the branch and bound starts from these.  t0: perf_counter
+    where timings['pack'] begins.  -> (results, status, nodes): with exact the branch and bound's int64 status and node
+    count per instance (n < 4: proved, 0 nodes), otherwise None."""
+    pk = _pack(checked, tri, init_tours, lower_bound=lower_bound, incumbents=incumbents)
+    status = nodes = None
     if exact is not None:
-        for k in range(B):
-            if checked[k][2] < 4:
-                exact[3][k], exact[4][k] = 0, 0
-    big = [k for k in range(B) if checked[k][2] >= 4]
-    for k in range(B):
-        if checked[k][2] < 4:
-            Ma, Mw, n = checked[k]
-            tour, cost, lb, feas = _host_small(Ma, Mw, n)
-            out[k] = TourResult(tour, cost, lb if lower_bound else float("nan"), feas, _target(Ma, Mw, tour))
-    if not big:
-        return out
-    # pack, grouped by n so that the penalties, costs and targets are array operations
-    ns = np.array([checked[k][2] for k in big], dtype=np.int32)
-    order = np.argsort(ns, kind="stable")            # launch order: by n (similar work per workgroup)
-    big = [big[k] for k in order]
-    ns = ns[order]
-    sq = ns.astype(np.int64) * (ns - 1) // 2 if tri else ns.astype(np.int64) ** 2   # floats per instance
-    w_off = np.concatenate([[0], np.cumsum(sq)[:-1]]).astype(np.int64)
-    t_off = np.concatenate([[0], np.cumsum(ns)[:-1]]).astype(np.int64)
-    Wflat = np.empty(int(sq.sum()), dtype=np.float32)
-    init = np.full(int(ns.sum()), -1, dtype=np.int32)
-    groups = {}
-    for pos, k in enumerate(big):
-        groups.setdefault(int(ns[pos]), []).append(pos)
-    stacked = {}
-    for n, poss in groups.items():
-        A = np.stack([_edge_mask(checked[big[p]][0]) for p in poss])
-        Mw = np.stack([checked[big[p]][1] for p in poss])
-        W32 = (_penalised_tri if tri else _penalised)(A, Mw)
-        for g, p in enumerate(poss):
-            Wflat[w_off[p]:w_off[p] + sq[p]] = W32[g].reshape(-1)
-            if incumbents is not None:
-                init[t_off[p]:t_off[p] + n] = incumbents[big[p]]
-            elif init_tours is not None and init_tours[big[p]] is not None:
-                it = np.asarray(init_tours[big[p]], dtype=np.int64).reshape(-1)
-                if it.shape[0] != n or not np.array_equal(np.sort(it), np.arange(n)):
-                    raise ValueError("init_tours[%d] is not a permutation of 0..%d" % (big[p], n - 1))
-                init[t_off[p]:t_off[p] + n] = it
-        stacked[n] = (A, Mw)
-    has_init = init_tours is not None and any(t is not None for t in init_tours)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    G = len(big)
+        status, nodes = np.zeros(len(checked), dtype=np.int64), np.zeros(len(checked), dtype=np.int64)
+    if not pk.big:
+        return pk.out, status, nodes
+    dev = _device(device)
     with torch.cuda.device(dev):
-        d_W = torch.from_numpy(Wflat).to(dev)
-        d_woff = torch.from_numpy(w_off).to(dev)
-        d_toff = torch.from_numpy(t_off).to(dev)
-        d_n = torch.from_numpy(ns).to(dev)
-        d_idx = torch.from_numpy(np.ascontiguousarray(index[big])).to(dev)
-        d_init = torch.from_numpy(init).to(dev) if has_init else None
-        d_tours = torch.empty(int(ns.sum()), dtype=torch.int32, device=dev)
-        d_cost = torch.empty(G, dtype=torch.float32, device=dev)
-        d_lb = torch.empty(G, dtype=torch.float64, device=dev)
+        a = _upload(pk, dev, index, bound=True)
         if incumbents is not None:
-            d_tours.copy_(torch.from_numpy(init))
-            d_cost = None   # the root's step then aims at the incumbent's own cost
-        t1, t2, t3, d_stat, d_nodes = _launch_labels(dev, ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost,
-                                                     d_lb, restarts, kicks, seed, lb_iters, chunk, tri, neighbors,
-                                                     lower_bound, exact, search=incumbents is None)
+            a.tours.copy_(torch.from_numpy(pk.init))
+            a = a._replace(cost=None)   # the root's step then aims at the incumbent's own cost
+        t1, t2, t3, d_stat, d_nodes = _launch_labels(dev, a, restarts=restarts, kicks=kicks, seed=seed, lb_iters=lb_iters,
+                                                     chunk=chunk, tri=tri, neighbors=neighbors, lower_bound=lower_bound,
+                                                     exact=exact, search=incumbents is None)
         if exact is not None:
-            exact[3][big] = d_stat.cpu().numpy()
-            exact[4][big] = d_nodes.cpu().numpy()
-        tours = d_tours.cpu().numpy().astype(np.int64)
-        lbs = d_lb.cpu().numpy() if lower_bound or exact is not None else np.full(G, np.nan)
-    for n, poss in groups.items():
-        A, Mw = stacked[n]
-        T = np.stack([tours[t_off[p]:t_off[p] + n] for p in poss])
-        cost = _cycle_cost(Mw, T)
-        nxt = np.roll(T, -1, axis=1)
-        feas = A[np.arange(len(poss))[:, None], T, nxt].all(axis=1)
-        for g, p in enumerate(poss):
-            k = big[p]
-            tour = [int(x) for x in T[g]]
-            out[k] = TourResult(tour, float(cost[g]), float(lbs[p]), bool(feas[g]),
-                                _target(checked[k][0], checked[k][1], tour))
-    if timings is not None:
-        timings["pack"] = timings.get("pack", 0.0) + (t1 - t0)
-        timings["search"] = timings.get("search", 0.0) + (t2 - t1)
-        leg = "bound" if exact is None else "exact"
-        timings[leg] = timings.get(leg, 0.0) + (t3 - t2)
-    return out
+            status[pk.big] = d_stat.cpu().numpy()
+            nodes[pk.big] = d_nodes.cpu().numpy()
+        tours = a.tours.cpu().numpy().astype(np.int64)
+        lbs = a.lb.cpu().numpy() if lower_bound or exact is not None else None
+    _add_time(timings, "pack", t1 - t0)
+    _add_time(timings, "search", t2 - t1)
+    _add_time(timings, "bound" if exact is None else "exact", t3 - t2)
+    return _finish(pk, tours, lbs), status, nodes
+
+
+def _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chunk=1):
+    """label_tours' settings, checked in label_tours' order (None: DEFAULT_* / DEFAULT_*_LARGE): -> ((restarts, kicks,
+    lb_iters) for n <= 128, the same for n 129-256, the branch and bound's (max_nodes, node_iters, opt_tol) or None)."""
+    _check_neighbors(neighbors)
+    bb = None
+    if exact:
+        bb = (DEFAULT_BB_NODES if max_nodes is None else max_nodes, DEFAULT_BB_ITERS, 1e-9)
+        _check_bb(*bb)
+    small = (DEFAULT_RESTARTS if restarts is None else restarts, DEFAULT_KICKS if kicks is None else kicks,
+             DEFAULT_LB_ITERS if lb_iters is None else lb_iters)
+    large = (DEFAULT_RESTARTS_LARGE if restarts is None else restarts,
+             DEFAULT_KICKS_LARGE if kicks is None else kicks, DEFAULT_LB_ITERS_LARGE if lb_iters is None else lb_iters)
+    _check_counts(*large, chunk)
+    _check_counts(*small, chunk)
+    return small, large, bb
+
+
+def _check_chains_fit(restarts, n_big, neighbors):
+    """n_big: the largest n above MAX_N among the instances (0: none), where ``restarts`` chains must fit in LDS."""
+    if n_big and restarts > tri_chains_fit(n_big, neighbors):
+        raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS"
+                         % (restarts, n_big, tri_chains_fit(n_big, neighbors)))
 
 
 def tri_chains_fit(n, neighbors=None):
@@ -401,13 +493,12 @@ def prove_tours(instances, results, max_nodes=DEFAULT_BB_NODES, node_iters=DEFAU
     out = list(results)
     times = {}
     if sel:
-        st, nd = np.zeros(len(sel), dtype=np.int64), np.zeros(len(sel), dtype=np.int64)
-        res = _solve([checked[k] for k in sel], np.arange(len(sel), dtype=np.int64), None, 1, 0, 0, True, device,
-                     root_iters, chunk, times, time.perf_counter(), False,
-                     exact=(max_nodes, node_iters, opt_tol, st, nd), incumbents=[results[k].tour for k in sel])
+        res, status[sel], nodes[sel] = _solve(
+            [checked[k] for k in sel], np.arange(len(sel), dtype=np.int64), tri=False, device=device, lb_iters=root_iters,
+            chunk=chunk, timings=times, t0=time.perf_counter(), exact=(max_nodes, node_iters, opt_tol),
+            incumbents=[results[k].tour for k in sel])
         for j, k in enumerate(sel):
             out[k] = res[j]
-        status[sel], nodes[sel] = st, nd
     _bb_stats(stats, status, nodes, times.get("exact", 0.0))
     return out
 
@@ -429,39 +520,27 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
     bound.  timings gets the launch under 'exact'.
     """
     t0 = time.perf_counter()
-    _check_neighbors(neighbors)
-    bb = None
-    if exact:
-        bb = (DEFAULT_BB_NODES if max_nodes is None else max_nodes, DEFAULT_BB_ITERS, 1e-9,
-              np.full(len(instances), 2, dtype=np.int64), np.zeros(len(instances), dtype=np.int64))
-        _check_bb(*bb[:3])
+    small, large, bb = _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chunk)
+    if bb is not None:
         timings = {} if timings is None else timings
         before = timings.get("exact", 0.0)
-    small = (DEFAULT_RESTARTS if restarts is None else restarts, DEFAULT_KICKS if kicks is None else kicks,
-             DEFAULT_LB_ITERS if lb_iters is None else lb_iters)
-    large = (DEFAULT_RESTARTS_LARGE if restarts is None else restarts,
-             DEFAULT_KICKS_LARGE if kicks is None else kicks, DEFAULT_LB_ITERS_LARGE if lb_iters is None else lb_iters)
-    _check_counts(*large, chunk)
     checked, index = _validate(instances, *small, chunk, index, init_tours, MAX_N_TRI)
-    n_big = max([c[2] for c in checked if c[2] > MAX_N], default=0)
-    if n_big and large[0] > tri_chains_fit(n_big, neighbors):
-        raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS"
-                         % (large[0], n_big, tri_chains_fit(n_big, neighbors)))
+    ns = [c[2] for c in checked]
+    _check_chains_fit(large[0], max([n for n in ns if n > MAX_N], default=0), neighbors)
     out = [None] * len(checked)
-    for tri, (r, k, it) in ((False, small), (True, large)):
-        sel = [i for i, c in enumerate(checked) if (c[2] > MAX_N) == tri]
-        if not sel:
-            continue
-        inits = None if init_tours is None else [init_tours[i] for i in sel]
-        sub = None if bb is None or tri else bb[:3] + (np.zeros(len(sel), dtype=np.int64), np.zeros(len(sel), dtype=np.int64))
-        res = _solve([checked[i] for i in sel], index[sel], inits, r, k, seed, lower_bound, device, it, chunk, timings,
-                     t0 if not tri else time.perf_counter(), tri, exact=sub, neighbors=neighbors)
+    status, nodes = np.full(len(checked), 2, dtype=np.int64), np.zeros(len(checked), dtype=np.int64)
+    for tri, sel in _split(ns):
+        r, k, it = large if tri else small
+        res, st, nd = _solve([checked[i] for i in sel], index[sel], tri=tri, restarts=r, kicks=k, seed=seed,
+                             init_tours=None if init_tours is None else [init_tours[i] for i in sel],
+                             lower_bound=lower_bound, device=device, lb_iters=it, chunk=chunk, timings=timings,
+                             t0=t0 if not tri else time.perf_counter(), exact=None if tri else bb, neighbors=neighbors)
         for i, x in zip(sel, res):
             out[i] = x
-        if sub is not None:
-            bb[3][sel], bb[4][sel] = sub[3], sub[4]
+        if st is not None:
+            status[sel], nodes[sel] = st, nd
     if bb is not None:
-        _bb_stats(stats, bb[3], bb[4], timings.get("exact", 0.0) - before)
+        _bb_stats(stats, status, nodes, timings.get("exact", 0.0) - before)
     return out
 
 
@@ -536,19 +615,10 @@ def metric_closure(matrices, device=None, chunk_bytes=1 << 30):
         return out
     ns = np.array([a.shape[0] for a in mats], dtype=np.int32)
     order = np.argsort(ns, kind="stable")
-    launches = []   # lists of positions in `mats`: one tier each, ascending n, at most chunk_bytes
-    for tier in (order[ns[order] <= CLOSURE_LDS_MAX_N], order[ns[order] > CLOSURE_LDS_MAX_N]):
-        cur, size = [], 0
-        for p in tier:
-            b = 8 * int(ns[p]) ** 2
-            if cur and size + b > chunk_bytes:
-                launches.append(cur)
-                cur, size = [], 0
-            cur.append(int(p))
-            size += b
-        if cur:
-            launches.append(cur)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    # lists of positions in `mats`: one tier each, ascending n, at most chunk_bytes
+    launches = (_byte_chunks(order[ns[order] <= CLOSURE_LDS_MAX_N], ns, chunk_bytes)
+                + _byte_chunks(order[ns[order] > CLOSURE_LDS_MAX_N], ns, chunk_bytes))
+    dev = _device(device)
     with torch.cuda.device(dev):
         st = _lib.current_stream()
         for sel in launches:
@@ -585,8 +655,7 @@ def _close_on_device(graphs, idx, device, timings):
     closed = metric_closure([graphs[i][1] for i in idx], device=device)
     for i, Mw in zip(idx, closed):
         graphs[i] = (graphs[i][0], Mw) + tuple(graphs[i][2:])
-    if timings is not None:
-        timings["closure"] = timings.get("closure", 0.0) + (time.perf_counter() - t0)
+    _add_time(timings, "closure", time.perf_counter() - t0)
 
 
 def _draw_graph(n, connectivity, distances="euc_2D", metric=True, close=True, timings=None):
@@ -614,8 +683,7 @@ def _draw_graph(n, connectivity, distances="euc_2D", metric=True, close=True, ti
     if close and _closes(distances, metric):
         t0 = time.perf_counter()
         Mw = floyd_warshall(Mw)
-        if timings is not None:
-            timings["closure"] = timings.get("closure", 0.0) + (time.perf_counter() - t0)
+        _add_time(timings, "closure", time.perf_counter() - t0)
     permutation = [int(x) for x in np.random.permutation(n)]
     for i, j in zip(permutation, permutation[1:] + permutation[:1]):
         Ma[i, j] = Ma[j, i] = 1

@@ -20,6 +20,7 @@ The host keeps ``n`` and ``m`` (int64): a batch's e_start / v_start are their pr
 flat streams (dataset.draw_streams) and csrc/dataset_build.hip builds, penalises and packs the instances around the
 existing closure, search and bound kernels.
 """
+import collections
 import ctypes
 import os
 import time
@@ -28,8 +29,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import dataset as D
 from .instance_loader import read_graph, route_cost
-from .parallel import stage_instances, stage_layout
+from .parallel import stage_instances, stage_layout, staged_batch
 
 MAX_CSR_ENTRIES = 2 ** 31   # 2 * sum(m) must stay below: CSR positions and edge ids are int32 on the device
 _CHUNK = 1024               # instances per host packing call (bounds the scratch of the one-off preprocessing)
@@ -67,8 +69,7 @@ def preprocess(instances):
     eid = np.empty(2 * int(e0[-1]), dtype=np.int32)
     rowptr = np.empty(int(v0[-1]) + I, dtype=np.int32)
     cost = np.empty(I, dtype=np.float64)
-    for lo in range(0, I, _CHUNK):
-        hi = min(lo + _CHUNK, I)
+    for lo, hi in D._spans(I, _CHUNK):
         # one tspgnn_host_stage_batch call over the chunk with dev = 0: its endpoints, CSR and (float)Mw are the batch's up
         # to the chunk-relative offsets taken off below (the cost column is not used: the fp64 cost is kept instead)
         Mc, Nc, Bc = int(e0[hi] - e0[lo]), int(v0[hi] - v0[lo]), hi - lo
@@ -128,7 +129,135 @@ def _prefix(lens):
     return ends - lens, int(ends[-1]) if len(lens) else 0
 
 
+def _default_device(device):
+    """``device``, or the current HIP device when it is None."""
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceDataset needs an MI355X (no HIP device visible)")
+        device = "cuda:%d" % torch.cuda.current_device()
+    return torch.device(device)
+
+
+def _clock(dev):
+    torch.cuda.synchronize(dev)
+    return time.perf_counter()
+
+
+# ---------------------------------------------------------------------------------------------- the phases of generate
 _GENERATE_KW = ("restarts", "kicks", "lb_iters", "seed", "neighbors", "max_nodes")
+
+# generate's checked arguments: small / large / bb as dataset._label_settings returns them, the search's seed and
+# neighbors, random_w (distances == 'random'), closes (the weights get their metric closure), dev.
+_Settings = collections.namedtuple("_Settings", "small large bb seed neighbors random_w closes dev")
+# One labelled chunk of generate.  pos: its stream positions (int64); nc: their n; c_off / t_off: an instance's first cell
+# in A / Mw and first vertex in tours, with the totals n_cells / n_verts; the device arrays A (uint8 mask), Mw (fp64) and
+# tours (int32); the host arrays m (edges), lb and, with the branch and bound, status / nodes (else None).
+_Chunk = collections.namedtuple("_Chunk", "pos nc c_off t_off n_cells n_verts n_max A Mw tours m lb status nodes")
+
+
+def _generate_settings(samples, nmin, nmax, distances, metric, device, exact, chunk_bytes, solve_kw):
+    """Every check of generate that needs no draw -> _Settings."""
+    unknown = sorted(set(solve_kw) - set(_GENERATE_KW))
+    if unknown:
+        raise TypeError("DeviceDataset.generate: unexpected keyword %s (label_tours' %s)" % (unknown, list(_GENERATE_KW)))
+    if not 4 <= nmin <= nmax <= D.MAX_N_TRI:
+        raise ValueError("DeviceDataset.generate: 4 <= nmin <= nmax <= %d, got nmin=%r nmax=%r" % (D.MAX_N_TRI, nmin, nmax))
+    if samples < 0 or chunk_bytes < 1:
+        raise ValueError("DeviceDataset.generate: samples=%r must be >= 0 and chunk_bytes=%r positive" % (samples, chunk_bytes))
+    if distances not in ("euc_2D", "random"):
+        raise ValueError("distances=%r must be 'euc_2D' or 'random'" % (distances,))
+    small, large, bb = D._label_settings(solve_kw.get("restarts"), solve_kw.get("kicks"), solve_kw.get("lb_iters"),
+                                         solve_kw.get("neighbors"), exact, solve_kw.get("max_nodes"))
+    dev = _default_device(device)
+    if dev.type != "cuda":
+        raise ValueError("DeviceDataset.generate: device=%r: the instances are made by HIP kernels" % str(dev))
+    return _Settings(small, large, bb, solve_kw.get("seed", 0), solve_kw.get("neighbors"), distances == "random",
+                     D._closes(distances, metric), dev)
+
+
+def _plan_chunks(ns, chunk_bytes):
+    """[(tri, stream positions int64)] in launch order: by n, the two size classes apart (as label_tours), each chunk at
+    most chunk_bytes of fp64 matrices."""
+    order = np.argsort(ns, kind="stable")
+    return [(tri, np.array(run, dtype=np.int64)) for tri, sel in D._split(ns[order])
+            for run in D._byte_chunks(order[sel], ns, chunk_bytes)]
+
+
+def _label_chunk(S, tri, pos, cfg, st, times):
+    """One chunk of generate, from the streams ``S`` at positions ``pos``: build the instances, close their weights (the
+    tiers apart), penalise them for the layout ``tri`` and label them.  -> _Chunk.  The seconds go to times['build'],
+    ['closure'], ['search'] and ['bound'] | ['exact'].  The streams' device copies and the search input die with the call."""
+    dev = cfg.dev
+    t0 = _clock(dev)
+    nc = S["n"][pos].astype(np.int64)
+    C, n_max = len(pos), int(nc.max())
+    pairs = nc * (nc - 1) // 2
+    p_off, n_pairs = _prefix(pairs)
+    t_off, n_verts = _prefix(nc)
+    c_off, n_cells = _prefix(nc * nc)
+    w_off, n_floats = _prefix(pairs if tri else nc * nc)
+    d_adj = D._to_device(_segments(S["adj_u"], S["pair_off"][pos], pairs), dev)
+    d_coord = D._to_device(_segments(S["wts"], S["pair_off"][pos], pairs) if cfg.random_w else
+                           _segments(S["pts"], 2 * S["vert_off"][pos], 2 * nc), dev)
+    d_perm = D._to_device(_segments(S["perm"], S["vert_off"][pos], nc), dev)
+    d_conn = D._to_device(S["conn"][pos], dev)
+    tab = np.ascontiguousarray(np.stack([nc, p_off, t_off, c_off], axis=1))
+    d_tab = D._to_device(tab, dev)
+    d_Mw = torch.empty(n_cells, dtype=torch.float64, device=dev)
+    d_A = torch.empty(n_cells, dtype=torch.uint8, device=dev)
+    d_m = torch.empty(C, dtype=torch.int32, device=dev)
+    _lib.call("tspgnn_build_instances", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(d_conn), _lib.ptr(d_adj),
+              _lib.ptr(d_coord), _lib.ptr(d_perm), int(cfg.random_w), C, n_max, n_pairs, n_verts, n_cells,
+              _lib.ptr(d_Mw), _lib.ptr(d_A), _lib.ptr(d_m), st)
+    d_coff, d_n = D._to_device(c_off, dev), D._to_device(nc.astype(np.int32), dev)
+    t1 = _clock(dev)
+    D._add_time(times, "build", t1 - t0)
+    if cfg.closes:   # the tiers apart, as metric_closure: a small instance is closed in LDS
+        cut = int(np.searchsorted(nc, D.CLOSURE_LDS_MAX_N, side="right"))
+        for lo, hi in ((0, cut), (cut, C)):
+            if hi > lo:
+                _lib.call("tspgnn_metric_closure", _lib.ptr(d_Mw), _lib.ptr(d_coff[lo:hi]), _lib.ptr(d_n[lo:hi]),
+                          hi - lo, int(nc[lo:hi].max()), st)
+        t0 = _clock(dev)
+        D._add_time(times, "closure", t0 - t1)
+        t1 = t0
+    ptab = np.ascontiguousarray(np.stack([nc, c_off, w_off], axis=1))
+    d_ptab = D._to_device(ptab, dev)
+    d_W = torch.empty(n_floats, dtype=torch.float32, device=dev)
+    _lib.call("tspgnn_penalise_instances", ptab.ctypes.data, _lib.ptr(d_ptab), _lib.ptr(d_A), _lib.ptr(d_Mw), C,
+              n_max, int(tri), n_cells, n_floats, _lib.ptr(d_W), st)
+    arrays = D.LabelArrays(nc.astype(np.int32), d_W, D._to_device(w_off, dev), D._to_device(t_off, dev), d_n,
+                           D._to_device(pos, dev), d_perm, torch.empty(n_verts, dtype=torch.int32, device=dev),
+                           torch.empty(C, dtype=torch.float32, device=dev),
+                           torch.empty(C, dtype=torch.float64, device=dev))
+    (restarts, kicks, lb_iters), bb = (cfg.large if tri else cfg.small), (None if tri else cfg.bb)
+    t1b, t2, t3, d_stat, d_nodes = D._launch_labels(dev, arrays, restarts=restarts, kicks=kicks, seed=cfg.seed,
+                                                    lb_iters=lb_iters, chunk=D.DEFAULT_CHUNK, tri=tri,
+                                                    neighbors=cfg.neighbors, exact=bb)
+    D._add_time(times, "build", t1b - t1)
+    D._add_time(times, "search", t2 - t1b)
+    D._add_time(times, "bound" if bb is None else "exact", t3 - t2)
+    return _Chunk(pos, nc, c_off, t_off, n_cells, n_verts, n_max, d_A, d_Mw, arrays.tours, d_m.cpu().numpy(),
+                  arrays.lb.cpu().numpy(), None if bb is None else d_stat.cpu().numpy(),
+                  None if bb is None else d_nodes.cpu().numpy())
+
+
+def _summary(n64, chunks, file_cost, cyc, feas, exact, times):
+    """create_dataset's summary dict from the labelled chunks and tspgnn_pack_dataset's per-instance outputs."""
+    I = len(n64)
+    lb = np.full(I, np.nan)
+    status, nodes = np.full(I, 2, dtype=np.int64), np.zeros(I, dtype=np.int64)
+    for c in chunks:
+        lb[c.pos] = c.lb
+        if c.status is not None:
+            status[c.pos], nodes[c.pos] = c.status, c.nodes
+    summary = {"samples": I, "n": n64.copy(), "cost": cyc, "lb": lb, "target": n64 * file_cost, "feasible": feas,
+               "times": times}
+    if exact:
+        summary["proved"], summary["nodes"] = status == 0, nodes
+    summary["gap"] = (cyc - lb) / np.where(cyc > 0, cyc, 1.0)
+    summary["certified_fraction"] = D.certify(summary, 0.02)["fraction"]
+    return summary
 
 
 class DeviceDataset(object):
@@ -147,18 +276,13 @@ class DeviceDataset(object):
     ``device='cpu'`` is plumbing only (host tests): the arrays stay on the host and batch() raises."""
 
     def __init__(self, instances, device=None):
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("DeviceDataset needs an MI355X (no HIP device visible)")
-            device = "cuda:%d" % torch.cuda.current_device()
-        self.device = torch.device(device)
+        self.device = _default_device(device)
         host = preprocess(instances)
         self.n, self.m = host["n"], host["m"]
         I = len(self.n)
         inst = np.stack([self.n, self.m, host["e0"][:-1], host["v0"][:-1]], axis=1).astype(np.int32).reshape(I, 4)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
-        self._inst, self._uv, self._w = up(inst), up(host["uv"]), up(host["w"])
-        self._rowptr, self._eid, self._cost = up(host["rowptr"]), up(host["eid"]), up(host["cost"])
+        self._inst, self._uv, self._w, self._rowptr, self._eid, self._cost = (
+            D._to_device(a, self.device) for a in (inst, host["uv"], host["w"], host["rowptr"], host["eid"], host["cost"]))
         self._init_batching()
 
     def _init_batching(self):
@@ -210,172 +334,58 @@ class DeviceDataset(object):
         file form of Mw, as create_dataset reports it (they differ only when the closing pair (route[-1], route[1]) is no
         edge).  The fp64 weight matrices stay on the device (8 sum n^2 bytes) for
         to_instances()."""
-        from . import dataset as D
         t_begin = time.perf_counter()
-        unknown = sorted(set(solve_kw) - set(_GENERATE_KW))
-        if unknown:
-            raise TypeError("DeviceDataset.generate: unexpected keyword %s (label_tours' %s)" % (unknown, list(_GENERATE_KW)))
-        restarts, kicks, lb_iters = (solve_kw.get(k) for k in ("restarts", "kicks", "lb_iters"))
-        seed, neighbors, max_nodes = solve_kw.get("seed", 0), solve_kw.get("neighbors"), solve_kw.get("max_nodes")
-        if not 4 <= nmin <= nmax <= D.MAX_N_TRI:
-            raise ValueError("DeviceDataset.generate: 4 <= nmin <= nmax <= %d, got nmin=%r nmax=%r" % (D.MAX_N_TRI, nmin, nmax))
-        if samples < 0 or chunk_bytes < 1:
-            raise ValueError("DeviceDataset.generate: samples=%r must be >= 0 and chunk_bytes=%r positive" % (samples, chunk_bytes))
-        if distances not in ("euc_2D", "random"):
-            raise ValueError("distances=%r must be 'euc_2D' or 'random'" % (distances,))
-        D._check_neighbors(neighbors)
-        small = (D.DEFAULT_RESTARTS if restarts is None else restarts, D.DEFAULT_KICKS if kicks is None else kicks,
-                 D.DEFAULT_LB_ITERS if lb_iters is None else lb_iters)
-        large = (D.DEFAULT_RESTARTS_LARGE if restarts is None else restarts,
-                 D.DEFAULT_KICKS_LARGE if kicks is None else kicks, D.DEFAULT_LB_ITERS_LARGE if lb_iters is None else lb_iters)
-        D._check_counts(*large, 1)
-        D._check_counts(*small, 1)
-        bb = None
-        if exact:
-            bb = (D.DEFAULT_BB_NODES if max_nodes is None else max_nodes, D.DEFAULT_BB_ITERS, 1e-9)
-            D._check_bb(*bb)
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("DeviceDataset needs an MI355X (no HIP device visible)")
-            device = "cuda:%d" % torch.cuda.current_device()
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise ValueError("DeviceDataset.generate: device=%r: the instances are made by HIP kernels" % str(dev))
-
+        cfg = _generate_settings(samples, nmin, nmax, distances, metric, device, exact, chunk_bytes, solve_kw)
         t0 = time.perf_counter()
         S = D.draw_streams(nmin, nmax, conn_min, conn_max, samples, distances)
         times = {"draw": time.perf_counter() - t0}
-        ns, I = S["n"], int(samples)
-        n_big = int(ns[ns > D.MAX_N].max(initial=0))
-        if n_big and large[0] > D.tri_chains_fit(n_big, neighbors):
-            raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS"
-                             % (large[0], n_big, D.tri_chains_fit(n_big, neighbors)))
-        random_w = distances == "random"
-        coord = S["wts"] if random_w else S["pts"]
-        closes = D._closes(distances, metric)
-        n64 = ns.astype(np.int64)
-        m = np.zeros(I, dtype=np.int64)
-        lb = np.full(I, np.nan)
-        status, nodes = np.full(I, 2, dtype=np.int64), np.zeros(I, dtype=np.int64)
-        order = np.argsort(ns, kind="stable")   # launch order: by n, the two size classes apart (as label_tours)
-        chunks = []                             # (tri, stream positions) of at most chunk_bytes of fp64 matrices
-        for tri in (False, True):
-            cur, size = [], 0
-            for p in order[(ns[order] > D.MAX_N) == tri]:
-                b = 8 * int(ns[p]) ** 2
-                if cur and size + b > chunk_bytes:
-                    chunks.append((tri, np.array(cur, dtype=np.int64)))
-                    cur, size = [], 0
-                cur.append(int(p))
-                size += b
-            if cur:
-                chunks.append((tri, np.array(cur, dtype=np.int64)))
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        clock = lambda: (torch.cuda.synchronize(dev), time.perf_counter())[1]
-        add = lambda key, dt: times.__setitem__(key, times.get(key, 0.0) + dt)
-        kept = []   # per chunk: positions, n, cell offsets, tour offsets, device A, Mw, tours
-        with torch.cuda.device(dev):
+        ns = S["n"]
+        D._check_chains_fit(cfg.large[0], int(ns[ns > D.MAX_N].max(initial=0)), cfg.neighbors)
+        with torch.cuda.device(cfg.dev):
             st = _lib.current_stream()
-            for tri, pos in chunks:
-                t0 = clock()
-                nc = n64[pos]
-                C, n_max = len(pos), int(nc.max())
-                pairs = nc * (nc - 1) // 2
-                p_off, n_pairs = _prefix(pairs)
-                t_off, n_verts = _prefix(nc)
-                c_off, n_cells = _prefix(nc * nc)
-                w_off, n_floats = _prefix(pairs if tri else nc * nc)
-                d_adj = up(_segments(S["adj_u"], S["pair_off"][pos], pairs))
-                d_coord = up(_segments(coord, S["pair_off"][pos], pairs) if random_w else
-                             _segments(coord, 2 * S["vert_off"][pos], 2 * nc))
-                d_perm = up(_segments(S["perm"], S["vert_off"][pos], nc))
-                d_conn = up(S["conn"][pos])
-                tab = np.ascontiguousarray(np.stack([nc, p_off, t_off, c_off], axis=1))
-                d_tab = up(tab)
-                d_Mw = torch.empty(n_cells, dtype=torch.float64, device=dev)
-                d_A = torch.empty(n_cells, dtype=torch.uint8, device=dev)
-                d_m = torch.empty(C, dtype=torch.int32, device=dev)
-                _lib.call("tspgnn_build_instances", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(d_conn), _lib.ptr(d_adj),
-                          _lib.ptr(d_coord), _lib.ptr(d_perm), int(random_w), C, n_max, n_pairs, n_verts, n_cells,
-                          _lib.ptr(d_Mw), _lib.ptr(d_A), _lib.ptr(d_m), st)
-                d_coff, d_n = up(c_off), up(nc.astype(np.int32))
-                t1 = clock()
-                add("build", t1 - t0)
-                if closes:   # the tiers apart, as metric_closure: a small instance is closed in LDS
-                    cut = int(np.searchsorted(nc, D.CLOSURE_LDS_MAX_N, side="right"))
-                    for lo, hi in ((0, cut), (cut, C)):
-                        if hi > lo:
-                            _lib.call("tspgnn_metric_closure", _lib.ptr(d_Mw), _lib.ptr(d_coff[lo:hi]), _lib.ptr(d_n[lo:hi]),
-                                      hi - lo, int(nc[lo:hi].max()), st)
-                    t0 = clock()
-                    add("closure", t0 - t1)
-                    t1 = t0
-                ptab = np.ascontiguousarray(np.stack([nc, c_off, w_off], axis=1))
-                d_ptab = up(ptab)
-                d_W = torch.empty(n_floats, dtype=torch.float32, device=dev)
-                _lib.call("tspgnn_penalise_instances", ptab.ctypes.data, _lib.ptr(d_ptab), _lib.ptr(d_A), _lib.ptr(d_Mw), C,
-                          n_max, int(tri), n_cells, n_floats, _lib.ptr(d_W), st)
-                d_tours = torch.empty(n_verts, dtype=torch.int32, device=dev)
-                d_cost = torch.empty(C, dtype=torch.float32, device=dev)
-                d_lb = torch.empty(C, dtype=torch.float64, device=dev)
-                r, k, it = large if tri else small
-                sub = None if bb is None or tri else bb
-                t1b, t2, t3, d_stat, d_nodes = D._launch_labels(
-                    dev, nc.astype(np.int32), d_W, up(w_off), up(t_off), d_n, up(pos), d_perm, d_tours, d_cost, d_lb, r, k,
-                    seed, it, D.DEFAULT_CHUNK, tri, neighbors, True, sub)
-                add("build", t1b - t1)
-                add("search", t2 - t1b)
-                add("bound" if sub is None else "exact", t3 - t2)
-                m[pos] = d_m.cpu().numpy()
-                lb[pos] = d_lb.cpu().numpy()
-                if sub is not None:
-                    status[pos], nodes[pos] = d_stat.cpu().numpy(), d_nodes.cpu().numpy()
-                kept.append((pos, nc, c_off, t_off, n_cells, n_verts, n_max, d_A, d_Mw, d_tours))
-                del d_W, d_adj, d_coord
-
-            # every m is known: the dataset's prefix sums, then one packing launch per chunk into the final arrays
-            t0 = clock()
-            check_size(m.sum())
-            e0, M = _prefix(m)
-            v0, N = _prefix(n64)
-            inst = np.stack([n64, m, e0, v0], axis=1).astype(np.int32).reshape(I, 4)
-            d_uv = torch.empty((M, 2), dtype=torch.int32, device=dev)
-            d_w = torch.empty(M, dtype=torch.float32, device=dev)
-            d_eid = torch.empty(2 * M, dtype=torch.int32, device=dev)
-            d_rowptr = torch.empty(N + I, dtype=torch.int32, device=dev)
-            d_rc = torch.empty(I, dtype=torch.float64, device=dev)
-            d_fc = torch.empty(I, dtype=torch.float64, device=dev)
-            d_cyc = torch.empty(I, dtype=torch.float64, device=dev)
-            d_feas = torch.empty(I, dtype=torch.int32, device=dev)
-            tours = np.empty(N, dtype=np.int32)
-            matrices = []
-            for pos, nc, c_off, t_off, n_cells, n_verts, n_max, d_A, d_Mw, d_tours in kept:
-                tab = np.ascontiguousarray(np.stack([nc, c_off, t_off, m[pos], e0[pos], v0[pos], pos], axis=1))
-                d_tab = up(tab)
-                _lib.call("tspgnn_pack_dataset", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(d_A), _lib.ptr(d_Mw),
-                          _lib.ptr(d_tours), len(pos), n_max, n_cells, n_verts, M, N + I, I, _lib.ptr(d_uv), _lib.ptr(d_w),
-                          _lib.ptr(d_rowptr), _lib.ptr(d_eid), _lib.ptr(d_rc), _lib.ptr(d_fc), _lib.ptr(d_cyc),
-                          _lib.ptr(d_feas), st)
-                flat = d_tours.cpu().numpy()
-                tours[np.arange(n_verts, dtype=np.int64) + np.repeat(v0[pos] - t_off, nc)] = flat
-                matrices.append((pos, c_off, d_Mw))
-            kept = None
-            ds = cls._adopt(dev, n64, m, up(inst), d_uv, d_w, d_rowptr, d_eid, d_rc)
-            file_cost, cyc, feas = d_fc.cpu().numpy(), d_cyc.cpu().numpy(), d_feas.cpu().numpy().astype(bool)
-            add("pack", clock() - t0)
+            chunks = [_label_chunk(S, tri, pos, cfg, st, times) for tri, pos in _plan_chunks(ns, chunk_bytes)]
+            t0 = _clock(cfg.dev)
+            ds, file_cost, cyc, feas = cls._from_chunks(chunks, ns.astype(np.int64), cfg.dev, st)
+            D._add_time(times, "pack", _clock(cfg.dev) - t0)
         if not feas.all():
             raise Exception("Unsolvable")
-        ds.tours = (tours, np.concatenate([v0, [N]]).astype(np.int64))
-        ds._matrices = matrices
-        summary = {"samples": I, "n": n64.copy(), "cost": cyc, "lb": lb, "target": n64 * file_cost, "feasible": feas,
-                   "times": times}
-        if exact:
-            summary["proved"], summary["nodes"] = status == 0, nodes
-        summary["gap"] = (cyc - lb) / np.where(cyc > 0, cyc, 1.0)
-        summary["certified_fraction"] = D.certify(summary, 0.02)["fraction"]
+        summary = _summary(ds.n, chunks, file_cost, cyc, feas, exact, times)
         times["total"] = time.perf_counter() - t_begin
         ds.summary = summary
         return ds
+
+    @classmethod
+    def _from_chunks(cls, chunks, n64, dev, st):
+        """generate's last phase, once every chunk's edge counts are known: the dataset's prefix sums, then one
+        tspgnn_pack_dataset launch per chunk into the final arrays.  -> (the dataset, with ``tours`` and the chunks' fp64
+        matrices; then per instance: the route cost on the file form of Mw, the cycle cost, the tour's feasibility)."""
+        I = len(n64)
+        m = np.zeros(I, dtype=np.int64)
+        for c in chunks:
+            m[c.pos] = c.m
+        check_size(m.sum())
+        e0, M = _prefix(m)
+        v0, N = _prefix(n64)
+        inst = np.stack([n64, m, e0, v0], axis=1).astype(np.int32).reshape(I, 4)
+        d_uv = torch.empty((M, 2), dtype=torch.int32, device=dev)
+        d_w = torch.empty(M, dtype=torch.float32, device=dev)
+        d_eid = torch.empty(2 * M, dtype=torch.int32, device=dev)
+        d_rowptr = torch.empty(N + I, dtype=torch.int32, device=dev)
+        d_rc, d_fc, d_cyc = (torch.empty(I, dtype=torch.float64, device=dev) for _ in range(3))
+        d_feas = torch.empty(I, dtype=torch.int32, device=dev)
+        tours = np.empty(N, dtype=np.int32)
+        for c in chunks:
+            tab = np.ascontiguousarray(np.stack([c.nc, c.c_off, c.t_off, m[c.pos], e0[c.pos], v0[c.pos], c.pos], axis=1))
+            d_tab = D._to_device(tab, dev)
+            _lib.call("tspgnn_pack_dataset", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(c.A), _lib.ptr(c.Mw),
+                      _lib.ptr(c.tours), len(c.pos), c.n_max, c.n_cells, c.n_verts, M, N + I, I, _lib.ptr(d_uv),
+                      _lib.ptr(d_w), _lib.ptr(d_rowptr), _lib.ptr(d_eid), _lib.ptr(d_rc), _lib.ptr(d_fc), _lib.ptr(d_cyc),
+                      _lib.ptr(d_feas), st)
+            tours[np.arange(c.n_verts, dtype=np.int64) + np.repeat(v0[c.pos] - c.t_off, c.nc)] = c.tours.cpu().numpy()
+        ds = cls._adopt(dev, n64, m, D._to_device(inst, dev), d_uv, d_w, d_rowptr, d_eid, d_rc)
+        ds.tours = (tours, np.concatenate([v0, [N]]).astype(np.int64))
+        ds._matrices = [(c.pos, c.c_off, c.Mw) for c in chunks]
+        return ds, d_fc.cpu().numpy(), d_cyc.cpu().numpy(), d_feas.cpu().numpy().astype(bool)
 
     def to_instances(self):
         """A generated dataset as the list of (np.triu(Ma), Mw, route) DeviceDataset(...) and write_graph take, downloaded
@@ -464,14 +474,12 @@ class DeviceDataset(object):
     # ------------------------------------------------------------------ batches
     def _plan_for(self, e_start, v_start, M):
         """The one-launch loop's work plan for a block structure, built once (device tensor, meta) or (None, None)."""
-        from .graphnn import choose_loop_plan, loop_enabled
+        from .graphnn import device_loop_plan, loop_enabled
         if not loop_enabled() or M == 0:
             return None, None
         key = (e_start.tobytes(), v_start.tobytes())
         if key not in self._plans:
-            grid = torch.cuda.get_device_properties(self.device).multi_processor_count
-            grid -= grid % 8
-            built = choose_loop_plan(e_start.astype(np.int64), v_start.astype(np.int64), grid)
+            built = device_loop_plan(e_start.astype(np.int64), v_start.astype(np.int64), self.device)
             if len(self._plans) >= _PLAN_CACHE:
                 self._plans.clear()
             self._plans[key] = (None, None) if built is None else (torch.from_numpy(built[0]).to(self.device), built[1])
@@ -483,8 +491,6 @@ class DeviceDataset(object):
         ``n_vertices``, ``n_edges`` (int64).  ``out``: a batch this dataset returned earlier for index lists of the same
         shape (the same instance sizes in the same order): the kernel writes into THAT batch's buffer, so a graph captured
         on it serves the new batch; ValueError when the shapes differ."""
-        from .graphnn import DeviceAdjacency
-        from .model import DeviceBatch
         idx = np.asarray(indices, dtype=np.int64).reshape(-1)
         e_start, v_start, M, N, labels = plan_batch(self.n, self.m, idx)
         B = idx.size
@@ -499,21 +505,9 @@ class DeviceDataset(object):
             plan, meta = self._plan_for(e_start, v_start, M)
             offsets, nbytes, total = stage_layout(M, N, B, 0 if plan is None else plan.numel())
             buf = torch.empty(total, dtype=torch.uint8, device=self.device)
-
-            def view(k, dtype, shape):
-                o, nb = offsets[k], nbytes[k]
-                return buf[o:o + nb].view(dtype).view(*shape)
-            uv = view(0, torch.int32, (M, 2))
-            csr = (torch.arange(0, 2 * M + 1, 2, dtype=torch.int32, device=self.device), uv.view(-1), None)
-            csr_t = (view(2, torch.int32, (N + 1,)), view(1, torch.int32, (2 * M,)), None)
-            adj = DeviceAdjacency((M, N), self.device, csr, csr_t, uv=uv)
+            b = staged_batch(buf, offsets, nbytes, M, N, B, meta)
             if plan is not None:
-                slot = view(7, torch.int32, (plan.numel(),))
-                slot.copy_(plan, non_blocking=True)
-                adj.loop_plan = (slot,) + tuple(meta)
-            b = DeviceBatch()
-            b.adj, b.M, b.N, b.B = adj, M, N, B
-            b.WC, b.labels, b.seg = view(3, torch.float32, (M, 2)), view(4, torch.float32, (B,)), view(5, torch.int32, (B + 1,))
+                b.adj.loop_plan[0].copy_(plan, non_blocking=True)
             b._dataset, b._buf, b._offsets, b._blocks = self, buf, offsets, (e_start, v_start)
         self.gather(idx, dev, target_cost, b._buf, b._offsets)
         b.T = int(time_steps)

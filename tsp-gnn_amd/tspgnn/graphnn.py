@@ -136,6 +136,13 @@ def choose_loop_plan(e_start, v_start, grid):
     return None
 
 
+def device_loop_plan(e_start, v_start, device):
+    """choose_loop_plan at the grid of ``device``: its compute units, rounded down to a multiple of 8."""
+    grid = torch.cuda.get_device_properties(device).multi_processor_count
+    grid -= grid % 8
+    return choose_loop_plan(e_start, v_start, grid)
+
+
 def _make_loop_plan(ev, device):
     """Work plan of the one-launch T-step loop for a SparseEV on a GPU: built where the batch is packed (host side, cached
     per block structure), uploaded with the adjacency -- a captured forward then serves any batch copied into its buffers
@@ -149,9 +156,7 @@ def _make_loop_plan(ev, device):
         blocks = loop_plan.block_structure(ev.uv, ev.shape[1])
         if blocks is None:
             return None
-    grid = torch.cuda.get_device_properties(dev).multi_processor_count
-    grid -= grid % 8
-    built = choose_loop_plan(blocks[0], blocks[1], grid)
+    built = device_loop_plan(blocks[0], blocks[1], dev)
     if built is None:
         return None
     plan, meta = built

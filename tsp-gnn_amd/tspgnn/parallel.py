@@ -200,6 +200,28 @@ def stage_layout(M, N, B, plan_ints):
     return off, sizes, max(pos, 256)
 
 
+def staged_batch(buf, offsets, nbytes, M, N, B, plan_meta=None):
+    """The DeviceBatch whose arrays are views of the staged uint8 device buffer ``buf`` at stage_layout's ``offsets`` /
+    ``nbytes``: endpoints, both CSRs, (weight, cost) pairs, labels and segment offsets.  plan_meta: choose_loop_plan's meta
+    when the layout has a work plan slot; the batch's adjacency then carries the slot (to be filled by the caller)."""
+    from .graphnn import DeviceAdjacency
+    from .model import DeviceBatch
+
+    def view(k, dtype, shape):
+        o, nb = offsets[k], nbytes[k]
+        return buf[o:o + nb].view(dtype).view(*shape)
+    uv = view(0, torch.int32, (M, 2))
+    csr = (torch.arange(0, 2 * M + 1, 2, dtype=torch.int32, device=buf.device), uv.view(-1), None)
+    csr_t = (view(2, torch.int32, (N + 1,)), view(1, torch.int32, (2 * M,)), None)
+    adj = DeviceAdjacency((M, N), buf.device, csr, csr_t, uv=uv)
+    if plan_meta is not None:
+        adj.loop_plan = (view(7, torch.int32, (nbytes[7] // 4,)),) + tuple(plan_meta)
+    b = DeviceBatch()
+    b.adj, b.M, b.N, b.B = adj, M, N, B
+    b.WC, b.labels, b.seg = view(3, torch.float32, (M, 2)), view(4, torch.float32, (B,)), view(5, torch.int32, (B + 1,))
+    return b
+
+
 def stage_instances(instances, dev, target_cost, M, N, stage_ptr, offsets):
     """tspgnn_host_stage_batch over a list of (Ma, Mw, route): everything Session.prepare would upload, written into the
     buffer at ``stage_ptr`` (the GIL is released inside the call).  Raises like create_batch on malformed instances."""
@@ -262,8 +284,7 @@ class BatchStager(object):
     (round 4) at 9-17 % behind the resident-batch rate at C2, the one packer thread nearly as slow as the forward itself."""
 
     def __init__(self, sess, template_instances, time_steps, dev=0.02, target_cost=None, slots=3):
-        from .graphnn import DeviceAdjacency, choose_loop_plan, loop_enabled
-        from .model import DeviceBatch
+        from .graphnn import device_loop_plan, loop_enabled
         if sess.device.type != "cuda":
             raise RuntimeError("BatchStager needs a GPU session (pinned staging, asynchronous copies)")
         self.sess, self.T, self.dev, self.target_cost = sess, int(time_steps), dev, target_cost
@@ -273,9 +294,8 @@ class BatchStager(object):
         B, M, N = len(self.sizes), int(sum(n_edges)), int(sum(self.sizes))
         plan, self.plan_meta = None, None
         if loop_enabled() and M > 0:
-            grid = torch.cuda.get_device_properties(sess.device).multi_processor_count
-            grid -= grid % 8
-            built = choose_loop_plan(np.concatenate([[0], np.cumsum(n_edges)]), np.concatenate([[0], np.cumsum(self.sizes)]), grid)
+            built = device_loop_plan(np.concatenate([[0], np.cumsum(n_edges)]), np.concatenate([[0], np.cumsum(self.sizes)]),
+                                     sess.device)
             if built is not None:
                 plan, self.plan_meta = built
         self.offsets, self.nbytes, total = stage_layout(M, N, B, 0 if plan is None else plan.size)
@@ -287,20 +307,8 @@ class BatchStager(object):
                 p[self.offsets[7]:self.offsets[7] + 4 * plan.size].view(torch.int32).copy_(torch.from_numpy(plan))
         self.dev_stage = [torch.empty(total, dtype=torch.uint8, device=sess.device) for _ in range(self.slots)]
         self.dev_buf = torch.empty(total, dtype=torch.uint8, device=sess.device)
-
-        def view(k, dtype, shape):
-            o, nb = self.offsets[k], self.nbytes[k]
-            return self.dev_buf[o:o + nb].view(dtype).view(*shape)
-        uv = view(0, torch.int32, (M, 2))
-        csr = (torch.arange(0, 2 * M + 1, 2, dtype=torch.int32, device=sess.device), uv.view(-1), None)
-        csr_t = (view(2, torch.int32, (N + 1,)), view(1, torch.int32, (2 * M,)), None)
-        adj = DeviceAdjacency((M, N), sess.device, csr, csr_t, uv=uv)
-        if plan is not None:
-            adj.loop_plan = (view(7, torch.int32, (plan.size,)),) + tuple(self.plan_meta)
-        b = DeviceBatch()
-        b.adj, b.M, b.N, b.B, b.T = adj, M, N, B, self.T
-        b.WC, b.labels, b.seg = view(3, torch.float32, (M, 2)), view(4, torch.float32, (B,)), view(5, torch.int32, (B + 1,))
-        self.batch = b
+        self.batch = staged_batch(self.dev_buf, self.offsets, self.nbytes, M, N, B, self.plan_meta)
+        self.batch.T = self.T
         self.load(template_instances)       # the buffer holds a valid batch from the start (capture_forward runs it)
 
     def load(self, instances):
