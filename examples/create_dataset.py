@@ -2,7 +2,7 @@
 
     python examples/create_dataset.py -path instances/train -samples 32768 -nmin 20 -nmax 40 [-seed 42]
         [-distances euc_2D|random] [--metric] [-cmin 1] [-cmax 1] [--require-certified DEV] [-exact] [-neighbors K]
-        [-closure host|device]
+        [-closure host|device] [-writer host|device]
 
 Unlike the reference's __main__, -seed is applied: random and np.random are seeded with it before the first draw, so
 the instance stream is the one the reference's train.py gets after its own seeding (train.py seeds both the same way).
@@ -12,6 +12,7 @@ and reports how many it proved within its node budget.
 -neighbors K restricts the search's descent to moves between K nearest neighbours (1..32; tspgnn.label_tours).
 --metric, as in the reference, turns the metric closure OFF for random distances.
 -closure device takes that closure on the GPU (tspgnn.metric_closure) instead of in NumPy: the same files, byte for byte.
+-writer device formats the .graph files on the GPU instead of in write_graph: the same files, byte for byte.
 """
 import argparse
 import os
@@ -44,13 +45,15 @@ def main():
                    help="candidate-list descent over the K nearest neighbours (1..32; default: the full scan)")
     p.add_argument("-closure", default="host", choices=("host", "device"),
                    help="where the metric closure of random distances is taken (the files are the same bytes)")
+    p.add_argument("-writer", default="host", choices=("host", "device"),
+                   help="who formats the .graph files: write_graph, or the GPU (the files are the same bytes)")
     a = p.parse_args()
     random.seed(a.seed)
     np.random.seed(a.seed)
     print("Creating {} instances".format(a.samples), flush=True)
     s = dataset.create_dataset(a.path, a.nmin, a.nmax, a.cmin, a.cmax, samples=a.samples, distances=a.distances,
                                metric=a.metric, require_certified=a.require_certified, verbose=True, exact=a.exact,
-                               neighbors=a.neighbors, closure=a.closure)
+                               neighbors=a.neighbors, closure=a.closure, writer=a.writer)
     t = s["times"]
     if "closure" in t:
         print("closure (%s) %.2f s" % (a.closure, t["closure"]), flush=True)

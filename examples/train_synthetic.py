@@ -11,7 +11,8 @@ cost (1-dev) and (1+dev) times its tour cost and labels 0/1, exactly like Instan
 (instance_loader.py:16-27,82-87).  The "tour" is the planted Hamiltonian cycle, not the optimum, so the
 accuracy printed here says nothing about TSP -- the point is the call sequence and the loss going down.
 With -generate SAMPLES the instances are create_dataset's (seeded with -seed) and the tours are the GPU search's labels:
-DeviceDataset.generate(SAMPLES, 20, 40), no matrix on the host and no file.
+DeviceDataset.generate(SAMPLES, 20, 40), no matrix on the host and no file; -write_dir PATH also writes them as .graph
+files (DeviceDataset.write_directory, formatted on the GPU) for the reference's train.py / test.py to read.
 """
 import argparse
 import os
@@ -46,7 +47,11 @@ if __name__ == '__main__':
     p.add_argument('-generate', default=0, type=int, metavar='SAMPLES',
                    help='train on DeviceDataset.generate(SAMPLES, 20, 40): the instances drawn from the reference\'s stream, '
                         'labelled and packed on the GPU, instead of a directory or synthetic instances')
+    p.add_argument('-write_dir', default=None, metavar='PATH',
+                   help='with -generate: also write the generated instances to PATH as .graph files, formatted on the GPU')
     a = p.parse_args()
+    if a.write_dir is not None and not a.generate:
+        p.error('-write_dir needs -generate SAMPLES')
     rng = np.random.RandomState(a.seed)
     loader = None
     if a.instances is not None:
@@ -65,6 +70,10 @@ if __name__ == '__main__':
         print('generated {} instances in {:.2f} s ({}); certified at dev 0.02: {:.3f}'.format(
             a.generate, t['total'], ', '.join('{} {:.3f}'.format(k, v) for k, v in t.items() if k != 'total'),
             dataset.summary['certified_fraction']), flush=True)
+        if a.write_dir is not None:
+            w = dataset.write_directory(a.write_dir)
+            print('wrote {} bytes of .graph files to {} ({})'.format(
+                w['bytes'], a.write_dir, ', '.join('{} {:.3f}'.format(k, v) for k, v in w['times'].items())), flush=True)
     elif a.device_dataset:   # the same instances every epoch, shuffled per epoch like InstanceLoader.reset()
         dataset = DeviceDataset.from_directory(a.instances) if a.instances is not None else DeviceDataset(
             [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize * a.batches)])

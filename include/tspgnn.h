@@ -947,6 +947,46 @@ int tspgnn_pack_dataset(const long long* tab, const long long* d_tab, const unsi
                         int32_t* eid, double* cost, double* file_cost, double* cycle_cost, int32_t* feasible,
                         void* stream);
 
+/* ------------------------------------------------------------------ ".graph" text made on the device (csrc/graph_text.hip)
+ *
+ * Python's repr(float) of count doubles: the shortest digit string that reads back to the same bits (of those the one
+ * nearest the value, a tie to the even digit), positional for 1e-4 <= |x| < 1e16 with ".0" on integers, d[.ddd]e+XX /
+ * e-XX otherwise, and "0.0", "-0.0", "inf", "-inf", "nan".  Value i goes to text[24 i .. 24 i + len[i]), len[i] <= 24; the
+ * rest of its 24 bytes is left alone.  Integer arithmetic only, the same routine on host and device.
+ * tspgnn_host_f64_repr takes HOST pointers and launches nothing; tspgnn_f64_repr takes device arrays (one thread per
+ * value).  NULL or count < 0: TSPGNN_EINVAL before any launch; count == 0: no-op.
+ */
+int tspgnn_host_f64_repr(const double* x, long long count, char* text, unsigned char* len);
+int tspgnn_f64_repr(const double* x, long long count, char* text, unsigned char* len, void* stream);
+
+/*
+ * The bytes tspgnn.write_graph(np.triu(A), Mw, path, route=tour) writes for each of count instances, one 256-thread
+ * workgroup per instance, 4 <= n <= n_max <= 256.  (A, Mw, tours) as tspgnn_pack_dataset takes them: A uint8[n][n] and Mw
+ * double[n][n] at cell c0, the tour of n int32 entries at t0; n_cells and n_tour are the extents.  Only the cells j > i of
+ * A are read: a pair is set when its byte is non-zero, every other cell prints "0".  tab is passed twice, on the HOST
+ * (every row is checked against the extents before anything launches) and on the device (d_tab).
+ *
+ * tspgnn_graph_text_sizes: tab[count][3] = n, c0, t0 -> bytes[i] (device) = the exact length of file i.  A tour entry
+ * outside [0, n) counts as one character; tspgnn_graph_text_write refuses such an instance.
+ *
+ * tspgnn_graph_text_write: tab[count][4] = n, c0, t0, b0 -> file i in text[b0 .. b0 + bytes[i]), where bytes is the
+ * DEVICE array the sizes launch filled and host_bytes its copy on the HOST: the host check of row i is b0 >= 0 and
+ * b0 + host_bytes[i] <= n_text (the kernel reads bytes, never host_bytes).  Every store is guarded by the instance's
+ * extent.  status[i] (device) = 0 written; 1 the kernel's own size differs from bytes[i], nothing written; 2 a tour entry
+ * outside [0, n), nothing written.  Both passes format the weights (the sizes pass keeps only the lengths): no scratch
+ * table travels between them.
+ *
+ * TSPGNN_EINVAL before any launch: a NULL pointer, count < 0, n_max outside [4, 256], an n outside [4, n_max], an
+ * offset that leaves its array.  count == 0: no-op.
+ */
+int tspgnn_graph_text_sizes(const long long* tab, const long long* d_tab, const unsigned char* A, const double* Mw,
+                            const int32_t* tours, int count, int n_max, long long n_cells, long long n_tour,
+                            long long* bytes, void* stream);
+int tspgnn_graph_text_write(const long long* tab, const long long* d_tab, const unsigned char* A, const double* Mw,
+                            const int32_t* tours, int count, int n_max, long long n_cells, long long n_tour,
+                            const long long* bytes, const long long* host_bytes, char* text, long long n_text,
+                            int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ host-side batch packing (no GPU work) */
 
 /*

@@ -4,6 +4,7 @@ at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per sha
 
     python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
         [--exact [--max-nodes N]] [--neighbors K] [--distances euc_2D|random] [--closure host|device] [--resident]
+        [--writer host|device|both]
 
 Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
 --exact labels with the branch and bound (label_tours(exact=True), n <= 128) and adds the proved fraction, the nodes per
@@ -15,6 +16,11 @@ instance (p50 / p90 / max) and the seconds of that launch; bound_s is then 0.
 --resident times, per shape, the two routes to a device-resident dataset, alternated twice in one process: "host" is
 draw_instances -> label_tours -> DeviceDataset(...), "generate" is DeviceDataset.generate; one JSON line per run with the
 wall seconds from the seeding to the synchronised dataset ("total_s") and the stages each route can name.
+--writer says who formats the .graph files, as create_dataset(writer=...): "host" is the write_graph loop, "device" the
+GPU writer (graph_text.write_instances, the call create_dataset makes) and "both" alternates the two twice over the same
+labelled instances; a device run adds one JSON line with its wall seconds ("total_s") and its stages (upload, the sizes
+and write launches, their sum "format_s", the download, the file writes).  With --resident every generated dataset is also written twice by DeviceDataset.write_directory and
+twice by to_instances() + write_graph, alternated, one JSON line each ("writer").
 """
 import argparse
 import json
@@ -31,11 +37,70 @@ sys.path.insert(0, os.path.join(ROOT, "tsp-gnn_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from tspgnn import dataset  # noqa: E402
+from tspgnn import dataset, graph_text  # noqa: E402
 from tspgnn.device_dataset import DeviceDataset  # noqa: E402
 
 SHAPES = {"train": (2 ** 15, 20, 40), "test": (2 ** 10, 20, 40), "n80": (2 ** 10, 80, 80), "n200": (2 ** 10, 200, 200),
           "n256": (2 ** 10, 256, 256)}
+
+
+def _scratch_dir(a):
+    out = a.out or tempfile.mkdtemp(prefix="dsbench_")
+    os.makedirs(out, exist_ok=True)
+    return out
+
+
+def _stage_columns(stages):
+    """The device writer's stages as JSON columns; its two launches are named for their kernels."""
+    names = {"sizes": "sizes_kernel_s", "write": "write_kernel_s"}
+    return {names.get(k, k + "_s"): round(v, 3) for k, v in stages.items()}
+
+
+def write_files(a, name, samples, instances):
+    """The files of one labelled shape by the writer(s) of --writer: -> seconds of the first run (the "write_s" column);
+    one JSON line per device run, and per run at all with --writer both."""
+    order = {"host": ["host"], "device": ["device"], "both": ["host", "device"] * 2}[a.writer]
+    first = None
+    for rep, writer in enumerate(order):
+        out = _scratch_dir(a)
+        stages = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if writer == "host":
+            for i, (Ma, Mw, tour) in enumerate(instances):
+                dataset.write_graph(np.triu(Ma), Mw, filepath=os.path.join(out, "%d.graph" % i), route=tour)
+        else:
+            graph_text.write_instances(out, instances, torch.device("cuda", torch.cuda.current_device()), times=stages)
+        seconds = time.perf_counter() - t0
+        first = seconds if first is None else first
+        if writer == "device" or a.writer == "both":
+            print(json.dumps({"shape": name, "samples": samples, "writer": writer, "rep": rep // 2,
+                              "total_s": round(seconds, 3), **_stage_columns(stages)}), flush=True)
+        if a.out is None:
+            shutil.rmtree(out)
+    return first
+
+
+def write_resident(a, name, samples, ds):
+    """A generated dataset to files: write_directory against to_instances() + write_graph, alternated twice."""
+    for rep in range(2):
+        for writer in ("to_instances+write_graph", "write_directory"):
+            out = _scratch_dir(a)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if writer == "write_directory":
+                report = ds.write_directory(out)
+                stages = dict(_stage_columns(report["times"]), bytes=report["bytes"])
+            else:
+                instances = ds.to_instances()
+                t1 = time.perf_counter()
+                for i, (Ma, Mw, tour) in enumerate(instances):
+                    dataset.write_graph(Ma, Mw, filepath=os.path.join(out, "%d.graph" % i), route=tour)
+                stages = {"to_instances_s": round(t1 - t0, 3), "write_graph_s": round(time.perf_counter() - t1, 3)}
+            print(json.dumps({"shape": name, "samples": samples, "writer": writer, "rep": rep,
+                              "total_s": round(time.perf_counter() - t0, 3), **stages}), flush=True)
+            if a.out is None:
+                shutil.rmtree(out)
 
 
 def resident(a, name, samples, nmin, nmax):
@@ -71,6 +136,8 @@ def resident(a, name, samples, nmin, nmax):
                               "distances": a.distances, **({} if a.neighbors is None else {"neighbors": a.neighbors}),
                               "total_s": round(total, 3), **r3(stages), "edges": int(ds.m.sum()),
                               "certified_0.02": round(certified, 4)}), flush=True)
+            if route == "generate" and rep == 1 and not a.no_write:
+                write_resident(a, name, samples, ds)
             del ds
 
 
@@ -89,6 +156,8 @@ def main():
     ap.add_argument("--samples", type=int, default=0, help="override the instance count of every shape")
     ap.add_argument("--resident", action="store_true",
                     help="time the host route and DeviceDataset.generate to a device-resident dataset, alternated twice")
+    ap.add_argument("--writer", default="host", choices=("host", "device", "both"),
+                    help="who formats the .graph files (create_dataset's writer=); both: alternated twice")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
     a = ap.parse_args()
@@ -132,14 +201,7 @@ def main():
         lb_iters = a.lb_iters or (dataset.DEFAULT_LB_ITERS_LARGE if large else dataset.DEFAULT_LB_ITERS)
         t_write = None
         if not a.no_write:
-            out = a.out or tempfile.mkdtemp(prefix="dsbench_")
-            os.makedirs(out, exist_ok=True)
-            t0 = time.perf_counter()
-            for i, (g, r) in enumerate(zip(graphs, res)):
-                dataset.write_graph(np.triu(g[0]), g[1], filepath=os.path.join(out, "%d.graph" % i), route=r.tour)
-            t_write = time.perf_counter() - t0
-            if a.out is None:
-                shutil.rmtree(out)
+            t_write = write_files(a, name, samples, [(g[0], g[1], r.tour) for g, r in zip(graphs, res)])
         c = dataset.certify(res, 0.02)
         gap = np.array([(r.cost - r.lb) / r.cost for r in res])
         exact = {}

@@ -116,10 +116,16 @@ SIGNATURES = {
     "tspgnn_pack_dataset": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong,
                             c_longlong, c_longlong, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p],
+    "tspgnn_f64_repr": [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_graph_text_sizes": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong,
+                                c_void_p, c_void_p],
+    "tspgnn_graph_text_write": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong,
+                                c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p],
 }
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",
-                  "tspgnn_host_read_graph", "tspgnn_host_count_edges", "tspgnn_host_pack_batch", "tspgnn_host_stage_batch")
+                  "tspgnn_host_read_graph", "tspgnn_host_count_edges", "tspgnn_host_pack_batch", "tspgnn_host_stage_batch",
+                  "tspgnn_host_f64_repr")
 
 # size queries: name -> argtypes; these return long long (floats of workspace; tspgnn_tour_branch_bound_ws: bytes)
 SIZE_QUERIES = {
@@ -272,6 +278,8 @@ def _load():
                                             ctypes.c_double, c_int, ctypes.c_double, c_longlong, c_int, c_void_p, c_void_p]
     lib.tspgnn_host_read_graph.restype = c_int
     lib.tspgnn_host_read_graph.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.tspgnn_host_f64_repr.restype = c_int
+    lib.tspgnn_host_f64_repr.argtypes = [c_void_p, c_longlong, c_void_p, c_void_p]
     return lib
 
 

@@ -760,7 +760,8 @@ def draw_streams(nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="eu
 
 
 def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, distances="euc_2D", metric=True,
-                   require_certified=None, max_redraw_rounds=20, verbose=False, exact=False, closure="host", **solve_kw):
+                   require_certified=None, max_redraw_rounds=20, verbose=False, exact=False, closure="host", writer="host",
+                   **solve_kw):
     """dataset.py:118-143: draw ``samples`` instances (the reference's stream), label them on the GPU in batches with
     the planted cycle as a starting tour, and write ``{path}/{i}.graph`` with write_graph.
 
@@ -771,6 +772,11 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     exact=True: label with label_tours(exact=True), the branch and bound for n <= 128 (prove_tours).
     closure: 'host' | 'device', as draw_instances: where the metric closure of non-Euclidean weights is taken, for the
     stream and for every redraw round (one metric_closure call each); the files are the same bytes either way.
+    writer: 'host' | 'device': who formats the files.  'host' is the write_graph loop; 'device' uploads each instance's
+    np.triu(Ma) as uint8, the fp64 Mw and the tours in chunks and formats the same bytes on the GPU (graph_text.py,
+    csrc/graph_text.hip; n >= 4).  It raises ValueError before any launch of the writer when a mask holds a non-zero entry
+    other than 1 or a tour is not n entries long.  times['write'] is filled either way; 'device' adds its stages as
+    times['write_upload'], ['write_format'] (the two launches), ['write_download'] and ['write_files'].
     solve_kw go to label_tours (restarts, kicks, seed, lb_iters, chunk, device, max_nodes, neighbors); n up to 256.
 
     Returns a summary dict: samples, n (per instance), cost, lb, target, feasible, gap = (cost - lb) / cost,
@@ -780,6 +786,8 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
     times['exact'].
     """
     _check_closure(closure)
+    if writer not in ("host", "device"):
+        raise ValueError("writer=%r must be 'host' or 'device'" % (writer,))
     os.makedirs(path, exist_ok=True)
     times = {}
     graphs = draw_instances(nmin, nmax, conn_min, conn_max, samples, distances, metric, closure=closure, timings=times,
@@ -821,10 +829,17 @@ def create_dataset(path, nmin, nmax, conn_min=1, conn_max=1, samples=1000, dista
             if not certify(results, require_certified)["both"].all():
                 raise RuntimeError("create_dataset: instances still uncertified after %d redraw rounds" % max_redraw_rounds)
     t0 = time.perf_counter()
-    for i, (g, r) in enumerate(zip(graphs, results)):
-        write_graph(np.triu(g[0]), g[1], filepath="{}/{}.graph".format(path, i), route=r.tour)
-        if verbose and samples >= 20 and (i + 1) % (samples // 20) == 0:
-            print("Dataset creation {}% complete".format(int(100 * (i + 1) / samples)), flush=True)
+    if writer == "device":
+        from . import graph_text
+        stages = {}
+        graph_text.write_instances(path, [(g[0], g[1], r.tour) for g, r in zip(graphs, results)],
+                                   _device(solve_kw.get("device")), times=stages)
+        times.update(("write_" + k, stages.get(k, 0.0)) for k in ("upload", "format", "download", "files"))
+    else:
+        for i, (g, r) in enumerate(zip(graphs, results)):
+            write_graph(np.triu(g[0]), g[1], filepath="{}/{}.graph".format(path, i), route=r.tour)
+            if verbose and samples >= 20 and (i + 1) % (samples // 20) == 0:
+                print("Dataset creation {}% complete".format(int(100 * (i + 1) / samples)), flush=True)
     times["write"] = time.perf_counter() - t0
     summary = {
         "samples": samples,

@@ -30,6 +30,7 @@ import torch
 
 from . import _lib
 from . import dataset as D
+from . import graph_text as G
 from .instance_loader import read_graph, route_cost
 from .parallel import stage_instances, stage_layout, staged_batch
 
@@ -153,6 +154,9 @@ _Settings = collections.namedtuple("_Settings", "small large bb seed neighbors r
 # in A / Mw and first vertex in tours, with the totals n_cells / n_verts; the device arrays A (uint8 mask), Mw (fp64) and
 # tours (int32); the host arrays m (edges), lb and, with the branch and bound, status / nodes (else None).
 _Chunk = collections.namedtuple("_Chunk", "pos nc c_off t_off n_cells n_verts n_max A Mw tours m lb status nodes")
+# What a generated dataset keeps of a chunk for to_instances() and write_directory(): the first seven fields of _Chunk
+# and its device arrays A, Mw and tours.
+_Kept = collections.namedtuple("_Kept", "pos nc c_off t_off n_cells n_verts A Mw tours")
 
 
 def _generate_settings(samples, nmin, nmax, distances, metric, device, exact, chunk_bytes, solve_kw):
@@ -323,8 +327,8 @@ class DeviceDataset(object):
         4 <= nmin <= nmax <= 256.  solve_kw: restarts, kicks, lb_iters, seed, neighbors, max_nodes as label_tours takes
         them (None: its defaults for n <= 128 and for n 129-256).  exact: the branch and bound for n <= 128.  chunk_bytes:
         most bytes of fp64 matrices built and labelled together (the search input and the streams of a chunk are dropped
-        after it; its mask and matrix wait on the device for the packing launches, 9 sum n^2 bytes in all); the result does
-        not depend on it.  Every argument is checked before the first launch (ValueError).
+        after it; its mask and matrix stay on the device, 9 sum n^2 bytes in all); the result does not depend on it.
+        Every argument is checked before the first launch (ValueError).
 
         Instance i is the i-th draw.  ``summary`` is create_dataset's dict: samples, n, cost, lb, target, feasible, gap,
         certified_fraction (at dev 0.02), with ``exact`` proved and nodes, and times {'draw', 'build', 'closure' when one
@@ -332,8 +336,8 @@ class DeviceDataset(object):
         ``tours`` is (int32 host array of all tours, int64 offsets[samples + 1]).  The device array ``_cost`` is
         tspgnn_host_route_cost on Mw, as DeviceDataset(instances) keeps it; summary['target'] is n times that cost on the
         file form of Mw, as create_dataset reports it (they differ only when the closing pair (route[-1], route[1]) is no
-        edge).  The fp64 weight matrices stay on the device (8 sum n^2 bytes) for
-        to_instances()."""
+        edge).  The fp64 weight matrices, the uint8 masks and the int32 tours of every chunk stay on the device (9 sum n^2 +
+        4 sum n bytes) for to_instances() and write_directory()."""
         t_begin = time.perf_counter()
         cfg = _generate_settings(samples, nmin, nmax, distances, metric, device, exact, chunk_bytes, solve_kw)
         t0 = time.perf_counter()
@@ -384,7 +388,7 @@ class DeviceDataset(object):
             tours[np.arange(c.n_verts, dtype=np.int64) + np.repeat(v0[c.pos] - c.t_off, c.nc)] = c.tours.cpu().numpy()
         ds = cls._adopt(dev, n64, m, D._to_device(inst, dev), d_uv, d_w, d_rowptr, d_eid, d_rc)
         ds.tours = (tours, np.concatenate([v0, [N]]).astype(np.int64))
-        ds._matrices = [(c.pos, c.c_off, c.Mw) for c in chunks]
+        ds._matrices = [_Kept(c.pos, c.nc, c.c_off, c.t_off, c.n_cells, c.n_verts, c.A, c.Mw, c.tours) for c in chunks]
         return ds, d_fc.cpu().numpy(), d_cyc.cpu().numpy(), d_feas.cpu().numpy().astype(bool)
 
     def to_instances(self):
@@ -397,9 +401,9 @@ class DeviceDataset(object):
         e0 = np.concatenate([[0], np.cumsum(self.m)])
         tours, t_off = self.tours
         Mw = [None] * I
-        for pos, c_off, d_Mw in self._matrices:
-            flat = d_Mw.cpu().numpy()
-            for p, o in zip(pos, c_off):
+        for kept in self._matrices:
+            flat = kept.Mw.cpu().numpy()
+            for p, o in zip(kept.pos, kept.c_off):
                 n = int(self.n[p])
                 Mw[p] = flat[o:o + n * n].reshape(n, n).copy()
         out = []
@@ -410,6 +414,24 @@ class DeviceDataset(object):
             Ma[e[:, 0], e[:, 1]] = 1.0
             out.append((Ma, Mw[i], [int(x) for x in tours[t_off[i]:t_off[i + 1]]]))
         return out
+
+    def write_directory(self, path, text_bytes=G.DEFAULT_TEXT_BYTES):
+        """``{path}/{i}.graph`` for every instance i of a generated dataset, byte for byte the files write_graph(*inst,
+        ...) writes over to_instances(), formatted on the GPU (csrc/graph_text.hip) from the masks, fp64 matrices and
+        tours generate kept there.  Per chunk of at most ``text_bytes`` of text: the sizes launch (per generate chunk),
+        the prefix sums on the host, the write launch, one download into a pinned buffer and one write per file; the
+        result does not depend on text_bytes.  -> {'bytes': bytes written, 'times': {'format', 'download', 'files'
+        seconds, and 'sizes' / 'write', the two launches 'format' is the sum of}}."""
+        if self._matrices is None:
+            raise RuntimeError("DeviceDataset.to_instances: only a dataset made by generate() keeps its fp64 matrices")
+        self._require_gpu()
+        os.makedirs(path, exist_ok=True)
+        times = {"sizes": 0.0, "write": 0.0, "format": 0.0, "download": 0.0, "files": 0.0}
+        buffers, written = G._Buffers(self.device), 0
+        for kept in self._matrices:
+            written += G.write_files(path, [int(p) for p in kept.pos], kept.nc, kept.c_off, kept.t_off, kept.n_cells,
+                                     kept.n_verts, kept.A, kept.Mw, kept.tours, self.device, text_bytes, times, buffers)
+        return {"bytes": written, "times": times}
 
     def _require_gpu(self):
         if self.device.type != "cuda":
