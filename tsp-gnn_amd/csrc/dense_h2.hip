@@ -640,9 +640,10 @@ static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t 
     {
         // A lock-step task is a latency chain (two LDS stagings per round) that the resident tasks of the launch hide.
         // It gets the workgroups of a whole number of rounds -- ONE round while that stays within about twice its share
-        // of the grid by cost (more workgroups would idle, fewer would double the chain: C2's 320 vertex tiles take 20
-        // of 256), otherwise as many rounds as bring it back to its share (C4's 1 586 vertex tiles: 7 rounds on 15
-        // workgroups instead of starving the edge task of 99); the resident tasks share the rest by cost.
+        // of the grid by cost (more workgroups would idle, fewer would double the chain: C2's 320 vertex tiles take 27
+        // of 256), otherwise as many rounds as bring it back to its share (C4's 1 586 vertex tiles: 5 rounds on 27
+        // workgroups instead of starving the edge task of 133); the resident tasks share the rest by cost.
+        // (Figures at 256 CUs and 12 working wavefronts, from tests/plan_replay.py: cell_fwd_plan.)
         long long total_cost = 0;
         for (int k = 0; k < n; ++k) total_cost += cost[k] > 0 ? cost[k] : 1;
         int fixed[kMaxTasks];
