@@ -1048,6 +1048,77 @@ int tspgnn_bucket_pack_f32(float* bucket, int n, int with_grad, float local_batc
                            const unsigned* range_flag, void* stream);
 int tspgnn_bucket_unpack_f32(float* bucket, int n, int with_grad, float* stats, unsigned* range_flag, void* stream);
 
+/*
+ * Launch plans: what an entry's launcher decides in host code from the task shapes and the CU count, answered by the
+ * same planner the launcher calls (csrc/launch_plan.h).  Host only -- nothing is launched, no device is needed, and no
+ * pointer is dereferenced: a pointer field of a task counts as null or non-null.  Every query takes the arguments that
+ * shape the plan of the entry it describes plus `cus` (0: the device's count, the one the launcher uses; 256 without a
+ * device), validates the shape fields as the entry does, answers TSPGNN_EUNSUPPORTED exactly where the launch would, and
+ * fills a zeroed plan (grid 0) where the entry would launch nothing (no rows).  The tests claim a branch through these
+ * before they launch (tests/plan_replay.py); tests/golden/launch_plans.json records them across their thresholds.
+ */
+enum { TSPGNN_LINEAR_SPLIT = 0, TSPGNN_LINEAR_TICKET = 1, TSPGNN_LINEAR_STREAMED = 2 };
+typedef struct tspgnn_linear_plan {   /* tspgnn_linear_f32 */
+    int path;       /* TSPGNN_LINEAR_*: linear_split_kernel / linear_kernel with W resident / W streamed through LDS */
+    int nw, grid;   /* wavefronts per workgroup, workgroups */
+    int qc;         /* 16-row blocks of W per LDS staging (>= kin / 16: resident) */
+    int per_cu;     /* workgroups per CU the LDS size allows */
+    int tiles;      /* 16-row tiles */
+    int lds_bytes;
+} tspgnn_linear_plan;
+int tspgnn_plan_linear(int kin, int n1, int n2, int rows, int cus, tspgnn_linear_plan* out);
+
+typedef struct tspgnn_tasks_plan {    /* the ticket launches that only share out workgroups */
+    int nw, grid, n;                  /* n: live tasks (rows > 0), in order */
+    int blk_end[4];                   /* task k owns the workgroups [blk_end[k-1], blk_end[k]) */
+} tspgnn_tasks_plan;
+int tspgnn_plan_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out); /* tspgnn_mlp_bwd_multi_f32 */
+int tspgnn_plan_mlp_fwd(const tspgnn_mlp_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out);     /* tspgnn_mlp_fwd_multi_h2 / _x3, tspgnn_mlp_head_fwd_h2 */
+
+enum { TSPGNN_WGRAD_GENERIC = 0, TSPGNN_WGRAD_X3 = 1, TSPGNN_WGRAD_X3_PAIR = 2 };
+typedef struct tspgnn_wgrad_plan {    /* tspgnn_wgrad_f32 (bf16x == 0), tspgnn_wgrad_bf16x_f32 (bf16x != 0) */
+    int kernel;             /* TSPGNN_WGRAD_*: wgrad_kernel<av, bv> / wgrad_x3_kernel / the same, two X blocks per wavefront */
+    int av, bv;             /* 16-wide feature blocks of X / dY per wavefront of the generic kernel */
+    int nob;                /* output blocks the chunking counts with: kin / (16 av) * nout / (16 bv) */
+    int n_chunks;           /* row chunks = partial results in the workspace = terms of the second stage's sums */
+    int launch_nob, grid;   /* output blocks (wavefronts per chunk) of the chosen kernel, its workgroups */
+    long long chunk_rows;
+} tspgnn_wgrad_plan;
+int tspgnn_plan_wgrad(long long rows, int kin, int nout, int bf16x, int cus, tspgnn_wgrad_plan* out);
+
+typedef struct tspgnn_wcolsum_plan {  /* tspgnn_wcolsum_f32 */
+    int n_chunks, capped;   /* capped: the 4 per CU cap on the chunk count took effect */
+    long long chunk_rows;
+} tspgnn_wcolsum_plan;
+int tspgnn_plan_wcolsum(long long rows, int d, int cus, tspgnn_wcolsum_plan* out);
+
+typedef struct tspgnn_einit_bwd_plan {   /* tspgnn_einit_bwd_f32 */
+    int grid, n_chunks;     /* persistent workgroups, 64-edge chunks */
+    int full_grid;          /* the grid before the clamp to the chunk count */
+} tspgnn_einit_bwd_plan;
+int tspgnn_plan_einit_bwd(int M, int d, int cus, tspgnn_einit_bwd_plan* out);
+
+enum { TSPGNN_ARITH_H2 = 0, TSPGNN_ARITH_X3 = 1 };
+typedef struct tspgnn_cell_fwd_plan {    /* tspgnn_lnlstm_mlp_fwd_multi_h2 / _x3 (arith: TSPGNN_ARITH_*) */
+    int nw, grid, n;
+    int blk_end[4];
+    int lockstep[4];        /* 0: K and the MLP resident, tiles by ticket; 1: lock-step rounds */
+    int kbc[4];             /* k-blocks (32 rows of K) per LDS chunk */
+    int together[4];        /* h2, lock step: MLP layers and projection matrix in one residency */
+    int lock_tiles[4];      /* lock step: working wavefronts per workgroup (0: resident) */
+    int n_lo_lds[4];        /* x3: MLP layers whose lo piece is in LDS */
+    int n_rounds[4];        /* lock step: rounds per workgroup behind the task's fixed share (0: resident) */
+    int split_fixed;        /* 1: the lock-step tasks kept their fixed share; 0: the plain split by cost */
+    int centered, wt;       /* h2: the template variant */
+    int lds_bytes;
+} tspgnn_cell_fwd_plan;
+int tspgnn_plan_cell_fwd(const tspgnn_cell_mlp_task* tasks, int n_tasks, int d, int arith, int cus, tspgnn_cell_fwd_plan* out);
+
+/* Slices of the chunk range per workgroup in the second stage of the split reductions (wgrad, wcolsum). */
+int tspgnn_plan_reduce_slices(int n_chunks);
+/* Workgroups of the launches that cap their grid and stride over the rest: clamp(ceil(total / per_block), 1, cap). */
+int tspgnn_plan_strided_blocks(long long total, int per_block, int cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 tspgnn_lnlstm_mlp_fwd_multi_h2 (csrc/dense_h2.hip) and, wherever its entry accepts the task, tspgnn_lnlstm_mlp_fwd_multi_x3
 (csrc/dense_x3.hip).  One task's operands, drawn as tests/test_gpu_split_kernels.py draws them, packed for the arithmetic;
 every output buffer with SPARE rows of SENTINEL behind it (blocked and projected-message buffers: the pad rows of the last
-16-row tile hold it too); a zeroed range_flag word; a float64 reference on the device.  The launchers' planning is replayed
+16-row tile hold it too); a zeroed range_flag word; a float64 reference on the device.  The launchers' plan is asked of the library
 in tests/plan_replay.py (cell_fwd_plan); FwdCell.plan() is the task's entry for it.
 
 The blocked layouts are written from the comments of include/tspgnn.h, not from the kernels: the float4 (columns

@@ -1,15 +1,17 @@
-"""Replay of the host-side launch plans of the fp32 backward kernels (csrc/dense_bwd.hip), the training-tail kernels
-(csrc/train.hip) and -- last section -- the forward cell and MLP launchers (csrc/dense_h2.hip, csrc/dense_x3.hip): plain
-functions of (shape, cus) that follow the C++ line by line and answer the branch taken and its grid.  The GPU tests that
-claim a branch (tests/test_gpu_fp32_backward_plans.py, tests/test_gpu_batch_kernels.py,
-tests/test_gpu_cell_forward_edges.py) derive their row counts from the device's CU count and assert the branch and its
-depth through these functions BEFORE they launch; tests/test_plan_replay_host.py pins the functions against the library
-wherever the library exposes a plan (the workspace-size queries), tests/test_cell_fwd_replay_host.py the forward launchers
-at the shapes the project runs.  A launcher that changes must be changed here too -- the host test, or a "deep" test's own
-assertion, then fails instead of the test going shallow without notice.
+"""The launch plans of the fp32 backward kernels (csrc/dense_bwd.hip), the training-tail kernels (csrc/train.hip) and the
+forward cell and MLP launchers (csrc/dense_h2.hip, csrc/dense_x3.hip), asked of the library: every launcher-level figure
+here -- path, wavefronts, grid, blk_end, LDS chunking, mode, variant, chunk counts -- is what the tspgnn_plan_* queries
+answer, and those run the planner the launcher itself calls (csrc/launch_plan.h).  The GPU tests that claim a branch
+(tests/test_gpu_fp32_backward_plans.py, tests/test_gpu_batch_kernels.py, tests/test_gpu_cell_forward_edges.py) derive
+their row counts from the device's CU count and assert the branch and its depth through these functions BEFORE they
+launch.  What remains in Python follows a KERNEL's own loop from the plan -- a workgroup's ticket range, its rounds, the
+rows of a last chunk -- and names the line it follows.  tests/golden/launch_plans.json records the answers across the
+thresholds (tools/launch_plan_table.py).
 
 Nothing here touches a device."""
 from collections import namedtuple
+
+from tspgnn import _lib
 
 
 def ceil_div(a, b):
@@ -17,21 +19,25 @@ def ceil_div(a, b):
 
 
 def tiles16(rows):
-    """tiles16 (csrc/launch_plan.h)."""
+    """tiles_total of the tiled kernels: 16 rows per MFMA tile."""
     return (rows + 15) // 16
 
 
-def clamp_grid(grid, tiles_all, nw):
-    """clamp_grid (csrc/launch_plan.h): min(grid, ceil(tiles_all / nw))."""
-    return min(grid, ceil_div(tiles_all, nw))
+def blocks_of(plan):
+    """Workgroups per task from blk_end[] (the kernels' my_grid = blk_end[k] - blk_end[k - 1])."""
+    end = list(plan.blk_end[:plan.n])
+    return [e - b for b, e in zip([0] + end, end)]
 
 
-def split_blocks(cost, grid):
-    """split_blocks (csrc/launch_plan.h): workgroups per task, proportional to cost, at least one each."""
-    cost = [c if c > 0 else 1 for c in cost]
-    total = sum(cost)
-    grid = max(grid, len(cost))
-    return [max(1, (c * grid + total // 2) // total) for c in cost]
+def ticket_shares(tiles, my_grid):
+    """Tiles of every workgroup of a ticket task: t_end - t_beg with t_beg = tiles * b / my_grid (linear_kernel,
+    mlp_bwd_kernel)."""
+    return [tiles * (b + 1) // my_grid - tiles * b // my_grid for b in range(my_grid)]
+
+
+def strided_walk(n, my_grid):
+    """Iterations of every workgroup of a loop `r = my_blk; r < n; r += my_grid`."""
+    return [len(range(b, n, my_grid)) for b in range(my_grid)]
 
 
 # ---------------------------------------------------------------------------------------------- tspgnn_linear_f32
@@ -45,27 +51,17 @@ the last round that do not exist."""
 
 
 def linear_plan(kin, n1, n2, rows, cus):
-    """launch_linear<NT> (csrc/dense_bwd.hip)."""
-    nt = (n1 + n2) // 16
-    tiles = tiles16(rows)
-    qt = kin // 16
-    per_q = 16 * nt * 16 * 4
-    qc = qt
-    if qt * per_q + 16 > 150 * 1024:
-        qc = (128 * 1024) // per_q
-    lds_bytes = qc * per_q + 16
-    per_cu = 1 if lds_bytes > 80 * 1024 else 2
-    grid = cus * per_cu
-    if nt % 4 == 0 and qc >= qt and tiles <= cus * 4:
-        return LinearPlan("split", 8, (tiles + 1) // 2, qc, per_cu, tiles, None, 1, 1, None)
-    nw = 4 if (qc >= qt and tiles <= grid * 4) else 8
-    grid = clamp_grid(grid, tiles, nw)
-    if qc >= qt:
-        share = [tiles * (b + 1) // grid - tiles * b // grid for b in range(grid)]
-        return LinearPlan("ticket", nw, grid, qc, per_cu, tiles, None, min(share) // nw, ceil_div(max(share), nw), None)
-    rounds = ceil_div(tiles, nw)
-    per_wg = [len(range(b, rounds, grid)) for b in range(grid)]
-    return LinearPlan("streamed", nw, grid, qc, per_cu, tiles, rounds, min(per_wg), max(per_wg), rounds * nw - tiles)
+    """tspgnn_plan_linear, and linear_kernel's walk of its tiles."""
+    p = _lib.plan("tspgnn_plan_linear", kin, n1, n2, rows, cus)
+    path = ("split", "ticket", "streamed")[p.path]
+    if path == "split":
+        return LinearPlan(path, p.nw, p.grid, p.qc, p.per_cu, p.tiles, None, 1, 1, None)
+    if path == "ticket":
+        share = ticket_shares(p.tiles, p.grid)
+        return LinearPlan(path, p.nw, p.grid, p.qc, p.per_cu, p.tiles, None, min(share) // p.nw, ceil_div(max(share), p.nw), None)
+    rounds = ceil_div(p.tiles, p.nw)                  # linear_kernel: rounds = (tiles_total + nw - 1) / nw
+    per_wg = strided_walk(rounds, p.grid)             # r = blockIdx.x; r < rounds; r += gridDim.x
+    return LinearPlan(path, p.nw, p.grid, p.qc, p.per_cu, p.tiles, rounds, min(per_wg), max(per_wg), rounds * p.nw - p.tiles)
 
 
 # ---------------------------------------------------------------------------------------- tspgnn_mlp_bwd_multi_f32
@@ -75,22 +71,11 @@ nw, rounded down / up)."""
 
 
 def mlp_bwd_plan(tasks, d, cus):
-    """launch_mlp_bwd<D, MAXL> (csrc/dense_bwd.hip).  tasks: [(rows, n_layers)] of the live tasks (rows > 0)."""
-    maxl = 2 if d >= 128 else 4
-    tiles = [tiles16(rows) for rows, _ in tasks]
-    cost = [t * n_layers for t, (_, n_layers) in zip(tiles, tasks)]
-    tiles_all = sum(tiles)
-    lds_bytes = maxl * d * d * 4 + 16
-    per_cu = 1 if lds_bytes > 80 * 1024 else 2
-    grid = cus * per_cu
-    nw = 4 if tiles_all <= grid * 4 else 8
-    blocks = split_blocks(cost, clamp_grid(grid, tiles_all, nw))
-    lo, hi = [], []
-    for n, nb in zip(tiles, blocks):
-        share = [n * (b + 1) // nb - n * b // nb for b in range(nb)]
-        lo.append(min(share) // nw)
-        hi.append(ceil_div(max(share), nw))
-    return MlpBwdPlan(nw, sum(blocks), blocks, lo, hi)
+    """tspgnn_plan_mlp_bwd.  tasks: [(rows, n_layers)] of the live tasks (rows > 0)."""
+    p = _lib.plan("tspgnn_plan_mlp_bwd", [_lib.MlpBwdTask(rows=rows, n_layers=L) for rows, L in tasks], len(tasks), d, cus)
+    blocks = blocks_of(p)
+    shares = [ticket_shares(tiles16(rows), nb) for (rows, _), nb in zip(tasks, blocks)]
+    return MlpBwdPlan(p.nw, p.grid, blocks, [min(s) // p.nw for s in shares], [ceil_div(max(s), p.nw) for s in shares])
 
 
 # ------------------------------------------------------------------------------------------------ tspgnn_wgrad_f32
@@ -99,28 +84,22 @@ WgradPlan = namedtuple("WgradPlan", "kernel av bv nob n_chunks chunk_rows last_r
 
 
 def pick_vec(width):
-    return 4 if width % 64 == 0 else (2 if width % 32 == 0 else 1)
+    """AV (= BV) of wgrad_kernel for a feature width: what the planner answers for it."""
+    return _lib.plan("tspgnn_plan_wgrad", 1, width, width, 0, 1).av
 
 
 def wgrad_plan(rows, kin, nout, cus):
-    """wgrad_plan and the kernel choice of tspgnn_wgrad_f32 (csrc/dense_bwd.hip)."""
-    av, bv = pick_vec(kin), pick_vec(nout)
-    nob = (kin // (16 * av)) * (nout // (16 * bv))
-    target = max(cus * 8 // nob, 1)
-    by_rows = (rows + 255) // 256
-    nc = max(min(target, by_rows), 1)
-    cr = ceil_div(rows, nc)
-    cr = max((cr + 15) // 16 * 16, 16)
-    nc = max(ceil_div(rows, cr), 1)
-    kernel = "x3" if (av == 4 and bv == 4 and rows >= 4096) else "generic"
-    return WgradPlan(kernel, av, bv, nob, nc, cr, rows - (nc - 1) * cr)
+    """tspgnn_plan_wgrad for tspgnn_wgrad_f32; the kernels' chunk c covers rows [c * chunk_rows, min(rows, ...))."""
+    p = _lib.plan("tspgnn_plan_wgrad", rows, kin, nout, 0, cus)
+    return WgradPlan(("generic", "x3")[p.kernel], p.av, p.bv, p.nob, p.n_chunks, p.chunk_rows, rows - (p.n_chunks - 1) * p.chunk_rows)
 
 
 def wgrad_workspace_floats(rows, kin, nout, cus):
-    """tspgnn_wgrad_workspace_floats."""
-    if rows <= 0 or kin <= 0 or nout <= 0 or kin % 16 or nout % 16:
+    """tspgnn_wgrad_workspace_floats: a [kin, nout] partial and a bias row per chunk; 0 for a shape the entry rejects."""
+    try:
+        return _lib.plan("tspgnn_plan_wgrad", rows, kin, nout, 0, cus).n_chunks * (kin * nout + nout)
+    except _lib.TspgnnError:
         return 0
-    return wgrad_plan(rows, kin, nout, cus).n_chunks * (kin * nout + nout)
 
 
 # ----------------------------------------------------------------------------------------------- tspgnn_wcolsum_f32
@@ -129,19 +108,13 @@ ColsumPlan = namedtuple("ColsumPlan", "n_chunks chunk_rows last_rows capped")
 
 
 def colsum_plan(rows, cus):
-    """colsum_plan (csrc/train.hip)."""
-    nc = (rows + 1023) // 1024
-    cap = cus * 4
-    capped = nc > cap
-    nc = max(min(nc, cap), 1)
-    cr = ceil_div(rows, nc)
-    nc = max(ceil_div(rows, cr), 1)
-    cr = max(cr, 1)
-    return ColsumPlan(nc, cr, rows - (nc - 1) * cr, capped)
+    """tspgnn_plan_wcolsum; wcolsum_kernel's workgroup c covers rows [c * chunk_rows, min(rows, ...))."""
+    p = _lib.plan("tspgnn_plan_wcolsum", rows, 4, cus)
+    return ColsumPlan(p.n_chunks, p.chunk_rows, rows - (p.n_chunks - 1) * p.chunk_rows, bool(p.capped))
 
 
 def wcolsum_workspace_floats(rows, d, cus):
-    """tspgnn_wcolsum_workspace_floats."""
+    """tspgnn_wcolsum_workspace_floats: d column partials and a weight sum per chunk."""
     return colsum_plan(max(rows, 1), cus).n_chunks * (d + 1)
 
 
@@ -156,63 +129,43 @@ EinitBwdPlan = namedtuple("EinitBwdPlan", "grid n_chunks lo hi")
 
 
 def einit_np(d):
+    """einit_np (csrc/train.hip): parameters of the E_init MLP 2 -> d/8 -> d/4 -> d/2 -> d, a partial row's length."""
     h1, h2, h3 = d // 8, d // 4, d // 2
     return 2 * h1 + h1 + h1 * h2 + h2 + h2 * h3 + h3 + h3 * d + d
 
 
 def einit_bwd_full_grid(d, cus):
     """The persistent grid of tspgnn_einit_bwd_f32 before the clamp to the chunk count."""
-    return cus * (1 if d >= 128 else 2)
+    return _lib.plan("tspgnn_plan_einit_bwd", 1, d, cus).full_grid
 
 
 def einit_bwd_plan(M, d, cus):
-    """The grid of tspgnn_einit_bwd_f32 (csrc/train.hip) and the kernel's chunk += gridDim.x walk."""
-    n_chunks = (M + 63) // 64
-    grid = min(einit_bwd_full_grid(d, cus), n_chunks)
-    per_wg = [len(range(b, n_chunks, grid)) for b in range(grid)]
-    return EinitBwdPlan(grid, n_chunks, min(per_wg), max(per_wg))
+    """tspgnn_plan_einit_bwd and einit_bwd_kernel's chunk += gridDim.x walk."""
+    p = _lib.plan("tspgnn_plan_einit_bwd", M, d, cus)
+    per_wg = strided_walk(p.n_chunks, p.grid)
+    return EinitBwdPlan(p.grid, p.n_chunks, min(per_wg), max(per_wg))
 
 
 def einit_bwd_workspace_floats(M, d):
     """tspgnn_einit_bwd_workspace_floats: one partial row per chunk (at least one per workgroup)."""
-    return ((M + 63) // 64) * einit_np(d)
+    return _lib.plan("tspgnn_plan_einit_bwd", M, d, 1).n_chunks * einit_np(d)
 
 
 # ------------------------------------------------------------------------------------------------- reduce_partials2
 def reduce_slices(n_chunks):
     """S of reduce_partials2 (csrc/dense_bwd.hip): slices of the chunk range per workgroup."""
-    return 16 if n_chunks >= 64 else (4 if n_chunks >= 8 else 1)
+    return _lib.lib.tspgnn_plan_reduce_slices(n_chunks)
 
 
 # ------------------------------------------------------------------------------------ capped grid-stride launches
 def strided_blocks(total, cap, per_block=256):
     """(workgroups, does a thread take a second element) of the launches that cap their grid and stride over the rest:
     tspgnn_tile_rows_f32 / tspgnn_rowdot_bwd_f32 (float4s, cap 4096), tspgnn_bucket_pack_f32 / _unpack_f32 (floats, 1024)."""
-    blocks = max(min(ceil_div(total, per_block), cap), 1)
+    blocks = _lib.lib.tspgnn_plan_strided_blocks(total, per_block, cap)
     return blocks, total > blocks * per_block
 
 
 # ------------------------------------------------------- tspgnn_lnlstm_mlp_fwd_multi_{h2,x3}, tspgnn_mlp_fwd_multi_{h2,x3}
-# The forward cell launchers launch_cell_h2 (csrc/dense_h2.hip) and launch_cell_x3 (csrc/dense_x3.hip), the MLP launchers
-# launch_mlp_h2 / launch_mlp_x3, split_blocks_fixed (csrc/launch_plan.h) and xcd_contiguous (csrc/common.h), restated.
-# They must follow the launchers and the kernels' own tile ranges: a change there has to be made here too, or the tests
-# that assert a branch through them (tests/test_gpu_cell_forward_edges.py) stop knowing what they reach --
-# tests/test_cell_fwd_replay_host.py pins the figures of the shapes the project runs.
-LDS_BUDGET = 160 * 1024
-H2_LOCK_TILES = 16      # h2_lock_tiles() without its development switch
-WT_FOOTPRINT = 200 * 1024 * 1024
-
-
-def split_blocks_fixed(cost, fixed, grid):
-    """split_blocks_fixed (csrc/launch_plan.h) -> (workgroups per task, "fixed" or "plain": which split ran)."""
-    fixed_sum = sum(fixed)
-    res = [c for c, f in zip(cost, fixed) if not f]
-    if not res or fixed_sum == 0 or fixed_sum > grid // 2:
-        return split_blocks(cost, grid), "plain"
-    it = iter(split_blocks(res, grid - fixed_sum))
-    return [f if f else next(it) for f in fixed], "fixed"
-
-
 def xcd_contiguous(b, n):
     """xcd_contiguous (csrc/common.h): workgroup b of n -> its position, the workgroups of one XCD (b mod 8) consecutive."""
     per, rem, x = n >> 3, n & 7, b & 7
@@ -236,96 +189,39 @@ rounds: all lock-step rounds, ceil(tiles / lock_tiles); rounds_per_wg: (fewest, 
 r = my_blk; r < rounds; r += my_grid.  ranges: resident, every workgroup's [t_beg, t_end)."""
 
 CellLaunchPlan = namedtuple("CellLaunchPlan", "nw grid blk_end split centered wt lds_bytes tasks")
-"""split: "fixed" or "plain" (split_blocks_fixed).  centered / wt: the template variant (h2; always False for x3).
+"""split: "fixed" (the lock-step tasks kept their set share of the workgroups) or "plain" (all by cost).  centered / wt: the template variant (h2; always False for x3).
 tasks: a CellTaskPlan per task."""
 
 
 def cell_fwd_plan(tasks, d, cus, arith="h2"):
-    """launch_cell_h2<D> / launch_cell_x3<D>.  tasks: (rows, dx, mlp_layers, has_proj, out_blocked, has_mlp_out, z_centered)
-    of the live tasks (rows > 0), in order.  Raises ValueError where the launcher answers TSPGNN_EUNSUPPORTED."""
+    """tspgnn_plan_cell_fwd.  tasks: (rows, dx, mlp_layers, has_proj, out_blocked, has_mlp_out, z_centered) of the live
+    tasks (rows > 0), in order.  Raises ValueError where the launcher answers TSPGNN_EUNSUPPORTED."""
     assert arith in ("h2", "x3") and d in (32, 64) and 1 <= len(tasks) <= 4
-    pieces = 2 if arith == "h2" else 3
-    head = (10 * d + 4) * 4
-    per_kb = pieces * 32 * 4 * d * 2
-    budget = LDS_BUDGET - head
-    layer_all = pieces * d * d * 2 + d * 4
-    proj_bytes = pieces * d * 4 * d * 2
-    mode, kbcs, together, cost, tiles, lds_w = [], [], [], [], [], 0
-    for rows, dx, L, proj, _, _, _ in tasks:
-        assert rows > 0 and dx % 32 == 0 and 0 <= L <= 4 and (not proj or L > 0)
-        KBT = (dx + d) // 32
-        k_bytes = KBT * per_kb
-        tog = 0
-        if arith == "h2":
-            if k_bytes + L * layer_all <= budget and not proj:
-                kbc, lock, need = KBT, False, k_bytes + L * layer_all
-            else:
-                kbc = KBT if k_bytes <= budget else budget // per_kb
-                if kbc < 1 or L * layer_all > budget or (proj and proj_bytes > budget):
-                    raise ValueError("dx=%d, d=%d, %d MLP layers do not fit LDS" % (dx, d, L))
-                lock, need, second = True, kbc * per_kb, L * layer_all
-                if proj:
-                    if L * layer_all + proj_bytes <= budget:
-                        tog = 1
-                        second += proj_bytes
-                    elif proj_bytes > second:
-                        second = proj_bytes
-                need = max(need, second)
-        else:
-            layer_hm, layer_lo = 2 * d * d * 2, d * d * 2
-            mlp_min = L * (layer_hm + d * 4)          # resident: hi, mid and the biases must be in LDS
-            if k_bytes + mlp_min <= budget and not proj:
-                n_lo = min((budget - k_bytes - mlp_min) // layer_lo, L)
-                kbc, lock, need = KBT, False, k_bytes + mlp_min + n_lo * layer_lo
-            else:
-                kbc = KBT if k_bytes <= budget else budget // per_kb
-                if kbc >= KBT:
-                    kbc = KBT - 1                     # lock-step mode is selected by kbc < KBT
-                if kbc < 1 or L * layer_all > budget or (proj and proj_bytes > budget):
-                    raise ValueError("dx=%d, d=%d, %d MLP layers do not fit LDS" % (dx, d, L))
-                lock, need = True, max(kbc * per_kb, L * layer_all, proj_bytes if proj else 0)
-        lds_w = max(lds_w, need)
-        n = tiles16(rows)
-        mode.append("lockstep" if lock else "resident")
-        kbcs.append(kbc)
-        together.append(tog)
-        tiles.append(n)
-        cost.append(n * (KBT * 4 + 2 * L + (8 if proj else 0) + (8 if arith == "h2" else 6)))
-    tiles_all = sum(tiles)
-    nw = 4 if tiles_all <= cus * 4 else (8 if tiles_all <= cus * 8 else 12)
-    grid = clamp_grid(cus, tiles_all, nw)
-    total_cost = sum(c if c > 0 else 1 for c in cost)
-    fixed, lock_tiles, n_rounds = [], [], []
-    for k, m in enumerate(mode):
-        if m != "lockstep":
-            fixed.append(0), lock_tiles.append(0), n_rounds.append(None)
-        elif arith == "h2":
-            lw = min(nw, H2_LOCK_TILES)
-            per_round = ceil_div(tiles[k], lw)
-            share = max(ceil_div(2 * cost[k] * grid, total_cost), 1)     # twice the proportional share
-            nr = ceil_div(per_round, share)
-            fixed.append(ceil_div(per_round, nr)), lock_tiles.append(lw), n_rounds.append(nr)
-        else:
-            fixed.append(ceil_div(tiles[k], nw)), lock_tiles.append(nw), n_rounds.append(1)
-    blocks, split = split_blocks_fixed(cost, fixed, grid)
-    centered = arith == "h2" and all(t[6] for t in tasks)
-    out_bytes = sum(rows * d * 4 * (3 if mlp_out else 2) for rows, _, _, _, _, mlp_out, _ in tasks)
-    loop_buffers = any(out_blk or mlp_out or proj for _, _, _, proj, out_blk, mlp_out, _ in tasks)
-    wt = arith == "h2" and loop_buffers and 2 * out_bytes <= WT_FOOTPRINT
+    structs = [_lib.CellMlpTask(cell=_lib.LstmTask(rows=rows, dx=dx, z_centered=int(zc)), mlp_layers=L, proj_w=int(proj),
+                                proj_out=int(proj), mlp_out=int(mlp_out), state_out_blocked=int(out_blk))
+               for rows, dx, L, proj, out_blk, mlp_out, zc in tasks]
+    try:
+        p = _lib.plan("tspgnn_plan_cell_fwd", structs, len(tasks), d, ("h2", "x3").index(arith), cus)
+    except _lib.TspgnnError as e:
+        if e.status != -2:
+            raise
+        raise ValueError(e.message)
+    blocks = blocks_of(p)
     plans = []
-    for k, (rows, dx, L, proj, _, _, _) in enumerate(tasks):
-        KBT = (dx + d) // 32
-        if mode[k] == "resident":
-            plans.append(CellTaskPlan("resident", kbcs[k], 1, False, 0, 0, None, blocks[k], tiles[k], None, None,
-                                      ticket_ranges(tiles[k], blocks[k], xcd=arith == "h2")))
-        else:
-            rounds = ceil_div(tiles[k], lock_tiles[k])
-            per_wg = [len(range(b, rounds, blocks[k])) for b in range(blocks[k])]
-            plans.append(CellTaskPlan("lockstep", kbcs[k], ceil_div(KBT, kbcs[k]), arith == "h2" and KBT <= 4, together[k],
-                                      lock_tiles[k], n_rounds[k], blocks[k], tiles[k], rounds, (min(per_wg), max(per_wg)),
-                                      None))
-    blk_end = [sum(blocks[:k + 1]) for k in range(len(blocks))]
-    return CellLaunchPlan(nw, blk_end[-1], blk_end, split, centered, wt, lds_w + head, plans)
+    for k, (rows, dx, *_) in enumerate(tasks):
+        tiles, KBT = tiles16(rows), (dx + d) // 32            # the kernels' tiles_total and KBT
+        if not p.lockstep[k]:
+            plans.append(CellTaskPlan("resident", p.kbc[k], 1, False, 0, 0, None, blocks[k], tiles, None, None,
+                                      ticket_ranges(tiles, blocks[k], xcd=arith == "h2")))
+            continue
+        rounds = ceil_div(tiles, p.lock_tiles[k])             # rounds = (tiles_total + lw - 1) / lw
+        per_wg = strided_walk(rounds, blocks[k])              # r = my_blk; r < rounds; r += my_grid
+        plans.append(CellTaskPlan("lockstep", p.kbc[k], ceil_div(KBT, p.kbc[k]),        # kb0 = 0; kb0 < KBT; kb0 += kbc
+                                  arith == "h2" and KBT <= 4,                           # pre = KBT <= KBP
+                                  p.together[k], p.lock_tiles[k], p.n_rounds[k], blocks[k], tiles, rounds,
+                                  (min(per_wg), max(per_wg)), None))
+    return CellLaunchPlan(p.nw, p.grid, list(p.blk_end[:p.n]), "fixed" if p.split_fixed else "plain", bool(p.centered),
+                          bool(p.wt), p.lds_bytes, plans)
 
 
 def cell_task(rows, dx=0, mlp_layers=0, proj=False, out_blocked=False, mlp_out=False, z_centered=False):
@@ -338,13 +234,9 @@ MlpFwdPlan = namedtuple("MlpFwdPlan", "nw grid blocks ranges")
 
 
 def mlp_fwd_plan(tasks, cus):
-    """launch_mlp_h2<D> / launch_mlp_x3<D> (the same arithmetic; tspgnn_mlp_head_fwd_h2 is the one-task launch).
-    tasks: [(rows, n_layers, has_proj)] of the live tasks."""
-    tiles = [tiles16(rows) for rows, _, _ in tasks]
-    cost = [n * (L + (5 if proj else 0)) for n, (_, L, proj) in zip(tiles, tasks)]
-    tiles_all = sum(tiles)
-    nw = 16
-    if tiles_all <= cus * 16:
-        nw = 4 if tiles_all <= cus * 4 else 8
-    blocks = split_blocks(cost, clamp_grid(cus, tiles_all, nw))
-    return MlpFwdPlan(nw, sum(blocks), blocks, [ticket_ranges(n, b, xcd=False) for n, b in zip(tiles, blocks)])
+    """tspgnn_plan_mlp_fwd (launch_mlp_h2 and launch_mlp_x3 share the planner; tspgnn_mlp_head_fwd_h2 is the one-task
+    launch).  tasks: [(rows, n_layers, has_proj)] of the live tasks."""
+    p = _lib.plan("tspgnn_plan_mlp_fwd", [_lib.MlpTask(rows=rows, n_layers=L, proj_w=int(proj)) for rows, L, proj in tasks],
+                  len(tasks), 64, cus)
+    blocks = blocks_of(p)
+    return MlpFwdPlan(p.nw, p.grid, blocks, [ticket_ranges(tiles16(rows), b, xcd=False) for (rows, _, _), b in zip(tasks, blocks)])

@@ -45,7 +45,11 @@ def test_abi_version_and_struct_layouts_agree(tmp_path):
     pairs = {"tspgnn_mlp_task": _lib.MlpTask, "tspgnn_lstm_task": _lib.LstmTask, "tspgnn_cell_mlp_task": _lib.CellMlpTask,
              "tspgnn_mlp_task_bf16": _lib.MlpTaskB, "tspgnn_lstm_task_bf16": _lib.LstmTaskB,
              "tspgnn_lstm_bwd_task": _lib.LstmBwdTask, "tspgnn_mlp_bwd_task": _lib.MlpBwdTask, "tspgnn_mlp_bwd_rc_task": _lib.MlpBwdRcTask,
-             "tspgnn_mp_loop_args": _lib.MpLoopArgs, "tspgnn_mp_resident_args": _lib.MpResidentArgs}
+             "tspgnn_mp_loop_args": _lib.MpLoopArgs, "tspgnn_mp_resident_args": _lib.MpResidentArgs,
+             "tspgnn_linear_plan": _lib.LinearPlan, "tspgnn_tasks_plan": _lib.TasksPlan, "tspgnn_wgrad_plan": _lib.WgradPlan,
+             "tspgnn_wcolsum_plan": _lib.WcolsumPlan, "tspgnn_einit_bwd_plan": _lib.EinitBwdPlan,
+             "tspgnn_cell_fwd_plan": _lib.CellFwdPlan}
+    assert set(_lib.PLANS.values()) <= set(pairs.values())
     src = ["#include <stdio.h>", "#include <stddef.h>", '#include "tspgnn.h"', "int main(void) {"]
     for cname, cls in pairs.items():
         src.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))

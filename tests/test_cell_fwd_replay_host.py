@@ -1,7 +1,8 @@
-"""The replay of the forward cell and MLP launchers (plan_replay.cell_fwd_plan / mlp_fwd_plan) against figures worked out
-from the launchers' text (csrc/dense_h2.hip, csrc/dense_x3.hip, csrc/launch_plan.h, csrc/common.h) -- no device.  The GPU
-tests of tests/test_gpu_cell_forward_edges.py assert their branches through the same functions; a launcher that changes
-has to be changed in the replay, and then the figures here say what moved."""
+"""The plans of the forward cell and MLP launchers (plan_replay.cell_fwd_plan / mlp_fwd_plan: the library's
+tspgnn_plan_cell_fwd / tspgnn_plan_mlp_fwd, and the kernels' own tile walks derived from them) against figures worked out
+by hand from the planners' text (csrc/launch_plan.h, csrc/common.h) at the shapes the project runs -- no device.  The GPU
+tests of tests/test_gpu_cell_forward_edges.py assert their branches through the same functions; when a planner changes,
+the figures here say what moved."""
 import pytest
 
 from plan_replay import cell_fwd_plan, cell_task, mlp_fwd_plan, ticket_ranges, xcd_contiguous

@@ -132,7 +132,7 @@ def einit_bwd_M(M, d, n_cus):
 def test_einit_bwd_persistent_workgroups_vs_float64(cuda_device, d, M):
     """dwb += the E_init_MLP parameter gradients: one chunk per workgroup, then the chunk += gridDim.x loop with its dE0
     prefetch and its accumulation over chunks (64 * grid + 1: a second chunk of ONE edge for the first workgroup only;
-    64 * 2 * grid + 1: two to three chunks each) -- against float64 autograd, the grid asserted through the replay."""
+    64 * 2 * grid + 1: two to three chunks each) -- against float64 autograd, the grid asserted through the plan query."""
     n_cus = cus(cuda_device)
     seed = d + (M if isinstance(M, int) else len(M))
     deep = not isinstance(M, int)

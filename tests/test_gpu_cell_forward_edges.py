@@ -253,7 +253,7 @@ def two_round_shape(d, n_cus):
 
 @pytest.mark.parametrize("d", [32, 64])
 def test_several_rounds_per_lockstep_workgroup_h2(cuda_device, d):
-    """The n_rounds > 1 branch of the workgroup split, at the smallest two-task launch the replay finds for this device (256
+    """The n_rounds > 1 branch of the workgroup split, at the smallest two-task launch the plan query finds for this device (256
     CUs: 94 002 + 47 001 rows at either width -- which at d = 64 is already past the write-through footprint, at d = 32 not)."""
     M, N = two_round_shape(d, cus(cuda_device))
     cells = [edge_cell("h2", d, M, 21, in_blocked=True, out_blocked=True, acts=None),

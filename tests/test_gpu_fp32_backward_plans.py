@@ -120,7 +120,7 @@ def _linear_cases():
 
 
 def linear_rows(kin, n1, n2, rows, n_cus):
-    """A parametrised row count -> (rows, check of the replayed plan)."""
+    """A parametrised row count -> (rows, check of the queried plan)."""
     p1 = PR.linear_plan(kin, n1, n2, 1, n_cus)
     streamed, full = p1.path == "streamed", n_cus * p1.per_cu
     small = "streamed" if streamed else "split"
@@ -146,7 +146,7 @@ def linear_rows(kin, n1, n2, rows, n_cus):
 @pytest.mark.parametrize("kin,n1,n2,rows", _linear_cases())
 def test_linear_f32_every_path_vs_float64(cuda_device, kin, n1, n2, rows, acc):
     """Y1 | Y2 (+)= X W on linear_split_kernel, linear_kernel with the ticket (nw = 4, nw = 8) and linear_kernel with W
-    streamed in rounds -- see the module docstring for the row counts; the path and its depth asserted through the replay."""
+    streamed in rounds -- see the module docstring for the row counts; the path and its depth asserted through the plan query."""
     seed = kin + 3 * n1 + 7 * n2 + acc + (rows if isinstance(rows, int) else sum(map(ord, rows)))
     rows, expected = linear_rows(kin, n1, n2, rows, cus(cuda_device))
     plan = PR.linear_plan(kin, n1, n2, rows, cus(cuda_device))

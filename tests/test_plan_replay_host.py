@@ -1,10 +1,11 @@
-"""tests/plan_replay.py against the library, wherever the library exposes a plan: the workspace-size queries
+"""The launch plans of the fp32 backward and training-tail kernels, as tests/plan_replay.py reads them from the library's
+tspgnn_plan_* queries -- the planners the launchers themselves call.  The workspace-size queries must agree with them:
 tspgnn_wgrad_workspace_floats = nc (kin nout + nout), tspgnn_wcolsum_workspace_floats = nc (d + 1) and
-tspgnn_einit_bwd_workspace_floats.  Without a device n_cus() answers 256, so the pins are for cus = 256; the grid of
+tspgnn_einit_bwd_workspace_floats.  Without a device n_cus() answers 256, so those pins are for cus = 256; the grid of
 shapes holds every row count that tests/test_gpu_fp32_backward_plans.py and tests/test_gpu_batch_kernels.py use there.
-The branches the library does not expose (launch_linear, launch_mlp_bwd, the einit_bwd grid, reduce_partials2's S) are
-pinned at the values the GPU tests name in their ids and docstrings for 256 CUs: a replay that is edited without the
-launcher -- or the other way round, for the exposed ones -- fails here, not silently in a "deep" test."""
+The other tests pin the planners (linear, mlp_bwd, the einit_bwd grid, reduce_partials2's S) at the values the GPU tests
+name in their ids and docstrings for 256 CUs: a launcher that changes fails here and says what moved, not silently in a
+"deep" test."""
 import pytest
 
 import plan_replay as PR

@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""The table of launch plans, tests/golden/launch_plans.json: every planner of csrc/launch_plan.h asked through
+tests/plan_replay.py (the tspgnn_plan_* queries) over a grid that crosses its thresholds -- CU counts 1, 104 and 256, row counts at,
+one below and one above the boundaries derived from the CU count, the LDS modes of the forward cell launchers.  No device
+is needed.
+
+    python tools/launch_plan_table.py            compare the library with the committed table (exit status 1: it moved)
+    python tools/launch_plan_table.py --write    rewrite the table: how a deliberate launcher change records itself
+
+tests/test_launch_plan_table.py holds the library to the committed table."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TABLE = os.path.join(ROOT, "tests", "golden", "launch_plans.json")
+
+CUS = (1, 104, 256)      # (the first recording crossed 1, 8, 64, 104, 256 and 304 with more row counts: the table is its thinning)
+
+
+def around(*bounds):
+    """Each boundary, one below and one above (positive values, ascending, once each)."""
+    return sorted({v for b in bounds for v in (b - 1, b, b + 1) if v > 0})
+
+
+def linear_cases():
+    for kin, n1, n2, per_cu in ((128, 64, 64, 2), (256, 64, 64, 1), (512, 128, 128, 1)):
+        for cus in CUS:
+            full = cus * per_cu
+            for r in around(16 * 4 * cus, 16 * 4 * full) + [16 * 4 * full - 15, 16 * 8 * (2 * full) + 17, 16 * (2 * full * 8) + 1]:
+                yield (kin, n1, n2, r, cus)
+
+
+def mlp_bwd_cases():
+    for d, per_cu in ((64, 2), (128, 1)):
+        for cus in CUS:
+            full = cus * per_cu
+            deep = 16 * (2 * full * 8) + 1
+            for r in around(16 * 4 * full) + [17, deep]:
+                yield ([(r, 2)], d, cus)
+            yield ([(333, 2), (deep, 2)], d, cus)
+            yield ([(5000, 2), (5000, 1), (100, 2), (16 * 8 * cus + 1, 1)], d, cus)
+
+
+def wgrad_cases():
+    for cus in CUS:
+        for kin in (16, 32, 64):
+            for nout in (16, 32, 64):
+                for r in ((255, 4095, 4096, 70001) if kin == nout else (257, 70001)):
+                    yield (r, kin, nout, cus)
+        for kin, nout in ((32, 128), (512, 512), (48, 96)):
+            for r in (1, 99840, 256 * cus * 8 + 1):
+                yield (r, kin, nout, cus)
+
+
+def colsum_cases():
+    for cus in CUS:
+        for r in around(1024, 1024 * 4 * cus) + [1, 64 * 1024 + 1, 5094400]:
+            yield (r, cus)
+
+
+def einit_bwd_cases():
+    for d, per_cu in ((64, 2), (128, 1)):
+        for cus in CUS:
+            full = cus * per_cu
+            for M in around(64 * full) + [1, 333, 64 * 2 * full + 1]:
+                yield (M, d, cus)
+
+
+def mlp_fwd_cases():
+    for cus in CUS:
+        for tiles in around(4 * cus, 16 * cus):
+            yield ([(16 * tiles, 3, False)], cus)
+        yield ([(9000, 3, False), (700, 4, True)], cus)
+        yield ([(5000, 2, False), (5000, 1, True), (100, 4, True), (16 * 16 * cus + 1, 3, False)], cus)
+
+
+def cell_fwd_cases(task):
+    """task: plan_replay.cell_task."""
+    for arith in ("h2", "x3"):
+        for d in (32, 64):
+            # the LDS modes: one task, among the shapes the entries accept (a projection needs an MLP layer)
+            for dx in (0, 64, 96, 192, 320, 512):
+                for L, proj in ((0, False), (1, True), (3, False), (4, False), (4, True)):
+                    yield ([task(333, dx, L, proj, proj, bool(L))], d, 256, arith)
+            for cus in CUS if d == 64 else ():       # (the split does not look at d)
+                edge = lambda rows: task(rows, 0, 3, False, True, True)
+                vert = lambda rows, zc=False: task(rows, d, 4, True, True, True, zc)
+                # the wavefront thresholds of a resident and of a lock-step task, and the vertex task's deep count
+                for tiles in around(4 * cus, 8 * cus):
+                    yield ([edge(16 * tiles)], d, cus, arith)
+                yield ([vert(16 * 4 * cus + 1)], d, cus, arith)
+                yield ([vert(16 * (12 * 2 * cus) + 1)], d, cus, arith)
+                # a step's launch: edge gather cell + 3 layers, vertex cell + 4 layers + projection
+                for M, N in ((7001, 333), (99840, 5120), (695849, 25362), (100, 5000)):
+                    yield ([edge(M), vert(N)], d, cus, arith)
+                yield ([vert(5120, True), task(99840, 0, 0, z_centered=True)], d, cus, arith)
+                yield ([task(2000, 64), edge(99840), vert(5120)], d, cus, arith)
+                yield ([task(2000, 64, 2), edge(40000), vert(5120), task(300, 192, 1, True)], d, cus, arith)
+
+
+def table(PR):
+    """{planner: [[arguments, answer]]} from a module with tests/plan_replay.py's functions."""
+    cell = []
+    for tasks, d, cus, arith in cell_fwd_cases(PR.cell_task):
+        try:
+            p = PR.cell_fwd_plan(tasks, d, cus, arith)
+            got = [p.nw, p.grid, p.blk_end, p.split, p.centered, p.wt, p.lds_bytes,
+                   [[t.mode, t.kbc, t.chunks, t.preload, t.together, t.lock_tiles, t.n_rounds, t.blocks, t.rounds,
+                     t.rounds_per_wg] for t in p.tasks]]
+        except ValueError:
+            got = "unsupported"
+        cell.append([[tasks, d, cus, arith], got])
+    mlp_fwd = []
+    for tasks, cus in mlp_fwd_cases():
+        p = PR.mlp_fwd_plan(tasks, cus)
+        mlp_fwd.append([[tasks, cus], [p.nw, p.grid, p.blocks]])
+    return {
+        "linear": [[list(a), list(PR.linear_plan(*a))] for a in linear_cases()],
+        "mlp_bwd": [[list(a), list(PR.mlp_bwd_plan(*a))] for a in mlp_bwd_cases()],
+        "wgrad": [[list(a), list(PR.wgrad_plan(*a))] for a in wgrad_cases()],
+        "wcolsum": [[list(a), list(PR.colsum_plan(*a))] for a in colsum_cases()],
+        "einit_bwd": [[list(a), list(PR.einit_bwd_plan(*a)) + [PR.einit_bwd_full_grid(a[1], a[2])]] for a in einit_bwd_cases()],
+        "mlp_fwd": mlp_fwd,
+        "cell_fwd": cell,
+        "reduce_slices": [[n, PR.reduce_slices(n)] for n in (1, 7, 8, 63, 64, 2048)],
+        "strided_blocks": [[[t, cap], list(PR.strided_blocks(t, cap))] for cap in (1024, 4096) for t in around(256 * cap) + [1]],
+    }
+
+
+def dumps(tab):
+    """One record per line, no spaces: the committed form."""
+    out = ["{"]
+    for i, (name, recs) in enumerate(tab.items()):
+        out.append('"%s":[' % name)
+        out += [json.dumps(json.loads(json.dumps(r)), separators=(",", ":")) + ("," if j + 1 < len(recs) else "")
+                for j, r in enumerate(recs)]
+        out.append("]" + ("," if i + 1 < len(tab) else ""))
+    out.append("}")
+    return "\n".join(out) + "\n"
+
+
+def main():
+    sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tsp-gnn_amd")]
+    import plan_replay
+    text = dumps(table(plan_replay))
+    if "--write" in sys.argv[1:]:
+        with open(TABLE, "w") as f:
+            f.write(text)
+        print("wrote %s: %d bytes" % (TABLE, len(text)))
+        return 0
+    same = os.path.exists(TABLE) and open(TABLE).read() == text
+    print("the library %s %s" % ("answers" if same else "does NOT answer", TABLE))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -338,7 +338,7 @@ __global__ __launch_bounds__(256) void reduce_partials_kernel(const ReduceSeg a,
 void reduce_partials2(const float* partial, int n_chunks, long long stride, float* out, int n, const float* partial_b,
                       long long stride_b, float* out_b, int n_b, float scale, int accumulate, hipStream_t st) {
     // many chunks: 16 outputs x 16 slices per workgroup; few chunks: 256 outputs x 1 slice
-    const int S = n_chunks >= 64 ? 16 : (n_chunks >= 8 ? 4 : 1);
+    const int S = reduce_slices(n_chunks);
     const dim3 block(256 / S, S);
     const ReduceSeg a = {partial, stride, out, n, (int)((n + block.x - 1) / block.x)};
     const ReduceSeg b = {partial_b, stride_b, out_b, n_b, out_b != nullptr ? (int)((n_b + block.x - 1) / block.x) : 0};
@@ -700,49 +700,21 @@ __global__ __launch_bounds__(256) void wgrad_x3_kernel(const float* __restrict__
     }
 }
 
-static int pick_vec(int width) { return width % 64 == 0 ? 4 : (width % 32 == 0 ? 2 : 1); }
-
-// Split of the row range used by tspgnn_wgrad_f32 (and its workspace size).
-static void wgrad_plan(long long rows, int kin, int nout, int* n_chunks, long long* chunk_rows) {
-    const int av = pick_vec(kin), bv = pick_vec(nout);
-    const int nob = (kin / (16 * av)) * (nout / (16 * bv));
-    long long target = (long long)n_cus() * 8 / nob;  // ~8 wavefronts per CU in total (HBM-bound: loads in flight)
-    if (target < 1) target = 1;
-    long long by_rows = (rows + 255) / 256;             // at least 256 rows per chunk
-    long long nc = target < by_rows ? target : by_rows;
-    if (nc < 1) nc = 1;
-    long long cr = (rows + nc - 1) / nc;
-    cr = (cr + 15) / 16 * 16;
-    if (cr < 16) cr = 16;
-    nc = (rows + cr - 1) / cr;
-    if (nc < 1) nc = 1;
-    *n_chunks = (int)nc;
-    *chunk_rows = cr;
-}
-
 template <int NT>
 static int launch_linear(const float* X, int kin, const float* Wp, float* Y1, int n1, float* Y2, int n2, int acc2,
                          int rows, hipStream_t st) {
-    const int tiles = (rows + 15) / 16;
-    const int QT = kin / 16;
-    const size_t per_q = (size_t)16 * NT * 16 * sizeof(float);
-    int qc = QT;
-    if ((size_t)QT * per_q + 16 > 150 * 1024) qc = (int)((128 * 1024) / per_q);
-    const size_t lds_bytes = (size_t)qc * per_q + 16;
-    int rc = set_dynamic_lds(&linear_kernel<NT>, lds_bytes, "linear");
+    tspgnn_linear_plan pl;
+    plan_linear(kin, NT, rows, n_cus(), &pl);
+    int rc = set_dynamic_lds(&linear_kernel<NT>, pl.lds_bytes, "linear");
     if (rc) return rc;
-    const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
-    int grid = n_cus() * per_cu;
     if constexpr (NT % 4 == 0) {
-        if (qc >= QT && tiles <= n_cus() * 4) {   // few tiles: split each tile's columns over four wavefronts
-            if ((rc = set_dynamic_lds(&linear_split_kernel<NT>, lds_bytes, "linear"))) return rc;
-            linear_split_kernel<NT><<<(tiles + 1) / 2, 512, lds_bytes, st>>>(X, kin, Wp, Y1, n1, Y2, n2, acc2, rows, tiles);
+        if (pl.path == TSPGNN_LINEAR_SPLIT) {
+            if ((rc = set_dynamic_lds(&linear_split_kernel<NT>, pl.lds_bytes, "linear"))) return rc;
+            linear_split_kernel<NT><<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(X, kin, Wp, Y1, n1, Y2, n2, acc2, rows, pl.tiles);
             return launched("tspgnn_linear_f32");
         }
     }
-    const int nw = (qc >= QT && tiles <= grid * 4) ? 4 : 8;
-    grid = clamp_grid(grid, tiles, nw);
-    linear_kernel<NT><<<grid, nw * 64, lds_bytes, st>>>(X, kin, Wp, Y1, n1, Y2, n2, acc2, rows, tiles, qc);
+    linear_kernel<NT><<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(X, kin, Wp, Y1, n1, Y2, n2, acc2, rows, pl.tiles, pl.qc);
     return launched("tspgnn_linear_f32");
 }
 
@@ -792,50 +764,78 @@ static int launch_lnlstm_bwd(const tspgnn_lstm_bwd_task* tasks, int n, hipStream
 
 template <int D, int MAXL>
 static int launch_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n, hipStream_t st) {
+    tspgnn_tasks_plan pl;
+    plan_mlp_bwd(tasks, n, D, n_cus(), &pl);
     MlpBwdTaskTable tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        const long long tiles = tiles16(tasks[k].rows);
-        cost[k] = tiles * tasks[k].n_layers;
-        tiles_all += tiles;
+        tt.blk_end[k] = pl.blk_end[k];
     }
     tt.n = n;
-    const int lds_bytes = MAXL * D * D * 4 + 16;
-    const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
-    int grid = n_cus() * per_cu;
-    const int nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
     // (one flag per launch: the tasks of a launch come from one tape)
-    if (tasks[0].acts_bf16) mlp_bwd_kernel<D, MAXL, true><<<grid, nw * 64, 0, st>>>(tt);
-    else mlp_bwd_kernel<D, MAXL, false><<<grid, nw * 64, 0, st>>>(tt);
+    if (tasks[0].acts_bf16) mlp_bwd_kernel<D, MAXL, true><<<pl.grid, pl.nw * 64, 0, st>>>(tt);
+    else mlp_bwd_kernel<D, MAXL, false><<<pl.grid, pl.nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_bwd_f32");
 }
 
-template <int AV, int BV>
-static int launch_wgrad(const float* X, const float* dY, long long rows, int kin, int nout, float* P, float* Pb,
-                        int n_chunks, long long chunk_rows, hipStream_t st) {
-    const int nob = (kin / (16 * AV)) * (nout / (16 * BV));
-    const long long waves = (long long)n_chunks * nob;
-    const unsigned grid = (unsigned)((waves + 3) / 4);
-    wgrad_kernel<AV, BV><<<grid, 256, 0, st>>>(X, dY, rows, kin, nout, P, Pb, n_chunks, chunk_rows);
-    return launched("tspgnn_wgrad_f32");
+// First stage of tspgnn_wgrad_f32 / tspgnn_wgrad_bf16x_f32 (XB): the kernel the plan names, partials into P / Pb.
+template <bool XB>
+static void launch_wgrad(const tspgnn_wgrad_plan& pl, const float* X, const float* dY, long long rows, int kin, int nout,
+                         float* P, float* Pb, hipStream_t st) {
+    const int nc = pl.n_chunks;
+    const long long cr = pl.chunk_rows;
+    if (pl.kernel == TSPGNN_WGRAD_X3_PAIR) {
+        wgrad_x3_kernel<XB, XB ? 2 : 1><<<pl.grid, 256, 0, st>>>(X, dY, rows, kin, nout, P, Pb, nc, cr, pl.launch_nob > 4);
+        return;
+    }
+    if (pl.kernel == TSPGNN_WGRAD_X3) {
+        wgrad_x3_kernel<XB, 1><<<pl.grid, 256, 0, st>>>(X, dY, rows, kin, nout, P, Pb, nc, cr, pl.launch_nob > 4);
+        return;
+    }
+    if constexpr (!XB) {
+#define TSPGNN_WG(A, B) \
+    if (pl.av == A && pl.bv == B) wgrad_kernel<A, B><<<pl.grid, 256, 0, st>>>(X, dY, rows, kin, nout, P, Pb, nc, cr)
+        TSPGNN_WG(4, 4); TSPGNN_WG(4, 2); TSPGNN_WG(4, 1);
+        TSPGNN_WG(2, 4); TSPGNN_WG(2, 2); TSPGNN_WG(2, 1);
+        TSPGNN_WG(1, 4); TSPGNN_WG(1, 2); TSPGNN_WG(1, 1);
+#undef TSPGNN_WG
+    }
+}
+
+// tspgnn_wgrad_f32 / tspgnn_wgrad_bf16x_f32 behind their validation: plan, first stage, fixed-order second stage.
+template <bool XB>
+static int wgrad(const float* X, const float* dY, long long rows, int kin, int nout, float* dW, float* db, float* workspace,
+                 hipStream_t st, const char* what, const char* what_reduce) {
+    tspgnn_wgrad_plan pl;
+    plan_wgrad(rows, kin, nout, XB, n_cus(), &pl);
+    float* P = workspace;
+    float* Pb = db ? workspace + (size_t)pl.n_chunks * kin * nout : nullptr;
+    launch_wgrad<XB>(pl, X, dY, rows, kin, nout, P, Pb, st);
+    const int rc = launched(what);
+    if (rc) return rc;
+    const int n = kin * nout;
+    reduce_partials2(P, pl.n_chunks, n, dW, n, Pb, nout, db, db ? nout : 0, 1.0f, 1, st);   // (the bias row in the same launch)
+    return launched(what_reduce);
 }
 
 }  // namespace tspgnn
 
 using namespace tspgnn;
 
-extern "C" int tspgnn_linear_f32(const float* X, int kin, const float* Wp, float* Y1, int n1, float* Y2, int n2,
-                                 int accumulate2, int rows, void* stream) {
+static int check_linear_shape(int kin, int n1, int n2, int rows) {
     TSPGNN_REQUIRE(rows >= 0, "linear: rows=%d", rows);
     TSPGNN_REQUIRE(kin > 0 && kin % 16 == 0, "linear: kin=%d must be a positive multiple of 16", kin);
     TSPGNN_REQUIRE(n1 >= 0 && n2 >= 0 && n1 % 16 == 0 && n2 % 16 == 0, "linear: n1=%d n2=%d must be multiples of 16", n1,
                    n2);
+    TSPGNN_REQUIRE(n1 + n2 == 64 || n1 + n2 == 128 || n1 + n2 == 256, "linear: n1+n2=%d must be 64, 128 or 256", n1 + n2);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_linear_f32(const float* X, int kin, const float* Wp, float* Y1, int n1, float* Y2, int n2,
+                                 int accumulate2, int rows, void* stream) {
+    const int rc = check_linear_shape(kin, n1, n2, rows);
+    if (rc || rows == 0) return rc;
     const int nout = n1 + n2;
-    TSPGNN_REQUIRE(nout == 64 || nout == 128 || nout == 256, "linear: n1+n2=%d must be 64, 128 or 256", nout);
-    if (rows == 0) return TSPGNN_OK;
     TSPGNN_REQUIRE(X && Wp && (n1 == 0 || Y1) && (n2 == 0 || Y2), "linear: null pointer");
     hipStream_t st = as_stream(stream);
     switch (nout) {
@@ -920,76 +920,72 @@ extern "C" int tspgnn_mlp_bwd_f32(const float* dY, const float* wt, const float*
 
 extern "C" long long tspgnn_wgrad_workspace_floats(long long rows, int kin, int nout) {
     if (rows <= 0 || kin <= 0 || nout <= 0 || kin % 16 || nout % 16) return 0;
-    int nc;
-    long long cr;
-    wgrad_plan(rows, kin, nout, &nc, &cr);
-    return (long long)nc * ((long long)kin * nout + nout);
+    tspgnn_wgrad_plan pl;
+    plan_wgrad(rows, kin, nout, false, n_cus(), &pl);
+    return (long long)pl.n_chunks * ((long long)kin * nout + nout);
+}
+
+// the shape requirements of tspgnn_wgrad_f32 / tspgnn_wgrad_bf16x_f32 (p: the prefix of the messages)
+static int check_wgrad_shape(long long rows, int kin, int nout, bool bf16x, const char* p) {
+    TSPGNN_REQUIRE(rows >= 0, "%s: rows=%lld", p, rows);
+    if (bf16x && (kin <= 0 || nout <= 0 || kin % 64 || nout % 64))
+        return fail(TSPGNN_EUNSUPPORTED, "%s: kin=%d and nout=%d must be positive multiples of 64", p, kin, nout);
+    TSPGNN_REQUIRE(kin > 0 && kin % 16 == 0 && nout > 0 && nout % 16 == 0,
+                   "%s: kin=%d and nout=%d must be positive multiples of 16", p, kin, nout);
+    return TSPGNN_OK;
 }
 
 extern "C" int tspgnn_wgrad_bf16x_f32(const void* X, const float* dY, long long rows, int kin, int nout, float* dW,
                                       float* db, float* workspace, void* stream) {
-    TSPGNN_REQUIRE(rows >= 0, "wgrad_bf16x: rows=%lld", rows);
-    if (kin <= 0 || nout <= 0 || kin % 64 || nout % 64)
-        return fail(TSPGNN_EUNSUPPORTED, "wgrad_bf16x: kin=%d and nout=%d must be positive multiples of 64", kin, nout);
-    if (rows == 0) return TSPGNN_OK;
+    const int rc = check_wgrad_shape(rows, kin, nout, true, "wgrad_bf16x");
+    if (rc || rows == 0) return rc;
     TSPGNN_REQUIRE(X && dY && dW && workspace, "wgrad_bf16x: null pointer");
-    int nc;
-    long long cr;
-    wgrad_plan(rows, kin, nout, &nc, &cr);
-    float* P = workspace;
-    float* Pb = db ? workspace + (size_t)nc * kin * nout : nullptr;
-    hipStream_t st = as_stream(stream);
-    if (kin % 128 == 0) {   // two X blocks per wavefront: every dY value is split once per 128 features
-        const int nob = (kin / 128) * (nout / 64);
-        const unsigned grid = (unsigned)(((long long)nc * nob + 3) / 4);
-        wgrad_x3_kernel<true, 2><<<grid, 256, 0, st>>>(reinterpret_cast<const float*>(X), dY, rows, kin, nout, P, Pb, nc, cr,
-                                                      nob > 4);
-    } else {
-        const int nob = (kin / 64) * (nout / 64);
-        const unsigned grid = (unsigned)(((long long)nc * nob + 3) / 4);
-        wgrad_x3_kernel<true, 1><<<grid, 256, 0, st>>>(reinterpret_cast<const float*>(X), dY, rows, kin, nout, P, Pb, nc, cr,
-                                                      nob > 4);
-    }
-    int rc = launched("tspgnn_wgrad_bf16x_f32");
-    if (rc) return rc;
-    const int n = kin * nout;
-    reduce_partials2(P, nc, n, dW, n, Pb, nout, db, db ? nout : 0, 1.0f, 1, st);
-    return launched("tspgnn_wgrad_bf16x_f32(reduce)");
+    return wgrad<true>(reinterpret_cast<const float*>(X), dY, rows, kin, nout, dW, db, workspace, as_stream(stream),
+                       "tspgnn_wgrad_bf16x_f32", "tspgnn_wgrad_bf16x_f32(reduce)");
 }
 
 extern "C" int tspgnn_wgrad_f32(const float* X, const float* dY, long long rows, int kin, int nout, float* dW,
                                 float* db, float* workspace, void* stream) {
-    TSPGNN_REQUIRE(rows >= 0, "wgrad: rows=%lld", rows);
-    TSPGNN_REQUIRE(kin > 0 && kin % 16 == 0 && nout > 0 && nout % 16 == 0,
-                   "wgrad: kin=%d and nout=%d must be positive multiples of 16", kin, nout);
-    if (rows == 0) return TSPGNN_OK;
+    const int rc = check_wgrad_shape(rows, kin, nout, false, "wgrad");
+    if (rc || rows == 0) return rc;
     TSPGNN_REQUIRE(X && dY && dW && workspace, "wgrad: null pointer");
-    int nc;
-    long long cr;
-    wgrad_plan(rows, kin, nout, &nc, &cr);
-    float* P = workspace;
-    float* Pb = db ? workspace + (size_t)nc * kin * nout : nullptr;
-    hipStream_t st = as_stream(stream);
-    const int av = pick_vec(kin), bv = pick_vec(nout);
-    int rc;
-#define TSPGNN_WG(A, B) rc = launch_wgrad<A, B>(X, dY, rows, kin, nout, P, Pb, nc, cr, st)
-    if (av == 4 && bv == 4 && rows >= 4096) {   // the big reductions over T*rows: bf16 matrix cores, fp32-class accuracy
-        const int nob = (kin / 64) * (nout / 64);
-        const unsigned grid = (unsigned)(((long long)nc * nob + 3) / 4);
-        wgrad_x3_kernel<false, 1><<<grid, 256, 0, st>>>(X, dY, rows, kin, nout, P, Pb, nc, cr, nob > 4);
-        rc = launched("tspgnn_wgrad_f32");
-    } else if (av == 4 && bv == 4) TSPGNN_WG(4, 4);
-    else if (av == 4 && bv == 2) TSPGNN_WG(4, 2);
-    else if (av == 4 && bv == 1) TSPGNN_WG(4, 1);
-    else if (av == 2 && bv == 4) TSPGNN_WG(2, 4);
-    else if (av == 2 && bv == 2) TSPGNN_WG(2, 2);
-    else if (av == 2 && bv == 1) TSPGNN_WG(2, 1);
-    else if (av == 1 && bv == 4) TSPGNN_WG(1, 4);
-    else if (av == 1 && bv == 2) TSPGNN_WG(1, 2);
-    else TSPGNN_WG(1, 1);
-#undef TSPGNN_WG
-    if (rc) return rc;
-    const int n = kin * nout;
-    reduce_partials2(P, nc, n, dW, n, Pb, nout, db, db ? nout : 0, 1.0f, 1, st);   // (the bias row in the same launch)
-    return launched("tspgnn_wgrad_f32(reduce)");
+    return wgrad<false>(X, dY, rows, kin, nout, dW, db, workspace, as_stream(stream), "tspgnn_wgrad_f32",
+                        "tspgnn_wgrad_f32(reduce)");
 }
+
+// ------------------------------------------------------------------------------------------------- plan queries
+// (host only: the planners of launch_plan.h behind the validation of the entries' shape fields)
+
+extern "C" int tspgnn_plan_linear(int kin, int n1, int n2, int rows, int cus, tspgnn_linear_plan* out) {
+    TSPGNN_REQUIRE(out && cus >= 0, "plan_linear: cus=%d", cus);
+    *out = tspgnn_linear_plan{};
+    const int rc = check_linear_shape(kin, n1, n2, rows);
+    if (rc || rows == 0) return rc;
+    plan_linear(kin, (n1 + n2) / 16, rows, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out) {
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "plan_mlp_bwd: 1..%d tasks", kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "plan_mlp_bwd: d=%d must be 32, 64 or 128", d);
+    TSPGNN_REQUIRE(cus >= 0, "plan_mlp_bwd: cus=%d", cus);
+    *out = tspgnn_tasks_plan{};
+    tspgnn_mlp_bwd_task live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n,
+                               [d](const tspgnn_mlp_bwd_task& t) { return check_mlp_bwd_shape(t, d, "plan_mlp_bwd"); });
+    if (rc || n == 0) return rc;
+    plan_mlp_bwd(live, n, d, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_wgrad(long long rows, int kin, int nout, int bf16x, int cus, tspgnn_wgrad_plan* out) {
+    TSPGNN_REQUIRE(out && cus >= 0, "plan_wgrad: cus=%d", cus);
+    *out = tspgnn_wgrad_plan{};
+    const int rc = check_wgrad_shape(rows, kin, nout, bf16x != 0, "plan_wgrad");
+    if (rc || rows == 0) return rc;
+    plan_wgrad(rows, kin, nout, bf16x != 0, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_reduce_slices(int n_chunks) { return reduce_slices(n_chunks); }

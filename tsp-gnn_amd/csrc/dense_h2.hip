@@ -553,137 +553,42 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTa
 template <int D>
 static int launch_mlp_h2(const tspgnn_mlp_task* tasks, int n, hipStream_t st, const float* head_w = nullptr,
                          const float* head_b = nullptr, float* head_y = nullptr) {
+    tspgnn_tasks_plan pl;
+    plan_mlp_fwd(tasks, n, n_cus(), &pl);
     MlpTaskTableH2 tt;
     tt.head_w = head_w;
     tt.head_b = head_b;
     tt.head_y = head_y;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += tiles16(tasks[k].rows);
+        tt.blk_end[k] = pl.blk_end[k];
     }
     tt.n = n;
-    int grid = n_cus();
-    int nw = 16;
-    if (tiles_all <= (long long)grid * 16) nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
-    mlp_fwd_h2_kernel<D><<<grid, nw * 64, 0, st>>>(tt);
+    mlp_fwd_h2_kernel<D><<<pl.grid, pl.nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_fwd_multi_h2");
-}
-
-// Working wavefronts per workgroup of a lock-step task (development switch TSPGNN_H2_LOCK_TILES; default: all of them --
-// 8 / 6 / 4 measured 40.3 / 54.1 / 52.3 us per C2 launch against 37.9: the edge task misses the CUs more than the vertex
-// chain gains from emptier matrix pipes).
-static int h2_lock_tiles() {
-    static const int v = [] {
-        const char* e = getenv("TSPGNN_H2_LOCK_TILES");
-        const int x = e ? atoi(e) : 0;
-        return (x >= 1 && x <= 16) ? x : 16;
-    }();
-    return v;
 }
 
 template <int D>
 static int launch_cell_h2(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t st, const char* what) {
-    const size_t head = (10 * D + 4) * sizeof(float);
-    const size_t per_kb = (size_t)2 * 32 * 4 * D * 2;  // bytes of one k-block, two pieces
-    const size_t budget = 160 * 1024 - head;
-    const size_t layer_all = 2 * D * D * 2 + D * 4, proj_bytes = (size_t)2 * D * 4 * D * 2;
+    tspgnn_cell_fwd_plan pl;
+    const int bad = plan_cell_fwd(tasks, n, D, TSPGNN_ARITH_H2, n_cus(), &pl);
+    if (bad >= 0) return cell_does_not_fit(tasks[bad], D, what);
     CellTaskTableH2 tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        const tspgnn_lstm_task& c = tasks[k].cell;
-        const int L = tasks[k].mlp_layers;
-        const int KBT = (c.dx + D) / 32;
-        const size_t k_bytes = (size_t)KBT * per_kb;
-        size_t need;
-        tt.together[k] = 0;
-        tt.lock_tiles[k] = 0;
-        if (k_bytes + L * layer_all <= budget && !tasks[k].proj_w) {
-            tt.kbc[k] = KBT;
-            tt.lockstep[k] = 0;
-            need = k_bytes + L * layer_all;
-        } else {
-            const int kbc = k_bytes <= budget ? KBT : (int)(budget / per_kb);
-            if (kbc < 1 || L * layer_all > budget || (tasks[k].proj_w && proj_bytes > budget))
-                return fail(TSPGNN_EUNSUPPORTED, "%s: dx=%d, d=%d, %d MLP layers do not fit LDS", what, c.dx, D, L);
-            tt.kbc[k] = kbc;
-            tt.lockstep[k] = 1;
-            need = (size_t)kbc * per_kb;
-            size_t second = L * layer_all;
-            if (tasks[k].proj_w) {
-                if (L * layer_all + proj_bytes <= budget) {
-                    tt.together[k] = 1;
-                    second += proj_bytes;
-                } else if (proj_bytes > second) {
-                    second = proj_bytes;
-                }
-            }
-            if (second > need) need = second;
-        }
-        if (need > lds_w) lds_w = need;
-        const long long tiles = tiles16(c.rows);
-        cost[k] = tiles * (KBT * 4 + 2 * L + (tasks[k].proj_w ? 8 : 0) + 8);
-        tiles_all += tiles;
+        tt.blk_end[k] = pl.blk_end[k];
+        tt.kbc[k] = pl.kbc[k];
+        tt.lockstep[k] = pl.lockstep[k];
+        tt.together[k] = pl.together[k];
+        tt.lock_tiles[k] = pl.lock_tiles[k];
     }
     tt.n = n;
-    const size_t lds_bytes = lds_w + head;
-    int grid = n_cus();
-    const int nw_max = 12;
-    const int nw = tiles_all <= (long long)grid * 4 ? 4 : (tiles_all <= (long long)grid * 8 ? 8 : nw_max);
-    grid = clamp_grid(grid, tiles_all, nw);
-    {
-        // A lock-step task is a latency chain (two LDS stagings per round) that the resident tasks of the launch hide.
-        // It gets the workgroups of a whole number of rounds -- ONE round while that stays within about twice its share
-        // of the grid by cost (more workgroups would idle, fewer would double the chain: C2's 320 vertex tiles take 27
-        // of 256), otherwise as many rounds as bring it back to its share (C4's 1 586 vertex tiles: 5 rounds on 27
-        // workgroups instead of starving the edge task of 133); the resident tasks share the rest by cost.
-        // (Figures at 256 CUs and 12 working wavefronts, from tests/plan_replay.py: cell_fwd_plan.)
-        long long total_cost = 0;
-        for (int k = 0; k < n; ++k) total_cost += cost[k] > 0 ? cost[k] : 1;
-        int fixed[kMaxTasks];
-        for (int k = 0; k < n; ++k) {
-            fixed[k] = 0;
-            if (tt.lockstep[k]) {
-                const long long tiles = tiles16(tasks[k].cell.rows);
-                const int lw = nw < h2_lock_tiles() ? nw : h2_lock_tiles();
-                tt.lock_tiles[k] = lw;
-                const long long per_round = (tiles + lw - 1) / lw;
-                long long share = (2 * cost[k] * grid + total_cost - 1) / total_cost;  // twice the proportional share
-                if (share < 1) share = 1;
-                const long long n_rounds = (per_round + share - 1) / share;
-                fixed[k] = (int)((per_round + n_rounds - 1) / n_rounds);
-            }
-        }
-        grid = split_blocks_fixed(cost, fixed, n, grid, tt.blk_end);
-    }
-    bool centered = true, loop_buffers = false;
-    long long out_bytes = 0;   // h', c' of every task and its messages: what the launch stores (and the next ones re-read)
-    for (int k = 0; k < n; ++k) {
-        centered = centered && tasks[k].cell.z_centered != 0;
-        out_bytes += (long long)tasks[k].cell.rows * D * 4 * (tasks[k].mlp_out ? 3 : 2);
-        loop_buffers = loop_buffers || tasks[k].state_out_blocked != 0 || tasks[k].mlp_out != nullptr || tasks[k].proj_out != nullptr;
-    }
-    // write-through output stores while the loop's arrays (two copies of the states, two of the messages: ~2x out_bytes)
-    // stay inside the 256 MB Infinity Cache; plain stores beyond (see st4o) -- and for a launch that writes nothing the next
-    // step's launch reads from these buffers (no blocked state, no messages: the training forward's cell launch stores
-    // into the tape, which the backward reads much later -- C2 training step 10.25-10.27 -> 10.12-10.16 ms)
-    static const int wt_forced = [] {   // (development switch TSPGNN_H2_WT=0/1)
-        const char* e = getenv("TSPGNN_H2_WT");
-        return e ? atoi(e) : -1;
-    }();
-    const bool wt = wt_forced >= 0 ? wt_forced != 0 : (loop_buffers && 2 * out_bytes <= (long long)200 * 1024 * 1024);
     void (*fn)(const CellTaskTableH2) =
-        centered ? (wt ? &lnlstm_mlp_fwd_h2_kernel<D, true, true> : &lnlstm_mlp_fwd_h2_kernel<D, true, false>)
-                 : (wt ? &lnlstm_mlp_fwd_h2_kernel<D, false, true> : &lnlstm_mlp_fwd_h2_kernel<D, false, false>);
-    const int rc = set_dynamic_lds(fn, lds_bytes, what, true);
+        pl.centered ? (pl.wt ? &lnlstm_mlp_fwd_h2_kernel<D, true, true> : &lnlstm_mlp_fwd_h2_kernel<D, true, false>)
+                    : (pl.wt ? &lnlstm_mlp_fwd_h2_kernel<D, false, true> : &lnlstm_mlp_fwd_h2_kernel<D, false, false>);
+    const int rc = set_dynamic_lds(fn, pl.lds_bytes, what, true);
     if (rc) return rc;
-    fn<<<grid, nw * 64, lds_bytes, st>>>(tt);
+    fn<<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(tt);
     return launched(what);
 }
 
@@ -773,4 +678,43 @@ extern "C" int tspgnn_lnlstm_fwd_multi_h2(const tspgnn_lstm_task* tasks, int n_t
         wrapped[k].cell = tasks[k];
     }
     return cell_mlp_h2(wrapped, n_tasks, d, stream, "tspgnn_lnlstm_fwd_multi_h2");
+}
+
+// ------------------------------------------------------------------------------------------------- plan queries
+// (host only: the planners of launch_plan.h behind the validation of the entries' shape fields)
+
+extern "C" int tspgnn_plan_mlp_fwd(const tspgnn_mlp_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out) {
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "plan_mlp_fwd: 1..%d tasks", kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64, "plan_mlp_fwd: d=%d must be 32 or 64", d);
+    TSPGNN_REQUIRE(cus >= 0, "plan_mlp_fwd: cus=%d", cus);
+    *out = tspgnn_tasks_plan{};
+    tspgnn_mlp_task live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [](const tspgnn_mlp_task& t) { return check_mlp_shape(t, "plan_mlp_fwd"); });
+    if (rc || n == 0) return rc;
+    plan_mlp_fwd(live, n, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_cell_fwd(const tspgnn_cell_mlp_task* tasks, int n_tasks, int d, int arith, int cus,
+                                    tspgnn_cell_fwd_plan* out) {
+    const char* what = "plan_cell_fwd";
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64, "%s: d=%d must be 32 or 64", what, d);
+    TSPGNN_REQUIRE(arith == TSPGNN_ARITH_H2 || arith == TSPGNN_ARITH_X3, "%s: arith=%d", what, arith);
+    TSPGNN_REQUIRE(cus >= 0, "%s: cus=%d", what, cus);
+    *out = tspgnn_cell_fwd_plan{};
+    tspgnn_cell_mlp_task live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [d, what](const tspgnn_cell_mlp_task& t) {
+        const int rc = check_cell_mlp_shape(t, d, what);
+        if (rc || t.cell.rows == 0) return rc;
+        TSPGNN_REQUIRE(!t.proj_w || t.mlp_layers > 0, "%s: a projection needs at least one MLP layer", what);
+        return TSPGNN_OK;
+    });
+    if (rc || n == 0) return rc;
+    const int bad = plan_cell_fwd(live, n, d, arith, cus ? cus : n_cus(), out);
+    if (bad < 0) return TSPGNN_OK;
+    *out = tspgnn_cell_fwd_plan{};
+    return cell_does_not_fit(live[bad], d, what);
 }

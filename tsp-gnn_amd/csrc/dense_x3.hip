@@ -505,82 +505,34 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_x3_kernel(const CellTaskTa
 
 template <int D>
 static int launch_mlp_x3(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
+    tspgnn_tasks_plan pl;
+    plan_mlp_fwd(tasks, n, n_cus(), &pl);
     MlpTaskTableX3 tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += tiles16(tasks[k].rows);
+        tt.blk_end[k] = pl.blk_end[k];
     }
     tt.n = n;
-    int grid = n_cus();
-    int nw = 16;
-    if (tiles_all <= (long long)grid * 16) nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
-    mlp_fwd_x3_kernel<D><<<grid, nw * 64, 0, st>>>(tt);
+    mlp_fwd_x3_kernel<D><<<pl.grid, pl.nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_fwd_multi_x3");
 }
 
 template <int D>
 static int launch_cell_x3(const tspgnn_cell_mlp_task* tasks, int n, hipStream_t st, const char* what) {
-    const size_t head = (10 * D + 4) * sizeof(float);
-    const size_t per_kb = (size_t)3 * 32 * 4 * D * 2;  // bytes of one k-block, three pieces
-    const size_t budget = 160 * 1024 - head;
-    const size_t layer_hm = (size_t)2 * D * D * 2, layer_lo = (size_t)D * D * 2, layer_all = 3 * D * D * 2 + D * 4;
+    tspgnn_cell_fwd_plan pl;
+    const int bad = plan_cell_fwd(tasks, n, D, TSPGNN_ARITH_X3, n_cus(), &pl);
+    if (bad >= 0) return cell_does_not_fit(tasks[bad], D, what);
     CellTaskTableX3 tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        const tspgnn_lstm_task& c = tasks[k].cell;
-        const int L = tasks[k].mlp_layers;
-        const int KBT = (c.dx + D) / 32;
-        const size_t k_bytes = (size_t)KBT * per_kb;
-        const size_t mlp_min = L * (layer_hm + D * 4);  // resident: hi, mid and biases must be in LDS
-        size_t need;
-        if (k_bytes + mlp_min <= budget && !tasks[k].proj_w) {
-            tt.kbc[k] = KBT;
-            int n_lo = (int)((budget - k_bytes - mlp_min) / layer_lo);
-            if (n_lo > L) n_lo = L;
-            tt.n_lo_lds[k] = n_lo;
-            need = k_bytes + mlp_min + n_lo * layer_lo;
-        } else {
-            int kbc = k_bytes <= budget ? KBT : (int)(budget / per_kb);
-            if (kbc >= KBT) kbc = KBT - 1;  // lock-step mode is selected by kbc < KBT
-            if (kbc < 1 || L * layer_all > budget || (tasks[k].proj_w && (size_t)3 * D * 4 * D * 2 > budget))
-                return fail(TSPGNN_EUNSUPPORTED, "%s: dx=%d, d=%d, %d MLP layers do not fit LDS", what, c.dx, D, L);
-            tt.kbc[k] = kbc;
-            tt.n_lo_lds[k] = L;
-            need = (size_t)kbc * per_kb;
-            if (L * layer_all > need) need = L * layer_all;
-            if (tasks[k].proj_w && (size_t)3 * D * 4 * D * 2 > need) need = (size_t)3 * D * 4 * D * 2;
-        }
-        if (need > lds_w) lds_w = need;
-        const long long tiles = tiles16(c.rows);
-        cost[k] = tiles * (KBT * 4 + 2 * L + (tasks[k].proj_w ? 8 : 0) + 6);
-        tiles_all += tiles;
+        tt.blk_end[k] = pl.blk_end[k];
+        tt.kbc[k] = pl.kbc[k];
+        tt.n_lo_lds[k] = pl.n_lo_lds[k];
     }
     tt.n = n;
-    const size_t lds_bytes = lds_w + head;
-    int grid = n_cus();
-    const int nw = tiles_all <= (long long)grid * 4 ? 4 : (tiles_all <= (long long)grid * 8 ? 8 : 12);
-    grid = clamp_grid(grid, tiles_all, nw);
-    {
-        // A lock-step task is a latency chain (several LDS re-stagings per round) that the resident tasks of the
-        // launch hide: it gets exactly the workgroups of ONE round (more would idle, fewer would double the chain),
-        // capped at half the grid; the resident tasks share the rest in proportion to their cost.
-        int fixed[kMaxTasks];
-        for (int k = 0; k < n; ++k) {
-            const bool lock = tt.kbc[k] < (tasks[k].cell.dx + D) / 32;
-            fixed[k] = lock ? (int)((tiles16(tasks[k].cell.rows) + nw - 1) / nw) : 0;
-        }
-        grid = split_blocks_fixed(cost, fixed, n, grid, tt.blk_end);
-    }
-    const int rc = set_dynamic_lds(&lnlstm_mlp_fwd_x3_kernel<D>, lds_bytes, what, true);
+    const int rc = set_dynamic_lds(&lnlstm_mlp_fwd_x3_kernel<D>, pl.lds_bytes, what, true);
     if (rc) return rc;
-    lnlstm_mlp_fwd_x3_kernel<D><<<grid, nw * 64, lds_bytes, st>>>(tt);
+    lnlstm_mlp_fwd_x3_kernel<D><<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(tt);
     return launched(what);
 }
 

@@ -1,8 +1,13 @@
-// Host side of the multi-task launches (tspgnn_*_multi_*), in one place: validating the tasks and dropping the empty ones,
-// pricing them in 16-row tiles, clamping the grid and handing each task a contiguous share of the workgroups (blk_end[]).
-// What is measured per kernel -- wavefronts per workgroup, workgroups per CU, LDS budgets, the cost formulas -- stays in
-// the launcher beside that kernel.  Host-only: nothing here is seen by device code.
+// Host side of the launches, in one place: validating the tasks and dropping the empty ones, pricing them in 16-row tiles,
+// clamping the grid, handing each task a contiguous share of the workgroups (blk_end[]) -- and the PLANNERS: per kernel, a
+// pure function of (task shapes, which pointers are null, width, CUs) that fills the plan structure of include/tspgnn.h with
+// everything the launcher decides before its <<<>>>.  A launcher calls its planner with n_cus() taken once, copies the plan
+// into the kernel's task table and launches; the tspgnn_plan_* queries answer the same planner to the tests.  What is
+// measured per kernel -- wavefronts per workgroup, workgroups per CU, LDS budgets, the cost formulas -- stands in that
+// kernel's planner.  Host-only: nothing here is seen by device code.
 #pragma once
+#include <stdlib.h>
+
 #include "common.h"
 
 namespace tspgnn {
@@ -34,15 +39,16 @@ inline int split_blocks(const long long* cost, int n, int grid, int* blk_end) {
 
 // The same with some tasks at a set size: a task with fixed[k] > 0 gets exactly that many workgroups, the others share
 // grid - sum(fixed) by cost.  The plain split when no task or every task is fixed, or the fixed ones would take more than
-// half the grid.
-inline int split_blocks_fixed(const long long* cost, const int* fixed, int n, int grid, int* blk_end) {
+// half the grid; *kept_fixed says which of the two ran.
+inline int split_blocks_fixed(const long long* cost, const int* fixed, int n, int grid, int* blk_end, int* kept_fixed) {
     int fixed_sum = 0, n_res = 0;
     long long res_cost[kMaxTasks];
     for (int k = 0; k < n; ++k) {
         fixed_sum += fixed[k];
         if (!fixed[k]) res_cost[n_res++] = cost[k];
     }
-    if (n_res == 0 || fixed_sum == 0 || fixed_sum > grid / 2) return split_blocks(cost, n, grid, blk_end);
+    *kept_fixed = !(n_res == 0 || fixed_sum == 0 || fixed_sum > grid / 2);
+    if (!*kept_fixed) return split_blocks(cost, n, grid, blk_end);
     int res_end[kMaxTasks];
     split_blocks(res_cost, n_res, grid - fixed_sum, res_end);
     int used = 0, j = 0;
@@ -126,13 +132,19 @@ int check_mlp_task(Task& t, int d, const char* p) {
     return TSPGNN_OK;
 }
 
-// tspgnn_mlp_bwd_task; first_live: the launch's first task with rows > 0 so far (NULL: none).  A task with pre_X may come
-// without dY (the f16x2 entry; the fp32 entry rejects pre_X itself).
-inline int check_mlp_bwd_task(tspgnn_mlp_bwd_task& t, int d, const tspgnn_mlp_bwd_task* first_live, const char* p) {
+// tspgnn_mlp_bwd_task: what holds for an empty task too
+inline int check_mlp_bwd_shape(const tspgnn_mlp_bwd_task& t, int d, const char* p) {
     const int rc = check_mlp_shape(t, p);
     if (rc) return rc;
     if (d == 128 && t.n_layers > 2) return fail(TSPGNN_EUNSUPPORTED, "%s: d=128 holds at most 2 layers in LDS (got %d)", p, t.n_layers);
-    if (t.rows == 0) return TSPGNN_OK;
+    return TSPGNN_OK;
+}
+
+// tspgnn_mlp_bwd_task; first_live: the launch's first task with rows > 0 so far (NULL: none).  A task with pre_X may come
+// without dY (the f16x2 entry; the fp32 entry rejects pre_X itself).
+inline int check_mlp_bwd_task(tspgnn_mlp_bwd_task& t, int d, const tspgnn_mlp_bwd_task* first_live, const char* p) {
+    const int rc = check_mlp_bwd_shape(t, d, p);
+    if (rc || t.rows == 0) return rc;
     TSPGNN_REQUIRE((t.dY || t.pre_X) && t.wt, "%s: null pointer", p);
     const unsigned inner = t.relu_mask & ((1u << (t.n_layers - 1)) - 1u);
     TSPGNN_REQUIRE(!inner || t.acts, "%s: relu layers need the saved activations", p);
@@ -149,16 +161,23 @@ inline int check_rows_32bit(int rows, int dx, int d, const char* p) {
     return TSPGNN_OK;
 }
 
-// tspgnn_cell_mlp_task (f16x2, bf16x3).  c == NULL passes here: the zero cell state of a run's first step for the f16x2
-// kernel, which reads nothing then; so do outputs that alias the inputs.
-inline int check_cell_mlp_task(const tspgnn_cell_mlp_task& ct, int d, const char* p) {
+// tspgnn_cell_mlp_task (f16x2, bf16x3): the shape fields, what holds for an empty task too
+inline int check_cell_mlp_shape(const tspgnn_cell_mlp_task& ct, int d, const char* p) {
     const tspgnn_lstm_task& t = ct.cell;
     TSPGNN_REQUIRE(t.rows >= 0, "%s: rows=%d", p, t.rows);
     const int rc = check_rows_32bit(t.rows, t.dx, d, p);
     if (rc) return rc;
     TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "%s: dx=%d must be a non-negative multiple of 32", p, t.dx);
     TSPGNN_REQUIRE(ct.mlp_layers >= 0 && ct.mlp_layers <= 4, "%s: mlp_layers=%d must be in 0..4", p, ct.mlp_layers);
-    if (t.rows == 0) return TSPGNN_OK;
+    return TSPGNN_OK;
+}
+
+// tspgnn_cell_mlp_task (f16x2, bf16x3).  c == NULL passes here: the zero cell state of a run's first step for the f16x2
+// kernel, which reads nothing then; so do outputs that alias the inputs.
+inline int check_cell_mlp_task(const tspgnn_cell_mlp_task& ct, int d, const char* p) {
+    const tspgnn_lstm_task& t = ct.cell;
+    const int rc = check_cell_mlp_shape(ct, d, p);
+    if (rc || t.rows == 0) return rc;
     TSPGNN_REQUIRE(t.h && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x), "%s: null pointer", p);
     TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "%s: gather-init mode needs dx == 0 and Zx", p);
     TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "%s: zbias needs zscale and excludes gather-init mode", p);
@@ -181,6 +200,285 @@ inline int check_lstm_bwd_task(const tspgnn_lstm_bwd_task& t, int d, bool fp32_m
     else
         TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "%s: gather-init mode needs dx == 0 and Zx", p);
     return TSPGNN_OK;
+}
+
+// -------------------------------------------------------------------------------------------------------- planners
+// Pure: no HIP call, no allocation, no global state but the two development switches below (read once).  `tasks` are the
+// live tasks (rows > 0) of a launch, validated; `cus` the CU count.
+
+// S of reduce_partials2: slices of the chunk range per workgroup (blockDim.x * S == 256)
+inline int reduce_slices(int n_chunks) { return n_chunks >= 64 ? 16 : (n_chunks >= 8 ? 4 : 1); }
+
+// Workgroups of a launch that caps its grid and strides over the rest: clamp(ceil(total / per_block), 1, cap)
+inline int strided_blocks(long long total, int per_block, int cap) {
+    const long long blocks = (total + per_block - 1) / per_block;
+    return blocks > cap ? cap : (blocks < 1 ? 1 : (int)blocks);
+}
+
+// blk_end[] of the tasks by cost over the clamped grid: the tail of the planners that only share out workgroups
+inline void plan_tasks(const long long* cost, long long tiles_all, int n, int grid, int nw, tspgnn_tasks_plan* p) {
+    p->nw = nw;
+    p->n = n;
+    p->grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), p->blk_end);
+}
+
+// tspgnn_linear_f32; nt = (n1 + n2) / 16
+inline void plan_linear(int kin, int nt, int rows, int cus, tspgnn_linear_plan* p) {
+    const int tiles = (rows + 15) / 16;
+    const int QT = kin / 16;
+    const size_t per_q = (size_t)16 * nt * 16 * sizeof(float);
+    int qc = QT;
+    if ((size_t)QT * per_q + 16 > 150 * 1024) qc = (int)((128 * 1024) / per_q);
+    const size_t lds_bytes = (size_t)qc * per_q + 16;
+    p->qc = qc;
+    p->tiles = tiles;
+    p->lds_bytes = (int)lds_bytes;
+    p->per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
+    const int grid = cus * p->per_cu;
+    if (nt % 4 == 0 && qc >= QT && tiles <= cus * 4) {   // few tiles: split each tile's columns over four wavefronts
+        p->path = TSPGNN_LINEAR_SPLIT;
+        p->nw = 8;
+        p->grid = (tiles + 1) / 2;
+        return;
+    }
+    p->path = qc >= QT ? TSPGNN_LINEAR_TICKET : TSPGNN_LINEAR_STREAMED;
+    p->nw = (qc >= QT && tiles <= grid * 4) ? 4 : 8;
+    p->grid = clamp_grid(grid, tiles, p->nw);
+}
+
+// tspgnn_mlp_bwd_multi_f32 (d = 128 holds two layers in LDS, else four)
+inline void plan_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n, int d, int cus, tspgnn_tasks_plan* p) {
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    for (int k = 0; k < n; ++k) {
+        const long long tiles = tiles16(tasks[k].rows);
+        cost[k] = tiles * tasks[k].n_layers;
+        tiles_all += tiles;
+    }
+    const int lds_bytes = (d >= 128 ? 2 : 4) * d * d * 4 + 16;
+    const int grid = cus * (lds_bytes > 80 * 1024 ? 1 : 2);
+    plan_tasks(cost, tiles_all, n, grid, tiles_all <= (long long)grid * 4 ? 4 : 8, p);
+}
+
+// tspgnn_mlp_fwd_multi_h2 / _x3, tspgnn_mlp_head_fwd_h2
+inline void plan_mlp_fwd(const tspgnn_mlp_task* tasks, int n, int cus, tspgnn_tasks_plan* p) {
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    for (int k = 0; k < n; ++k) {
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
+    }
+    int nw = 16;
+    if (tiles_all <= (long long)cus * 16) nw = tiles_all <= (long long)cus * 4 ? 4 : 8;
+    plan_tasks(cost, tiles_all, n, cus, nw, p);
+}
+
+inline int pick_vec(int width) { return width % 64 == 0 ? 4 : (width % 32 == 0 ? 2 : 1); }
+
+// tspgnn_wgrad_f32 / tspgnn_wgrad_bf16x_f32 (and the workspace size): the split of the row range, the kernel, its grid
+inline void plan_wgrad(long long rows, int kin, int nout, bool bf16x, int cus, tspgnn_wgrad_plan* p) {
+    const int av = pick_vec(kin), bv = pick_vec(nout);
+    const int nob = (kin / (16 * av)) * (nout / (16 * bv));
+    long long target = (long long)cus * 8 / nob;  // ~8 wavefronts per CU in total (HBM-bound: loads in flight)
+    if (target < 1) target = 1;
+    long long by_rows = (rows + 255) / 256;       // at least 256 rows per chunk
+    long long nc = target < by_rows ? target : by_rows;
+    if (nc < 1) nc = 1;
+    long long cr = (rows + nc - 1) / nc;
+    cr = (cr + 15) / 16 * 16;
+    if (cr < 16) cr = 16;
+    nc = (rows + cr - 1) / cr;
+    if (nc < 1) nc = 1;
+    p->av = av;
+    p->bv = bv;
+    p->nob = nob;
+    p->n_chunks = (int)nc;
+    p->chunk_rows = cr;
+    if (bf16x) {   // (kin a multiple of 128: two X blocks per wavefront, every dY value is split once per 128 features)
+        p->kernel = kin % 128 == 0 ? TSPGNN_WGRAD_X3_PAIR : TSPGNN_WGRAD_X3;
+        p->launch_nob = (kin / (kin % 128 == 0 ? 128 : 64)) * (nout / 64);
+    } else if (av == 4 && bv == 4 && rows >= 4096) {   // the big reductions over T*rows: bf16 matrix cores, fp32-class accuracy
+        p->kernel = TSPGNN_WGRAD_X3;
+        p->launch_nob = (kin / 64) * (nout / 64);
+    } else {
+        p->kernel = TSPGNN_WGRAD_GENERIC;
+        p->launch_nob = nob;
+    }
+    p->grid = (int)((nc * p->launch_nob + 3) / 4);
+}
+
+// tspgnn_wcolsum_f32 (and the workspace size): chunks of about 1024 rows, at most 4 per CU
+inline void plan_wcolsum(long long rows, int cus, tspgnn_wcolsum_plan* p) {
+    long long nc = (rows + 1023) / 1024;
+    const long long cap = (long long)cus * 4;
+    p->capped = nc > cap;
+    if (nc > cap) nc = cap;
+    if (nc < 1) nc = 1;
+    long long cr = (rows + nc - 1) / nc;
+    nc = (rows + cr - 1) / cr;
+    p->n_chunks = (int)(nc < 1 ? 1 : nc);
+    p->chunk_rows = cr < 1 ? 1 : cr;
+}
+
+// tspgnn_einit_bwd_f32: persistent workgroups (LDS: 1 / 2 per CU) over 64-edge chunks
+inline void plan_einit_bwd(int M, int d, int cus, tspgnn_einit_bwd_plan* p) {
+    p->n_chunks = (M + 63) / 64;
+    p->full_grid = cus * (d >= 128 ? 1 : 2);
+    p->grid = p->full_grid > p->n_chunks ? p->n_chunks : p->full_grid;
+}
+
+// Working wavefronts per workgroup of a lock-step f16x2 cell task (development switch TSPGNN_H2_LOCK_TILES; default: all of
+// them -- 8 / 6 / 4 measured 40.3 / 54.1 / 52.3 us per C2 launch against 37.9: the edge task misses the CUs more than the
+// vertex chain gains from emptier matrix pipes).
+inline int h2_lock_tiles() {
+    static const int v = [] {
+        const char* e = getenv("TSPGNN_H2_LOCK_TILES");
+        const int x = e ? atoi(e) : 0;
+        return (x >= 1 && x <= 16) ? x : 16;
+    }();
+    return v;
+}
+
+// Development switch TSPGNN_H2_WT=0/1 forces the write-through variant of the f16x2 cell launch off / on (-1: not set).
+inline int h2_wt_forced() {
+    static const int v = [] {
+        const char* e = getenv("TSPGNN_H2_WT");
+        return e ? atoi(e) : -1;
+    }();
+    return v;
+}
+
+// LDS residency of one f16x2 cell task: K and the MLP resident together, or lock-step rounds (K whole or in chunks of kbc
+// k-blocks, then the MLP layers and -- `together`, where both fit -- the projection matrix).  false: does not fit.
+inline bool cell_h2_residency(int KBT, int L, bool proj, int d, size_t per_kb, size_t budget, tspgnn_cell_fwd_plan* p, int k,
+                              size_t* need) {
+    const size_t layer_all = 2 * d * d * 2 + d * 4, proj_bytes = (size_t)2 * d * 4 * d * 2;
+    const size_t k_bytes = (size_t)KBT * per_kb;
+    if (k_bytes + L * layer_all <= budget && !proj) {
+        p->kbc[k] = KBT;
+        *need = k_bytes + L * layer_all;
+        return true;
+    }
+    const int kbc = k_bytes <= budget ? KBT : (int)(budget / per_kb);
+    if (kbc < 1 || L * layer_all > budget || (proj && proj_bytes > budget)) return false;
+    p->kbc[k] = kbc;
+    p->lockstep[k] = 1;
+    *need = (size_t)kbc * per_kb;
+    size_t second = L * layer_all;
+    if (proj) {
+        if (L * layer_all + proj_bytes <= budget) {
+            p->together[k] = 1;
+            second += proj_bytes;
+        } else if (proj_bytes > second) {
+            second = proj_bytes;
+        }
+    }
+    if (second > *need) *need = second;
+    return true;
+}
+
+// The same for a bf16x3 task: resident needs hi, mid and the biases of every MLP layer in LDS beside K (the lo pieces of
+// n_lo_lds layers where they fit); the kernel selects the lock step by kbc < KBT, so a K that would fit whole goes in
+// chunks of KBT - 1 there.
+inline bool cell_x3_residency(int KBT, int L, bool proj, int d, size_t per_kb, size_t budget, tspgnn_cell_fwd_plan* p, int k,
+                              size_t* need) {
+    const size_t layer_hm = (size_t)2 * d * d * 2, layer_lo = (size_t)d * d * 2, layer_all = 3 * d * d * 2 + d * 4;
+    const size_t proj_bytes = (size_t)3 * d * 4 * d * 2;
+    const size_t k_bytes = (size_t)KBT * per_kb;
+    const size_t mlp_min = L * (layer_hm + d * 4);
+    if (k_bytes + mlp_min <= budget && !proj) {
+        p->kbc[k] = KBT;
+        int n_lo = (int)((budget - k_bytes - mlp_min) / layer_lo);
+        if (n_lo > L) n_lo = L;
+        p->n_lo_lds[k] = n_lo;
+        *need = k_bytes + mlp_min + n_lo * layer_lo;
+        return true;
+    }
+    int kbc = k_bytes <= budget ? KBT : (int)(budget / per_kb);
+    if (kbc >= KBT) kbc = KBT - 1;
+    if (kbc < 1 || L * layer_all > budget || (proj && proj_bytes > budget)) return false;
+    p->kbc[k] = kbc;
+    p->lockstep[k] = 1;
+    p->n_lo_lds[k] = L;
+    *need = (size_t)kbc * per_kb;
+    if (L * layer_all > *need) *need = L * layer_all;
+    if (proj && proj_bytes > *need) *need = proj_bytes;
+    return true;
+}
+
+// tspgnn_lnlstm_mlp_fwd_multi_h2 / _x3 (arith: TSPGNN_ARITH_*; d in {32, 64}).  -1, or the index of the (first) task whose
+// K chunk, MLP or projection matrix does not fit LDS: TSPGNN_EUNSUPPORTED.
+inline int plan_cell_fwd(const tspgnn_cell_mlp_task* tasks, int n, int d, int arith, int cus, tspgnn_cell_fwd_plan* p) {
+    const bool h2 = arith == TSPGNN_ARITH_H2;
+    const size_t head = (10 * d + 4) * sizeof(float);
+    const size_t per_kb = (size_t)(h2 ? 2 : 3) * 32 * 4 * d * 2;  // bytes of one k-block, two / three pieces
+    const size_t budget = 160 * 1024 - head;
+    *p = tspgnn_cell_fwd_plan{};
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    size_t lds_w = 0;
+    for (int k = 0; k < n; ++k) {
+        const int L = tasks[k].mlp_layers;
+        const bool proj = tasks[k].proj_w != nullptr;
+        const int KBT = (tasks[k].cell.dx + d) / 32;
+        size_t need;
+        if (!(h2 ? cell_h2_residency : cell_x3_residency)(KBT, L, proj, d, per_kb, budget, p, k, &need)) return k;
+        if (need > lds_w) lds_w = need;
+        const long long tiles = tiles16(tasks[k].cell.rows);
+        cost[k] = tiles * (KBT * 4 + 2 * L + (proj ? 8 : 0) + (h2 ? 8 : 6));
+        tiles_all += tiles;
+    }
+    p->n = n;
+    p->lds_bytes = (int)(lds_w + head);
+    const int nw = tiles_all <= (long long)cus * 4 ? 4 : (tiles_all <= (long long)cus * 8 ? 8 : 12);
+    const int grid = clamp_grid(cus, tiles_all, nw);
+    p->nw = nw;
+    // A lock-step task is a latency chain (LDS re-stagings every round) that the resident tasks of the launch hide.  It
+    // gets the workgroups of a whole number of rounds; the resident tasks share the rest by cost.
+    // bf16x3: exactly ONE round (more workgroups would idle, fewer would double the chain), capped at half the grid.
+    // f16x2: ONE round while that stays within about twice its share of the grid by cost (C2's 320 vertex tiles take 27
+    // of 256), otherwise as many rounds as bring it back to its share (C4's 1 586 vertex tiles: 5 rounds on 27 workgroups
+    // instead of starving the edge task of 133).  (Figures at 256 CUs and 12 working wavefronts: tspgnn_plan_cell_fwd.)
+    long long total_cost = 0;
+    for (int k = 0; k < n; ++k) total_cost += cost[k] > 0 ? cost[k] : 1;
+    int fixed[kMaxTasks];
+    for (int k = 0; k < n; ++k) {
+        fixed[k] = 0;
+        if (!p->lockstep[k]) continue;
+        const long long tiles = tiles16(tasks[k].cell.rows);
+        const int lw = h2 && h2_lock_tiles() < nw ? h2_lock_tiles() : nw;
+        const long long per_round = (tiles + lw - 1) / lw;
+        long long n_rounds = 1;
+        if (h2) {
+            long long share = (2 * cost[k] * grid + total_cost - 1) / total_cost;  // twice the proportional share
+            if (share < 1) share = 1;
+            n_rounds = (per_round + share - 1) / share;
+        }
+        p->lock_tiles[k] = lw;
+        p->n_rounds[k] = (int)n_rounds;
+        fixed[k] = (int)((per_round + n_rounds - 1) / n_rounds);
+    }
+    p->grid = split_blocks_fixed(cost, fixed, n, grid, p->blk_end, &p->split_fixed);
+    if (!h2) return -1;
+    bool centered = true, loop_buffers = false;
+    long long out_bytes = 0;   // h', c' of every task and its messages: what the launch stores (and the next ones re-read)
+    for (int k = 0; k < n; ++k) {
+        centered = centered && tasks[k].cell.z_centered != 0;
+        out_bytes += (long long)tasks[k].cell.rows * d * 4 * (tasks[k].mlp_out ? 3 : 2);
+        loop_buffers = loop_buffers || tasks[k].state_out_blocked != 0 || tasks[k].mlp_out != nullptr || tasks[k].proj_out != nullptr;
+    }
+    // write-through output stores while the loop's arrays (two copies of the states, two of the messages: ~2x out_bytes)
+    // stay inside the 256 MB Infinity Cache; plain stores beyond (see st4o) -- and for a launch that writes nothing the next
+    // step's launch reads from these buffers (no blocked state, no messages: the training forward's cell launch stores
+    // into the tape, which the backward reads much later -- C2 training step 10.25-10.27 -> 10.12-10.16 ms)
+    p->centered = centered;
+    p->wt = h2_wt_forced() >= 0 ? h2_wt_forced() != 0 : (loop_buffers && 2 * out_bytes <= (long long)200 * 1024 * 1024);
+    return -1;
+}
+
+// what plan_cell_fwd's caller answers for the task it names
+inline int cell_does_not_fit(const tspgnn_cell_mlp_task& t, int d, const char* what) {
+    return fail(TSPGNN_EUNSUPPORTED, "%s: dx=%d, d=%d, %d MLP layers do not fit LDS", what, t.cell.dx, d, t.mlp_layers);
 }
 
 }  // namespace tspgnn

@@ -2,6 +2,7 @@
 // edge-embedding initialisation, vertex-embedding tiling, the vote head's final Dense(1),
 // per-problem segment mean, and sigmoid / cross-entropy / confusion counts.
 #include "common.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 
 namespace tspgnn {
@@ -223,9 +224,7 @@ extern "C" int tspgnn_tile_rows_f32(const float* v, float scale, float* Y, int r
     if (rows == 0) return TSPGNN_OK;
     TSPGNN_REQUIRE(v && Y, "tile_rows: null pointer");
     const long long total4 = (long long)rows * (d / 4);
-    long long blocks = (total4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    tile_rows_kernel<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(v, scale, reinterpret_cast<float4*>(Y), total4,
+    tile_rows_kernel<<<strided_blocks(total4, 256, 4096), 256, 0, as_stream(stream)>>>(v, scale, reinterpret_cast<float4*>(Y), total4,
                                                                       d / 4);
     return launched("tspgnn_tile_rows_f32");
 }

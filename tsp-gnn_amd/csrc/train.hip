@@ -2,6 +2,7 @@
 // loss -> edge votes, the vote head's Dense(1), column sums, E_init_MLP weight gradients,
 // L2 term + global-norm clip + Adam on the flat parameter buffer.
 #include "common.h"
+#include "launch_plan.h"
 #include "mfma_tile.h"
 
 namespace tspgnn {
@@ -392,17 +393,6 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ thet
     }
 }
 
-static void colsum_plan(long long rows, int* n_chunks, long long* chunk_rows) {
-    long long nc = (rows + 1023) / 1024;
-    const long long cap = (long long)n_cus() * 4;
-    if (nc > cap) nc = cap;
-    if (nc < 1) nc = 1;
-    long long cr = (rows + nc - 1) / nc;
-    nc = (rows + cr - 1) / cr;
-    *n_chunks = (int)(nc < 1 ? 1 : nc);
-    *chunk_rows = cr < 1 ? 1 : cr;
-}
-
 }  // namespace tspgnn
 
 using namespace tspgnn;
@@ -421,38 +411,48 @@ extern "C" int tspgnn_rowdot_bwd_f32(const float* dy, const float* w, float* dX,
     if (rows == 0) return TSPGNN_OK;
     TSPGNN_REQUIRE(dy && w && dX, "rowdot_bwd: null pointer");
     const long long total4 = (long long)rows * (d / 4);
-    long long blocks = (total4 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    rowdot_bwd_kernel<<<(unsigned)blocks, 256, 0, as_stream(stream)>>>(
+    rowdot_bwd_kernel<<<strided_blocks(total4, 256, 4096), 256, 0, as_stream(stream)>>>(
         dy, reinterpret_cast<const float4*>(w), reinterpret_cast<float4*>(dX), total4, d / 4);
     return launched("tspgnn_rowdot_bwd_f32");
 }
 
 extern "C" long long tspgnn_wcolsum_workspace_floats(long long rows, int d) {
-    int nc;
-    long long cr;
-    colsum_plan(rows < 1 ? 1 : rows, &nc, &cr);
-    return (long long)nc * (d + 1);
+    tspgnn_wcolsum_plan pl;
+    plan_wcolsum(rows < 1 ? 1 : rows, n_cus(), &pl);
+    return (long long)pl.n_chunks * (d + 1);
+}
+
+static int check_wcolsum_shape(long long rows, int d) {
+    TSPGNN_REQUIRE(rows >= 0, "wcolsum: rows=%lld", rows);
+    TSPGNN_REQUIRE(d > 0 && d % 4 == 0 && d <= 1024 && 256 % (d / 4) == 0, "wcolsum: d=%d must divide 1024 and be a multiple of 4", d);
+    return TSPGNN_OK;
 }
 
 extern "C" int tspgnn_wcolsum_f32(const float* X, const float* wt, long long rows, int d, float scale, float* out,
                                   float* out_wsum, float* workspace, void* stream) {
-    TSPGNN_REQUIRE(rows >= 0, "wcolsum: rows=%lld", rows);
-    TSPGNN_REQUIRE(d > 0 && d % 4 == 0 && d <= 1024 && 256 % (d / 4) == 0, "wcolsum: d=%d must divide 1024 and be a multiple of 4", d);
-    if (rows == 0) return TSPGNN_OK;
+    int rc = check_wcolsum_shape(rows, d);
+    if (rc || rows == 0) return rc;
     TSPGNN_REQUIRE(X && out && workspace, "wcolsum: null pointer");
-    int nc;
-    long long cr;
-    colsum_plan(rows, &nc, &cr);
+    tspgnn_wcolsum_plan pl;
+    plan_wcolsum(rows, n_cus(), &pl);
+    const int nc = pl.n_chunks;
     hipStream_t st = as_stream(stream);
     float* Pw = workspace + (size_t)nc * d;
     wcolsum_kernel<<<(unsigned)nc, 256, 0, st>>>(reinterpret_cast<const float4*>(X), wt,
                                                  reinterpret_cast<float4*>(workspace), out_wsum ? Pw : nullptr, rows,
-                                                 d / 4, cr);
-    int rc = launched("tspgnn_wcolsum_f32");
-    if (rc) return rc;
+                                                 d / 4, pl.chunk_rows);
+    if ((rc = launched("tspgnn_wcolsum_f32"))) return rc;
     reduce_partials2(workspace, nc, d, out, d, Pw, 1, out_wsum, out_wsum ? 1 : 0, scale, 1, st);
     return launched("tspgnn_wcolsum_f32(reduce)");
+}
+
+extern "C" int tspgnn_plan_wcolsum(long long rows, int d, int cus, tspgnn_wcolsum_plan* out) {
+    TSPGNN_REQUIRE(out && cus >= 0, "plan_wcolsum: cus=%d", cus);
+    *out = tspgnn_wcolsum_plan{};
+    const int rc = check_wcolsum_shape(rows, d);
+    if (rc || rows == 0) return rc;
+    plan_wcolsum(rows, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
 }
 
 static int einit_np(int d) {
@@ -464,27 +464,44 @@ extern "C" long long tspgnn_einit_bwd_workspace_floats(int M, int d) {
     return (long long)((M + 63) / 64) * einit_np(d);
 }
 
-extern "C" int tspgnn_einit_bwd_f32(const float* WC, const float* wb, const float* dE0, float* dwb, float* workspace,
-                                    int M, int d, void* stream) {
+static int check_einit_bwd_shape(int M, int d) {
     TSPGNN_REQUIRE(M >= 0, "einit_bwd: M=%d", M);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "einit_bwd: d=%d must be 32, 64 or 128", d);
-    if (M == 0) return TSPGNN_OK;
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_einit_bwd_f32(const float* WC, const float* wb, const float* dE0, float* dwb, float* workspace,
+                                    int M, int d, void* stream) {
+    int rc = check_einit_bwd_shape(M, d);
+    if (rc || M == 0) return rc;
     TSPGNN_REQUIRE(WC && wb && dE0 && dwb && workspace, "einit_bwd: null pointer");
-    const int n_chunks = (M + 63) / 64;
-    unsigned grid = (unsigned)n_cus() * (d >= 128 ? 1u : 2u);   // persistent workgroups (LDS: 1 / 2 per CU)
-    if (grid > (unsigned)n_chunks) grid = (unsigned)n_chunks;
+    tspgnn_einit_bwd_plan pl;
+    plan_einit_bwd(M, d, n_cus(), &pl);
     hipStream_t st = as_stream(stream);
     const float2* WC2 = reinterpret_cast<const float2*>(WC);
     switch (d) {
-        case 32: einit_bwd_kernel<32><<<grid, 256, 0, st>>>(WC2, wb, dE0, workspace, M, n_chunks); break;
-        case 64: einit_bwd_kernel<64><<<grid, 256, 0, st>>>(WC2, wb, dE0, workspace, M, n_chunks); break;
-        default: einit_bwd_kernel<128><<<grid, 256, 0, st>>>(WC2, wb, dE0, workspace, M, n_chunks); break;
+        case 32: einit_bwd_kernel<32><<<pl.grid, 256, 0, st>>>(WC2, wb, dE0, workspace, M, pl.n_chunks); break;
+        case 64: einit_bwd_kernel<64><<<pl.grid, 256, 0, st>>>(WC2, wb, dE0, workspace, M, pl.n_chunks); break;
+        default: einit_bwd_kernel<128><<<pl.grid, 256, 0, st>>>(WC2, wb, dE0, workspace, M, pl.n_chunks); break;
     }
-    int rc = launched("tspgnn_einit_bwd_f32");
-    if (rc) return rc;
+    if ((rc = launched("tspgnn_einit_bwd_f32"))) return rc;
     const int np = einit_np(d);
-    reduce_partials(workspace, (int)grid, np, dwb, np, 1.0f, 1, st);
+    reduce_partials(workspace, pl.grid, np, dwb, np, 1.0f, 1, st);
     return launched("tspgnn_einit_bwd_f32(reduce)");
+}
+
+extern "C" int tspgnn_plan_einit_bwd(int M, int d, int cus, tspgnn_einit_bwd_plan* out) {
+    TSPGNN_REQUIRE(out && cus >= 0, "plan_einit_bwd: cus=%d", cus);
+    *out = tspgnn_einit_bwd_plan{};
+    const int rc = check_einit_bwd_shape(M, d);
+    if (rc || M == 0) return rc;
+    plan_einit_bwd(M, d, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_strided_blocks(long long total, int per_block, int cap) {
+    TSPGNN_REQUIRE(total >= 0 && per_block > 0 && cap > 0, "plan_strided_blocks: total=%lld per_block=%d cap=%d", total, per_block, cap);
+    return strided_blocks(total, per_block, cap);
 }
 
 #define TSPGNN_OPT_PARTIALS 256
@@ -550,9 +567,7 @@ __global__ __launch_bounds__(256) void bucket_unpack_kernel(float* __restrict__ 
 extern "C" int tspgnn_bucket_pack_f32(float* bucket, int n, int with_grad, float local_batch, const float* stats,
                                       const unsigned* range_flag, void* stream) {
     TSPGNN_REQUIRE(n >= 0 && bucket, "bucket_pack: n=%d, bucket=%p", n, (void*)bucket);
-    int blocks = with_grad ? (n + 255) / 256 : 1;
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
+    const int blocks = with_grad ? strided_blocks(n, 256, 1024) : 1;
     bucket_pack_kernel<<<blocks, 256, 0, as_stream(stream)>>>(bucket, n, with_grad, local_batch, stats, range_flag);
     return launched("tspgnn_bucket_pack_f32");
 }
@@ -560,9 +575,7 @@ extern "C" int tspgnn_bucket_pack_f32(float* bucket, int n, int with_grad, float
 extern "C" int tspgnn_bucket_unpack_f32(float* bucket, int n, int with_grad, float* stats, unsigned* range_flag,
                                         void* stream) {
     TSPGNN_REQUIRE(n >= 0 && bucket, "bucket_unpack: n=%d, bucket=%p", n, (void*)bucket);
-    int blocks = with_grad ? (n + 255) / 256 : 1;
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
+    const int blocks = with_grad ? strided_blocks(n, 256, 1024) : 1;
     bucket_unpack_kernel<<<blocks, 256, 0, as_stream(stream)>>>(bucket, n, with_grad, stats, range_flag);
     return launched("tspgnn_bucket_unpack_f32");
 }

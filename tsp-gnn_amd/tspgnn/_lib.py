@@ -121,6 +121,16 @@ SIGNATURES = {
                                 c_void_p, c_void_p],
     "tspgnn_graph_text_write": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong,
                                 c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p],
+    # launch-plan queries (host only; the last argument is the plan structure to fill, see plan())
+    "tspgnn_plan_linear": [c_int, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_mlp_bwd": [c_void_p, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_mlp_fwd": [c_void_p, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_wgrad": [c_longlong, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_wcolsum": [c_longlong, c_int, c_int, c_void_p],
+    "tspgnn_plan_einit_bwd": [c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_cell_fwd": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_reduce_slices": [c_int],
+    "tspgnn_plan_strided_blocks": [c_longlong, c_int, c_int],
 }
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",
@@ -231,6 +241,45 @@ class MlpBwdRcTask(ctypes.Structure):
                 ("partial", c_void_p)]
 
 
+class LinearPlan(ctypes.Structure):
+    """tspgnn_linear_plan (include/tspgnn.h)."""
+    _fields_ = [("path", c_int), ("nw", c_int), ("grid", c_int), ("qc", c_int), ("per_cu", c_int), ("tiles", c_int),
+                ("lds_bytes", c_int)]
+
+
+class TasksPlan(ctypes.Structure):
+    """tspgnn_tasks_plan (include/tspgnn.h)."""
+    _fields_ = [("nw", c_int), ("grid", c_int), ("n", c_int), ("blk_end", c_int * 4)]
+
+
+class WgradPlan(ctypes.Structure):
+    """tspgnn_wgrad_plan (include/tspgnn.h)."""
+    _fields_ = [("kernel", c_int), ("av", c_int), ("bv", c_int), ("nob", c_int), ("n_chunks", c_int),
+                ("launch_nob", c_int), ("grid", c_int), ("chunk_rows", c_longlong)]
+
+
+class WcolsumPlan(ctypes.Structure):
+    """tspgnn_wcolsum_plan (include/tspgnn.h)."""
+    _fields_ = [("n_chunks", c_int), ("capped", c_int), ("chunk_rows", c_longlong)]
+
+
+class EinitBwdPlan(ctypes.Structure):
+    """tspgnn_einit_bwd_plan (include/tspgnn.h)."""
+    _fields_ = [("grid", c_int), ("n_chunks", c_int), ("full_grid", c_int)]
+
+
+class CellFwdPlan(ctypes.Structure):
+    """tspgnn_cell_fwd_plan (include/tspgnn.h)."""
+    _fields_ = [("nw", c_int), ("grid", c_int), ("n", c_int), ("blk_end", c_int * 4), ("lockstep", c_int * 4),
+                ("kbc", c_int * 4), ("together", c_int * 4), ("lock_tiles", c_int * 4), ("n_lo_lds", c_int * 4),
+                ("n_rounds", c_int * 4), ("split_fixed", c_int), ("centered", c_int), ("wt", c_int), ("lds_bytes", c_int)]
+
+
+PLANS = {"tspgnn_plan_linear": LinearPlan, "tspgnn_plan_mlp_bwd": TasksPlan, "tspgnn_plan_mlp_fwd": TasksPlan,
+         "tspgnn_plan_wgrad": WgradPlan, "tspgnn_plan_wcolsum": WcolsumPlan, "tspgnn_plan_einit_bwd": EinitBwdPlan,
+         "tspgnn_plan_cell_fwd": CellFwdPlan}
+
+
 class TspgnnError(RuntimeError):
     """A libtspgnn entry point returned a non-zero status."""
 
@@ -304,6 +353,17 @@ def call(name, *args):
         status = getattr(lib, name)(*args)
     if status != 0:
         raise TspgnnError(name, status, lib.tspgnn_last_error().decode("utf-8", "replace"))
+
+
+def plan(query, *args):
+    """The filled plan structure of one of the tspgnn_plan_* queries of PLANS (host only: no stream, no timeline);
+    a task list among the arguments is passed as its array.  Raises TspgnnError as call() does."""
+    out = PLANS[query]()
+    args = [ctypes.cast(task_array(a), c_void_p) if isinstance(a, list) else a for a in args]
+    status = getattr(lib, query)(*args, ctypes.addressof(out))
+    if status != 0:
+        raise TspgnnError(query, status, lib.tspgnn_last_error().decode("utf-8", "replace"))
+    return out
 
 
 def ptr(t):
