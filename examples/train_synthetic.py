@@ -5,6 +5,7 @@ the MI355X path, over synthetic Euclidean instances (no Concorde, no dataset on 
     python examples/train_synthetic.py -d 64 -timesteps 32 -batchsize 8 -epochs 2 --batches 8
     python examples/train_synthetic.py --instances /tmp/tsp/instances --checkpoints /tmp/tsp/ckpt   # .graph files + resume
     python examples/train_synthetic.py -generate 512     # the reference's stream (n 20-40), drawn, labelled, packed on the GPU
+    python examples/train_synthetic.py -accumulate 4     # one optimiser step per 4 batches: a step on 4 x the batch
 
 The flags keep train.py's names (train.py:107-119).  Every instance appears twice in a batch with target
 cost (1-dev) and (1+dev) times its tour cost and labels 0/1, exactly like InstanceLoader.get_batches
@@ -25,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tsp-gnn_amd"))
 from tspgnn import (DeviceDataset, InstanceLoader, Session, build_network, global_variables_initializer, load_weights,  # noqa: E402
                     random_instance, save_weights, write_graph)
-from tspgnn.train import run_batch, summarize_epoch  # noqa: E402
+from tspgnn.train import run_batch, run_batches_accumulated, summarize_epoch  # noqa: E402
 
 
 if __name__ == '__main__':
@@ -49,7 +50,12 @@ if __name__ == '__main__':
                         'labelled and packed on the GPU, instead of a directory or synthetic instances')
     p.add_argument('-write_dir', default=None, metavar='PATH',
                    help='with -generate: also write the generated instances to PATH as .graph files, formatted on the GPU')
+    p.add_argument('-accumulate', default=1, type=int, metavar='K',
+                   help='gradient accumulation: every K consecutive batches of an epoch form ONE optimiser step on their '
+                        'union (run_batches_accumulated; a short last group is a smaller step); 1: a step per batch')
     a = p.parse_args()
+    if a.accumulate < 1:
+        p.error('-accumulate K needs K >= 1')
     if a.write_dir is not None and not a.generate:
         p.error('-write_dir needs -generate SAMPLES')
     rng = np.random.RandomState(a.seed)
@@ -98,8 +104,18 @@ if __name__ == '__main__':
                         base = [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize)]
                         yield InstanceLoader.create_batch([inst for inst in base for _ in (0, 1)], dev=a.dev)   # each twice
                 batches = synthetic()
-            for b, batch in enumerate(batches):
-                stats.append(run_batch(sess, GNN, batch, b, epoch, a.timesteps, train=True)[:4])
+            if a.accumulate == 1:
+                for b, batch in enumerate(batches):
+                    stats.append(run_batch(sess, GNN, batch, b, epoch, a.timesteps, train=True)[:4])
+            else:
+                group, step = [], 0
+                for batch in batches:
+                    group.append(batch)
+                    if len(group) == a.accumulate:
+                        stats.append(run_batches_accumulated(sess, GNN, group, step, epoch, a.timesteps)[:4])
+                        group, step = [], step + 1
+                if group:
+                    stats.append(run_batches_accumulated(sess, GNN, group, step, epoch, a.timesteps)[:4])
             summarize_epoch(epoch, *zip(*stats), train=True)
             if a.checkpoints is not None:
                 save_weights(sess, '{}/epoch={}'.format(a.checkpoints, epoch))

@@ -1049,6 +1049,19 @@ int tspgnn_bucket_pack_f32(float* bucket, int n, int with_grad, float local_batc
 int tspgnn_bucket_unpack_f32(float* bucket, int n, int with_grad, float* stats, unsigned* range_flag, void* stream);
 
 /*
+ * Gradient accumulation: one optimiser step over several micro-batches (a micro-batch is a rank that runs later).  accum
+ * has the bucket's layout, n floats and the 10 tail slots; grad (n floats, the gradient of the micro-batch's mean loss) is
+ * only read.  For i < n: t = local_batch * grad[i], accum[i] = first ? t : accum[i] + t, the product and the sum each
+ * rounded to fp32 (no fma).  For tail slot k: v = what tspgnn_bucket_pack_f32 writes there from local_batch, stats and
+ * range_flag (NULL: zeros), accum[n + k] = first ? v : accum[n + k] + v -- a guard slot counts the flagged micro-batches.
+ * first != 0 WRITES: whatever accum held, NaN included, is gone.  n == 0 touches the tail only.  TSPGNN_EINVAL: accum NULL,
+ * n < 0, grad NULL with n > 0, accum == grad.  tspgnn_bucket_unpack_f32 on the accumulated (and, across ranks, once
+ * all-reduced) bucket finishes the step: it divides by the summed batch size, copies the counts, rebuilds the flag word.
+ */
+int tspgnn_bucket_accumulate_f32(float* accum, const float* grad, int n, int first, float local_batch,
+                                 const float* stats, const unsigned* range_flag, void* stream);
+
+/*
  * Launch plans: what an entry's launcher decides in host code from the task shapes and the CU count, answered by the
  * same planner the launcher calls (csrc/launch_plan.h).  Host only -- nothing is launched, no device is needed, and no
  * pointer is dereferenced: a pointer field of a task counts as null or non-null.  Every query takes the arguments that

@@ -579,3 +579,36 @@ extern "C" int tspgnn_bucket_unpack_f32(float* bucket, int n, int with_grad, flo
     bucket_unpack_kernel<<<blocks, 256, 0, as_stream(stream)>>>(bucket, n, with_grad, stats, range_flag);
     return launched("tspgnn_bucket_unpack_f32");
 }
+
+// Gradient accumulation (Session.train_step_accumulated): a micro-batch is a rank that runs later, so its gradient and
+// statistics enter a second bucket with the weights bucket_pack_kernel gives a rank -- accum = first ? B_k * [grad | tail
+// values] : accum + B_k * [...] -- and bucket_unpack_kernel on the sum finishes the step.  grad is only read.  The product
+// and the sum round separately (no fma), so a float32 restatement matches bit for bit; a guard slot counts the
+// micro-batches whose launches left the word's bit up, and unpack turns "non-zero" back into the bit.
+__global__ __launch_bounds__(256) void bucket_accumulate_kernel(float* __restrict__ accum, const float* __restrict__ grad,
+                                                                int n, int first, float nb,
+                                                                const float* __restrict__ stats,
+                                                                const unsigned* __restrict__ flag) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float t = __fmul_rn(nb, grad[i]);
+        accum[i] = first ? t : __fadd_rn(accum[i], t);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 10) {
+        const int k = threadIdx.x;
+        float v = 0.f;
+        if (k == 0) v = nb;
+        else if (k < 3) v = stats ? __fmul_rn(nb, stats[k - 1]) : 0.f;
+        else if (k < 7) v = stats ? stats[k - 1] : 0.f;
+        else v = flag ? (float)((flag[0] >> (k - 7)) & 1u) : 0.f;
+        accum[n + k] = first ? v : __fadd_rn(accum[n + k], v);
+    }
+}
+
+extern "C" int tspgnn_bucket_accumulate_f32(float* accum, const float* grad, int n, int first, float local_batch,
+                                            const float* stats, const unsigned* range_flag, void* stream) {
+    TSPGNN_REQUIRE(n >= 0 && accum && (grad || n == 0) && accum != grad, "bucket_accumulate: n=%d, accum=%p, grad=%p", n,
+                   (void*)accum, (const void*)grad);
+    const int blocks = strided_blocks(n, 256, 1024);
+    bucket_accumulate_kernel<<<blocks, 256, 0, as_stream(stream)>>>(accum, grad, n, first, local_batch, stats, range_flag);
+    return launched("tspgnn_bucket_accumulate_f32");
+}

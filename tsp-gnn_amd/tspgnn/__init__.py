@@ -19,14 +19,14 @@ from .model import build_network, Session, global_variables_initializer
 from .variables import VariableStore, get_default_store, reset_default_store
 from . import tf_checkpoint
 from .util import load_weights, save_weights
-from .train import run_batch, summarize_epoch
+from .train import run_batch, run_batches_accumulated, summarize_epoch
 from . import experiments
 
 __all__ = [
     "TspgnnError", "GraphNN", "LSTMStateTuple", "DeviceAdjacency", "LayerNormBasicLSTMCell", "InstanceLoader",
     "SparseEV", "read_graph", "write_graph", "synthetic_batch", "random_instance", "Mlp", "build_network",
     "Session", "global_variables_initializer", "get_cost", "get_costs", "BatchPrefetcher", "BatchStager", "shard_instances", "VariableStore", "get_default_store", "reset_default_store",
-    "load_weights", "save_weights", "run_batch", "summarize_epoch", "solve_tours", "label_tours", "prove_tours", "solve", "certify", "create_graph",
+    "load_weights", "save_weights", "run_batch", "run_batches_accumulated", "summarize_epoch", "solve_tours", "label_tours", "prove_tours", "solve", "certify", "create_graph",
     "create_dataset", "TourResult", "nearest_neighbor_tours", "anneal_tours", "decide",
     "metric_closure", "DeviceDataset", "draw_instances", "draw_streams",
 ]

@@ -84,6 +84,7 @@ SIGNATURES = {
     "tspgnn_convert_bf16_to_f32": [c_void_p, c_void_p, c_longlong, c_void_p],
     "tspgnn_bucket_pack_f32": [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "tspgnn_bucket_unpack_f32": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    "tspgnn_bucket_accumulate_f32": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "tspgnn_cost_search_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p],
     "tspgnn_tour_search": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -509,13 +509,17 @@ class Session(object):
         # device="cpu" (plumbing: the gloo tests): the same arithmetic as tensor ops
         if with_grad:
             store.grad.mul_(nb)
+        return self._fill_tail(tail, nb, stats)
+
+    def _fill_tail(self, tail, nb, stats):
+        """The bucket's tail of a rank (or a micro-batch) of ``nb`` graphs, as bucket_pack_kernel writes it: tensor ops."""
         tail.zero_()
         tail[0:1].fill_(nb)
         if stats is not None:
             tail[1:3].copy_(stats[0:2])
             tail[1:3].mul_(nb)
             tail[3:7].copy_(stats[2:6])
-        store.guard.flags_to_bucket(tail)   # one slot per bit
+        self.store.guard.flags_to_bucket(tail)   # one slot per bit
         return tail
 
     def _unpack_bucket(self, stats, with_grad):
@@ -550,6 +554,47 @@ class Session(object):
         tail = self._pack_bucket(local_batch, stats, False)
         dist.all_reduce(tail, group=self.process_group)
         self._unpack_bucket(stats, False)
+
+    # Gradient accumulation: a micro-batch is a rank that runs later.  Its gradient and statistics enter a second bucket
+    # (VariableStore.accum_bucket) with the weights _pack_bucket gives a rank; the sum is handed to ``store.bucket``,
+    # all-reduced ONCE when there are ranks, and unpacked like any reduced bucket.
+    def accumulate_grads(self, local_batch, stats=None, first=False):
+        """Folds ``store.grad`` -- the gradient of the mean loss of a micro-batch of ``local_batch`` graphs -- and its
+        tail (batch size, ``stats``, guard bits) into the accumulation bucket: accum = B_k * [grad | ...] when ``first``
+        (whatever the buffer held is gone), accum += B_k * [grad | ...] otherwise.  ``store.grad`` is not modified.  The
+        product and the sum are rounded separately, on the GPU (tspgnn_bucket_accumulate_f32) as in the tensor ops of a
+        ``device='cpu'`` session."""
+        store = self.store
+        if store.grad is None:
+            store.zero_grad()
+        nb = float(local_batch)
+        n = store.theta.numel()
+        accum = store.accum_bucket()
+        if self.device.type == "cuda":
+            _lib.call("tspgnn_bucket_accumulate_f32", _lib.ptr(accum), _lib.ptr(store.grad), n, 1 if first else 0, nb,
+                      _lib.ptr(stats), store.guard.flag_ptr(), _lib.current_stream())
+            return
+        term = torch.empty_like(accum)
+        torch.mul(store.grad, nb, out=term[:n])
+        self._fill_tail(term[n:], nb, stats)
+        if first:
+            accum.copy_(term)
+        else:
+            accum.add_(term)
+
+    def reduce_accumulated(self, stats=None):
+        """Finishes what accumulate_grads summed: the accumulated bucket becomes ``store.bucket``, ONE all-reduce follows
+        when there are ranks, then the unpack -- always, also with one rank: ``store.grad`` holds the gradient of the mean
+        loss over every micro-batch (of every rank), ``stats`` (optional 6-vector) the statistics of their union, and the
+        guard word is rebuilt from the summed flag slots."""
+        store = self.store
+        if store.grad is None:
+            store.zero_grad()
+        store.bucket.copy_(store.accum_bucket())
+        if self.world_size > 1:
+            import torch.distributed as dist
+            dist.all_reduce(store.bucket, group=self.process_group)
+        self._unpack_bucket(stats, True)
 
     def allreduce_host_sums(self, values):
         """Sum of a small float64 host vector over the ranks (run_batch's label / prediction means)."""
@@ -638,6 +683,11 @@ class Session(object):
         repeat together -- and the "do we need to re-synchronise?" question rides in the step's ONE all-reduce instead of
         a collective and a host round trip of its own before every step: the price is one wasted forward +
         backward in the step after a checkpoint restore."""
+        return self._guarded_step(lambda: self._train_step_once(feed))
+
+    def _guarded_step(self, once):
+        """train_step's guard and retry rules around ``once()``, one whole optimiser step (train_step: one batch;
+        train_step_accumulated: every micro-batch of the step)."""
         on_gpu = self.device.type == "cuda"
         dp = self.world_size > 1
         if dp and not self._ever_synced:
@@ -649,18 +699,18 @@ class Session(object):
         guard = self.store.guard
         if on_gpu:
             guard.arm(need)     # always: the optimiser kernel skips on a non-zero word
-        out = self._train_step_once(feed)
+        out = once()
         act, resync = flag_bits(guard.take_flags()) if on_gpu and (h2 or dp) else (0, False)
         if resync:   # skipped everywhere: some replica had been assigned to.  Make them identical, then take the step.
             self._adam["step"] -= 1
             self.broadcast_variables(0)
-            out = self._train_step_once(feed)
+            out = once()
             act = flag_bits(guard.take_flags())[0] if h2 else 0
         if act:
             self.last_range_bits = act
             self._adam["step"] -= 1     # (Adam skipped the update on the device: theta, m, v and t are untouched)
             with self.model["gnn"].forced_off_h2():
-                out = self._train_step_once(feed)
+                out = once()
         return out
 
     def _train_step_once(self, feed):
@@ -669,11 +719,51 @@ class Session(object):
         out["global_norm"] = self.apply_gradients()
         return out
 
-    def capture_train_step(self, batch):
+    def train_step_accumulated(self, feeds):
+        """ONE optimiser step over the micro-batches ``feeds`` (a non-empty sequence of feeds or DeviceBatches; their
+        time steps may differ): the step ``train_step`` would take on their union, shard after shard, so the batch of a
+        step is not bounded by what one training tape holds.  Per micro-batch: forward + backward, then its gradient
+        enters the accumulation bucket with weight B_k (accumulate_grads).  Then ONE all-reduce when there are ranks
+        (their numbers of micro-batches may differ: it is the only collective), the division by the summed batch size,
+        and L2 + clip + Adam once -- the variables, and with them every packed-weight copy, do not change in between.
+
+        Returns the last micro-batch's outputs with ``stats`` those of the union (the global ones in a data-parallel
+        session), ``global_norm`` the optimiser launch's, ``predictions`` the list of the micro-batches' prediction
+        tensors and ``batches`` the list of their DeviceBatches.  train_step's guard rules hold for the WHOLE step: the
+        word is armed once before the first micro-batch, read once after the optimiser launch, and a flagged (skipped)
+        step is repeated from its first micro-batch."""
+        feeds = list(feeds)
+        if not feeds:
+            raise ValueError("train_step_accumulated: an optimiser step needs at least one micro-batch")
+        self._require_gpu("a training step")
+        batches = [f if isinstance(f, DeviceBatch) else self.prepare(f) for f in feeds]
+        return self._guarded_step(lambda: self._accumulated_step_once(batches))
+
+    def _accumulated_step_once(self, batches):
+        predictions = []
+        for k, b in enumerate(batches):
+            out = self.loss_and_grads(b)
+            self.accumulate_grads(b.B, out["stats"], first=(k == 0))
+            predictions.append(out["predictions"])
+        self.reduce_accumulated(out["stats"])
+        out["global_norm"] = self.apply_gradients()
+        out["predictions"], out["batches"] = predictions, batches
+        return out
+
+    def capture_train_step(self, batch, micro_batches=None):
         """HIP-graph replay of the training step on a resident batch: graph A = zero grads + forward +
         backward (+ re-packing of the weights, which change every step), then the gradient all-reduce
         (eager: RCCL), then graph B = L2 + clip + Adam with the step counter on the device.  ~600 kernel
-        launches per step stop costing host time.  Returns ``replay() -> outputs``."""
+        launches per step stop costing host time.  Returns ``replay() -> outputs``.
+
+        ``micro_batches=K``: the same two graphs, and ``replay(refill=None)`` is ONE optimiser step over K micro-batches
+        (train_step_accumulated's arithmetic): for k in range(K) ``refill(k)`` if given, graph A, the accumulate launch;
+        then the accumulated bucket's hand-over, the all-reduce, the unpack and graph B.  ``refill(k)`` is where the
+        caller writes micro-batch k into the captured batch's buffers -- ``ds.batch(ids_k, ..., out=batch)``, which
+        refuses other shapes; without it the resident batch is taken K times (timing only).  ``out["stats"]`` are the
+        union's; ``out["predictions"]`` are the last micro-batch's."""
+        if micro_batches is not None and int(micro_batches) < 1:
+            raise ValueError("capture_train_step: micro_batches=%r must be at least 1" % (micro_batches,))
         b = batch if isinstance(batch, DeviceBatch) else self.prepare(batch)
         self._ensure_adam()
         self._sync_replicas_once()
@@ -693,7 +783,7 @@ class Session(object):
             self.last_range_bits = bits
             guard.clear_flags()
             gnn.leave_h2()
-            return self.capture_train_step(b)
+            return self.capture_train_step(b, micro_batches)
         side = torch.cuda.Stream(device=self.device)
         ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         self.store.version += 1               # force every packed-weight copy to be rebuilt INSIDE graph A
@@ -718,7 +808,7 @@ class Session(object):
 
         dead = [None]    # once the guard has fired this closure is finished: graph A holds the f16x2 kernels
 
-        def replay():
+        def look():      # before a replay enqueues anything: the words as replay i - LAG left them
             if dead[0] is not None:
                 raise RuntimeError(dead[0])
             if len(inflight) >= LAG:
@@ -744,9 +834,8 @@ class Session(object):
                                "(its graph holds the f16x2 kernels): call capture_train_step() again -- it will run on "
                                "bf16x3 (bf16 storage: with the message MLPs' backward on the fp32 matrix instruction)" % why)
                     raise RuntimeError(dead[0])
-            ga.replay()
-            self.allreduce_grads(b.B, out["stats"])   # device-side only: no host sync between the two graphs
-            gb.replay()
+
+        def done():      # after graph B: this replay's words start their way to the host, the host mirrors move on
             if gnn.training_packs_h2():
                 words = ring[count[0] % (LAG + 1)]
                 count[0] += 1
@@ -757,5 +846,27 @@ class Session(object):
             self._adam["step"] += 1
             self.store.touch()
             return out
+
+        if micro_batches is None:
+            def replay():
+                look()
+                ga.replay()
+                self.allreduce_grads(b.B, out["stats"])   # device-side only: no host sync between the two graphs
+                gb.replay()
+                return done()
+        else:
+            K = int(micro_batches)
+            store.accum_bucket()
+
+            def replay(refill=None):
+                look()
+                for k in range(K):
+                    if refill is not None:
+                        refill(k)         # micro-batch k into b's buffers, on this stream: graph A reads them next
+                    ga.replay()
+                    self.accumulate_grads(b.B, out["stats"], first=(k == 0))
+                self.reduce_accumulated(out["stats"])
+                gb.replay()
+                return done()
         replay.graphs = (ga, gb)
         return replay

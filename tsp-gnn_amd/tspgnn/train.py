@@ -84,6 +84,41 @@ def run_batch(sess, model, batch, batch_i, epoch_i, time_steps, train=False, ver
             stats["TP"], stats["FP"], stats["TN"], stats["FN"])
 
 
+def run_batches_accumulated(sess, model, batches, batch_i, epoch_i, time_steps, verbose=True):
+    """ONE optimiser step over ``batches`` (Session.train_step_accumulated): create_batch 6-tuples or DeviceBatches, each
+    a micro-batch whose gradient counts with weight B_k / B.  Returns run_batch's 8-tuple for their union: loss and acc
+    are the B-weighted means, TP .. FN the sums, the label / prediction means are taken over all graphs (reduced across
+    ranks as run_batch's are)."""
+    from .model import DeviceBatch
+    feeds, labels, n_vertices, n_edges = [], [], [], []
+    for batch in batches:
+        if isinstance(batch, DeviceBatch):
+            batch.T = int(time_steps)
+            feeds.append(batch)
+            host = (batch.route_exists, batch.n_vertices, batch.n_edges)
+        else:
+            feeds.append(_feed_for(model, batch, time_steps))
+            host = batch[3:6]
+        for dest, part in zip((labels, n_vertices, n_edges), host):
+            dest.append(np.asarray(part).reshape(-1))
+    out = sess.train_step_accumulated(feeds)
+    values = out["stats"].cpu().numpy()
+    stats = {key: np.float32(values[k]) for k, key in enumerate(("loss", "acc", "TP", "FP", "TN", "FN"))}
+    predictions = np.concatenate([p.cpu().numpy() for p in out["predictions"]])
+    labels, n_vertices, n_edges = (np.concatenate(x) for x in (labels, n_vertices, n_edges))
+    mean_label, mean_pred = _batch_means(sess, labels, predictions)
+    if verbose:
+        _log("train", epoch_i, (
+            ("batch", batch_i), ("micro_batches", len(feeds)),
+            ("vertices", int(np.sum(n_vertices))), ("edges", int(np.sum(n_edges))), ("graphs", len(n_vertices)),
+            ("loss", "%.4f" % stats["loss"]), ("acc", "%.4f" % stats["acc"]),
+            ("label_mean", "%.4f" % mean_label),
+            ("decided_yes", "%.4f" % float(np.mean(np.round(predictions)))),
+        ))
+    return (stats["loss"], stats["acc"], mean_label, mean_pred,
+            stats["TP"], stats["FP"], stats["TN"], stats["FN"])
+
+
 def summarize_epoch(epoch_i, loss, acc, sat, pred, train=False):
     """Epoch line: the means of the per-batch values ``run_batch`` returned (train.py:66-76)."""
     _log("train" if train else "test", epoch_i, (

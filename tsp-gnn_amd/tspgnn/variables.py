@@ -52,6 +52,7 @@ class VariableStore(object):
                               # Session re-broadcasts from rank 0 before its next training step
         self._packed = {}
         self.grad = None      # flat gradient buffer, same layout as theta (allocated on first use)
+        self.accum = None     # gradient accumulation's second bucket (accum_bucket(): allocated on first use)
         self.guard = None     # the f16x2 range guard's device words and host latches (range_guard.py): made by finalize()
 
     def h2_guard(self):
@@ -164,6 +165,14 @@ class VariableStore(object):
         else:
             self.bucket.zero_()
         return self.grad
+
+    def accum_bucket(self):
+        """The second buffer of gradient accumulation (Session.accumulate_grads), of the bucket's size and layout: the
+        micro-batches' B_k-weighted gradients and tails are summed here while ``bucket`` takes the next micro-batch's.
+        Allocated on first use; its contents are whatever the last accumulated step left (``first=True`` overwrites)."""
+        if self.accum is None:
+            self.accum = torch.empty(self.theta.numel() + self.BUCKET_TAIL, dtype=torch.float32, device=self.theta.device)
+        return self.accum
 
     def grad_view(self, name):
         off, n = self._offsets[name]
