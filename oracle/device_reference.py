@@ -38,7 +38,7 @@ def spread_draw(params, draw):
             for k, v in params.items()}
 
 
-def trajectory(params, batch, depths, dtype, device, start=None, bf16=False, fold=INFERENCE_FOLD):
+def trajectory(params, batch, depths, dtype, device, start=None, bf16=False, fold=INFERENCE_FOLD, msg_last_relu=False):
     """The forward at each depth of ``depths`` (steps taken): {t: {"V.h", "V.c", "E.h", "E.c": state [rows, d],
     "predictions", "loss", "acc", "TP", "FP", "TN", "FN": vote head on E.h}}, tensors of ``dtype`` on ``device``, no
     autograd.  ``params``: the variables (NumPy).  ``start``: (Vh, Vc, Eh, Ec) to step from instead of the initial
@@ -48,7 +48,7 @@ def trajectory(params, batch, depths, dtype, device, start=None, bf16=False, fol
     depths = sorted(set(int(t) for t in depths))
     tp = TO.to_torch(params, dtype, device=device)
     d = tp["V_init"].shape[1]
-    step = TF._step_fn(bf16, d, fold)
+    step = TF._step_fn(bf16, d, fold, msg_last_relu)
     uv = torch.as_tensor(np.asarray(batch["ev_uv"]), dtype=torch.long, device=device)
     out = {}
     with torch.no_grad():
@@ -97,18 +97,19 @@ def no_tf32():
         torch.backends.cuda.matmul.allow_tf32 = tf32
 
 
-def reference(params, batch, depths, device, start=None):
+def reference(params, batch, depths, device, start=None, msg_last_relu=False):
     """-> (float64 trajectory, {t: {"V.h" | "V.c" | "E.h" | "E.c" | "predictions" | "loss": bar per row}}).  The float32
     run must not use TF32 / XF32 on the matrix cores (asserted).  Its index_add sums in atomic order on the GPU, so the
     float32 term moves slightly from run to run."""
-    ref = trajectory(params, batch, depths, torch.float64, device, start=start)
+    kw = dict(start=start, msg_last_relu=msg_last_relu)
+    ref = trajectory(params, batch, depths, torch.float64, device, **kw)
     with no_tf32():
-        f32 = trajectory(params, batch, depths, torch.float32, device, start=start)
+        f32 = trajectory(params, batch, depths, torch.float32, device, **kw)
     err32 = {t: {k: row_err(f32[t][k], ref[t][k]) for k in OUTPUTS} for t in ref}
     del f32
     spread = {t: {k: torch.zeros_like(err32[t][k]) for k in OUTPUTS} for t in ref}
     for draw in range(SPREAD_DRAWS):
-        fd = trajectory(spread_draw(params, draw), batch, depths, torch.float64, device, start=start)
+        fd = trajectory(spread_draw(params, draw), batch, depths, torch.float64, device, **kw)
         for t in ref:
             for k in OUTPUTS:
                 spread[t][k] = torch.maximum(spread[t][k], row_err(fd[t][k], ref[t][k]))

@@ -21,21 +21,22 @@ import numpy as np
 LN_GATES = ("input", "transform", "forget", "output", "state")
 
 
-def mlp_layer_sizes(d):
+def mlp_layer_sizes(d, msg_layers=4):
     """(in,out) per Dense layer of each MLP; int() mirrors tf.layers.Dense(int(units))
-    for the float sizes d/8, d/4, d/2 at model.py:34."""
+    for the float sizes d/8, d/4, d/2 at model.py:34.  ``msg_layers``: Dense layers of a message MLP,
+    GraphNN's MLP_depth + 1 (graphnn.py:116: [d] * MLP_depth and the output layer)."""
     return {
         "E_init_MLP": [(2, int(d / 8)), (int(d / 8), int(d / 4)), (int(d / 4), int(d / 2)), (int(d / 2), d)],
-        "TSP/V_msg_E": [(d, d)] * 4,
-        "TSP/E_msg_V": [(d, d)] * 4,
+        "TSP/V_msg_E": [(d, d)] * int(msg_layers),
+        "TSP/E_msg_V": [(d, d)] * int(msg_layers),
         "E_vote": [(d, d), (d, d), (d, d), (d, 1)],
     }
 
 
-def param_shapes(d):
+def param_shapes(d, msg_layers=4):
     """OrderedDict name -> shape, in canonical flat order."""
     shapes = OrderedDict()
-    sizes = mlp_layer_sizes(d)
+    sizes = mlp_layer_sizes(d, msg_layers)
     for i, (a, b) in enumerate(sizes["E_init_MLP"]):
         shapes["E_init_MLP_MLP_layer_%d/kernel" % (i + 1)] = (a, b)
         shapes["E_init_MLP_MLP_layer_%d/bias" % (i + 1)] = (b,)
@@ -75,7 +76,7 @@ def _xavier(rng, shape):
     return rng.uniform(-lim, lim, size=shape)
 
 
-def init_params(d, seed=0, perturb=False, round_f32=True):
+def init_params(d, seed=0, perturb=False, round_f32=True, msg_layers=4):
     """float64 numpy parameters with the reference's initialisers.  ``round_f32`` (default) rounds
     every value to the nearest float32 so that the fp32 device copy and the float64 oracle hold
     IDENTICAL weights (otherwise the 6e-8 rounding of the upload is amplified by the recurrence).
@@ -83,10 +84,11 @@ def init_params(d, seed=0, perturb=False, round_f32=True):
     ``perturb=True`` additionally randomises every bias / LayerNorm gain / shift so
     that parity tests exercise the terms that are 0 or 1 at initialisation.
     Weight-*stream* parity with TF's RNG is not attempted.
+    ``msg_layers``: Dense layers of each message MLP (mlp_layer_sizes).
     """
     rng = np.random.RandomState(seed)
     out = OrderedDict()
-    for name, shape in param_shapes(d).items():
+    for name, shape in param_shapes(d, msg_layers).items():
         if name == "V_init":
             p = rng.standard_normal(shape)
         elif name.endswith("/kernel"):

@@ -18,14 +18,15 @@ import torch
 from . import torch_oracle as TO
 
 
-def _step_fn(bf16, d, fold=None):
+def _step_fn(bf16, d, fold=None, msg_last_relu=False):
     """The oracle step of the semantics; bf16: with the edge cell folded exactly where the build's TRAINING forward folds it
     (d = 64, LayerNormBasicLSTMCell.can_fold), or as ``fold`` says: the two forms round at different points
-    (torch_oracle.step_bf16).  The inference forward folds at every width (oracle/device_reference.INFERENCE_FOLD)."""
+    (torch_oracle.step_bf16).  The inference forward folds at every width (oracle/device_reference.INFERENCE_FOLD).
+    ``msg_last_relu``: the message MLPs end in a relu (GraphNN's Msg_last_activation)."""
     if not bf16:
-        return TO.step
+        return TO.step if not msg_last_relu else (lambda *a, **kw: TO.step(*a, msg_last_relu=True, **kw))
     fold = (d == 64) if fold is None else bool(fold)
-    return lambda *a, **kw: TO.step_bf16(*a, fold=fold, **kw)
+    return lambda *a, **kw: TO.step_bf16(*a, fold=fold, msg_last_relu=msg_last_relu, **kw)
 
 
 def _uv(batch, device):
@@ -57,7 +58,7 @@ def _stored_at(stored, t, device, dtype):
     return {k: v.to(device=device, dtype=dtype) for k, v in stored(t).items()}
 
 
-def forced_grads(params, batch, T, H, C, *, bf16, device, dtype, weights=None, stored=None):
+def forced_grads(params, batch, T, H, C, *, bf16, device, dtype, weights=None, stored=None, msg_last_relu=False):
     """Back-propagation through time of the message passing (bf16=True: in the bf16-storage semantics, roundings passed
     straight through), one step at a time at the stored states H[t], C[t], then through the initial embeddings and the vote
     head.  ``params``: the variables (NumPy); ``weights`` (default: params): the values the graph is evaluated at -- e.g. a
@@ -68,7 +69,7 @@ def forced_grads(params, batch, T, H, C, *, bf16, device, dtype, weights=None, s
     names, plist = list(params.keys()), [tp[k] for k in params]
     total = [torch.zeros_like(p) for p in plist]
     uv = _uv(batch, device)
-    step = _step_fn(bf16, H["V"].shape[2])
+    step = _step_fn(bf16, H["V"].shape[2], msg_last_relu=msg_last_relu)
 
     def leaf(a):
         return a.to(device=device, dtype=dtype).detach().requires_grad_(True)
@@ -98,7 +99,8 @@ def forced_grads(params, batch, T, H, C, *, bf16, device, dtype, weights=None, s
     return OrderedDict((k, g.detach().to(torch.float64).cpu().numpy()) for k, g in zip(names, total))
 
 
-def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.float64, stored=None, fold=None):
+def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.float64, stored=None, fold=None,
+                       msg_last_relu=False):
     """Every row of every stored state H[t+1], C[t+1] against one oracle step from the stored (H[t], C[t]), t = 0..T-1.
     -> {"V.h" | "V.c" | "E.h" | "E.c": statistics over all rows of all steps}:
          max    largest |stored - oracle|,            sumsq  sum of the squared differences,   n  entries compared,
@@ -109,7 +111,7 @@ def forced_step_errors(params, batch, T, H, C, *, bf16, device, dtype=torch.floa
     ``stored``: as in forced_grads.  ``fold``: the bf16 edge cell's form (default: the training forward's, _step_fn)."""
     tp = TO.to_torch(params, dtype, device=device)
     uv = _uv(batch, device)
-    step = _step_fn(bf16, H["V"].shape[2], fold)
+    step = _step_fn(bf16, H["V"].shape[2], fold, msg_last_relu)
     keys = (("V", "h"), ("V", "c"), ("E", "h"), ("E", "c"))
     acc = {"%s.%s" % k: {"max": 0.0, "sumsq": 0.0, "n": 0, "scale": 0.0, "ulps": 0.0, "whole": 0, "ulps_top": 0.0}
            for k in keys}

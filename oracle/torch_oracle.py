@@ -96,8 +96,17 @@ def dense_ev(ev_uv, n_total, dtype):
     return EV
 
 
-def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, trace=None):
-    """GraphNN.__call__ for the TSP wiring (graphnn.py:134-179, model.py:57-94): ``time_steps`` iterations of ``step``."""
+def msg_layers(params, msg="V_msg_E"):
+    """Dense layers of the message MLP ``msg``, counted from the variables' names (GraphNN's MLP_depth + 1)."""
+    n = 0
+    while "TSP/%s_MLP_layer_%d/kernel" % (msg, n + 1) in params:
+        n += 1
+    return n
+
+
+def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, trace=None, msg_last_relu=False):
+    """GraphNN.__call__ for the TSP wiring (graphnn.py:134-179, model.py:57-94): ``time_steps`` iterations of ``step``.
+    ``msg_last_relu``: GraphNN's Msg_last_activation is relu (graphnn.py:119), not the default None."""
     N = V0.shape[0]
     uv = torch.as_tensor(np.asarray(ev_uv), dtype=torch.long, device=V0.device)
     if dense and EV is None:
@@ -105,24 +114,25 @@ def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, tra
     Vh, Vc = V0, torch.zeros_like(V0)  # graphnn.py:135-138
     Eh, Ec = E0, torch.zeros_like(E0)
     for t in range(int(time_steps)):
-        Vh, Vc, Eh, Ec = step(params, uv, Vh, Vc, Eh, Ec, EV=EV if dense else None)
+        Vh, Vc, Eh, Ec = step(params, uv, Vh, Vc, Eh, Ec, EV=EV if dense else None, msg_last_relu=msg_last_relu)
         if trace is not None:
             trace.append((Vh.detach().clone(), Eh.detach().clone()))
     return {"V": (Vh, Vc), "E": (Eh, Ec)}
 
 
-def step(params, uv, Vh, Vc, Eh, Ec, EV=None):
+def step(params, uv, Vh, Vc, Eh, Ec, EV=None, msg_last_relu=False):
     """One message-passing step of message_passing (graphnn.py:143-170): -> the next (Vh, Vc, Eh, Ec).  Both updates
     read the *old* states (new_states is a fresh dict, graphnn.py:143).  uv: long tensor [M,2]; EV given: the
-    adjacency products by the dense block-diagonal matrix (tf.matmul op for op) instead of index_add / gather."""
+    adjacency products by the dense block-diagonal matrix (tf.matmul op for op) instead of index_add / gather.
+    The message MLPs have as many layers as ``params`` names (msg_layers); ``msg_last_relu``: relu on their last one."""
     # V <- LSTM_V( EV^T x E_msg_V(E.h) )
-    y = mlp(Eh, params, "TSP/E_msg_V")
+    y = mlp(Eh, params, "TSP/E_msg_V", msg_layers(params, "E_msg_V"), msg_last_relu)
     if EV is not None:
         vagg = EV.t() @ y  # tf.matmul(..., adjoint_a=True)
     else:
         vagg = torch.zeros_like(Vh).index_add(0, uv[:, 0], y).index_add(0, uv[:, 1], y)
     # E <- LSTM_E( EV x V_msg_E(V.h) )
-    y2 = mlp(Vh, params, "TSP/V_msg_E")
+    y2 = mlp(Vh, params, "TSP/V_msg_E", msg_layers(params, "V_msg_E"), msg_last_relu)
     if EV is not None:
         eagg = EV @ y2
     else:
@@ -139,7 +149,7 @@ def _rb(x):
     return x + (x.to(torch.bfloat16).to(x.dtype) - x).detach()
 
 
-def message_passing_bf16(params, ev_uv, V0, E0, time_steps, fold=True):
+def message_passing_bf16(params, ev_uv, V0, E0, time_steps, fold=True, msg_last_relu=False):
     """The build's bf16-storage mode (BASELINE config 5: "bf16 embeddings with fp32 accumulate"; the reference has
     no reduced-precision path, this restates where tsp-gnn_amd rounds): embeddings h, every stored MLP activation,
     the V<-E aggregate and the projected vertex messages Zx = V_msg_E(V.h) Kx are rounded to bf16, GEMM weights are
@@ -149,11 +159,11 @@ def message_passing_bf16(params, ev_uv, V0, E0, time_steps, fold=True):
     Vh, Vc = _rb(V0), torch.zeros_like(V0)
     Eh, Ec = _rb(E0), torch.zeros_like(E0)
     for t in range(int(time_steps)):
-        Vh, Vc, Eh, Ec = step_bf16(params, uv, Vh, Vc, Eh, Ec, fold=fold)
+        Vh, Vc, Eh, Ec = step_bf16(params, uv, Vh, Vc, Eh, Ec, fold=fold, msg_last_relu=msg_last_relu)
     return {"V": (Vh, Vc), "E": (Eh, Ec)}
 
 
-def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True):
+def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True, msg_last_relu=False):
     """One message-passing step of message_passing_bf16 on stored (bf16-valued) h and fp32-class c: -> the next
     (Vh, Vc, Eh, Ec), h rounded for storage.  uv: long tensor [M,2].
     ``fold``: the edge cell's input in the folded form, z = Zx[u] + Zx[v] + h Kh with Zx = bf16(y Kx) -- what the build runs
@@ -161,7 +171,9 @@ def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True):
     the other widths: the two round at different points.
     ``stored`` (optional): values a device stored for this step's bf16-rounded intermediates, used IN PLACE of the
     oracle's own rounding (straight through, like it): "E_msg_V" / "V_msg_E" the hidden activations of the message MLPs
-    [3, rows, d], "vagg" the V<-E aggregate [N, d], "y2" the vertex messages [N, d], "zx" the projected messages [N, 4d]."""
+    [layers - 1 or more, rows, d], "vagg" the V<-E aggregate [N, d], "y2" the vertex messages [N, d], "zx" the projected
+    messages [N, 4d].
+    The message MLPs have as many layers as ``params`` names (msg_layers); ``msg_last_relu``: relu on their last one."""
     d = Vh.shape[1]
     stored = stored or {}
 
@@ -169,10 +181,14 @@ def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True):
         return _rb(x) if s is None else x + (s.to(x.dtype) - x).detach()
 
     def mlp_b(x, prefix, acts=None, out=None):
-        for i in range(4):
+        n = msg_layers(params, prefix[len("TSP/"):])
+        for i in range(n):
             W = _rb(params["%s_MLP_layer_%d/kernel" % (prefix, i + 1)])
             x = x @ W + params["%s_MLP_layer_%d/bias" % (prefix, i + 1)]
-            x = pin(torch.relu(x), None if acts is None else acts[i]) if i < 3 else pin(x, out)
+            if i < n - 1:
+                x = pin(torch.relu(x), None if acts is None else acts[i])
+            else:
+                x = pin(torch.relu(x) if msg_last_relu else x, out)
         return x
 
     def cell_b(z, c, cell):
@@ -200,7 +216,7 @@ def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True):
     return nVh, nVc, nEh, nEc
 
 
-def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold=True):
+def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold=True, msg_last_relu=False):
     """build_network forward (model.py:18-157) on a packed batch.
 
     batch: dict with ev_uv int[M,2], W[M], C[M], route_exists[B], n_vertices[B], n_edges[B].
@@ -208,9 +224,10 @@ def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold
     """
     V0, E0 = initial_embeddings(params, batch)
     if bf16:
-        last = message_passing_bf16(params, batch["ev_uv"], V0, E0, time_steps, fold=fold)
+        last = message_passing_bf16(params, batch["ev_uv"], V0, E0, time_steps, fold=fold, msg_last_relu=msg_last_relu)
     else:
-        last = message_passing(params, batch["ev_uv"], V0, E0, time_steps, dense=dense, trace=trace)
+        last = message_passing(params, batch["ev_uv"], V0, E0, time_steps, dense=dense, trace=trace,
+                               msg_last_relu=msg_last_relu)
     out = vote_head(params, batch, last["E"][0])
     out["last_states"] = last
     return out
@@ -267,11 +284,12 @@ def sigmoid_cross_entropy_with_logits(x, z):
     return torch.clamp(x, min=0) - x * z + torch.log1p(torch.exp(-x.abs()))
 
 
-def loss_and_grads(params_np, batch, time_steps, dtype=torch.float64, dense=False, bf16=False, fold=True):
+def loss_and_grads(params_np, batch, time_steps, dtype=torch.float64, dense=False, bf16=False, fold=True,
+                   msg_last_relu=False):
     """tf.gradients(loss + 1e-10 * sum l2_loss(var)) (model.py:163-166), unclipped.  bf16=True: of the bf16-storage
     forward (message_passing_bf16), roundings passed straight through, gradients w.r.t. the unrounded variables."""
     params = to_torch(params_np, dtype=dtype, requires_grad=True)
-    out = forward(params, batch, time_steps, dense=dense, bf16=bf16, fold=fold)
+    out = forward(params, batch, time_steps, dense=dense, bf16=bf16, fold=fold, msg_last_relu=msg_last_relu)
     vars_cost = sum((p ** 2).sum() / 2 for p in params.values())
     total = out["loss"] + L2NORM_SCALING * vars_cost
     grads = torch.autograd.grad(total, list(params.values()))

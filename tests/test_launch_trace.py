@@ -107,10 +107,15 @@ def recording(forward, env={}):
 
 
 # ---------------------------------------------------------------------------------------------------------------- wirings
-def _tsp(d, float_dtype=torch.float32):
-    """The network's own wiring (build_network): V <- EV^T msg(E), E <- EV msg(V)."""
-    model = tspgnn.build_network(d, store=V.VariableStore(), float_dtype=float_dtype)
+def _tsp(d, float_dtype=torch.float32, **msg):
+    """The network's own wiring (build_network): V <- EV^T msg(E), E <- EV msg(V).  ``msg``: MLP_depth, Msg_last_activation."""
+    model = tspgnn.build_network(d, store=V.VariableStore(), float_dtype=float_dtype, **msg)
     return model["gnn"], {"V": "N", "E": "M"}, lambda ev: {"EV": ev}
+
+
+def _tsp_msg(depth, last):
+    """_tsp with message MLPs of ``depth`` hidden layers and the last layer's activation ``last`` (None / "relu")."""
+    return lambda d, float_dtype=torch.float32: _tsp(d, float_dtype, MLP_depth=depth, Msg_last_activation=last)
 
 
 def _two_entries(d, float_dtype=torch.float32):
@@ -148,6 +153,17 @@ def _generic(d, float_dtype=torch.float32):
     return gnn, {"U": 9, "W": 7}, lambda ev: {"M": A, "F": F}
 
 
+# message MLPs off the default (three hidden layers, a linear last one): the depth decides whether the vertex cell is pushed,
+# the layers and relu masks of every message task, the tape's acts and how many kernels a chain takes (two layers each at 128)
+MSG_DEPTH = {
+    "tsp-d64-f16x2-depth0": (_tsp_msg(0, None), 64, torch.float32, dict(gemm="f16x2"), "h2"),
+    "tsp-d64-f16x2-depth1": (_tsp_msg(1, None), 64, torch.float32, dict(gemm="f16x2"), "h2"),
+    "tsp-d64-f16x2-depth2-relu": (_tsp_msg(2, "relu"), 64, torch.float32, dict(gemm="f16x2"), "h2"),
+    "tsp-d64-f16x2-depth3-relu": (_tsp_msg(3, "relu"), 64, torch.float32, dict(gemm="f16x2"), "h2"),
+    "tsp-d128-depth1": (_tsp_msg(1, None), 128, torch.float32, dict(gemm="f16x2"), "h2"),
+    "tsp-d128-depth2": (_tsp_msg(2, None), 128, torch.float32, dict(gemm="f16x2"), "h2"),
+    "tsp-d64-bf16-depth1-relu": (_tsp_msg(1, "relu"), 64, BF16, dict(gemm="f16x2"), "h2"),
+}
 # case -> (wiring, d, storage type, attributes set on the GraphNN, active_arith() expected)
 FORWARD = {
     "tsp-d64-f16x2": (_tsp, 64, torch.float32, dict(gemm="f16x2"), "h2"),
@@ -163,6 +179,7 @@ FORWARD = {
     "two-entries-d64-bf16": (_two_entries, 64, BF16, dict(gemm="f16x2"), "h2"),
     "generic-d32": (_generic, 32, torch.float32, dict(gemm="f16x2"), "h2"),
 }
+FORWARD.update(MSG_DEPTH)
 TRAIN = {
     "tsp-d64-f16x2-pushed": (_tsp, 64, torch.float32, dict(gemm="f16x2"), "h2"),
     "tsp-d64-f16x2-unpushed": (_tsp, 64, torch.float32, dict(gemm="f16x2", push_training=False), "h2"),
@@ -177,6 +194,7 @@ TRAIN = {
     "generic-d32-f16x2": (_generic, 32, torch.float32, dict(gemm="f16x2"), "h2"),
     "generic-d32-f32": (_generic, 32, torch.float32, dict(gemm="f32"), None),
 }
+TRAIN.update(MSG_DEPTH)
 SWITCHES = dict(fold_adjacency=True, center_gates=True, persistent_loop=False, push_training=True,
                 fuse_training_messages=False, mlp_backward_h2=True, recompute_messages=False)
 
@@ -264,7 +282,7 @@ TRAIN_IDS = [("train/%s/T3" % case, case, 3) for case in TRAIN]
 NATIVE = ("tsp-d64-bf16", "two-entries-d64-bf16")       # the wirings whose bf16 tape the backward reads as it is
 PUSHED, UNPUSHED = "tsp-d64-f16x2-pushed", "tsp-d64-f16x2-unpushed"
 # (key, wiring, T, run_backward_case's keywords)
-BACKWARD_IDS = [("backward/%s/T3" % case, case, 3, dict(h2_ok=case in NATIVE)) for case in TRAIN]
+BACKWARD_IDS = [("backward/%s/T3" % case, case, 3, dict(h2_ok=case in NATIVE + ("tsp-d64-bf16-depth1-relu",))) for case in TRAIN]
 BACKWARD_IDS += [("backward/%s/T3/mlp-f32" % case, case, 3, dict(attrs=dict(mlp_backward_h2=False))) for case in NATIVE]
 BACKWARD_IDS += [("backward/%s/T3/chunk-1" % PUSHED, PUSHED, 3, dict(chunks="one")),
                  ("backward/%s/T5/chunk-partial" % PUSHED, PUSHED, 5, dict(chunks="partial")),
@@ -308,6 +326,28 @@ def test_training_forward_launches(key, case, T):
 @pytest.mark.parametrize("key,case,T,how", BACKWARD_IDS, ids=[k for k, _, _, _ in BACKWARD_IDS])
 def test_backward_launches(key, case, T, how):
     _check(key, run_backward_case(case, T, **how))
+
+
+def test_a_relu_on_a_chain_s_last_layer_comes_with_its_output():
+    """Every message-MLP backward task of every recorded backward pass: a relu on the task's last layer (bit n_layers - 1
+    of relu_mask) is masked by the chain's forward output, so Yout is not null -- the library refuses the task otherwise
+    (csrc/launch_plan.h, check_mlp_bwd_task; tspgnn_mlp_bwd_rc_h2 likewise)."""
+    fields = {s.__name__: [name for name, _ in s._fields_] for s in (_lib.MlpBwdTask, _lib.MlpBwdRcTask)}
+    seen = ended_in_relu = 0
+    for key, case, T, how in BACKWARD_IDS:
+        for call in run_backward_case(case, T, **how).get("trace", []):
+            if isinstance(call, dict) and call["struct"] in fields:
+                tasks = [dict(zip(fields[call["struct"]], t)) for t in call["tasks"]]
+            elif isinstance(call, list) and call[0] in BY_POINTER:
+                tasks = [dict(zip(fields[BY_POINTER[call[0]].__name__], call[1]))]
+            else:
+                continue
+            for t in tasks:
+                seen += 1
+                if (t["relu_mask"] >> (t["n_layers"] - 1)) & 1:
+                    ended_in_relu += 1
+                    assert t["Yout"] is not None, (key, t)
+    assert seen > 0 and ended_in_relu > 0       # (the pushed prefixes and the chains of Msg_last_activation="relu")
 
 
 def test_fixture_holds_exactly_these_cases():

@@ -177,7 +177,8 @@ class _States(dict):
 class Tape(object):
     """What GraphNN.forward_train keeps for the backward pass: every step's states H, C ([T+1, rows, d]), cell inputs
     X (for a folded cell: the message y per SOURCE row, with ZX = y Kx), hidden MLP activations acts
-    ([layers-1, T, rows, d]).  fp32 in the default mode; in the bf16-storage mode H, X, ZX, acts are the bf16 arrays
+    ([layers-1, T, rows, d]; one more slot for the output of a chain that ends in a relu and feeds an adjacency product,
+    GraphNN._message_output_slot).  fp32 in the default mode; in the bf16-storage mode H, X, ZX, acts are the bf16 arrays
     the forward stored (C stays fp32) and the accessors below widen a step -- or a range of steps for the weight
     gradients -- to the fp32 operands the backward kernels take."""
 
@@ -808,6 +809,21 @@ class GraphNN(object):
         """Stored entries per row of the adjacency product behind a pushed cell (the factor of its bias b Kx)."""
         u0 = self.loop[v][0]
         return mats[u0["mat"]].row_degrees(bool(u0.get("transpose?", False)))
+
+    def _message_to_tape(self, v, i, folded):
+        """The training forward writes loop entry (v, i)'s message straight into the tape's cell input X[v]: a folded
+        cell keeps the message per source row, a cell whose only entry has no matrix takes it as it is."""
+        return folded[v] is not None or (len(self.loop[v]) == 1 and "mat" not in self.loop[v][i])
+
+    def _message_output_slot(self, v, i, folded):
+        """Layer slot of the tape's acts[(v, i)] that keeps loop entry (v, i)'s message, or None.  The backward of a chain
+        that ends in a relu masks by the chain's output (tspgnn_mlp_bwd_task.Yout); where that output is only a
+        temporary of the forward -- it goes into an adjacency product or a concatenation -- the tape gets one more slot
+        behind the hidden activations for it.  A linear last layer (the default) needs none."""
+        mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
+        if not mlp.relu[-1] or self._message_to_tape(v, i, folded):
+            return None
+        return mlp.n_square - 1
 
     def _matrices(self, adjacency_matrices, device):
         """-> ({name: DeviceAdjacency} of the matrices that multiply an embedding, {name: dense fp32 tensor} of those a
@@ -1501,6 +1517,18 @@ class GraphNN(object):
         return new_states
 
     # ---------------------------------------------------------------- training: forward with a tape
+    def check_training(self):
+        """What forward_train / backward cover of this network's construction, asked before a training step launches or
+        zeroes anything (Session.loss_and_grads, forward_train): NotImplementedError otherwise.  A message MLP trains
+        with at most four layers (MLP_depth <= 3): the f16x2 / bf16x3 / bf16 training forwards and the fused backward
+        tasks take single-kernel chains, and the several-kernel fp32 chain is only exercised at width 128."""
+        if self.float_dtype not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError("training runs with float_dtype torch.float32 or torch.bfloat16")
+        for name, mlp in self._msg_MLPs.items():
+            if mlp.n_square > 4:
+                raise NotImplementedError("training: message MLP %s has %d layers, at most 4 (MLP_depth <= 3) are covered"
+                                          % (name, mlp.n_square))
+
     def forward_train(self, adjacency_matrices, initial_embeddings, time_steps):
         """Same computation as __call__, keeping what the backward pass needs: every step's states,
         cell inputs and hidden MLP activations, each stored [T, rows, width] contiguous so that a
@@ -1512,8 +1540,7 @@ class GraphNN(object):
         LayerNorm / gates) and the tape holds those bf16 arrays -- half the bytes; see backward()."""
         T = int(time_steps)
         bf16 = self.float_dtype == torch.bfloat16
-        if self.float_dtype not in (torch.float32, torch.bfloat16):
-            raise NotImplementedError("training runs with float_dtype torch.float32 or torch.bfloat16")
+        self.check_training()
         self.check_run(adjacency_matrices, initial_embeddings, T, {})
         device = next(iter(initial_embeddings.values())).device
         f32 = dict(dtype=torch.float32, device=device)
@@ -1549,6 +1576,8 @@ class GraphNN(object):
                 u = self.loop[v][i]
                 mlp, src = self._msg_MLPs[u["msg"]], u["var"]
                 layers = 1 if tape.rc.get((v, i)) else max(mlp.n_square - 1, 1)   # (recomputed: the messages only)
+                if self._message_output_slot(v, i, tape.folded) is not None:
+                    layers = mlp.n_square
                 tape.acts[(v, i)] = torch.empty((layers, T, n[src], self.var[src]), **stored)
         if bf16:
             tape.arith = "bf16"
@@ -1585,8 +1614,11 @@ class GraphNN(object):
             """(out, projection) of loop entry (v, i)'s message MLP at step t: outputs straight into the tape."""
             u = self.loop[v][i]
             mlp = self._msg_MLPs[u["msg"]]
-            to_tape = tape.folded[v] is not None or (len(self.loop[v]) == 1 and "mat" not in u)
-            out = tape.X[v][t] if to_tape else torch.empty((n[u["var"]], mlp.sizes[-1]), **f32)
+            slot = self._message_output_slot(v, i, tape.folded)
+            if self._message_to_tape(v, i, tape.folded):
+                out = tape.X[v][t]
+            else:
+                out = torch.empty((n[u["var"]], mlp.sizes[-1]), **f32) if slot is None else tape.acts[(v, i)][slot, t]
             proj = None
             if tape.folded[v] is not None:
                 cv = self._RNN_cells[v]
@@ -1715,8 +1747,11 @@ class GraphNN(object):
                     if "msg" in u:
                         mlp = self._msg_MLPs[u["msg"]]
                         d = mlp.sizes[-1]
-                        to_tape = tape.folded[v] is not None or (len(self.loop[v]) == 1 and "mat" not in u)
-                        out = tape.X[v][t] if to_tape else torch.empty((y.shape[0], d), **bf)
+                        slot = self._message_output_slot(v, i, tape.folded)
+                        if self._message_to_tape(v, i, tape.folded):
+                            out = tape.X[v][t]
+                        else:
+                            out = torch.empty((y.shape[0], d), **bf) if slot is None else tape.acts[(v, i)][slot, t]
                         proj = (None, None)
                         if tape.folded[v] is not None:
                             proj = (self._RNN_cells[v].packed("Kx", "bf16"), tape.ZX[v][t])
@@ -1949,7 +1984,13 @@ class GraphNN(object):
         adjoint = dict(transpose=not u.get("transpose?", False))    # of mat (x) y: mat^T (x) dy, and vice versa
         if mlp is not None and not tape.rc.get((v, i)):
             (acts_t, acts_stride), dpre = tape.acts_at((v, i), t), buf.DPRE[(v, i)]
-            chain = (acts_t, acts_stride, None, dpre[:, k], dpre.stride(0))
+            # the chain's forward output, read when its last layer has a relu (a pushed chain ends in a linear layer)
+            y_out = None
+            if mlp.relu[-1]:
+                slot = self._message_output_slot(v, i, tape.folded)
+                y_out = tape.x(v, t) if slot is None else acts_t[slot]
+                s.keep.append(y_out)
+            chain = (acts_t, acts_stride, y_out, dpre[:, k], dpre.stride(0))
         if "fun" in u:
             # graphnn.py:149-151: y = fun(h) ahead of the message MLP.  The gradient w.r.t. fun's OUTPUT is formed apart
             # (adjoint product, the MLP's backward on its own, never fused with another writer of dh), then pulled back

@@ -94,10 +94,12 @@ class Network(dict):
     """The dict build_network returns, plus the objects Session needs."""
 
 
-def build_network(d, store=None, float_dtype=torch.float32):
+def build_network(d, store=None, float_dtype=torch.float32, MLP_depth=3, Msg_last_activation=None):
     """model.py:9-170.  ``float_dtype=torch.bfloat16`` (the reference GraphNN's own float_dtype argument,
     graphnn.py:18) stores the embeddings as bf16 with fp32 accumulation (BASELINE config 5); training in that mode is
-    mixed precision: bf16 tape, fp32 gradients and fp32 master variables (GraphNN.backward)."""
+    mixed precision: bf16 tape, fp32 gradients and fp32 master variables (GraphNN.backward).  ``MLP_depth`` and
+    ``Msg_last_activation`` are GraphNN's own (graphnn.py:15-16): hidden layers of the message MLPs, and the activation of
+    their last layer."""
     d = int(d)
     store = store if store is not None else V.reset_default_store()
     GNN = Network()
@@ -136,6 +138,8 @@ def build_network(d, store=None, float_dtype=torch.float32):
             "E": [{"mat": "EV", "msg": "V_msg_E", "var": "V"}],
         },
         name="TSP",
+        MLP_depth=MLP_depth,
+        Msg_last_activation=Msg_last_activation,
         float_dtype=float_dtype,
         store=store,
     )
@@ -431,6 +435,7 @@ class Session(object):
         message passing's tape under "tape", for inspection -- it holds every step's states)."""
         self._require_gpu("a training step")
         m, d, st = self.model, self.model.d, _lib.current_stream()
+        m["gnn"].check_training()     # (a network that does not train is refused before the gradients are zeroed)
         b = feed if isinstance(feed, DeviceBatch) else self.prepare(feed)
         store = self.store
         store.zero_grad()
