@@ -44,9 +44,37 @@ def to_torch(params, dtype=torch.float64, requires_grad=False, device=None):
     return out
 
 
-def mlp(x, params, prefix, n_layers=4, last_activation=False):
+class RangeSites(object):
+    """Optional collector for mlp, lnlstm_cell, step, message_passing and forward (their ``sites`` argument; None, the
+    default, records nothing and changes nothing): what the f16x2 range guard of the build looks at, in the oracle's own
+    precision.  absmax[site]: the largest magnitude of a GEMM operand -- "<prefix>_MLP_layer_<l>" the input of that
+    Dense layer, "<cell>_cell/x" and "<cell>_cell/h" the two halves of a cell's operand, "<cell>_cell/x_pushed" the row-sum
+    of the sending MLP's LAST HIDDEN activation (the operand of the build's pushed form, z = rowsum(a) (W Kx) + degree (b Kx)
+    + h Kh), "<prefix>_out" the output of a message MLP (the operand of the projection through the receiving cell's Kx).
+    minvar[(cell, gate)]: the smallest positive variance (layer_norm's, biased) of a row of that gate's z; gate in
+    "input", "transform", "forget", "output".  Both over every call since the collector was made."""
+
+    def __init__(self):
+        self.absmax, self.minvar, self.last = {}, {}, {}
+
+    def operand(self, site, x):
+        self.last[site] = x
+        if x.numel():
+            self.absmax[site] = max(self.absmax.get(site, 0.0), float(x.detach().abs().max()))
+
+    def gates(self, cell, z):
+        for name, zg in zip(("input", "transform", "forget", "output"), torch.chunk(z.detach(), 4, dim=1)):
+            var = ((zg - zg.mean(dim=-1, keepdim=True)) ** 2).mean(dim=-1)
+            var = var[var > 0]
+            if var.numel():
+                self.minvar[(cell, name)] = min(self.minvar.get((cell, name), float("inf")), float(var.min()))
+
+
+def mlp(x, params, prefix, n_layers=4, last_activation=False, sites=None):
     """mlp.py:57-63 with activations [relu]*3 + [None] (graphnn.py:116-119, model.py:34-37)."""
     for i in range(n_layers):
+        if sites is not None:
+            sites.operand("%s_MLP_layer_%d" % (prefix, i + 1), x)
         W = params["%s_MLP_layer_%d/kernel" % (prefix, i + 1)]
         b = params["%s_MLP_layer_%d/bias" % (prefix, i + 1)]
         x = x @ W + b  # tf.layers.Dense: x @ kernel + bias, kernel[in,out]
@@ -64,7 +92,7 @@ def layer_norm(x, gamma, beta):
     return x * inv + (beta - mean * inv)
 
 
-def lnlstm_cell(x, h, c, params, cell, activation=torch.relu, base=None):
+def lnlstm_cell(x, h, c, params, cell, activation=torch.relu, base=None, sites=None):
     """tf.contrib.rnn.LayerNormBasicLSTMCell.call with activation=relu (graphnn.py:110,168-170).
     args = concat([inputs, h]); no bias; gates i,j,f,o; forget bias added after LN;
     the *normalised* new_c is both stored and fed to the output.
@@ -73,6 +101,10 @@ def lnlstm_cell(x, h, c, params, cell, activation=torch.relu, base=None):
     (tests/test_oracle.py::test_lnlstm_cell_reproduces_tensorflow_unit_test_constants)."""
     base = base if base is not None else "TSP/%s_cell/layer_norm_basic_lstm_cell" % cell
     z = torch.cat([x, h], dim=1) @ params[base + "/kernel"]
+    if sites is not None:
+        sites.operand("%s_cell/x" % cell, x)
+        sites.operand("%s_cell/h" % cell, h)
+        sites.gates(cell, z)
     i, j, f, o = torch.chunk(z, 4, dim=1)
     i = layer_norm(i, params[base + "/input/gamma"], params[base + "/input/beta"])
     j = layer_norm(j, params[base + "/transform/gamma"], params[base + "/transform/beta"])
@@ -104,7 +136,7 @@ def msg_layers(params, msg="V_msg_E"):
     return n
 
 
-def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, trace=None, msg_last_relu=False):
+def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, trace=None, msg_last_relu=False, sites=None):
     """GraphNN.__call__ for the TSP wiring (graphnn.py:134-179, model.py:57-94): ``time_steps`` iterations of ``step``.
     ``msg_last_relu``: GraphNN's Msg_last_activation is relu (graphnn.py:119), not the default None."""
     N = V0.shape[0]
@@ -114,31 +146,37 @@ def message_passing(params, ev_uv, V0, E0, time_steps, dense=False, EV=None, tra
     Vh, Vc = V0, torch.zeros_like(V0)  # graphnn.py:135-138
     Eh, Ec = E0, torch.zeros_like(E0)
     for t in range(int(time_steps)):
-        Vh, Vc, Eh, Ec = step(params, uv, Vh, Vc, Eh, Ec, EV=EV if dense else None, msg_last_relu=msg_last_relu)
+        Vh, Vc, Eh, Ec = step(params, uv, Vh, Vc, Eh, Ec, EV=EV if dense else None, msg_last_relu=msg_last_relu, sites=sites)
         if trace is not None:
             trace.append((Vh.detach().clone(), Eh.detach().clone()))
     return {"V": (Vh, Vc), "E": (Eh, Ec)}
 
 
-def step(params, uv, Vh, Vc, Eh, Ec, EV=None, msg_last_relu=False):
+def step(params, uv, Vh, Vc, Eh, Ec, EV=None, msg_last_relu=False, sites=None):
     """One message-passing step of message_passing (graphnn.py:143-170): -> the next (Vh, Vc, Eh, Ec).  Both updates
     read the *old* states (new_states is a fresh dict, graphnn.py:143).  uv: long tensor [M,2]; EV given: the
     adjacency products by the dense block-diagonal matrix (tf.matmul op for op) instead of index_add / gather.
     The message MLPs have as many layers as ``params`` names (msg_layers); ``msg_last_relu``: relu on their last one."""
     # V <- LSTM_V( EV^T x E_msg_V(E.h) )
-    y = mlp(Eh, params, "TSP/E_msg_V", msg_layers(params, "E_msg_V"), msg_last_relu)
+    y = mlp(Eh, params, "TSP/E_msg_V", msg_layers(params, "E_msg_V"), msg_last_relu, sites=sites)
     if EV is not None:
         vagg = EV.t() @ y  # tf.matmul(..., adjoint_a=True)
     else:
         vagg = torch.zeros_like(Vh).index_add(0, uv[:, 0], y).index_add(0, uv[:, 1], y)
     # E <- LSTM_E( EV x V_msg_E(V.h) )
-    y2 = mlp(Vh, params, "TSP/V_msg_E", msg_layers(params, "V_msg_E"), msg_last_relu)
+    y2 = mlp(Vh, params, "TSP/V_msg_E", msg_layers(params, "V_msg_E"), msg_last_relu, sites=sites)
+    if sites is not None:
+        a = sites.last["TSP/E_msg_V_MLP_layer_%d" % msg_layers(params, "E_msg_V")]      # the last hidden activation
+        sites.operand("V_cell/x_pushed", torch.zeros((Vh.shape[0], a.shape[1]), dtype=a.dtype, device=a.device)
+                      .index_add(0, uv[:, 0], a).index_add(0, uv[:, 1], a))
+        sites.operand("TSP/E_msg_V_out", y)
+        sites.operand("TSP/V_msg_E_out", y2)
     if EV is not None:
         eagg = EV @ y2
     else:
         eagg = y2[uv[:, 0]] + y2[uv[:, 1]]
-    nVh, nVc = lnlstm_cell(vagg, Vh, Vc, params, "V")
-    nEh, nEc = lnlstm_cell(eagg, Eh, Ec, params, "E")
+    nVh, nVc = lnlstm_cell(vagg, Vh, Vc, params, "V", sites=sites)
+    nEh, nEc = lnlstm_cell(eagg, Eh, Ec, params, "E", sites=sites)
     return nVh, nVc, nEh, nEc
 
 
@@ -216,7 +254,7 @@ def step_bf16(params, uv, Vh, Vc, Eh, Ec, stored=None, fold=True, msg_last_relu=
     return nVh, nVc, nEh, nEc
 
 
-def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold=True, msg_last_relu=False):
+def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold=True, msg_last_relu=False, sites=None):
     """build_network forward (model.py:18-157) on a packed batch.
 
     batch: dict with ev_uv int[M,2], W[M], C[M], route_exists[B], n_vertices[B], n_edges[B].
@@ -227,8 +265,8 @@ def forward(params, batch, time_steps, dense=False, trace=None, bf16=False, fold
         last = message_passing_bf16(params, batch["ev_uv"], V0, E0, time_steps, fold=fold, msg_last_relu=msg_last_relu)
     else:
         last = message_passing(params, batch["ev_uv"], V0, E0, time_steps, dense=dense, trace=trace,
-                               msg_last_relu=msg_last_relu)
-    out = vote_head(params, batch, last["E"][0])
+                               msg_last_relu=msg_last_relu, sites=sites)
+    out = vote_head(params, batch, last["E"][0], sites=sites)
     out["last_states"] = last
     return out
 
@@ -248,13 +286,13 @@ def initial_embeddings(params, batch):
     return V0, E0
 
 
-def vote_head(params, batch, E_n):
+def vote_head(params, batch, E_n, sites=None):
     """model.py:107-157 from the final edge embeddings: votes, per-problem mean, predictions, metrics, loss."""
     dtype = E_n.dtype
     labels = torch.as_tensor(np.asarray(batch["route_exists"]), dtype=dtype, device=E_n.device)
     n_edges = np.asarray(batch["n_edges"]).astype(np.int64)
     # model.py:128
-    E_vote = mlp(E_n, params, "E_vote").reshape(-1)
+    E_vote = mlp(E_n, params, "E_vote", sites=sites).reshape(-1)
     # model.py:134-145: mean of each problem's edge-vote segment
     offs = np.concatenate([[0], np.cumsum(n_edges)])
     logits = torch.stack([E_vote[offs[i]:offs[i + 1]].mean() for i in range(len(n_edges))])

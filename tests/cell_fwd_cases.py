@@ -95,7 +95,8 @@ class FwdCell(object):
     c_out == c (the layouts of both sides must agree).  zbias_scale: zbias times this, and zscale = 1 on the last row."""
 
     def __init__(self, arith, d, rows, seed, dx=0, mode="plain", mlp_layers=0, relu_mask=None, mlp_out=True, proj=False,
-                 acts=None, in_blocked=False, out_blocked=False, null_c=False, inplace=False, n_src=257, zbias_scale=1.0):
+                 acts=None, in_blocked=False, out_blocked=False, null_c=False, inplace=False, n_src=257, zbias_scale=1.0,
+                 pad_fill=SENTINEL):
         assert arith in ("h2", "x3") and mode in ("plain", "gather", "bias") and not (mode == "gather" and dx)
         assert arith == "h2" or not (in_blocked or out_blocked or acts or null_c or inplace)
         assert not inplace or in_blocked == out_blocked
@@ -124,8 +125,8 @@ class FwdCell(object):
         self.with_out = bool(mlp_out and mlp_layers)
         self.acts = acts if mlp_layers > 1 else None
         self.in_blocked, self.out_blocked, self.null_c, self.inplace = in_blocked, out_blocked, null_c, inplace
-        self.z_centered = False
-        self._ref = None
+        self.z_centered, self.pad_fill = False, pad_fill
+        self._ref = self._ops = None
 
     def centred(self):
         """Centres K, the projected messages (= the Kx behind them) and zbias per gate over its d columns, so that every
@@ -141,7 +142,7 @@ class FwdCell(object):
             self.Zx = per_gate(self.Zx)
         if self.mode == "bias":
             self.zbias = per_gate(self.zbias[None])[0]
-        self.z_centered, self._ref = True, None
+        self.z_centered, self._ref, self._ops = True, None, None
         return self
 
     def plan(self):
@@ -151,7 +152,7 @@ class FwdCell(object):
     # ------------------------------------------------------------------------------------------------------ the task
     def _state_in(self, a, device):
         t = dev(a, device)      # (SPARE rows behind an input too: in place it is the output)
-        b = torch.cat([blocked_pack(t, SENTINEL) if self.in_blocked else t, torch.full((SPARE, self.d), SENTINEL, device=device)])
+        b = torch.cat([blocked_pack(t, self.pad_fill) if self.in_blocked else t, torch.full((SPARE, self.d), SENTINEL, device=device)])
         _KEEP.append(b)
         return b
 
@@ -255,19 +256,23 @@ class FwdCell(object):
         return int(self.flag.item())
 
     # ------------------------------------------------------------------------------------------------------- reference
-    def reference(self, device):
-        """float64 on the device, from the stored fp32 operands: {h, c, msg, proj, acts} as outputs().  Computed once."""
-        if self._ref is not None:
-            return self._ref
-        d = self.d
-        h = t64(self.h, device)
-        z = torch.cat([t64(self.x, device), h], dim=1) @ t64(self.K, device)
+    def _z64(self, device):
+        """z of every row in float64, from the stored fp32 operands."""
+        z = torch.cat([t64(self.x, device), t64(self.h, device)], dim=1) @ t64(self.K, device)
         if self.mode == "gather":
             uv = torch.as_tensor(self.uv, dtype=torch.long, device=device)
             Zx = t64(self.Zx, device)
             z = z + Zx[uv[:, 0]] + Zx[uv[:, 1]]
         if self.mode == "bias":
             z = z + t64(self.zscale, device)[:, None] * t64(self.zbias, device)[None]
+        return z
+
+    def reference(self, device):
+        """float64 on the device, from the stored fp32 operands: {h, c, msg, proj, acts} as outputs().  Computed once."""
+        if self._ref is not None:
+            return self._ref
+        d = self.d
+        z = self._z64(device)
         ln = t64(self.ln, device)
         base = "cell"
         params = {base + "/kernel": torch.eye(4 * d, dtype=torch.float64, device=device)}      # the cell's GEMM: z itself
@@ -275,13 +280,32 @@ class FwdCell(object):
             params[base + "/%s/gamma" % g], params[base + "/%s/beta" % g] = ln[i, 0], ln[i, 1]
         nh, nc = TO.lnlstm_cell(z, z[:, :0], t64(self.c, device), params, None, base=base)
         ref = {"h": nh, "c": nc}
+        outs = mlp64(nh, self.layers, self.mask, device) if self.L else []
         if self.L:
-            outs = mlp64(nh, self.layers, self.mask, device)
             if self.with_out:
                 ref["msg"] = outs[-1]
             if self.P is not None:
                 ref["proj"] = outs[-1] @ t64(self.P, device)
             if self.acts:
                 ref["acts"] = torch.stack(outs[:-1])
-        self._ref = ref
+        # what the f16x2 range guard looks at (operands): every tensor a kernel splits, and the variance LayerNorm divides a
+        # gate row by -- oracle/torch_oracle.layer_norm's, the biased one
+        ops = {"h": t64(self.h, device)}
+        if self.dx:
+            ops["x"] = t64(self.x, device)
+        for l, a in enumerate([nh] + outs[:-1] if self.L else []):
+            ops["layer%d" % (l + 1)] = a          # layer 1 takes h', layer l + 1 the output of layer l
+        if self.P is not None:
+            ops["proj"] = outs[-1]
+        zg = z.reshape(self.rows, 4, d)
+        ops["var"] = ((zg - zg.mean(dim=2, keepdim=True)) ** 2).mean(dim=2)       # [rows, 4]: gates i, j, f, o
+        self._ref, self._ops = ref, ops
         return ref
+
+    def operands(self, device):
+        """float64 (device "cpu" works), from the same stored fp32 operands as reference(): {site: tensor} of every tensor
+        a kernel splits into fp16 pieces -- "x" (dx > 0), "h", "layer1" (h' into the fused MLP's first layer), "layer2" ..
+        (the input of each later layer), "proj" (the projection's input) -- and "var": [rows, 4], per row the variance of z
+        over each gate's d columns (i, j, f, o)."""
+        self.reference(device)
+        return self._ops
