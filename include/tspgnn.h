@@ -1084,9 +1084,12 @@ int tspgnn_plan_linear(int kin, int n1, int n2, int rows, int cus, tspgnn_linear
 typedef struct tspgnn_tasks_plan {    /* the ticket launches that only share out workgroups */
     int nw, grid, n;                  /* n: live tasks (rows > 0), in order */
     int blk_end[4];                   /* task k owns the workgroups [blk_end[k-1], blk_end[k]) */
+    int lds_bytes;                    /* dynamic LDS of the launch (0: none) */
 } tspgnn_tasks_plan;
 int tspgnn_plan_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out); /* tspgnn_mlp_bwd_multi_f32 */
 int tspgnn_plan_mlp_fwd(const tspgnn_mlp_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out);     /* tspgnn_mlp_fwd_multi_h2 / _x3, tspgnn_mlp_head_fwd_h2 */
+/* tspgnn_mlp_fwd_multi_bf16; nw: the wavefronts per workgroup its dispatch chooses (16 at d = 128 without a projection, else 8) */
+int tspgnn_plan_mlp_fwd_bf16(const tspgnn_mlp_task_bf16* tasks, int n_tasks, int d, int nw, int cus, tspgnn_tasks_plan* out);
 
 enum { TSPGNN_WGRAD_GENERIC = 0, TSPGNN_WGRAD_X3 = 1, TSPGNN_WGRAD_X3_PAIR = 2 };
 typedef struct tspgnn_wgrad_plan {    /* tspgnn_wgrad_f32 (bf16x == 0), tspgnn_wgrad_bf16x_f32 (bf16x != 0) */
@@ -1111,7 +1114,7 @@ typedef struct tspgnn_einit_bwd_plan {   /* tspgnn_einit_bwd_f32 */
 } tspgnn_einit_bwd_plan;
 int tspgnn_plan_einit_bwd(int M, int d, int cus, tspgnn_einit_bwd_plan* out);
 
-enum { TSPGNN_ARITH_H2 = 0, TSPGNN_ARITH_X3 = 1 };
+enum { TSPGNN_ARITH_H2 = 0, TSPGNN_ARITH_X3 = 1, TSPGNN_ARITH_F32 = 2, TSPGNN_ARITH_BF16 = 3 };
 typedef struct tspgnn_cell_fwd_plan {    /* tspgnn_lnlstm_mlp_fwd_multi_h2 / _x3 (arith: TSPGNN_ARITH_*) */
     int nw, grid, n;
     int blk_end[4];
@@ -1126,6 +1129,18 @@ typedef struct tspgnn_cell_fwd_plan {    /* tspgnn_lnlstm_mlp_fwd_multi_h2 / _x3
     int lds_bytes;
 } tspgnn_cell_fwd_plan;
 int tspgnn_plan_cell_fwd(const tspgnn_cell_mlp_task* tasks, int n_tasks, int d, int arith, int cus, tspgnn_cell_fwd_plan* out);
+
+typedef struct tspgnn_cell_chunk_plan {  /* the cell launches whose only LDS decision is K resident or in chunks */
+    int nw, grid, n;
+    int blk_end[4];
+    int qc[4];          /* units of K per LDS chunk: 16-row blocks (f32 backward), 32-row k-blocks (bf16), 0 (h2 backward: always resident) */
+    int chunked[4];     /* K streamed through LDS rather than resident */
+    int lds_bytes;
+} tspgnn_cell_chunk_plan;
+/* tspgnn_lnlstm_bwd_multi_f32 / _h2 / _bf16 (arith: TSPGNN_ARITH_F32 / _H2 / _BF16) */
+int tspgnn_plan_cell_bwd(const tspgnn_lstm_bwd_task* tasks, int n_tasks, int d, int arith, int cus, tspgnn_cell_chunk_plan* out);
+/* tspgnn_lnlstm_fwd_multi_bf16; nw: the wavefronts per workgroup its dispatch chooses (12 for the staged kernel at d = 64, else 8) */
+int tspgnn_plan_lstm_fwd_bf16(const tspgnn_lstm_task_bf16* tasks, int n_tasks, int d, int nw, int cus, tspgnn_cell_chunk_plan* out);
 
 /* Slices of the chunk range per workgroup in the second stage of the split reductions (wgrad, wcolsum). */
 int tspgnn_plan_reduce_slices(int n_chunks);

@@ -1,8 +1,8 @@
 """Cases for the LN-LSTM cell backward kernels called directly (tests/test_gpu_h2_backward_kernels.py,
 tests/test_gpu_bf16_backward_kernels.py): one task's inputs, its operands packed for an arithmetic, a float64 autograd
-reference on the device, and a replay of the launchers' planning arithmetic, so that a test that claims to reach a path
-(a second tile per wavefront, the chunked K) asserts that it does.  The device-buffer helpers (dev, empty, release, SENTINEL,
-SPARE) and the row-by-row measure row_err also serve tests/test_gpu_fp32_backward_plans.py and tests/test_gpu_batch_kernels.py.
+reference on the device, and the launchers' plans as the library answers them (tests/plan_replay.py), so that a test that
+claims to reach a path (a second tile per wavefront, the chunked K) asserts that it does.  The device-buffer helpers (dev,
+empty, release, SENTINEL, SPARE) and the row-by-row measure row_err also serve tests/test_gpu_fp32_backward_plans.py and tests/test_gpu_batch_kernels.py.
 
 The arithmetic decides the packing of K / K^T, the form of the projected messages Zx, and the entry point:
   "h2"    tspgnn_lnlstm_bwd_multi_h2   (csrc/dense_bwd_h2.hip)    pack_weights_h2 of K and of K^T, Zx scaled and blocked
@@ -12,6 +12,7 @@ The arithmetic decides the packing of K / K^T, the form of the projected message
 import numpy as np
 import torch
 
+import plan_replay as PR
 from conftest import h2_zx_pack
 from oracle import torch_oracle as TO
 from tspgnn import _lib
@@ -93,65 +94,38 @@ def workspace(d, device):
     return empty((int(_lib.lib.tspgnn_lnlstm_bwd_workspace_floats(d)),), device, 0.0)
 
 
-# ------------------------------------------------------------------------------------- the launchers' planning, replayed
+# ------------------------------------------------------------------------------ the launchers' plans, asked of the library
 def k_chunked(d, dx):
-    """launch_lnlstm_bwd_bf16's LDS arithmetic: is K streamed through LDS in chunks (rather than resident)?  A copy of the
-    launcher's NWMAX, tail and 160 KB budget (csrc/dense_bwd_bf16.hip): a change there must be made here too, or the tests
-    that assert the chunked path stop knowing whether they reach it."""
-    nwmax = 4 if d >= 128 else 8
-    tail = (10 * d + nwmax * 10 * d + 4) * 4
-    per_kb = 32 * 4 * d * 2
-    return (dx + d) // 32 * per_kb > 160 * 1024 - tail
+    """Does tspgnn_lnlstm_bwd_multi_bf16 stream K through LDS in chunks (rather than keep it resident)?  The planner's answer
+    (plan_replay.cell_bwd_plan); it does not depend on the rows or the CU count."""
+    return PR.cell_bwd_plan([(16, dx, False, False)], d, 256, "bf16").chunked[0]
 
 
 def k_resident_f32(d, dx, with_KT=False):
-    """launch_lnlstm_bwd's LDS arithmetic (csrc/dense_bwd.hip): does the whole of K stay in LDS (else it is streamed in
-    chunks of qc 16-row blocks, the tiles taken in rounds of nw)?  A copy of the launcher's NWMAX, per_q, extra() and 160 KB
-    budget: a change there must be made here too.  with_KT: K^T ([4d, dx + d] floats) has to fit beside a resident K, which
-    the launcher grants only at d = 64, dx = 0 -- asserted, since the launch is refused otherwise."""
-    nwmax = 4 if d >= 128 else 8
-    extra = (10 * d + nwmax * 10 * d + 4) * 4
-    per_q = 16 * 4 * d * 4
-    qt = (dx + d) // 16
-    resident = qt * per_q + extra <= 160 * 1024
+    """Does the whole of K stay in LDS in tspgnn_lnlstm_bwd_multi_f32 (else it is streamed in chunks of qc 16-row blocks, the
+    tiles taken in rounds of nw)?  The planner's answer.  with_KT: K^T ([4d, dx + d] floats) has to fit beside a resident K,
+    which the launcher grants only at d = 64, dx = 0 -- asserted: the planner accepts the task (it raises where the launch is
+    refused) and answers a resident K."""
+    chunked = PR.cell_bwd_plan([(16, dx, with_KT, False)], d, 256, "f32").chunked[0]
     if with_KT:
-        assert d == 64 and dx == 0 and resident and qt * per_q + 4 * d * (dx + d) * 4 + extra <= 160 * 1024
-    return resident
-
-
-def _split_blocks(cost, grid):
-    """split_blocks (csrc/launch_plan.h): workgroups per task, proportional to cost, at least one each."""
-    cost = [c if c > 0 else 1 for c in cost]
-    total = sum(cost)
-    grid = max(grid, len(cost))
-    return [max(1, (c * grid + total // 2) // total) for c in cost]
+        assert not chunked
+    return not chunked
 
 
 def tiles_per_wavefront(tasks, d, cus, arith="h2"):
     """How many 16-row tiles each wavefront of a launch works through: -> per task (nw, workgroups, min, max), None for
     an empty task (dropped before the launch).  tasks: (rows, dx, with_KT, with_KTg) each -- Cell.plan().
 
-    A copy of the host arithmetic of launch_lnlstm_bwd_h2 (csrc/dense_bwd_h2.hip) and, for arith = "f32", of
-    launch_lnlstm_bwd (csrc/dense_bwd.hip) -- the cost per tile, nw, clamp_grid, split_blocks (csrc/launch_plan.h) -- and of
-    the kernels' t_beg / t_end and round-robin over the wavefronts (f32 with a chunked K: rounds of nw tiles, round r to
-    workgroup r mod workgroups).  It must follow the launchers: a change there has to be made here too, or the tests that
-    assert their tile depth stop knowing what they reach."""
+    nw, the workgroups per task and whether K is chunked are the launcher's plan (plan_replay.cell_bwd_plan); what follows
+    them here is the kernels' own walk: t_beg / t_end of a workgroup and the round-robin over its wavefronts (f32 with a
+    chunked K: rounds of nw tiles, round r to workgroup r mod workgroups)."""
     assert arith in ("h2", "f32")
     live = [t for t in tasks if t[0] > 0]
-    tiles = [(rows + 15) // 16 for rows, _, _, _ in live]
-    if arith == "h2":
-        nwmax = 8
-        cost = [n * ((dx + d) // 32 + (2 if kt else 0) + (5 if ktg else 0) + 10) for n, (_, dx, kt, ktg) in zip(tiles, live)]
-        chunked = [False] * len(live)
-    else:
-        nwmax = 4 if d >= 128 else 8
-        cost = [n * ((dx + d) // 16 + 8) for n, (_, dx, _, _) in zip(tiles, live)]
-        chunked = [not k_resident_f32(d, dx) for _, dx, _, _ in live]
-    tiles_all = sum(tiles)
-    nw = 4 if (not any(chunked) and tiles_all <= 4 * cus) else nwmax
-    grid = min(cus, (tiles_all + nw - 1) // nw)                     # clamp_grid
+    plan = PR.cell_bwd_plan(live, d, cus, arith)
+    nw = plan.nw
     out = []
-    for n, blocks, ch in zip(tiles, _split_blocks(cost, grid), chunked):
+    for (rows, *_), blocks, ch in zip(live, plan.blocks, plan.chunked):
+        n = PR.tiles16(rows)
         counts = []
         for b in range(blocks):
             if ch:

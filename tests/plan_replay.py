@@ -1,8 +1,10 @@
-"""The launch plans of the fp32 backward kernels (csrc/dense_bwd.hip), the training-tail kernels (csrc/train.hip) and the
-forward cell and MLP launchers (csrc/dense_h2.hip, csrc/dense_x3.hip), asked of the library: every launcher-level figure
+"""The launch plans of the fp32 backward kernels (csrc/dense_bwd.hip), the training-tail kernels (csrc/train.hip), the
+forward cell and MLP launchers (csrc/dense_h2.hip, csrc/dense_x3.hip, csrc/bf16.hip) and the three cell backward launchers
+(csrc/dense_bwd.hip, csrc/dense_bwd_h2.hip, csrc/dense_bwd_bf16.hip), asked of the library: every launcher-level figure
 here -- path, wavefronts, grid, blk_end, LDS chunking, mode, variant, chunk counts -- is what the tspgnn_plan_* queries
 answer, and those run the planner the launcher itself calls (csrc/launch_plan.h).  The GPU tests that claim a branch
-(tests/test_gpu_fp32_backward_plans.py, tests/test_gpu_batch_kernels.py, tests/test_gpu_cell_forward_edges.py) derive
+(tests/test_gpu_fp32_backward_plans.py, tests/test_gpu_batch_kernels.py, tests/test_gpu_cell_forward_edges.py, and through
+tests/lstm_bwd_cases.py tests/test_gpu_h2_backward_kernels.py and tests/test_gpu_bf16_backward_kernels.py) derive
 their row counts from the device's CU count and assert the branch and its depth through these functions BEFORE they
 launch.  What remains in Python follows a KERNEL's own loop from the plan -- a workgroup's ticket range, its rounds, the
 rows of a last chunk -- and names the line it follows.  tests/golden/launch_plans.json records the answers across the
@@ -240,3 +242,60 @@ def mlp_fwd_plan(tasks, cus):
                   len(tasks), 64, cus)
     blocks = blocks_of(p)
     return MlpFwdPlan(p.nw, p.grid, blocks, [ticket_ranges(tiles16(rows), b, xcd=False) for (rows, _, _), b in zip(tasks, blocks)])
+
+
+# ------------------------------------------------- tspgnn_lnlstm_bwd_multi_{f32,h2,bf16}, tspgnn_{lnlstm,mlp}_fwd_multi_bf16
+def unsupported_as_value_error(query, *args):
+    """_lib.plan, with ValueError where the launcher answers TSPGNN_EUNSUPPORTED."""
+    try:
+        return _lib.plan(query, *args)
+    except _lib.TspgnnError as e:
+        if e.status != -2:
+            raise
+        raise ValueError(e.message)
+
+
+CellChunkPlan = namedtuple("CellChunkPlan", "nw grid blocks qc chunked lds_bytes")
+"""blocks: workgroups per task; qc: units of K per LDS chunk (16-row blocks for the fp32 backward, 32-row k-blocks for bf16,
+0 for the f16x2 backward, which never chunks); chunked: K streamed through LDS rather than resident, per task."""
+
+
+def _chunk_plan(p):
+    return CellChunkPlan(p.nw, p.grid, blocks_of(p), list(p.qc[:p.n]), [bool(c) for c in p.chunked[:p.n]], p.lds_bytes)
+
+
+def cell_bwd_plan(tasks, d, cus, arith):
+    """tspgnn_plan_cell_bwd.  tasks: (rows, dx, with_KT, with_KTg[, gather]) of the live tasks (rows > 0), in order; a task
+    with K^T is a gather-init task unless said otherwise.  The outputs each mode wants (dxh, dxg) and Zx count as given.
+    Raises ValueError where the launcher answers TSPGNN_EUNSUPPORTED."""
+    structs = []
+    for rows, dx, kt, ktg, *gather in tasks:
+        gather = bool(gather[0]) if gather else bool(kt)
+        structs.append(_lib.LstmBwdTask(rows=rows, dx=dx, KT=int(bool(kt)), KTg=int(bool(ktg)), dxh=int(bool(kt or ktg)),
+                                        dxg=int(bool(ktg)), uv=int(gather), Zx=int(gather)))
+    arith = {"h2": 0, "f32": 2, "bf16": 3}[arith]           # TSPGNN_ARITH_*
+    return _chunk_plan(unsupported_as_value_error("tspgnn_plan_cell_bwd", structs, len(tasks), d, arith, cus))
+
+
+LSTM_FWD_BF16_NW = {32: (8,), 64: (12, 8), 128: (8,)}
+"""NW of the kernel tspgnn_lnlstm_fwd_multi_bf16 dispatches to, per d (csrc/bf16.hip); the first is the default, the second
+the all-gates kernel behind the development switch TSPGNN_BF16_CELL=0."""
+
+
+def lstm_fwd_bf16_plan(tasks, d, cus, nw=None):
+    """tspgnn_plan_lstm_fwd_bf16.  tasks: (rows, dx) of the live tasks."""
+    nw = LSTM_FWD_BF16_NW[d][0] if nw is None else nw
+    structs = [_lib.LstmTaskB(rows=rows, dx=dx) for rows, dx in tasks]
+    return _chunk_plan(unsupported_as_value_error("tspgnn_plan_lstm_fwd_bf16", structs, len(tasks), d, nw, cus))
+
+
+MlpFwdBf16Plan = namedtuple("MlpFwdBf16Plan", "nw grid blocks lds_bytes")
+
+
+def mlp_fwd_bf16_plan(tasks, d, cus):
+    """tspgnn_plan_mlp_fwd_bf16 at the NW of the entry's dispatch (csrc/bf16.hip: 16 at d = 128 when no task has a projection,
+    else 8).  tasks: [(rows, n_layers, has_proj)] of the live tasks."""
+    nw = 16 if d == 128 and not any(proj for _, _, proj in tasks) else 8
+    structs = [_lib.MlpTaskB(rows=rows, n_layers=L, proj_w=int(proj)) for rows, L, proj in tasks]
+    p = unsupported_as_value_error("tspgnn_plan_mlp_fwd_bf16", structs, len(tasks), d, nw, cus)
+    return MlpFwdBf16Plan(p.nw, p.grid, blocks_of(p), p.lds_bytes)

@@ -48,7 +48,7 @@ def test_abi_version_and_struct_layouts_agree(tmp_path):
              "tspgnn_mp_loop_args": _lib.MpLoopArgs, "tspgnn_mp_resident_args": _lib.MpResidentArgs,
              "tspgnn_linear_plan": _lib.LinearPlan, "tspgnn_tasks_plan": _lib.TasksPlan, "tspgnn_wgrad_plan": _lib.WgradPlan,
              "tspgnn_wcolsum_plan": _lib.WcolsumPlan, "tspgnn_einit_bwd_plan": _lib.EinitBwdPlan,
-             "tspgnn_cell_fwd_plan": _lib.CellFwdPlan}
+             "tspgnn_cell_fwd_plan": _lib.CellFwdPlan, "tspgnn_cell_chunk_plan": _lib.CellChunkPlan}
     assert set(_lib.PLANS.values()) <= set(pairs.values())
     src = ["#include <stdio.h>", "#include <stddef.h>", '#include "tspgnn.h"', "int main(void) {"]
     for cname, cls in pairs.items():

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import plan_replay
 from conftest import h2_zx_pack, h2_zx_unpack, rel_err
 from oracle import np_oracle as NO
 from tspgnn import _lib
@@ -198,6 +199,8 @@ def test_lnlstm_bf16_gather_and_plain_tasks(cuda_device, d, c_blocked):
     tv = _lib.LstmTaskB(_lib.ptr(dev_bf16(xv, cuda_device)), d, _lib.ptr(h_dev(hv, cin)), _lib.ptr(c_dev(cv, cin)),
                         _lib.ptr(packed_bf16(Kv, cuda_device)), _lib.ptr(dev(ln_v, cuda_device)), _lib.ptr(hv_o), _lib.ptr(cv_o), N,
                         None, None, int(cin), int(cout))
+    cus = torch.cuda.get_device_properties(cuda_device).multi_processor_count
+    assert plan_replay.lstm_fwd_bf16_plan([(M, 0), (N, d)], d, cus).chunked == [False, d == 128]
     _lib.call_multi("tspgnn_lnlstm_fwd_multi_bf16", [te, tv], d)
     torch.cuda.synchronize()
     z0 = rb(Zx)[uv[:, 0]] + rb(Zx)[uv[:, 1]]

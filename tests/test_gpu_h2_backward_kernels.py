@@ -4,7 +4,7 @@ device -- at the kernels' own edges: every mode (plain, gather-init, bias-init, 
 to ROWS_DEEP = 16 * 17 * CUs + 1 rows, where a single-task launch gives every wavefront two or three tiles (so the f16x2
 kernel's software pipeline runs in its steady state, and its last, prefetched tile holds one row) and the fp32 kernel's
 chunked-K path runs several rounds with dead tiles in the last.  Every test that claims such a depth asserts it through
-lstm_bwd_cases.tiles_per_wavefront, a replay of the launcher.
+lstm_bwd_cases.tiles_per_wavefront, which walks the launcher's own plan (tspgnn_plan_cell_bwd).
 
 Bars, all against float64: whole tensor rel_err < TOL = 5e-6 (the bar of test_gpu_backward_kernels.py and the bf16 file);
 row by row, max |got - ref| over a row by max |ref| over that row < ROW_TOL = 2e-5 (the bar of

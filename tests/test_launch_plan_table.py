@@ -51,6 +51,22 @@ def test_the_table_reaches_every_branch():
             assert len(plans) == len(recs)
         else:
             assert len(plans) < len(recs) and not any(p[4] or p[5] for p in plans)
+    # the cell backward launchers: both wavefront counts, K resident and chunked, each refusal; per record
+    # [nw, grid, blocks, qc, chunked, lds_bytes]
+    for arith, nws, declined in (("f32", {4, 8}, {"unsupported", "invalid"}), ("h2", {4, 8}, {"unsupported", "invalid"}),
+                                 ("bf16", {4, 8}, set())):
+        recs = [r for r in tab["cell_bwd"] if r[0][3] == arith]
+        plans = [r[1] for r in recs if not isinstance(r[1], str)]
+        assert {r[1] for r in recs if isinstance(r[1], str)} == declined, arith
+        assert {p[0] for p in plans} == nws and {len(r[0][0]) for r in recs} >= {1, 2, 3, 4}
+        assert {c for p in plans for c in p[4]} == ({False} if arith == "h2" else {False, True})
+        assert all(p[0] == 8 for r, p in ((r, r[1]) for r in recs if not isinstance(r[1], str))
+                   if arith == "f32" and r[0][1] == 64 and any(p[4]))       # a chunked fp32 task keeps all eight wavefronts
+    for d in (32, 64, 128):
+        assert {c for r in tab["lstm_fwd_bf16"] if r[0][1] == d for c in r[1][4]} == {False, True}
+        assert {r[1][0] for r in tab["lstm_fwd_bf16"] if r[0][1] == d} == set(plan_replay.LSTM_FWD_BF16_NW[d])
+    assert {r[1][0] for r in tab["mlp_fwd_bf16"]} == {8, 16} and not any(isinstance(r[1], str) for r in tab["mlp_fwd_bf16"])
+    assert {(r[0][0][0][1], r[0][0][0][2]) for r in tab["mlp_fwd_bf16"] if len(r[0][0]) == 1} == {(L, p) for L in (1, 2, 3, 4) for p in (False, True)}
 
 
 def test_queries_validate_as_their_entries_do():
@@ -74,10 +90,26 @@ def test_queries_validate_as_their_entries_do():
     assert status("tspgnn_plan_cell_fwd", cell(), 1, 48, 0, 256) == -1 and status("tspgnn_plan_cell_fwd", cell(), 1, 64, 2, 256) == -1
     assert status("tspgnn_plan_cell_fwd", cell(mlp_layers=1, proj_w=1), 1, 32, 1, 256) == -2     # one k-block, no lock step
     assert status("tspgnn_plan_cell_fwd", cell(mlp_layers=1, proj_w=1), 1, 32, 0, 256) == 0
+    bwd = lambda **k: [_lib.LstmBwdTask(rows=k.pop("rows", 5), **k)]
+    assert status("tspgnn_plan_cell_bwd", bwd(), 1, 64, 1, 256) == -1                      # no bf16x3 backward
+    assert status("tspgnn_plan_cell_bwd", bwd(), 1, 128, 0, 256) == -1 and status("tspgnn_plan_cell_bwd", bwd(), 1, 128, 2, 256) == 0
+    assert status("tspgnn_plan_cell_bwd", bwd(dx=16), 1, 64, 2, 256) == 0 and status("tspgnn_plan_cell_bwd", bwd(dx=16), 1, 64, 3, 256) == -1
+    assert status("tspgnn_plan_cell_bwd", bwd(KT=1), 1, 64, 0, 256) == -1 and status("tspgnn_plan_cell_bwd", bwd(KT=1, dxh=1), 1, 64, 0, 256) == 0
+    assert status("tspgnn_plan_cell_bwd", bwd(KT=1), 1, 64, 3, 256) == -1 and status("tspgnn_plan_cell_bwd", bwd(zbias=1), 1, 64, 2, 256) == -1
+    assert status("tspgnn_plan_cell_bwd", bwd(rows=1 << 23), 1, 64, 0, 256) == -1 and status("tspgnn_plan_cell_bwd", bwd(rows=1 << 23), 1, 64, 2, 256) == 0
+    assert status("tspgnn_plan_cell_bwd", bwd(KT=1), 1, 32, 2, 256) == -2 and status("tspgnn_plan_cell_bwd", bwd(dx=96), 1, 64, 0, 256) == -2
+    assert status("tspgnn_plan_lstm_fwd_bf16", [_lib.LstmTaskB(rows=5, dx=48)], 1, 64, 12, 256) == -1
+    assert status("tspgnn_plan_lstm_fwd_bf16", [_lib.LstmTaskB(rows=5)], 1, 48, 8, 256) == -1
+    assert status("tspgnn_plan_lstm_fwd_bf16", [_lib.LstmTaskB(rows=5)], 1, 64, 0, 256) == -1
+    assert status("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=5, n_layers=5)], 1, 64, 8, 256) == -1
+    assert status("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=5, n_layers=2)], 1, 64, 8, -1) == -1
     assert status("tspgnn_plan_linear", 64, 0, 64, 100, -1) == -1
     assert _lib.plan("tspgnn_plan_linear", 64, 0, 64, 0, 256).grid == 0
     assert _lib.plan("tspgnn_plan_wgrad", 0, 64, 64, 0, 256).n_chunks == 0
     assert _lib.plan("tspgnn_plan_cell_fwd", cell(rows=0), 1, 64, 0, 256).grid == 0
+    assert _lib.plan("tspgnn_plan_cell_bwd", bwd(rows=0), 1, 64, 0, 256).grid == 0
+    assert _lib.plan("tspgnn_plan_lstm_fwd_bf16", [_lib.LstmTaskB(rows=0)], 1, 64, 12, 256).grid == 0
+    assert _lib.plan("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=0, n_layers=2)], 1, 64, 8, 256).grid == 0
 
 
 def queries_at(cus):
@@ -90,6 +122,10 @@ def queries_at(cus):
              ("tspgnn_plan_mlp_bwd", [_lib.MlpBwdTask(rows=333, n_layers=2), _lib.MlpBwdTask(rows=131073, n_layers=2)], 2, 64, cus),
              ("tspgnn_plan_mlp_fwd", [_lib.MlpTask(rows=9000, n_layers=3), _lib.MlpTask(rows=700, n_layers=4, proj_w=1)], 2, 64, cus),
              ("tspgnn_plan_cell_fwd", cell, 2, 64, 0, cus), ("tspgnn_plan_cell_fwd", cell, 2, 64, 1, cus)]
+    bwd = [_lib.LstmBwdTask(rows=5120, dx=64), _lib.LstmBwdTask(rows=99840)]
+    calls += [("tspgnn_plan_cell_bwd", bwd, 2, 64, arith, cus) for arith in (0, 2, 3)]
+    calls += [("tspgnn_plan_lstm_fwd_bf16", [_lib.LstmTaskB(rows=99840), _lib.LstmTaskB(rows=5120, dx=64)], 2, 64, 12, cus),
+              ("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=9000, n_layers=3), _lib.MlpTaskB(rows=700, n_layers=4, proj_w=1)], 2, 64, 8, cus)]
     return [bytes(_lib.plan(*c)) for c in calls]
 
 

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The table of launch plans, tests/golden/launch_plans.json: every planner of csrc/launch_plan.h asked through
 tests/plan_replay.py (the tspgnn_plan_* queries) over a grid that crosses its thresholds -- CU counts 1, 104 and 256, row counts at,
-one below and one above the boundaries derived from the CU count, the LDS modes of the forward cell launchers.  No device
+one below and one above the boundaries derived from the CU count, the LDS modes of the forward cell launchers, K resident
+and chunked in the cell backward and bf16 forward launchers.  No device
 is needed.
 
     python tools/launch_plan_table.py            compare the library with the committed table (exit status 1: it moved)
@@ -99,6 +100,89 @@ def cell_fwd_cases(task):
                 yield ([task(2000, 64, 2), edge(40000), vert(5120), task(300, 192, 1, True)], d, cus, arith)
 
 
+STEPS = ((12801, 70001), (333, 7001))     # (vertex rows, edge rows) of a training step's cell launch
+
+
+def cell_bwd_cases():
+    """(tasks, d, cus, arith); tasks: plan_replay.cell_bwd_plan's (rows, dx, with_KT, with_KTg[, gather])."""
+    plain = lambda rows, dx: (rows, dx, False, False)
+    kt = lambda rows, dx=0, gather=True: (rows, dx, True, False, gather)
+    # fp32 residency either side of the boundary (d = 128 streams K even at dx = 0, four 16-row blocks at a time), K^T beside
+    # K only at d = 64 and dx = 0, and a gather-init task at d = 128, which the entry's validation turns away first
+    for d, dx in ((32, 256), (32, 272), (64, 64), (64, 80), (128, 0)):
+        yield ([plain(333, dx)], d, 256, "f32")
+    for d, dx, gather in ((64, 0, True), (64, 64, False), (32, 0, True)):
+        yield ([kt(333, dx, gather)], d, 256, "f32")
+    yield ([(333, 0, False, False, True)], 128, 256, "f32")
+    # f16x2: every K it offers, the fused data gradients, and at d = 64 the last dx that fits LDS and the first that does not
+    # (in steps of 32; with K^T the entry wants dx = 0, so no dx beyond it reaches the planner)
+    for d in (32, 64):
+        for dx in (0, d, 4 * d):
+            yield ([plain(333, dx)], d, 256, "h2")
+        yield ([kt(333)], d, 256, "h2")
+    yield ([(333, 64, False, True)], 64, 256, "h2")
+    for task in (plain(333, 96), kt(333, 32, False)):           # (dx = 64 above is the last that fits)
+        yield ([task], 64, 256, "h2")
+    # bf16: resident and chunked K at each d (a chunked task's tiles cost twice: blk_end beside a resident task of equal rows)
+    for d, dx in ((128, 0), (128, 32), (64, 192), (64, 224), (32, 544), (32, 576)):
+        yield ([plain(333, dx)], d, 256, "bf16")
+    for cus in CUS:
+        # four wavefronts up to 4 tiles per CU: f16x2 and a resident fp32 K; never beside a chunked fp32 task
+        for tiles in around(4 * cus):
+            yield ([plain(16 * tiles, 64)], 64, cus, "h2")
+            yield ([plain(16 * tiles, 64)], 64, cus, "f32")
+            yield ([plain(16 * tiles - 16, 64), plain(16, 128)], 64, cus, "f32")
+        yield ([plain(5000, 0), plain(5000, 32)], 128, cus, "bf16")
+        for N, M in STEPS:
+            yield ([(N, 64, False, True), kt(M)], 64, cus, "h2")
+            yield ([plain(N, 64), kt(M)], 64, cus, "f32")
+            yield ([plain(N, 128), plain(M, 0)], 128, cus, "f32")
+            for d in (64, 128):
+                yield ([plain(N, d), (M, 0, False, False, True)], d, cus, "bf16")
+        for arith in ("h2", "f32", "bf16"):
+            yield ([plain(2000, 64), plain(40000, 0), plain(5120, 64), plain(300, 32)], 64, cus, arith)
+            yield ([plain(5120, 64), plain(0, 64), plain(40000, 0)], 64, cus, arith)
+
+
+def lstm_fwd_bf16_cases(nws):
+    """(tasks, d, cus, nw); nws: plan_replay.LSTM_FWD_BF16_NW, every NW the entry dispatches at a d."""
+    for d, fits, chunked in ((32, 576, 608), (64, 224, 256), (128, 0, 32)):       # under the forward's own 156 KB budget
+        for nw in nws[d]:
+            for dx in (fits, chunked):
+                yield ([(333, dx)], d, 256, nw)
+            for cus in CUS:
+                for N, M in STEPS:
+                    yield ([(M, 0), (N, d)], d, cus, nw)
+                yield ([(5000, fits), (5000, chunked)], d, cus, nw)
+                yield ([(2000, 64), (40000, 0), (5120, d), (300, 32)], d, cus, nw)
+                yield ([(5120, d), (0, 32), (40000, 0)], d, cus, nw)
+
+
+def mlp_fwd_bf16_cases():
+    for d in (32, 64, 128):
+        for L in (1, 2, 3, 4):
+            for proj in (False, True):
+                yield ([(333, L, proj)], d, 256)
+        for cus in CUS:
+            for N, M in STEPS:
+                yield ([(M, 3, False), (N, 4, True)], d, cus)
+                yield ([(M, 3, False), (N, 4, False)], d, cus)
+            yield ([(5000, 2, False), (5000, 1, True), (100, 4, True), (16 * 16 * cus + 1, 3, False)], d, cus)
+
+
+def answer(plan, *args):
+    """A plan as a list, or how the query declined: "unsupported" (the launch is refused) or "invalid" (the entry's
+    validation)."""
+    try:
+        return list(plan(*args))
+    except ValueError:
+        return "unsupported"
+    except RuntimeError as e:
+        if getattr(e, "status", None) != -1:
+            raise
+        return "invalid"
+
+
 def table(PR):
     """{planner: [[arguments, answer]]} from a module with tests/plan_replay.py's functions."""
     cell = []
@@ -123,6 +207,9 @@ def table(PR):
         "einit_bwd": [[list(a), list(PR.einit_bwd_plan(*a)) + [PR.einit_bwd_full_grid(a[1], a[2])]] for a in einit_bwd_cases()],
         "mlp_fwd": mlp_fwd,
         "cell_fwd": cell,
+        "cell_bwd": [[list(a), answer(PR.cell_bwd_plan, *a)] for a in cell_bwd_cases()],
+        "lstm_fwd_bf16": [[list(a), answer(PR.lstm_fwd_bf16_plan, *a)] for a in lstm_fwd_bf16_cases(PR.LSTM_FWD_BF16_NW)],
+        "mlp_fwd_bf16": [[list(a), answer(PR.mlp_fwd_bf16_plan, *a)] for a in mlp_fwd_bf16_cases()],
         "reduce_slices": [[n, PR.reduce_slices(n)] for n in (1, 7, 8, 63, 64, 2048)],
         "strided_blocks": [[[t, cap], list(PR.strided_blocks(t, cap))] for cap in (1024, 4096) for t in around(256 * cap) + [1]],
     }

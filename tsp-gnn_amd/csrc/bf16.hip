@@ -462,56 +462,34 @@ __global__ __launch_bounds__(NW * 64) void lnlstm_fwd_bf16_kernel(const LstmTabl
 
 template <int D, int NW, bool PROJ>
 static int launch_mlp_b(const tspgnn_mlp_task_bf16* tasks, int n, hipStream_t st) {
+    tspgnn_tasks_plan pl;
+    int rc = plan_mlp_fwd_bf16(tasks, n, D, NW, n_cus(), &pl);
+    if (rc) return rc;
     MlpTableB tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        const size_t need = tasks[k].proj_w ? (size_t)D * 4 * D * 2 : 0;
-        const size_t lay = (size_t)tasks[k].n_layers * (D * D * 2 + D * 4);
-        lds_w = lds_w > need ? lds_w : need;
-        lds_w = lds_w > lay ? lds_w : lay;
-        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += tiles16(tasks[k].rows);
+        tt.blk_end[k] = pl.blk_end[k];
     }
     tt.n = n;
-    const size_t lds_bytes = lds_w + 16;
-    if (lds_bytes > 160 * 1024) return fail(TSPGNN_EUNSUPPORTED, "mlp_fwd_bf16: %zu bytes of weights do not fit LDS", lds_bytes);
-    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, NW), tt.blk_end);
-    const int rc = set_dynamic_lds(&mlp_fwd_bf16_kernel<D, NW, PROJ>, lds_bytes, "mlp_fwd_bf16");
-    if (rc) return rc;
-    mlp_fwd_bf16_kernel<D, NW, PROJ><<<grid, NW * 64, lds_bytes, st>>>(tt);
+    if ((rc = set_dynamic_lds(&mlp_fwd_bf16_kernel<D, NW, PROJ>, pl.lds_bytes, "mlp_fwd_bf16"))) return rc;
+    mlp_fwd_bf16_kernel<D, NW, PROJ><<<pl.grid, NW * 64, pl.lds_bytes, st>>>(tt);
     return launched("tspgnn_mlp_fwd_multi_bf16");
 }
 
 template <int D, int NW, bool STAGED>
 static int launch_lstm_b(const tspgnn_lstm_task_bf16* tasks, int n, hipStream_t st) {
-    const size_t head = (10 * D + 4) * sizeof(float);
-    const size_t per_kb = (size_t)32 * 4 * D * 2;
-    const size_t budget = 156 * 1024 - head;
+    tspgnn_cell_chunk_plan pl;
+    int rc = plan_lstm_fwd_bf16(tasks, n, D, NW, n_cus(), &pl);
+    if (rc) return rc;
     LstmTableB tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_w = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        const int KBT = (tasks[k].dx + D) / 32;
-        int kbc = KBT;
-        if ((size_t)KBT * per_kb > budget) kbc = (int)(budget / per_kb);
-        if (kbc < 1) return fail(TSPGNN_EUNSUPPORTED, "lnlstm_fwd_bf16: d=%d does not fit LDS", D);
-        tt.kbc[k] = kbc;
-        if ((size_t)kbc * per_kb > lds_w) lds_w = (size_t)kbc * per_kb;
-        const long long tiles = tiles16(tasks[k].rows);
-        cost[k] = tiles * (KBT + 4) * (kbc < KBT ? 2 : 1);
-        tiles_all += tiles;
+        tt.kbc[k] = pl.qc[k];
+        tt.blk_end[k] = pl.blk_end[k];
     }
     tt.n = n;
-    const size_t lds_bytes = lds_w + head;
-    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, NW), tt.blk_end);
-    const int rc = set_dynamic_lds(&lnlstm_fwd_bf16_kernel<D, NW, STAGED>, lds_bytes, "lnlstm_fwd_bf16");
-    if (rc) return rc;
-    lnlstm_fwd_bf16_kernel<D, NW, STAGED><<<grid, NW * 64, lds_bytes, st>>>(tt);
+    if ((rc = set_dynamic_lds(&lnlstm_fwd_bf16_kernel<D, NW, STAGED>, pl.lds_bytes, "lnlstm_fwd_bf16"))) return rc;
+    lnlstm_fwd_bf16_kernel<D, NW, STAGED><<<pl.grid, NW * 64, pl.lds_bytes, st>>>(tt);
     return launched("tspgnn_lnlstm_fwd_multi_bf16");
 }
 
@@ -582,15 +560,21 @@ static bool bf16_cell_staged() {
     return v;
 }
 
+// tspgnn_lstm_task_bf16: the shape fields, what holds for an empty task too
+static int check_lstm_b_shape(const tspgnn_lstm_task_bf16& t, const char* p) {
+    TSPGNN_REQUIRE(t.rows >= 0, "%s: rows=%d", p, t.rows);
+    TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "%s: dx=%d must be a non-negative multiple of 32", p, t.dx);
+    return TSPGNN_OK;
+}
+
 extern "C" int tspgnn_lnlstm_fwd_multi_bf16(const tspgnn_lstm_task_bf16* tasks, int n_tasks, int d, void* stream) {
     TSPGNN_REQUIRE(tasks && n_tasks >= 1 && n_tasks <= kMaxTasks, "lnlstm_fwd_multi_bf16: 1..%d tasks", kMaxTasks);
     TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "lnlstm_fwd_bf16: d=%d must be 32, 64 or 128", d);
     tspgnn_lstm_task_bf16 live[kMaxTasks];
     int n;
     const int rc = filter_live(tasks, n_tasks, live, &n, [](const tspgnn_lstm_task_bf16& t) {
-        TSPGNN_REQUIRE(t.rows >= 0, "lnlstm_fwd_bf16: rows=%d", t.rows);
-        TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 32 == 0, "lnlstm_fwd_bf16: dx=%d must be a non-negative multiple of 32", t.dx);
-        if (t.rows == 0) return TSPGNN_OK;
+        const int rc = check_lstm_b_shape(t, "lnlstm_fwd_bf16");
+        if (rc || t.rows == 0) return rc;
         // (c == NULL: the zero cell state of a run's first step, nothing is read)
         TSPGNN_REQUIRE(t.h && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x), "lnlstm_fwd_bf16: null pointer");
         TSPGNN_REQUIRE(t.h_out != t.h && t.c_out != t.c, "lnlstm_fwd_bf16: outputs may not alias inputs");
@@ -605,6 +589,39 @@ extern "C" int tspgnn_lnlstm_fwd_multi_bf16(const tspgnn_lstm_task_bf16* tasks, 
     if (d == 32) return launch_lstm_b<32, 8, false>(live, n, st);
     if (d == 64) return staged ? launch_lstm_b<64, 12, true>(live, n, st) : launch_lstm_b<64, 8, false>(live, n, st);
     return staged ? launch_lstm_b<128, 8, true>(live, n, st) : launch_lstm_b<128, 8, false>(live, n, st);
+}
+
+// ------------------------------------------------------------------------------------------------- plan queries
+// (host only: the planners of launch_plan.h behind the validation of the entries' shape fields)
+
+extern "C" int tspgnn_plan_lstm_fwd_bf16(const tspgnn_lstm_task_bf16* tasks, int n_tasks, int d, int nw, int cus,
+                                         tspgnn_cell_chunk_plan* out) {
+    const char* what = "plan_lstm_fwd_bf16";
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "%s: d=%d must be 32, 64 or 128", what, d);
+    TSPGNN_REQUIRE(nw >= 1 && nw <= 16 && cus >= 0, "%s: nw=%d cus=%d", what, nw, cus);
+    *out = tspgnn_cell_chunk_plan{};
+    tspgnn_lstm_task_bf16 live[kMaxTasks];
+    int n;
+    int rc = filter_live(tasks, n_tasks, live, &n, [what](const tspgnn_lstm_task_bf16& t) { return check_lstm_b_shape(t, what); });
+    if (rc || n == 0) return rc;
+    if ((rc = plan_lstm_fwd_bf16(live, n, d, nw, cus ? cus : n_cus(), out))) *out = tspgnn_cell_chunk_plan{};
+    return rc;
+}
+
+extern "C" int tspgnn_plan_mlp_fwd_bf16(const tspgnn_mlp_task_bf16* tasks, int n_tasks, int d, int nw, int cus,
+                                        tspgnn_tasks_plan* out) {
+    const char* what = "plan_mlp_fwd_bf16";
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "%s: d=%d must be 32, 64 or 128", what, d);
+    TSPGNN_REQUIRE(nw >= 1 && nw <= 16 && cus >= 0, "%s: nw=%d cus=%d", what, nw, cus);
+    *out = tspgnn_tasks_plan{};
+    tspgnn_mlp_task_bf16 live[kMaxTasks];
+    int n;
+    int rc = filter_live(tasks, n_tasks, live, &n, [what](const tspgnn_mlp_task_bf16& t) { return check_mlp_shape(t, what); });
+    if (rc || n == 0) return rc;
+    if ((rc = plan_mlp_fwd_bf16(live, n, d, nw, cus ? cus : n_cus(), out))) *out = tspgnn_tasks_plan{};
+    return rc;
 }
 
 extern "C" int tspgnn_convert_f32_to_bf16(const float* x, void* y, long long n, void* stream) {

@@ -720,46 +720,8 @@ static int launch_linear(const float* X, int kin, const float* Wp, float* Y1, in
 
 template <int D>
 static int launch_lnlstm_bwd(const tspgnn_lstm_bwd_task* tasks, int n, hipStream_t st) {
-    // D=128 keeps 4D/16 + temporaries > 256 registers live: one wavefront per SIMD (512-register budget).
-    constexpr int NWMAX = D >= 128 ? 4 : 8;
-    const size_t per_q = (size_t)16 * 4 * D * sizeof(float);
-    auto extra = [&](int nw_) { return (size_t)(10 * D + nw_ * 10 * D + 4) * sizeof(float); };
-    LstmBwdTaskTable tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_k = 0;
-    bool any_chunked = false;
-    for (int k = 0; k < n; ++k) {
-        tt.task[k] = tasks[k];
-        const int QT = (tasks[k].dx + D) / 16;
-        int qc = QT;
-        if ((size_t)QT * per_q + extra(NWMAX) > 160 * 1024) {
-            qc = (int)((160 * 1024 - extra(NWMAX)) / per_q);
-            if (qc < 1 || tasks[k].uv) return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd: d=%d does not fit LDS", D);
-            any_chunked = true;
-        }
-        tt.qc[k] = qc;
-        size_t need = (size_t)qc * per_q;
-        if (tasks[k].KT != nullptr) {
-            need += (size_t)4 * D * (tasks[k].dx + D) * sizeof(float);
-            if (D != 64 || tasks[k].dx != 0 || qc < QT || need + extra(NWMAX) > 160 * 1024)
-                return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd: the fused data gradient needs d=64, dx=0 and K, K^T resident in LDS");
-        }
-        if (need > lds_k) lds_k = need;
-        const long long tiles = tiles16(tasks[k].rows);
-        cost[k] = tiles * (QT + 8);  // k-blocks + ~8 blocks' worth of elementwise backward
-        tiles_all += tiles;
-    }
-    tt.n = n;
-    int nw = NWMAX;
-    if (!any_chunked && tiles_all <= (long long)n_cus() * 4) nw = 4;
-    const size_t lds_bytes = lds_k + extra(nw);
-    int rc = set_dynamic_lds(&lnlstm_bwd_kernel<D, NWMAX>, lds_bytes, "lnlstm_bwd");
-    if (rc) return rc;
-    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, nw), tt.blk_end);
-    lnlstm_bwd_kernel<D, NWMAX><<<grid, nw * 64, lds_bytes, st>>>(tt);
-    if ((rc = launched("tspgnn_lnlstm_bwd_f32"))) return rc;
-    return reduce_ln_partials(tasks, n, tt.blk_end, D, st, "tspgnn_lnlstm_bwd_f32(reduce)");
+    return launch_cell_bwd(&lnlstm_bwd_kernel<D, cell_bwd_nwmax(D, TSPGNN_ARITH_F32)>, tasks, n, D, TSPGNN_ARITH_F32, st,
+                           "lnlstm_bwd", "tspgnn_lnlstm_bwd_f32", "tspgnn_lnlstm_bwd_f32(reduce)");
 }
 
 template <int D, int MAXL>
@@ -853,10 +815,7 @@ extern "C" int tspgnn_lnlstm_bwd_multi_f32(const tspgnn_lstm_bwd_task* tasks, in
     tspgnn_lstm_bwd_task live[kMaxTasks];
     int n;
     const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_bwd_task& t) {
-        const int rc = check_lstm_bwd_task(t, d, true, "lnlstm_bwd");
-        if (rc || t.rows == 0) return rc;
-        TSPGNN_REQUIRE(!t.zbias && !t.KTg, "lnlstm_bwd: a bias-init z / a streamed data gradient are f16x2 features (tspgnn_lnlstm_bwd_multi_h2)");
-        return TSPGNN_OK;
+        return check_cell_bwd_mode(t, d, TSPGNN_ARITH_F32, "lnlstm_bwd");
     });
     if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);
@@ -977,6 +936,26 @@ extern "C" int tspgnn_plan_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n_tasks
     if (rc || n == 0) return rc;
     plan_mlp_bwd(live, n, d, cus ? cus : n_cus(), out);
     return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_cell_bwd(const tspgnn_lstm_bwd_task* tasks, int n_tasks, int d, int arith, int cus,
+                                    tspgnn_cell_chunk_plan* out) {
+    const char* what = "plan_cell_bwd";
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
+    TSPGNN_REQUIRE(arith == TSPGNN_ARITH_H2 || arith == TSPGNN_ARITH_F32 || arith == TSPGNN_ARITH_BF16, "%s: arith=%d", what,
+                   arith);
+    TSPGNN_REQUIRE(d == 32 || d == 64 || (d == 128 && arith != TSPGNN_ARITH_H2), "%s: d=%d must be 32, 64 or (f32, bf16) 128",
+                   what, d);
+    TSPGNN_REQUIRE(cus >= 0, "%s: cus=%d", what, cus);
+    *out = tspgnn_cell_chunk_plan{};
+    tspgnn_lstm_bwd_task live[kMaxTasks];
+    int n;
+    int rc = filter_live(tasks, n_tasks, live, &n, [=](const tspgnn_lstm_bwd_task& t) {
+        return check_cell_bwd_mode(t, d, arith, what, false);
+    });
+    if (rc || n == 0) return rc;
+    if ((rc = plan_cell_bwd(live, n, d, arith, cus ? cus : n_cus(), out))) *out = tspgnn_cell_chunk_plan{};
+    return rc;
 }
 
 extern "C" int tspgnn_plan_wgrad(long long rows, int kin, int nout, int bf16x, int cus, tspgnn_wgrad_plan* out) {

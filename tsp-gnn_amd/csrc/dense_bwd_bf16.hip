@@ -157,37 +157,8 @@ __global__ __launch_bounds__(NW * 64) void lnlstm_bwd_bf16_kernel(const LstmBwdT
 
 template <int D>
 static int launch_lnlstm_bwd_bf16(const tspgnn_lstm_bwd_task* tasks, int n, hipStream_t st) {
-    // D=128 keeps 4D/16 + temporaries > 256 registers live: one wavefront per SIMD (512-register budget)
-    constexpr int NWMAX = D >= 128 ? 4 : 8;
-    const size_t tail = (size_t)(10 * D + NWMAX * 10 * D + 4) * sizeof(float);
-    const size_t per_kb = (size_t)32 * 4 * D * 2;
-    const size_t budget = 160 * 1024 - tail;
-    LstmBwdTaskTable tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_k = 0;
-    for (int k = 0; k < n; ++k) {
-        tt.task[k] = tasks[k];
-        const int KBT = (tasks[k].dx + D) / 32;
-        int kbc = KBT;
-        if ((size_t)KBT * per_kb > budget) kbc = (int)(budget / per_kb);
-        if (kbc < 1) return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd_bf16: d=%d does not fit LDS", D);
-        tt.qc[k] = kbc;
-        if ((size_t)kbc * per_kb > lds_k) lds_k = (size_t)kbc * per_kb;
-        const long long tiles = tiles16(tasks[k].rows);
-        cost[k] = tiles * (KBT + 12) * (kbc < KBT ? 2 : 1);
-        tiles_all += tiles;
-    }
-    tt.n = n;
-    const size_t lds_bytes = lds_k + tail;
-    int rc = set_dynamic_lds(&lnlstm_bwd_bf16_kernel<D, NWMAX>, lds_bytes, "lnlstm_bwd_bf16");
-    if (rc) return rc;
-    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, NWMAX), tt.blk_end);
-    // (the workspace holds one row of LayerNorm-gradient partials per workgroup of a task: n_cus + 8 rows,
-    // tspgnn_lnlstm_bwd_workspace_floats)
-    lnlstm_bwd_bf16_kernel<D, NWMAX><<<grid, NWMAX * 64, lds_bytes, st>>>(tt);
-    if ((rc = launched("tspgnn_lnlstm_bwd_multi_bf16"))) return rc;
-    return reduce_ln_partials(tasks, n, tt.blk_end, D, st, "tspgnn_lnlstm_bwd_multi_bf16(reduce)");
+    return launch_cell_bwd(&lnlstm_bwd_bf16_kernel<D, cell_bwd_nwmax(D, TSPGNN_ARITH_BF16)>, tasks, n, D, TSPGNN_ARITH_BF16, st,
+                           "lnlstm_bwd_bf16", "tspgnn_lnlstm_bwd_multi_bf16", "tspgnn_lnlstm_bwd_multi_bf16(reduce)");
 }
 
 // ------------------------------------------------------------------------------------ Y = X W, W bf16 (fragment order)
@@ -284,10 +255,7 @@ extern "C" int tspgnn_lnlstm_bwd_multi_bf16(const tspgnn_lstm_bwd_task* tasks, i
     tspgnn_lstm_bwd_task live[kMaxTasks];
     int n;
     const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_bwd_task& t) {
-        const int rc = check_lstm_bwd_task(t, d, false, "lnlstm_bwd_bf16");
-        if (rc || t.rows == 0) return rc;
-        TSPGNN_REQUIRE(!t.KT && !t.dxh && !t.zbias && !t.KTg, "lnlstm_bwd_bf16: no fused data gradient / bias-init in this mode");
-        return TSPGNN_OK;
+        return check_cell_bwd_mode(t, d, TSPGNN_ARITH_BF16, "lnlstm_bwd_bf16");
     });
     if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);

@@ -299,38 +299,8 @@ __global__ __launch_bounds__(NW * 64) void lnlstm_bwd_h2_kernel(const LstmBwdTas
 
 template <int D>
 static int launch_lnlstm_bwd_h2(const tspgnn_lstm_bwd_task* tasks, int n, hipStream_t st) {
-#ifndef H2_BWD_NW
-#define H2_BWD_NW 8
-#endif
-    constexpr int NWMAX = H2_BWD_NW;
-    auto extra = [&](int nw_) { return (size_t)(10 * D + nw_ * 10 * D + 4) * sizeof(float); };
-    LstmBwdTaskTable tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    size_t lds_k = 0;
-    for (int k = 0; k < n; ++k) {
-        tt.task[k] = tasks[k];
-        tt.qc[k] = 0;
-        size_t need = (size_t)(tasks[k].dx + D) * 4 * D * 4;               // two fp16 pieces
-        if (tasks[k].KT != nullptr) need += (size_t)4 * D * D * 4;
-        if (need + extra(NWMAX) > 160 * 1024)
-            return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd_h2: dx=%d, d=%d%s does not fit LDS", tasks[k].dx, D,
-                        tasks[k].KT ? " with K^T" : "");
-        if (need > lds_k) lds_k = need;
-        const long long tiles = tiles16(tasks[k].rows);
-        cost[k] = tiles * ((tasks[k].dx + D) / 32 + (tasks[k].KT ? 2 : 0) + (tasks[k].KTg ? 5 : 0) + 10);
-        tiles_all += tiles;
-    }
-    tt.n = n;
-    int nw = NWMAX;
-    if (tiles_all <= (long long)n_cus() * 4) nw = 4;
-    const size_t lds_bytes = lds_k + extra(nw);
-    int rc = set_dynamic_lds(&lnlstm_bwd_h2_kernel<D, NWMAX>, lds_bytes, "lnlstm_bwd_h2");
-    if (rc) return rc;
-    const int grid = split_blocks(cost, n, clamp_grid(n_cus(), tiles_all, nw), tt.blk_end);
-    lnlstm_bwd_h2_kernel<D, NWMAX><<<grid, nw * 64, lds_bytes, st>>>(tt);
-    if ((rc = launched("tspgnn_lnlstm_bwd_multi_h2"))) return rc;
-    return reduce_ln_partials(tasks, n, tt.blk_end, D, st, "tspgnn_lnlstm_bwd_multi_h2(reduce)");
+    return launch_cell_bwd(&lnlstm_bwd_h2_kernel<D, cell_bwd_nwmax(D, TSPGNN_ARITH_H2)>, tasks, n, D, TSPGNN_ARITH_H2, st,
+                           "lnlstm_bwd_h2", "tspgnn_lnlstm_bwd_multi_h2", "tspgnn_lnlstm_bwd_multi_h2(reduce)");
 }
 
 }  // namespace tspgnn
@@ -343,14 +313,7 @@ extern "C" int tspgnn_lnlstm_bwd_multi_h2(const tspgnn_lstm_bwd_task* tasks, int
     tspgnn_lstm_bwd_task live[kMaxTasks];
     int n;
     const int rc = filter_live(tasks, n_tasks, live, &n, [d](const tspgnn_lstm_bwd_task& t) {
-        int rc = check_rows_32bit(t.rows, t.dx, d, "lnlstm_bwd_h2");
-        if (!rc) rc = check_lstm_bwd_task(t, d, false, "lnlstm_bwd_h2");
-        if (rc || t.rows == 0) return rc;
-        TSPGNN_REQUIRE(!t.KT || (t.dxh && t.dx == 0), "lnlstm_bwd_h2: the fused data gradient needs dxh and dx == 0");
-        TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "lnlstm_bwd_h2: zbias needs zscale and excludes gather-init mode");
-        TSPGNN_REQUIRE(!t.KTg || (d == 64 && t.dx == 64 && t.dxg && t.dxh && !t.KT && !t.uv),
-                       "lnlstm_bwd_h2: the streamed data gradient needs d == dx == 64, dxg, dxh and excludes KT / gather-init mode");
-        return TSPGNN_OK;
+        return check_cell_bwd_mode(t, d, TSPGNN_ARITH_H2, "lnlstm_bwd_h2");
     });
     if (rc || n == 0) return rc;
     hipStream_t st = as_stream(stream);

@@ -2,7 +2,8 @@
 // clamping the grid, handing each task a contiguous share of the workgroups (blk_end[]) -- and the PLANNERS: per kernel, a
 // pure function of (task shapes, which pointers are null, width, CUs) that fills the plan structure of include/tspgnn.h with
 // everything the launcher decides before its <<<>>>.  A launcher calls its planner with n_cus() taken once, copies the plan
-// into the kernel's task table and launches; the tspgnn_plan_* queries answer the same planner to the tests.  What is
+// into the kernel's task table and launches (the three cell backward launchers through one frame, launch_cell_bwd); the
+// tspgnn_plan_* queries answer the same planner to the tests.  What is
 // measured per kernel -- wavefronts per workgroup, workgroups per CU, LDS budgets, the cost formulas -- stands in that
 // kernel's planner.  Host-only: nothing here is seen by device code.
 #pragma once
@@ -186,19 +187,37 @@ inline int check_cell_mlp_task(const tspgnn_cell_mlp_task& ct, int d, const char
     return TSPGNN_OK;
 }
 
-// tspgnn_lstm_bwd_task.  fp32_mfma: the fp32 kernels step K by 16 rows (dx a multiple of 16, else 32) and gather only at
-// d in {32, 64}.  KT / KTg / zbias are per arithmetic: at the entries.
-inline int check_lstm_bwd_task(const tspgnn_lstm_bwd_task& t, int d, bool fp32_mfma, const char* p) {
-    const int step = fp32_mfma ? 16 : 32;
+// tspgnn_lstm_bwd_task of the three cell backward entries and of their plan query (arith: TSPGNN_ARITH_F32 / _H2 / _BF16):
+// the shape fields, the operands, and what each arithmetic offers.  The fp32 kernels step K by 16 rows (dx a multiple of 16,
+// else 32) and gather only at d in {32, 64}; the f16x2 backward indexes rows with 32-bit offsets.  operands = false (the
+// query, which reads no pointer as more than null or non-null) skips the null-pointer requirement alone.
+inline int check_cell_bwd_mode(const tspgnn_lstm_bwd_task& t, int d, int arith, const char* p, bool operands = true) {
+    const bool f32 = arith == TSPGNN_ARITH_F32;
+    if (arith == TSPGNN_ARITH_H2) {
+        const int rc = check_rows_32bit(t.rows, t.dx, d, p);
+        if (rc) return rc;
+    }
     TSPGNN_REQUIRE(t.rows >= 0, "%s: rows=%d", p, t.rows);
+    const int step = f32 ? 16 : 32;
     TSPGNN_REQUIRE(t.dx >= 0 && t.dx % step == 0, "%s: dx=%d must be a non-negative multiple of %d", p, t.dx, step);
     if (t.rows == 0) return TSPGNN_OK;
-    TSPGNN_REQUIRE(t.h && t.c && t.K && t.ln && t.dz && t.dc_in && t.ln_grad && t.workspace && (t.dx == 0 || t.x),
+    TSPGNN_REQUIRE(!operands || (t.h && t.c && t.K && t.ln && t.dz && t.dc_in && t.ln_grad && t.workspace && (t.dx == 0 || t.x)),
                    "%s: null pointer", p);
-    if (fp32_mfma)
+    if (f32)
         TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx && (d == 32 || d == 64)), "%s: gather-init mode needs dx == 0, Zx and d in {32,64}", p);
     else
         TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx), "%s: gather-init mode needs dx == 0 and Zx", p);
+    if (f32) {
+        TSPGNN_REQUIRE(!t.zbias && !t.KTg,
+                       "%s: a bias-init z / a streamed data gradient are f16x2 features (tspgnn_lnlstm_bwd_multi_h2)", p);
+    } else if (arith == TSPGNN_ARITH_H2) {
+        TSPGNN_REQUIRE(!t.KT || (t.dxh && t.dx == 0), "%s: the fused data gradient needs dxh and dx == 0", p);
+        TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "%s: zbias needs zscale and excludes gather-init mode", p);
+        TSPGNN_REQUIRE(!t.KTg || (d == 64 && t.dx == 64 && t.dxg && t.dxh && !t.KT && !t.uv),
+                       "%s: the streamed data gradient needs d == dx == 64, dxg, dxh and excludes KT / gather-init mode", p);
+    } else {
+        TSPGNN_REQUIRE(!t.KT && !t.dxh && !t.zbias && !t.KTg, "%s: no fused data gradient / bias-init in this mode", p);
+    }
     return TSPGNN_OK;
 }
 
@@ -220,6 +239,7 @@ inline void plan_tasks(const long long* cost, long long tiles_all, int n, int gr
     p->nw = nw;
     p->n = n;
     p->grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), p->blk_end);
+    p->lds_bytes = 0;
 }
 
 // tspgnn_linear_f32; nt = (n1 + n2) / 16
@@ -479,6 +499,153 @@ inline int plan_cell_fwd(const tspgnn_cell_mlp_task* tasks, int n, int d, int ar
 // what plan_cell_fwd's caller answers for the task it names
 inline int cell_does_not_fit(const tspgnn_cell_mlp_task& t, int d, const char* what) {
     return fail(TSPGNN_EUNSUPPORTED, "%s: dx=%d, d=%d, %d MLP layers do not fit LDS", what, t.cell.dx, d, t.mlp_layers);
+}
+
+// ------------------------------------------------------------ cell launches that keep K resident or stream it in chunks
+// The LayerNorm tail of a cell backward workgroup's LDS: the 10 d parameters, nw wavefront slabs of 10 d partials, 4 words.
+inline size_t ln_tail_bytes(int d, int nw) { return (size_t)(10 * d + nw * 10 * d + 4) * sizeof(float); }
+
+// Units of K (per_unit bytes each: a 16-row block of fp32, a 32-row k-block of bf16) per LDS chunk under `budget`: all
+// `total` of them where they fit (resident), else as many as fit (0: not even one).
+inline int k_units_per_chunk(int total, size_t per_unit, size_t budget) {
+    return (size_t)total * per_unit > budget ? (int)(budget / per_unit) : total;
+}
+
+// bf16 K, shared by the bf16 backward and the bf16 forward cell: task k's k-blocks per chunk into p (false: none fits), its
+// bytes into *lds_k (the launch's maximum), and its tiles priced per_tile + KBT each, twice where K is streamed.
+inline bool plan_bf16_k(int rows, int dx, int d, size_t budget, int per_tile, tspgnn_cell_chunk_plan* p, int k, size_t* lds_k,
+                        long long* cost) {
+    const size_t per_kb = (size_t)32 * 4 * d * 2;
+    const int KBT = (dx + d) / 32;
+    const int kbc = k_units_per_chunk(KBT, per_kb, budget);
+    if (kbc < 1) return false;
+    p->qc[k] = kbc;
+    p->chunked[k] = kbc < KBT;
+    if ((size_t)kbc * per_kb > *lds_k) *lds_k = (size_t)kbc * per_kb;
+    *cost = tiles16(rows) * (KBT + per_tile) * (kbc < KBT ? 2 : 1);
+    return true;
+}
+
+// Most wavefronts per workgroup of the cell backward kernels = their NWMAX template argument.  fp32 and bf16: D = 128 keeps
+// 4D/16 + temporaries > 256 registers live, one wavefront per SIMD (512-register budget).
+#ifndef H2_BWD_NW
+#define H2_BWD_NW 8
+#endif
+constexpr int cell_bwd_nwmax(int d, int arith) { return arith == TSPGNN_ARITH_H2 ? H2_BWD_NW : (d >= 128 ? 4 : 8); }
+
+// tspgnn_lnlstm_bwd_multi_f32 / _h2 / _bf16 (arith: TSPGNN_ARITH_F32 / _H2 / _BF16).  TSPGNN_EUNSUPPORTED, by the first task
+// that does not fit, where the launch is refused.
+inline int plan_cell_bwd(const tspgnn_lstm_bwd_task* tasks, int n, int d, int arith, int cus, tspgnn_cell_chunk_plan* p) {
+    const int nwmax = cell_bwd_nwmax(d, arith);
+    const size_t budget = 160 * 1024 - ln_tail_bytes(d, nwmax);
+    *p = tspgnn_cell_chunk_plan{};
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    size_t lds_k = 0;
+    bool any_chunked = false;
+    for (int k = 0; k < n; ++k) {
+        const tspgnn_lstm_bwd_task& t = tasks[k];
+        const long long tiles = tiles16(t.rows);
+        if (arith == TSPGNN_ARITH_BF16) {
+            if (!plan_bf16_k(t.rows, t.dx, d, budget, 12, p, k, &lds_k, &cost[k]))
+                return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd_bf16: d=%d does not fit LDS", d);
+        } else if (arith == TSPGNN_ARITH_H2) {   // never chunked (qc = 0)
+            size_t need = (size_t)(t.dx + d) * 4 * d * 4;               // two fp16 pieces
+            if (t.KT != nullptr) need += (size_t)4 * d * d * 4;
+            if (need > budget)
+                return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd_h2: dx=%d, d=%d%s does not fit LDS", t.dx, d,
+                            t.KT ? " with K^T" : "");
+            if (need > lds_k) lds_k = need;
+            cost[k] = tiles * ((t.dx + d) / 32 + (t.KT ? 2 : 0) + (t.KTg ? 5 : 0) + 10);
+        } else {
+            const size_t per_q = (size_t)16 * 4 * d * sizeof(float);
+            const int QT = (t.dx + d) / 16;
+            const int qc = k_units_per_chunk(QT, per_q, budget);
+            if (qc < QT && (qc < 1 || t.uv)) return fail(TSPGNN_EUNSUPPORTED, "lnlstm_bwd: d=%d does not fit LDS", d);
+            size_t need = (size_t)qc * per_q;
+            if (t.KT != nullptr) {
+                need += (size_t)4 * d * (t.dx + d) * sizeof(float);
+                if (d != 64 || t.dx != 0 || qc < QT || need > budget)
+                    return fail(TSPGNN_EUNSUPPORTED,
+                                "lnlstm_bwd: the fused data gradient needs d=64, dx=0 and K, K^T resident in LDS");
+            }
+            p->qc[k] = qc;
+            p->chunked[k] = qc < QT;
+            if (need > lds_k) lds_k = need;
+            cost[k] = tiles * (QT + 8);  // k-blocks + ~8 blocks' worth of elementwise backward
+        }
+        any_chunked = any_chunked || p->chunked[k];
+        tiles_all += tiles;
+    }
+    // four wavefronts while every one of them still has a tile -- the fp32 rounds of a chunked K and the bf16 kernel
+    // always run all of them
+    const bool few = arith != TSPGNN_ARITH_BF16 && !any_chunked && tiles_all <= (long long)cus * 4;
+    p->n = n;
+    p->nw = few ? 4 : nwmax;
+    p->lds_bytes = (int)(lds_k + ln_tail_bytes(d, p->nw));
+    p->grid = split_blocks(cost, n, clamp_grid(cus, tiles_all, p->nw), p->blk_end);
+    return TSPGNN_OK;
+}
+
+// The frame of the three cell backward launchers: plan, the kernel's table from the plan, the launch, and the second stage
+// over the LayerNorm-gradient partials.  (The workspace holds one row of partials per workgroup of a task: n_cus + 8 rows,
+// tspgnn_lnlstm_bwd_workspace_floats.)  p: the prefix of the LDS message; what / what_reduce: the launches' names.
+template <class Table>
+int launch_cell_bwd(void (*kernel)(Table), const tspgnn_lstm_bwd_task* tasks, int n, int d, int arith, hipStream_t st,
+                    const char* p, const char* what, const char* what_reduce) {
+    tspgnn_cell_chunk_plan pl;
+    int rc = plan_cell_bwd(tasks, n, d, arith, n_cus(), &pl);
+    if (rc) return rc;
+    Table tt;
+    for (int k = 0; k < n; ++k) {
+        tt.task[k] = tasks[k];
+        tt.qc[k] = pl.qc[k];
+        tt.blk_end[k] = pl.blk_end[k];
+    }
+    tt.n = n;
+    if ((rc = set_dynamic_lds(kernel, pl.lds_bytes, p))) return rc;
+    kernel<<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(tt);
+    if ((rc = launched(what))) return rc;
+    return reduce_ln_partials(tasks, n, pl.blk_end, d, st, what_reduce);
+}
+
+// tspgnn_lnlstm_fwd_multi_bf16 at the nw wavefronts per workgroup of the kernel its dispatch chose
+inline int plan_lstm_fwd_bf16(const tspgnn_lstm_task_bf16* tasks, int n, int d, int nw, int cus, tspgnn_cell_chunk_plan* p) {
+    const size_t head = (10 * d + 4) * sizeof(float);
+    *p = tspgnn_cell_chunk_plan{};
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    size_t lds_w = 0;
+    for (int k = 0; k < n; ++k) {
+        if (!plan_bf16_k(tasks[k].rows, tasks[k].dx, d, 156 * 1024 - head, 4, p, k, &lds_w, &cost[k]))
+            return fail(TSPGNN_EUNSUPPORTED, "lnlstm_fwd_bf16: d=%d does not fit LDS", d);
+        tiles_all += tiles16(tasks[k].rows);
+    }
+    p->n = n;
+    p->nw = nw;
+    p->lds_bytes = (int)(lds_w + head);
+    p->grid = split_blocks(cost, n, clamp_grid(cus, tiles_all, nw), p->blk_end);
+    return TSPGNN_OK;
+}
+
+// tspgnn_mlp_fwd_multi_bf16, likewise: LDS holds the layers of the deepest task or a projection matrix, whichever is larger
+inline int plan_mlp_fwd_bf16(const tspgnn_mlp_task_bf16* tasks, int n, int d, int nw, int cus, tspgnn_tasks_plan* p) {
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    size_t lds_w = 0;
+    for (int k = 0; k < n; ++k) {
+        const size_t need = tasks[k].proj_w ? (size_t)d * 4 * d * 2 : 0;
+        const size_t lay = (size_t)tasks[k].n_layers * (d * d * 2 + d * 4);
+        lds_w = lds_w > need ? lds_w : need;
+        lds_w = lds_w > lay ? lds_w : lay;
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
+    }
+    const size_t lds_bytes = lds_w + 16;
+    if (lds_bytes > 160 * 1024) return fail(TSPGNN_EUNSUPPORTED, "mlp_fwd_bf16: %zu bytes of weights do not fit LDS", lds_bytes);
+    plan_tasks(cost, tiles_all, n, cus, nw, p);
+    p->lds_bytes = (int)lds_bytes;
+    return TSPGNN_OK;
 }
 
 }  // namespace tspgnn

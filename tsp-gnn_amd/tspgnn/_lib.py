@@ -130,6 +130,9 @@ SIGNATURES = {
     "tspgnn_plan_wcolsum": [c_longlong, c_int, c_int, c_void_p],
     "tspgnn_plan_einit_bwd": [c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_cell_fwd": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_cell_bwd": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_lstm_fwd_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_mlp_fwd_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_reduce_slices": [c_int],
     "tspgnn_plan_strided_blocks": [c_longlong, c_int, c_int],
 }
@@ -250,7 +253,7 @@ class LinearPlan(ctypes.Structure):
 
 class TasksPlan(ctypes.Structure):
     """tspgnn_tasks_plan (include/tspgnn.h)."""
-    _fields_ = [("nw", c_int), ("grid", c_int), ("n", c_int), ("blk_end", c_int * 4)]
+    _fields_ = [("nw", c_int), ("grid", c_int), ("n", c_int), ("blk_end", c_int * 4), ("lds_bytes", c_int)]
 
 
 class WgradPlan(ctypes.Structure):
@@ -276,9 +279,16 @@ class CellFwdPlan(ctypes.Structure):
                 ("n_rounds", c_int * 4), ("split_fixed", c_int), ("centered", c_int), ("wt", c_int), ("lds_bytes", c_int)]
 
 
+class CellChunkPlan(ctypes.Structure):
+    """tspgnn_cell_chunk_plan (include/tspgnn.h)."""
+    _fields_ = [("nw", c_int), ("grid", c_int), ("n", c_int), ("blk_end", c_int * 4), ("qc", c_int * 4),
+                ("chunked", c_int * 4), ("lds_bytes", c_int)]
+
+
 PLANS = {"tspgnn_plan_linear": LinearPlan, "tspgnn_plan_mlp_bwd": TasksPlan, "tspgnn_plan_mlp_fwd": TasksPlan,
          "tspgnn_plan_wgrad": WgradPlan, "tspgnn_plan_wcolsum": WcolsumPlan, "tspgnn_plan_einit_bwd": EinitBwdPlan,
-         "tspgnn_plan_cell_fwd": CellFwdPlan}
+         "tspgnn_plan_cell_fwd": CellFwdPlan, "tspgnn_plan_cell_bwd": CellChunkPlan,
+         "tspgnn_plan_lstm_fwd_bf16": CellChunkPlan, "tspgnn_plan_mlp_fwd_bf16": TasksPlan}
 
 
 class TspgnnError(RuntimeError):
