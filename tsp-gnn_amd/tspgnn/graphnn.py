@@ -174,6 +174,45 @@ class _States(dict):
         self._keep = keep
 
 
+class _Ends(object):
+    """Where one message-passing step reads and writes: all that a step builder (GraphNN._split_step, _fused_step,
+    _bf16_step) knows of its driver.  Inference makes one per parity of its ping-pong buffers (and per first / last step
+    where those differ), training one per step from the Tape (GraphNN._tape_ends).  What a dict does not name is the
+    builder's to allocate; it puts the buffer into the dict (msg, zx) or into ``keep``, so whoever keeps the _Ends keeps
+    every buffer the step's tasks point at.
+      src, dst         {var: LSTMStateTuple} the step reads / writes (src c None: the zero cell state, as a null pointer)
+      rows             {var: rows of its states} (a blocked buffer is padded beyond them)
+      blk_in, blk_out  {var: the src / dst state buffers are blocked by 16 rows}; not named: row-major
+      zx               {var: the projected messages Zx of a folded cell}
+      x                {var: where the cell input goes} (training: the tape's X[v][t])
+      msg              {(var, i): where loop entry i's message goes} (training: the tape's X or the extra acts slot).  Once
+                       the messages are built it holds EVERY entry's rows -- the source h or 'fun' of it, the appended
+                       matrix, the message -- which is what the cell inputs are made of
+      acts             {(var, i): (hidden-activation slice [layers-1, rows, d], element stride between layers)}, training"""
+
+    def __init__(self, src, dst, rows=None, blk_in=None, blk_out=None, zx=None, x=None, msg=None, acts=None):
+        self.src, self.dst = src, dst
+        self.rows = rows if rows is not None else {v: st.h.shape[0] for v, st in src.items()}
+        self.blk_in, self.blk_out = blk_in or {}, blk_out or {}
+        self.zx, self.x, self.acts = {} if zx is None else zx, x or {}, acts or {}
+        self.msg = {} if msg is None else msg
+        self.keep = []
+
+
+def _launch_ops(name, by_width):
+    """_lib.launches(by_width) of entry point ``name`` as (fn, args) operations, like the adjacency products between them."""
+    return [(_lib.call_multi, (name, tasks, d)) for tasks, d in _lib.launches(by_width)]
+
+
+def _run(parts):
+    """Run a step: ``parts`` = lists of (fn, args) in order.  A builder (a generator) builds a part only when asked for it,
+    so an eager driver, which hands the generator itself, has run a part before the next one is built -- the weight
+    packings of the cell tasks are enqueued behind the adjacency products; a plan keeps list(builder) and replays it."""
+    for ops in parts:
+        for fn, args in ops:
+            fn(*args)
+
+
 class Tape(object):
     """What GraphNN.forward_train keeps for the backward pass: every step's states H, C ([T+1, rows, d]), cell inputs
     X (for a folded cell: the message y per SOURCE row, with ZX = y Kx), hidden MLP activations acts
@@ -935,6 +974,216 @@ class GraphNN(object):
                              acts_stride=0 if acts is None else acts.stride(0), x_blocked=int(blocked),
                              y_interleaved=int(interleave))
 
+    # ---------------------------------------------------------------- step builders
+    # One synchronous step (graphnn.py:142-173) in each of its three launch shapes, as a function of where it reads and
+    # writes (_Ends).  The drivers decide the selectors (folded, pushed, arith, centered, rc, consumers, interleave) and
+    # hand them in; the builders read no switch of their own.  Each is a generator of the step's parts in running order
+    # -- message launches, adjacency products, cell launches --, see _run.  An eager driver must hand _run the generator
+    # itself, not a list of it: a cell task's first use packs its weights, and tests/test_launch_trace.py pins those
+    # packings BEHIND the adjacency products the driver has already run (the bf16 training forward: variable by variable,
+    # which is why _bf16_step yields one part of products per variable).
+    def _split_messages(self, ep, dense, folded, pushed, arith=None, centered=False, rc={}, project=True):
+        """-> the message-MLP launches of a step (per width): every loop entry's MLP -- the whole chain, with Zx = msg(y) Kx
+        riding behind it for a folded receiver (``project``), or for a pushed receiver all but the last layer, whose output
+        is the last saved activation (``rc``: the backward recomputes them, none is saved).  Fills ep.msg (and ep.zx).
+        What has no task runs while the step is built, which only an eager driver's wiring asks for: a Python 'fun'
+        (graphnn.py:149-151; the backward differentiates it again: _fun_vjp) and a chain of several fp32 kernels."""
+        f32 = dict(dtype=torch.float32, device=self.store.theta.device)
+        tasks = {}
+        for v in self.var:
+            for i, u in enumerate(self.loop[v]):
+                if "var" not in u:          # an appended matrix: joins the cell input as it is
+                    ep.msg[(v, i)] = dense[u["mat"]]
+                    continue
+                y = h = ep.src[u["var"]].h
+                if "fun" in u:
+                    y = u["fun"](h)
+                    if not torch.is_tensor(y) or y.shape != h.shape:
+                        raise ValueError("loop entry 'fun' must map [rows, d] to a tensor of the same shape")
+                    y = y.to(torch.float32).contiguous()
+                    ep.keep.append(y)
+                if "msg" in u:
+                    mlp = self._msg_MLPs[u["msg"]]
+                    out = ep.msg.get((v, i))
+                    if out is None:
+                        out = torch.empty((y.shape[0], mlp.sizes[-1]), **f32)
+                    acts, stride = ep.acts.get((v, i), (None, 0))
+                    proj = None
+                    if pushed[v]:   # last hidden activation only; the last layer is folded into the cell
+                        if rc.get((v, i)):
+                            acts, stride = None, 0
+                        task = mlp.prefix_task(y, out, mlp.n_square - 1, arith=arith, acts=acts, acts_stride=stride)
+                    else:
+                        if project and folded[v] is not None:   # Zx = msg(y) Kx rides in the MLP launch
+                            if v not in ep.zx:
+                                ep.zx[v] = torch.empty((_pad16(y.shape[0]), 4 * self.var[v]), **f32)
+                            proj = (self._RNN_cells[v].packed("Kx", arith or "f32", centered), ep.zx[v])
+                        task = mlp.task(y, out, acts, stride, proj=proj, arith=arith)
+                    if task is not None:
+                        tasks.setdefault(mlp.sizes[-1], []).append(task)
+                    else:   # run here, once: never inside a plan, which declines such a wiring before it builds anything
+                        assert not pushed[v] and (acts is not None or not project), "a replayed step needs single-kernel MLPs"
+                        if acts is None:
+                            out = mlp(y)
+                        elif arith:
+                            raise NotImplementedError("bf16x3 training forward needs single-kernel message MLPs")
+                        else:
+                            mlp.forward_saving(y, out, acts, stride)
+                        if proj is not None:
+                            self._RNN_cells[v].premultiply(out, out=proj[1])
+                    y = out
+                ep.msg[(v, i)] = y
+        return _launch_ops("tspgnn_mlp_fwd_multi_" + (arith or "f32"), tasks)
+
+    def _split_step(self, ep, mats, dense, folded, pushed, arith=None, centered=False, rc={}, project=True):
+        """The split shape: (A) every message MLP, (B) the adjacency products / the projection Zx = y Kx of a folded
+        cell that no MLP launch made, (C) every cell -- independent work of the same kind shares a launch per width."""
+        yield self._split_messages(ep, dense, folded, pushed, arith, centered, rc, project)
+        xs, mid = {}, []
+        for v in self.var:
+            u = folded[v]
+            if u is None:
+                xs[v], ops = self._cell_input(v, ep.msg, mats, ep.rows[v], torch.float32, out=ep.x.get(v))
+                mid += ops
+            elif project and "msg" in u:
+                xs[v] = ep.zx[v]
+            else:   # no message launch to project behind: Zx = y Kx by a launch of its own (f16x2: times 2^s, blocked)
+                y, x = ep.msg[(v, 0)], ep.x.get(v)
+                if x is not None and x.data_ptr() != y.data_ptr():   # (training: the tape keeps y per source row)
+                    mid.append((x.copy_, (y,)))
+                    y = x
+                xs[v] = ep.zx[v] if v in ep.zx else torch.empty((_pad16(y.shape[0]), 4 * self.var[v]), dtype=torch.float32,
+                                                                device=y.device)
+                mid.append((self._RNN_cells[v].premultiply,
+                            (y, xs[v], _lib.lib.tspgnn_h2_weight_scale() if arith == "h2" else None)))
+        ep.keep.append(xs)
+        yield mid
+        tasks = {}
+        for v, d in self.var.items():
+            tasks.setdefault(d, []).append(self._cell_forward_task(v, xs[v], ep.src[v], (ep.dst[v].h, ep.dst[v].c), folded,
+                                                                   pushed, mats, arith, centered))
+        yield _launch_ops("tspgnn_lnlstm_fwd_multi_" + (arith or "f32"), tasks)
+
+    def _fused_message(self, v, i, ep, folded, pushed, arith, centered):
+        """(wb, n_layers, relu_mask, out, proj_w, proj_out) of loop entry (v, i)'s message MLP writing into ``ep``, as the
+        fused cell + message launch and the one-launch loop take it; out None: a folded receiver only takes Zx."""
+        mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
+        n = mlp.n_square - 1 if pushed[v] else mlp.n_square   # >= 1 (_pushable needs two square layers)
+        pw = po = None
+        if folded[v] is not None:
+            pw, po = self._RNN_cells[v].packed("Kx", arith, centered), ep.zx[v]
+        elif (v, i) not in ep.msg:
+            ep.msg[(v, i)] = torch.empty((ep.rows[self.loop[v][i]["var"]], mlp.sizes[-1]), dtype=torch.float32,
+                                         device=self.store.theta.device)
+        return (mlp.wb_packed(0, n - 1, mlp.sizes[-1], arith), n, mlp.relu_mask(0, n), ep.msg.get((v, i)), pw, po)
+
+    def _fused_step(self, ep, nxt, mats, folded, pushed, consumers, arith, centered=False, rc={}):
+        """The fused shape (tspgnn_lnlstm_mlp_fwd_multi_x3 / _h2): the adjacency products over the messages in ep.msg, then
+        ONE launch per width that updates the states and, on the rows of h' it still holds in registers, evaluates the
+        message MLP that reads them in the next step, writing where ``nxt`` (that step's _Ends) says; nxt None: the last
+        step, the cells alone.  consumers = _single_consumers()."""
+        xs, mid = {}, []
+        for v in self.var:
+            if folded[v] is not None:
+                xs[v] = ep.zx[v]
+            else:
+                xs[v], ops = self._cell_input(v, ep.msg, mats, ep.rows[v], torch.float32, out=ep.x.get(v))
+                mid += ops
+        ep.keep.append(xs)
+        yield mid
+        tasks = {}
+        for v, d in self.var.items():
+            n_v, c = ep.rows[v], ep.src[v].c
+            st = LSTMStateTuple(c=c if c is None else c[:n_v], h=ep.src[v].h[:n_v])
+            t = self._cell_forward_task(v, xs[v], st, (ep.dst[v].h, ep.dst[v].c), folded, pushed, mats, arith, centered)
+            more = {}
+            if nxt is not None:   # the message MLP that reads this variable's new h in the next step
+                key = consumers[v]
+                wb, n, mask, out, pw, po = self._fused_message(key[0], key[1], nxt, folded, pushed, arith, centered)
+                saved, stride = nxt.acts.get(key, (None, 0))
+                if rc.get(key) or n == 1:
+                    saved = None
+                more = dict(mlp_wb=_lib.ptr(wb), mlp_layers=n, relu_mask=mask, mlp_out=_lib.ptr(out), proj_w=_lib.ptr(pw),
+                            proj_out=_lib.ptr(po), mlp_acts=_lib.ptr(saved), mlp_acts_stride=stride)
+            tasks.setdefault(d, []).append(_lib.CellMlpTask(t, state_in_blocked=int(ep.blk_in.get(v, False)),
+                                                            state_out_blocked=int(ep.blk_out.get(v, False)), **more))
+        yield _launch_ops("tspgnn_lnlstm_mlp_fwd_multi_" + arith, tasks)
+
+    def _bf16_step(self, ep, mats, folded, interleave=False):
+        """The bf16-storage shape, three launches per step: message MLPs (a folded receiver's with its Kx projection),
+        adjacency products, cells (a folded cell in gather-init mode).  ``interleave``: a plain message (no projection
+        rides behind it) has its last layer's columns interleaved in the packing, 16-byte stores of Y
+        (tspgnn_mlp_task_bf16.y_interleaved)."""
+        bf = dict(dtype=torch.bfloat16, device=self.store.theta.device)
+        mlp_tasks = {}
+        for v in self.var:
+            for i, u in enumerate(self.loop[v]):
+                src = u["var"]
+                y = ep.src[src].h
+                if "msg" in u:
+                    mlp = self._msg_MLPs[u["msg"]]
+                    d, rows = mlp.sizes[-1], ep.rows[src]
+                    out = ep.msg.get((v, i))
+                    if out is None:
+                        out = torch.empty((rows, d), **bf)
+                    proj = (None, None)
+                    if folded[v] is not None:
+                        if v not in ep.zx:
+                            ep.zx[v] = torch.empty((_pad16(rows), 4 * self.var[v]), **bf)
+                        proj = (self._RNN_cells[v].packed("Kx", "bf16"), ep.zx[v])
+                    mlp_tasks.setdefault(d, []).append(self._bf16_message_task(
+                        mlp, y, rows, out, proj, interleave=interleave and proj[0] is None and d % 32 == 0,
+                        blocked=ep.blk_in.get(src, False), acts=ep.acts.get((v, i), (None, 0))[0]))
+                    y = out
+                ep.msg[(v, i)] = y
+        # tasks with a projection go to their own launch: without them the MLP kernel needs a third of the registers (the
+        # projection's 4d accumulators) and the big edge task runs at twice the occupancy
+        launches = []
+        for d, ts in mlp_tasks.items():
+            for group in ([t for t in ts if not t.proj_w], [t for t in ts if t.proj_w]):
+                launches += _launch_ops("tspgnn_mlp_fwd_multi_bf16", {d: group})
+        yield launches
+        cell_tasks = {}
+        for v, d in self.var.items():
+            if folded[v] is not None:
+                x, adj = ep.zx[v], mats[folded[v]["mat"]]
+            else:
+                x, ops = self._cell_input(v, ep.msg, mats, ep.rows[v], torch.bfloat16, out=ep.x.get(v))
+                adj = None
+                ep.keep.append(x)
+                yield ops
+            cell_tasks.setdefault(d, []).append(self._RNN_cells[v].task_bf16(
+                x, ep.src[v].h, ep.src[v].c, ep.dst[v].h, ep.dst[v].c, ep.rows[v], adj=adj,
+                state_in_blocked=ep.blk_in.get(v, False), state_out_blocked=ep.blk_out.get(v, False)))
+        yield _launch_ops("tspgnn_lnlstm_fwd_multi_bf16", cell_tasks)
+
+    def _tape_ends(self, tape):
+        """-> ends(t), the _Ends of step t of a training forward: it reads slot t of the tape and writes slot t + 1; cell
+        inputs, messages, projected messages and hidden activations go straight into the tape.  Which array and layer an
+        entry's message goes to does not depend on t and is worked out once: the eager forward pays for every index."""
+        H, C, X, ZX = tape.H, tape.C, tape.X, tape.ZX
+        rows = {v: h.shape[1] for v, h in H.items()}
+        # X[v] as the cell input's place: not for a folded cell behind a message MLP, whose X is that message's place
+        own_x = [v for v in self.var if tape.folded[v] is None or "msg" not in tape.folded[v]]
+        saved, where = [], []   # (key, acts or None, stride between layers), (key, array, layer or None)
+        for (v, i), acts in tape.acts.items():
+            rc = tape.rc.get((v, i))
+            saved.append(((v, i), None if rc else acts, acts.stride(0)))   # (recomputed by the backward: none is saved)
+            slot = self._message_output_slot(v, i, tape.folded)
+            if tape.pushed[v]:   # the message is the last hidden activation
+                where.append(((v, i), acts, 0 if rc else self._msg_MLPs[self.loop[v][i]["msg"]].n_square - 2))
+            elif self._message_to_tape(v, i, tape.folded):
+                where.append(((v, i), X[v], None))
+            elif slot is not None:
+                where.append(((v, i), acts, slot))
+
+        def ends(t):
+            return _Ends({v: LSTMStateTuple(C[v][t], H[v][t]) for v in rows}, {v: LSTMStateTuple(C[v][t + 1], H[v][t + 1]) for v in rows},
+                         rows=rows, zx={v: zx[t] for v, zx in ZX.items()}, x={v: X[v][t] for v in own_x},
+                         msg={key: a[t] if k is None else a[k, t] for key, a, k in where},
+                         acts={key: (a if a is None else a[:, t], stride) for key, a, stride in saved})
+        return ends
+
     # ---------------------------------------------------------------- forward
     def __call__(self, adjacency_matrices, initial_embeddings, time_steps, LSTM_initial_states={}):
         """-> {var: LSTMStateTuple(c, h)} after ``time_steps`` synchronous steps
@@ -993,81 +1242,23 @@ class GraphNN(object):
         # MLP (it goes to an aggregation or straight into a cell input) stays row-major.
         f32 = dict(dtype=torch.float32, device=self.store.theta.device)
         blocked = {v: all("msg" in u for w in self.var for u in self.loop[w] if u["var"] == v) for v in self.var}
-
-        def buffers(dtype):
-            return [{v: torch.empty((_pad16(st.h.shape[0]) if blocked[v] else st.h.shape[0], st.h.shape[1]),
-                                    dtype=dtype, device=st.h.device) for v, st in states.items()} for _ in (0, 1)]
-        hbuf, cbuf = buffers(torch.bfloat16), buffers(torch.float32)
+        rows = {v: st.h.shape[0] for v, st in states.items()}
+        shape = {v: (_pad16(rows[v]) if blocked[v] else rows[v], d) for v, d in self.var.items()}
+        buf = [{v: LSTMStateTuple(c=torch.empty(shape[v], **f32), h=torch.empty(shape[v], **bf)) for v in self.var}
+               for _ in (0, 1)]
         last = {v: LSTMStateTuple(c=torch.empty(st.h.shape, **f32), h=torch.empty_like(st.h)) for v, st in states.items()}
         folded = {v: self._folded(v, mats, bf16_inference=True) for v in self.var}
-        keep = [hbuf, cbuf, last, states]
+        interleave = os.environ.get("TSPGNN_BF16_INTERLEAVE", "1") != "0"
         built = {}
-
-        def step_launches(p, first, final):
-            """(message-MLP launches, adjacency products, cell launches) of a step reading parity-p buffers."""
-            key = (p, first, final)
-            if key in built:
-                return built[key]
-            h_in = {v: states[v].h if first else hbuf[p][v] for v in self.var}
-            c_in = {v: states[v].c if first else cbuf[p][v] for v in self.var}
-            h_out = {v: last[v].h if final else hbuf[1 - p][v] for v in self.var}
-            c_out = {v: last[v].c if final else cbuf[1 - p][v] for v in self.var}
-            blk_in = {v: blocked[v] and not first for v in self.var}
-            blk_out = {v: blocked[v] and not final for v in self.var}
-            mlp_tasks, mid, msg_out, zxs, cell_tasks = {}, [], {}, {}, {}
-            for v in self.var:
-                for i, u in enumerate(self.loop[v]):
-                    src = u["var"]
-                    y = h_in[src]
-                    if "msg" in u:
-                        mlp = self._msg_MLPs[u["msg"]]
-                        d = mlp.sizes[-1]
-                        rows = states[src].h.shape[0]
-                        out = torch.empty((rows, d), **bf)
-                        proj = (None, None)
-                        if folded[v] is not None:
-                            zxs[v] = torch.empty((_pad16(rows), 4 * self.var[v]), **bf)
-                            proj = (self._RNN_cells[v].packed("Kx", "bf16"), zxs[v])
-                        # a plain message (no projection rides behind it): the last layer's columns interleaved in the
-                        # packing, 16-byte stores of Y (tspgnn_mlp_task_bf16.y_interleaved)
-                        il = proj[0] is None and d % 32 == 0 and os.environ.get("TSPGNN_BF16_INTERLEAVE", "1") != "0"
-                        mlp_tasks.setdefault(d, []).append(
-                            self._bf16_message_task(mlp, y, rows, out, proj, interleave=il, blocked=blk_in[src]))
-                        y = out
-                    msg_out[(v, i)] = y
-            for v, d in self.var.items():
-                cell = self._RNN_cells[v]
-                rows = states[v].h.shape[0]
-                if folded[v] is not None:
-                    adj, x = mats[folded[v]["mat"]], zxs[v]
-                else:
-                    x, ops = self._cell_input(v, msg_out, mats, rows, torch.bfloat16)
-                    mid += ops
-                    adj = None
-                    keep.append(x)
-                cell_tasks.setdefault(d, []).append(cell.task_bf16(
-                    x, h_in[v], c_in[v], h_out[v], c_out[v], rows, adj=adj, state_in_blocked=blk_in[v],
-                    state_out_blocked=blk_out[v]))
-            keep.extend([msg_out, zxs])
-            # tasks with a projection go to their own launch: without them the MLP kernel needs a third of the
-            # registers (the projection's 4d accumulators) and the big edge task runs at twice the occupancy
-            mlp_calls = []
-            for d, ts in mlp_tasks.items():
-                for group in ([t for t in ts if not t.proj_w], [t for t in ts if t.proj_w]):
-                    mlp_calls += _lib.launches({d: group})
-            cell_calls = _lib.launches(cell_tasks)
-            built[key] = (mlp_calls, mid, cell_calls)
-            return built[key]
-        keep.append(built)
-        self._plan_keep = keep
+        self._plan_keep = keep = [buf, last, states, built]
         for t in range(T):
-            mlp_calls, mid, cell_calls = step_launches(t & 1, t == 0, t == T - 1)
-            for arr, d in mlp_calls:
-                _lib.call_multi("tspgnn_mlp_fwd_multi_bf16", arr, d)
-            for fn, args in mid:
-                fn(*args)
-            for arr, d in cell_calls:
-                _lib.call_multi("tspgnn_lnlstm_fwd_multi_bf16", arr, d)
+            p, first, final = kind = (t & 1, t == 0, t == T - 1)
+            if kind not in built:   # the step's _Ends and its parts: built once per kind, replayed
+                ep = _Ends(states if first else buf[p], last if final else buf[1 - p], rows=rows,
+                           blk_in={v: blocked[v] and not first for v in self.var},
+                           blk_out={v: blocked[v] and not final for v in self.var})
+                built[kind] = (ep, list(self._bf16_step(ep, mats, folded, interleave)))
+            _run(built[kind][1])
         return _States(last, keep)
 
     def _split_arith(self, n_rows=None):
@@ -1204,66 +1395,23 @@ class GraphNN(object):
                         zxs[p][v] = torch.empty((_pad16(rows), 4 * self.var[v]), **f32)   # (fused plan: f16x2 / x3 only)
                     else:
                         mo[p][(v, i)] = torch.empty((rows, width), **f32)
-        keep = [buf, mo, zxs, first_state]
+
+        def ends(p, with_messages=True, first=False):
+            """A step of parity p: it reads the messages of mo[p] / zxs[p]; ``first``: and the caller's (row-major) states;
+            a step without messages is the last one and writes row-major states."""
+            return _Ends(first_state if first else buf[p], buf[1 - p], rows=rows_of, zx=zxs[p], msg=mo[p],
+                         blk_in={v: blocked[v] and not first for v in self.var},
+                         blk_out={v: blocked[v] and with_messages for v in self.var})
 
         def message(v, i, p):
             """(wb, n_layers, relu_mask, out, proj_w, proj_out) of loop entry (v, i) writing parity-p buffers."""
-            mlp = self._msg_MLPs[self.loop[v][i]["msg"]]
-            d = mlp.sizes[-1]
-            n = mlp.n_square - 1 if pushed[v] else mlp.n_square   # >= 1 (_pushable needs two square layers)
-            pw = po = None
-            if folded[v] is not None:
-                cv = self._RNN_cells[v]
-                pw, po = cv.packed("Kx", arith, cen), zxs[p][v]
-            out = mo[p].get((v, i))
-            return (mlp.wb_packed(0, n - 1, d, arith), n, mlp.relu_mask(0, n), out, pw, po)
+            return self._fused_message(v, i, ends(p), folded, pushed, arith, cen)
 
-        def cell_tasks(p, with_messages, first):
-            """Launches of a step of parity p; ``first``: the step reads the caller's (row-major) states; a step
-            without messages is the last one and writes row-major states."""
-            src, dst = buf[p], buf[1 - p]
-            mid, tasks = [], {}
-            for v, d in self.var.items():
-                n_v = rows_of[v]
-                st = first_state[v] if first else LSTMStateTuple(c=src[v].c[:n_v], h=src[v].h[:n_v])
-                out = (dst[v].h, dst[v].c)
-                if folded[v] is not None:
-                    x = zxs[p][v]
-                else:
-                    x, ops = self._cell_input(v, mo[p], mats, n_v, torch.float32)
-                    mid += ops
-                    keep.append(x)
-                t = self._cell_forward_task(v, x, st, out, folded, pushed, mats, arith, cen)
-                s_in = 1 if blocked[v] and not first else 0
-                s_out = 1 if blocked[v] and with_messages else 0
-                if with_messages:   # the message MLP that reads this variable's new h in the next step
-                    cv, ci = consumers[v]
-                    wb, n, mask, mout, pw, po = message(cv, ci, 1 - p)
-                    ct = _lib.CellMlpTask(t, mlp_wb=_lib.ptr(wb), mlp_layers=n, relu_mask=mask, mlp_out=_lib.ptr(mout),
-                                          proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po), state_in_blocked=s_in,
-                                          state_out_blocked=s_out)
-                else:
-                    ct = _lib.CellMlpTask(t, state_in_blocked=s_in, state_out_blocked=s_out)
-                tasks.setdefault(d, []).append(ct)
-            calls = _lib.launches(tasks)
-            return mid, calls
-
-        # messages of step 0 from the initial states
-        pre = {}
-        for v in self.var:
-            for i, u in enumerate(self.loop[v]):
-                wb, n, mask, mout, pw, po = message(v, i, 0)
-                y = first_state[u["var"]].h
-                if mout is None:
-                    mout = torch.empty((y.shape[0], self._msg_MLPs[u["msg"]].sizes[-1]), **f32)
-                    keep.append(mout)
-                pre.setdefault(self._msg_MLPs[u["msg"]].sizes[-1], []).append(
-                    _lib.MlpTask(X=_lib.ptr(y), wb=_lib.ptr(wb), Y=_lib.ptr(mout), rows=y.shape[0], n_layers=n, relu_mask=mask,
-                                 proj_w=_lib.ptr(pw), proj_out=_lib.ptr(po),
-                                 range_flag=self.store.guard.flag_ptr() if arith == "h2" else None))
-        pre_calls = _lib.launches(pre)
+        # messages of step 0 from the initial states (a folded receiver's message itself goes to a temporary of this launch)
+        pre_ends = _Ends(first_state, None, zx=zxs[0], msg=dict(mo[0]))
+        pre = [self._split_messages(pre_ends, {}, folded, pushed, arith, cen)]
         built = {}
-        self._plan_keep = keep
+        self._plan_keep = keep = [buf, mo, zxs, first_state, pre_ends, built]
         # the cells' packings are made here, not at the first step: the caller vets their range (check_h2_weights) between
         # the construction of the plan and its first launch
         self._prepack_cells(folded, pushed, arith, cen)
@@ -1272,21 +1420,19 @@ class GraphNN(object):
             if arith == "h2" else None
 
         def run(T):
-            for arr, d in pre_calls:
-                _lib.call_multi("tspgnn_mlp_fwd_multi_" + arith, arr, d)
+            _run(pre)
             if loop_launch is not None:
                 done = loop_launch(T)
                 if done is not None:
                     return done
             for t in range(T):
-                kind = (t & 1, t < T - 1, t == 0)
-                if kind not in built:
-                    built[kind] = cell_tasks(*kind)
-                mid, calls = built[kind]
-                for fn, args in mid:
-                    fn(*args)
-                for arr, d in calls:
-                    _lib.call_multi("tspgnn_lnlstm_mlp_fwd_multi_" + arith, arr, d)
+                p, with_messages, first = kind = (t & 1, t < T - 1, t == 0)
+                if kind not in built:   # the step's _Ends and its parts: built once per kind, replayed.  (The next step's
+                    # _Ends is not kept: it names nothing but mo[1 - p] / zxs[1 - p], which _plan_keep holds.)
+                    ep = ends(p, with_messages, first)
+                    built[kind] = (ep, list(self._fused_step(ep, ends(1 - p) if with_messages else None, mats, folded, pushed,
+                                                             consumers, arith, cen)))
+                _run(built[kind][1])
             final = buf[T & 1]
             return {v: LSTMStateTuple(c=final[v].c[:rows_of[v]], h=final[v].h[:rows_of[v]]) for v in self.var}
         return run
@@ -1400,7 +1546,6 @@ class GraphNN(object):
         without HIP-graph replay).  Returns (run_even, run_odd, (states_if_T_even, states_if_T_odd)), or
         None when the wiring needs the general path (Python 'fun' entries, dense matrices, MLPs that do
         not fit one kernel)."""
-        f32 = dict(dtype=torch.float32, device=self.store.theta.device)
         for v in self.var:
             for u in self.loop[v]:
                 if "var" not in u or "fun" in u:
@@ -1410,110 +1555,18 @@ class GraphNN(object):
         # buf[p] holds the states a step of parity p READS; it writes buf[1-p]
         buf = [{v: LSTMStateTuple(c=st.c.clone(), h=st.h.clone()) for v, st in states.items()},
                {v: LSTMStateTuple(c=torch.empty_like(st.c), h=torch.empty_like(st.h)) for v, st in states.items()}]
-        runs, keep = [], []
         arith = self._split_arith({v: st.h.shape[0] for v, st in states.items()})
-        zx_scale = _lib.lib.tspgnn_h2_weight_scale() if arith == "h2" else None
-        for p in (0, 1):
-            src_states, dst_states = buf[p], buf[1 - p]
-            mlp_tasks, lstm_tasks, mid, msg_out, zxs = {}, {}, [], {}, {}
-            pushed = {v: self._pushable(v, mats, folded) for v in self.var}
-            for v in self.var:
-                for i, u in enumerate(self.loop[v]):
-                    y = src_states[u["var"]].h
-                    if "msg" in u:
-                        mlp = self._msg_MLPs[u["msg"]]
-                        out = torch.empty((y.shape[0], mlp.sizes[-1]), **f32)
-                        if pushed[v]:   # last hidden activation only; the last layer is folded into the cell
-                            mlp_tasks.setdefault(mlp.sizes[-1], []).append(mlp.prefix_task(y, out, mlp.n_square - 1, arith=arith))
-                            msg_out[(v, i)] = out
-                            continue
-                        proj = None
-                        if folded[v] is not None:   # Zx = msg(y) Kx rides in the MLP launch
-                            zxs[v] = torch.empty((_pad16(y.shape[0]), 4 * self.var[v]), **f32)
-                            cv = self._RNN_cells[v]
-                            proj = (cv.packed("Kx", arith or "f32"), zxs[v])
-                        mlp_tasks.setdefault(mlp.sizes[-1], []).append(mlp.task(y, out, proj=proj, arith=arith))
-                        y = out
-                    msg_out[(v, i)] = y
-            for v, d in self.var.items():
-                cell, st = self._RNN_cells[v], src_states[v]
-                out = (dst_states[v].h, dst_states[v].c)
-                if folded[v] is None:
-                    x, ops = self._cell_input(v, msg_out, mats, st.h.shape[0], torch.float32)
-                    mid += ops
-                elif v in zxs:
-                    x = zxs[v]
-                else:   # no message MLP to project behind: Zx = y Kx by a launch of its own
-                    x = torch.empty((_pad16(msg_out[(v, 0)].shape[0]), 4 * d), **f32)
-                    mid.append((cell.premultiply, (msg_out[(v, 0)], x, zx_scale)))
-                lstm_tasks.setdefault(d, []).append(self._cell_forward_task(v, x, st, out, folded, pushed, mats, arith))
-                keep.append(x)
-            keep.append(msg_out)
-
-            mlp_calls = _lib.launches(mlp_tasks)
-            lstm_calls = _lib.launches(lstm_tasks)
-
-            mlp_fn = "tspgnn_mlp_fwd_multi_" + (arith or "f32")
-            lstm_fn = "tspgnn_lnlstm_fwd_multi_" + (arith or "f32")
-
-            def run(mlp_calls=mlp_calls, mid=mid, lstm_calls=lstm_calls, mlp_fn=mlp_fn, lstm_fn=lstm_fn):
-                for arr, d in mlp_calls:
-                    _lib.call_multi(mlp_fn, arr, d)
-                for fn, args in mid:
-                    fn(*args)
-                for arr, d in lstm_calls:
-                    _lib.call_multi(lstm_fn, arr, d)
-            runs.append(run)
-        self._plan_keep = keep   # buffers referenced by raw pointers inside the task structures
-        return runs[0], runs[1], (buf[0], buf[1])
+        pushed = {v: self._pushable(v, mats, folded) for v in self.var}
+        ends = [_Ends(buf[p], buf[1 - p]) for p in (0, 1)]
+        steps = [list(self._split_step(ep, mats, {}, folded, pushed, arith)) for ep in ends]
+        self._plan_keep = [ends, steps]   # buffers referenced by raw pointers inside the task structures
+        return (lambda: _run(steps[0])), (lambda: _run(steps[1])), (buf[0], buf[1])
 
     def _step(self, states, mats, dense_mats, folded):
-        """One synchronous step (graphnn.py:142-173) in three phases, so that independent work of the
-        same kind shares a launch: (A) every message MLP, (B) the adjacency products / vertex-side
-        pre-multiplications, (C) every cell."""
-        f32 = dict(dtype=torch.float32, device=self.store.theta.device)
-        # ---- A: message MLPs of all loop entries
-        msg_out, tasks, keep = {}, {}, []
-        for v in self.var:
-            for i, u in enumerate(self.loop[v]):
-                if "var" not in u:          # an appended matrix: joins the cell input in B
-                    msg_out[(v, i)] = dense_mats[u["mat"]]
-                    continue
-                y = states[u["var"]].h
-                if "fun" in u:
-                    y = u["fun"](y)
-                if "msg" in u:
-                    mlp = self._msg_MLPs[u["msg"]]
-                    out = torch.empty((y.shape[0], mlp.sizes[-1]), **f32)
-                    yc = y if (y.dtype == torch.float32 and y.is_contiguous()) else y.to(torch.float32).contiguous()
-                    t = mlp.task(yc, out)
-                    if t is None:
-                        out = mlp(y)
-                    else:
-                        tasks.setdefault(mlp.sizes[-1], []).append(t)
-                        keep.append(yc)
-                    y = out
-                msg_out[(v, i)] = y
-        _lib.call_by_width("tspgnn_mlp_fwd_multi_f32", tasks)
-        # ---- B: adjacency products (or, for a folded cell, Zx = y Kx on the source rows)
-        cell_in = {}
-        for v in self.var:
-            if folded[v] is not None:
-                cell_in[v] = self._RNN_cells[v].premultiply(msg_out[(v, 0)])
-                continue
-            x, ops = self._cell_input(v, msg_out, mats, states[v].h.shape[0], torch.float32)
-            for fn, args in ops:
-                fn(*args)
-            cell_in[v] = x if x.is_contiguous() else x.contiguous()
-        # ---- C: all cells
-        new_states, tasks = {}, {}
-        unpushed = {v: False for v in self.var}
-        for v, d in self.var.items():
-            st = states[v]
-            out = (torch.empty_like(st.h), torch.empty_like(st.c))
-            new_states[v] = LSTMStateTuple(c=out[1], h=out[0])
-            tasks.setdefault(d, []).append(self._cell_forward_task(v, cell_in[v], st, out, folded, unpushed, mats))
-        _lib.call_by_width("tspgnn_lnlstm_fwd_multi_f32", tasks)
+        """One synchronous step (graphnn.py:142-173) of the general path, built and run on the spot in the fp32 kernels: no
+        cell is pushed, and a folded cell's Zx = y Kx is a launch of its own even behind a message MLP."""
+        new_states = {v: LSTMStateTuple(c=torch.empty_like(st.c), h=torch.empty_like(st.h)) for v, st in states.items()}
+        _run(self._split_step(_Ends(states, new_states), mats, dense_mats, folded, {v: False for v in self.var}, project=False))
         return new_states
 
     # ---------------------------------------------------------------- training: forward with a tape
@@ -1583,7 +1636,10 @@ class GraphNN(object):
             tape.arith = "bf16"
             tape.pushed = {v: False for v in self.var}
             alloc_acts()
-            self._forward_train_bf16(tape, n, T)
+            self._check_bf16_wiring(tape.folded)
+            ends = self._tape_ends(tape)
+            for t in range(T):   # (three launches per step as in _run_bf16, every output written into the tape)
+                _run(self._bf16_step(ends(t), mats, tape.folded))
             return {v: LSTMStateTuple(c=tape.C[v][T], h=tape.H[v][T]) for v in self.var}, tape
         # forward GEMMs in the split-operand arithmetic selected by self.gemm (fp32-class accuracy).  With f16x2 the
         # cells' backward recomputes z in the same arithmetic (tspgnn_lnlstm_bwd_multi_h2; the tape's projected
@@ -1598,8 +1654,6 @@ class GraphNN(object):
             if not self.check_h2_weights():
                 arith = self._split_arith({v: initial_embeddings[v].shape[0] for v in self.var})
         tape.arith = arith
-        mlp_fn = "tspgnn_mlp_fwd_multi_" + (arith or "f32")
-        lstm_fn = "tspgnn_lnlstm_fwd_multi_" + (arith or "f32")
         # pushed cells (f16x2): the tape's X[v] holds the row-sum of the message MLP's LAST HIDDEN activation and the cell
         # runs with K' = [W Kx ; Kh], z starting at degree * (b Kx) (LayerNormBasicLSTMCell.pushed_kernel)
         tape.pushed = {v: arith == "h2" and pushable[v] for v in self.var}
@@ -1610,169 +1664,25 @@ class GraphNN(object):
                 tape.rc[(v, 0)] = mlp.recompute_ok(mlp.n_square - 1)
         alloc_acts()
 
-        def message_dest(v, i, t):
-            """(out, projection) of loop entry (v, i)'s message MLP at step t: outputs straight into the tape."""
-            u = self.loop[v][i]
-            mlp = self._msg_MLPs[u["msg"]]
-            slot = self._message_output_slot(v, i, tape.folded)
-            if self._message_to_tape(v, i, tape.folded):
-                out = tape.X[v][t]
-            else:
-                out = torch.empty((n[u["var"]], mlp.sizes[-1]), **f32) if slot is None else tape.acts[(v, i)][slot, t]
-            proj = None
-            if tape.folded[v] is not None:
-                cv = self._RNN_cells[v]
-                proj = (cv.packed("Kx", arith or "f32"), tape.ZX[v][t])
-            return out, proj
-
-        def messages(t):
-            """A: every message MLP of step t in one launch (per width); -> {(v, i): message rows}."""
-            msg_out, mlp_tasks = {}, {}
-            for v in self.var:
-                for i, u in enumerate(self.loop[v]):
-                    if "var" not in u:          # an appended matrix: joins the cell input in aggregate()
-                        msg_out[(v, i)] = tape.dense[u["mat"]]
-                        continue
-                    y = tape.H[u["var"]][t]
-                    if "fun" in u:              # graphnn.py:149-151 (the backward differentiates it again: _fun_vjp)
-                        y = u["fun"](y)
-                        if not torch.is_tensor(y) or y.shape != tape.H[u["var"]][t].shape:
-                            raise ValueError("loop entry 'fun' must map [rows, d] to a tensor of the same shape")
-                        y = y.to(torch.float32).contiguous()
-                    if "msg" in u:
-                        mlp = self._msg_MLPs[u["msg"]]
-                        acts = tape.acts[(v, i)]
-                        if tape.pushed[v]:      # all but the last layer; its output is the last saved activation
-                            k = mlp.n_square - 1
-                            if tape.rc.get((v, i)):
-                                out = acts[0, t]
-                                task = mlp.prefix_task(y, out, k, arith=arith)
-                            else:
-                                out = acts[k - 1, t]
-                                task = mlp.prefix_task(y, out, k, arith=arith, acts=acts[:, t], acts_stride=acts.stride(0))
-                            mlp_tasks.setdefault(mlp.sizes[-1], []).append(task)
-                            msg_out[(v, i)] = out
-                            continue
-                        out, proj = message_dest(v, i, t)
-                        task = mlp.task(y, out, acts[:, t], acts.stride(0), proj=proj, arith=arith)
-                        if task is None:
-                            if arith:
-                                raise NotImplementedError("bf16x3 training forward needs single-kernel message MLPs")
-                            mlp.forward_saving(y, out, acts[:, t], acts.stride(0))
-                            if proj is not None:
-                                self._RNN_cells[v].premultiply(out, out=tape.ZX[v][t])
-                        else:
-                            mlp_tasks.setdefault(mlp.sizes[-1], []).append(task)
-                        y = out
-                    msg_out[(v, i)] = y
-            _lib.call_by_width(mlp_fn, mlp_tasks)
-            return msg_out
-
-        def aggregate(t, msg_out):
-            """B: adjacency products / vertex-side pre-multiplication of step t."""
-            for v in self.var:
-                if tape.folded[v] is not None:
-                    u = tape.folded[v]
-                    if "msg" not in u:   # with a message MLP, Zx was produced by the MLP launch itself
-                        tape.X[v][t].copy_(msg_out[(v, 0)])
-                        self._RNN_cells[v].premultiply(tape.X[v][t], out=tape.ZX[v][t],
-                                                       scale=_lib.lib.tspgnn_h2_weight_scale() if arith == "h2" else None)
-                    continue
-                for fn, args in self._cell_input(v, msg_out, mats, n[v], torch.float32, out=tape.X[v][t])[1]:
-                    fn(*args)
-
-        def cell_task(v, t):
-            x = (tape.X if tape.folded[v] is None else tape.ZX)[v][t]
-            return self._cell_forward_task(v, x, LSTMStateTuple(c=tape.C[v][t], h=tape.H[v][t]),
-                                           (tape.H[v][t + 1], tape.C[v][t + 1]), tape.folded, tape.pushed, mats, arith)
-
         # f16x2, opt-in (fuse_training_messages): the message MLPs of step t+1 ride in the cell launch of step t, on the
         # rows of h' it still holds in registers (tspgnn_lnlstm_mlp_fwd_multi_h2 as in the inference plan, here writing
         # the tape: states, hidden activations, messages and projected messages of every step)
         consumers = self._single_consumers(own_width=True) \
             if arith == "h2" and (self.fuse_training_messages or any(tape.rc.values())) else None
         tape.fused = consumers is not None
+        ends = self._tape_ends(tape)
         if consumers is not None:
-            msg_out = messages(0) if T > 0 else {}
+            nxt = ends(0) if T > 0 else None
+            if T > 0:   # the messages of step 0 from one plain launch
+                _run([self._split_messages(nxt, dense, tape.folded, tape.pushed, arith, rc=tape.rc)])
             for t in range(T):
-                aggregate(t, msg_out)
-                tasks, nxt = {}, {}
-                for v, d in self.var.items():
-                    task = cell_task(v, t)
-                    if t < T - 1:
-                        cv, ci = consumers[v]
-                        mlp = self._msg_MLPs[self.loop[cv][ci]["msg"]]
-                        acts = tape.acts[(cv, ci)]
-                        if tape.pushed[cv]:     # all but the last layer; the message is the last hidden activation
-                            k = mlp.n_square - 1
-                            rc = tape.rc.get((cv, ci))
-                            out, (pw, po) = acts[0 if rc else k - 1, t + 1], (None, None)
-                            saved = None if (rc or k == 1) else acts[:, t + 1]
-                        else:
-                            out, proj = message_dest(cv, ci, t + 1)
-                            pw, po = proj if proj is not None else (None, None)
-                            k = mlp.n_square
-                            saved = acts[:, t + 1] if k > 1 else None
-                        ct = _lib.CellMlpTask(task, mlp_wb=_lib.ptr(mlp.wb_packed(0, k - 1, d, arith)), mlp_layers=k,
-                                              relu_mask=mlp.relu_mask(0, k), mlp_out=_lib.ptr(out), proj_w=_lib.ptr(pw),
-                                              proj_out=_lib.ptr(po), mlp_acts=_lib.ptr(saved), mlp_acts_stride=acts.stride(0))
-                        nxt[(cv, ci)] = out
-                    else:
-                        ct = _lib.CellMlpTask(task)
-                    tasks.setdefault(d, []).append(ct)
-                _lib.call_by_width("tspgnn_lnlstm_mlp_fwd_multi_h2", tasks)
-                msg_out = nxt
+                ep, nxt = nxt, ends(t + 1) if t < T - 1 else None
+                _run(self._fused_step(ep, nxt, mats, tape.folded, tape.pushed, consumers, arith, rc=tape.rc))
         else:
             for t in range(T):
-                aggregate(t, messages(t))
-                # ---- C: every cell of the step in one launch (per width)
-                lstm_tasks = {}
-                for v, d in self.var.items():
-                    lstm_tasks.setdefault(d, []).append(cell_task(v, t))
-                _lib.call_by_width(lstm_fn, lstm_tasks)
+                _run(self._split_step(ends(t), mats, dense, tape.folded, tape.pushed, arith, rc=tape.rc))
         states = {v: LSTMStateTuple(c=tape.C[v][T], h=tape.H[v][T]) for v in self.var}
         return states, tape
-
-    def _forward_train_bf16(self, tape, n, T):
-        """The T steps of the bf16-storage forward (three launches per step as in _run_bf16: message MLPs -- the vertex
-        task with its Kx projection --, adjacency products, cells), every output written into the tape."""
-        mats = tape.mats
-        bf = dict(dtype=torch.bfloat16, device=self.store.theta.device)
-        self._check_bf16_wiring(tape.folded)
-        for t in range(T):
-            msg_out, plain, with_proj = {}, {}, {}
-            for v in self.var:
-                for i, u in enumerate(self.loop[v]):
-                    y = tape.H[u["var"]][t]
-                    if "msg" in u:
-                        mlp = self._msg_MLPs[u["msg"]]
-                        d = mlp.sizes[-1]
-                        slot = self._message_output_slot(v, i, tape.folded)
-                        if self._message_to_tape(v, i, tape.folded):
-                            out = tape.X[v][t]
-                        else:
-                            out = torch.empty((y.shape[0], d), **bf) if slot is None else tape.acts[(v, i)][slot, t]
-                        proj = (None, None)
-                        if tape.folded[v] is not None:
-                            proj = (self._RNN_cells[v].packed("Kx", "bf16"), tape.ZX[v][t])
-                        task = self._bf16_message_task(mlp, y, y.shape[0], out, proj, acts=tape.acts[(v, i)][:, t])
-                        (plain if proj[0] is None else with_proj).setdefault(d, []).append(task)
-                        y = out
-                    msg_out[(v, i)] = y
-            for group in (plain, with_proj):   # (projections in their own launch: see _run_bf16)
-                _lib.call_by_width("tspgnn_mlp_fwd_multi_bf16", group)
-            cells = {}
-            for v, d in self.var.items():
-                cell = self._RNN_cells[v]
-                if tape.folded[v] is not None:
-                    x, adj = tape.ZX[v][t], mats[tape.folded[v]["mat"]]
-                else:
-                    x, adj = tape.X[v][t], None
-                    for fn, args in self._cell_input(v, msg_out, mats, n[v], torch.bfloat16, out=x)[1]:
-                        fn(*args)
-                cells.setdefault(d, []).append(cell.task_bf16(x, tape.H[v][t], tape.C[v][t], tape.H[v][t + 1],
-                                                              tape.C[v][t + 1], n[v], adj=adj))
-            _lib.call_by_width("tspgnn_lnlstm_fwd_multi_bf16", cells)
 
     def backward(self, tape, dstates):
         """Back-propagation through time of forward_train.  dstates: {var: (dh, dc)} gradients w.r.t. the
