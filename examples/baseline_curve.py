@@ -10,7 +10,8 @@ feasible and costs at most C.
 Instances come from a directory of .graph files or are synthetic Euclidean graphs (n in [20, 40]) labelled with
 label_tours.  One line per deviation, tab-separated: dev, then tpr / fpr / acc of nearest neighbour, then of annealing;
 with -checkpoint a last column has the network's accuracy at that deviation (experiments.get_accuracy, as the
-reference's test_varying_dev.py measures it).
+reference's test_varying_dev.py measures it), and with -decoded one more: the accuracy of the tour decoded from the
+network's edge votes at its own cost estimate, scored like the two heuristics (experiments.decoded_tour_curve).
 """
 import argparse
 import os
@@ -55,12 +56,23 @@ def network_accuracy(a, instances, devs):
     return out
 
 
+def decoded_curve(a, instances, devs):
+    """The tour decoded from the network's edge votes as a decision-TSP predictor (experiments.decoded_tour_curve)."""
+    model = build_network(a.d)
+    sess = Session(model)
+    sess.run(global_variables_initializer(seed=a.seed))
+    load_weights(sess, a.checkpoint)
+    return experiments.decoded_tour_curve(sess, model, instances, a.timesteps, devs)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("-devs", default="0.001,0.002,0.005,0.01,0.02,0.05,0.1,0.2", help="comma-separated deviations")
     p.add_argument("-d", default=64, type=int)
     p.add_argument("-timesteps", default=32, type=int)
     p.add_argument("-checkpoint", default=None, help="TensorFlow-format checkpoint directory .../epoch=N")
+    p.add_argument("-decoded", action="store_true",
+                   help="with -checkpoint: one more column, the accuracy of the tour decoded from the network's edge votes")
     p.add_argument("--batch-size", default=16, type=int)
     p.add_argument("--instances", default=None, help="directory of .graph files")
     p.add_argument("--limit", default=0, type=int, help="first N files of --instances (0: all)")
@@ -69,6 +81,8 @@ def main(argv=None):
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--out", default="baseline-curve.dat")
     a = p.parse_args(argv)
+    if a.decoded and not a.checkpoint:
+        p.error("-decoded needs -checkpoint")
 
     devs = [float(x) for x in a.devs.split(",")]
     instances = load_instances(a)
@@ -76,15 +90,17 @@ def main(argv=None):
     nn = experiments.baseline_curve(instances, devs, method="nn", start=start)
     sa = experiments.baseline_curve(instances, devs, method="sa", seed=a.seed)
     net = network_accuracy(a, instances, devs) if a.checkpoint else None
+    decoded = decoded_curve(a, instances, devs) if a.decoded else None
     if os.path.dirname(a.out):
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as out:
         for k, dev in enumerate(devs):
-            cols = [dev] + [c[key][k] for c in (nn, sa) for key in ("tpr", "fpr", "acc")] + ([net[k]] if net else [])
+            cols = [dev] + [c[key][k] for c in (nn, sa) for key in ("tpr", "fpr", "acc")] + ([net[k]] if net else []) \
+                + ([decoded["acc"][k]] if decoded else [])
             out.write("\t".join(str(x) for x in cols) + "\n")
     print("%d instances, %d deviations; accuracy at dev %g: nearest neighbour %.4f, annealing %.4f; wrote %s"
           % (len(instances), len(devs), devs[len(devs) // 2], nn["acc"][len(devs) // 2], sa["acc"][len(devs) // 2], a.out))
-    return nn, sa, net
+    return (nn, sa, net, decoded) if a.decoded else (nn, sa, net)
 
 
 if __name__ == "__main__":

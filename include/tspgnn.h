@@ -652,6 +652,37 @@ int tspgnn_tour_anneal_tri(const float* W, const long long* w_off, const int* n,
                            int n_inst, int n_max, int chains, int levels, unsigned long long seed, int32_t* tours,
                            float* costs, void* stream);
 
+/* ------------------------------------------------------------------ tours from the edge votes (tspgnn/decode.py) */
+
+/*
+ * A tour per instance from the network's per-edge logits (E_vote, model.py:106-128), one workgroup per instance, reading
+ * the batch as Session.prepare / DeviceDataset.batch leave it on the device: vote:[M] fp32; uv:[M][2] the global endpoint
+ * ids; wc:[M][2], column 0 the edge weight; seg:[B+1] the edge prefix sums; vseg:[B+1] the vertex prefix sums.  Instance b
+ * has n = vseg[b+1] - vseg[b] vertices and the edges e = 0 .. m-1 of seg[b] .. seg[b+1], endpoints in local ids
+ * uv - vseg[b].  4 <= n <= n_max <= 256.  The result is exactly this sequential process:
+ *   Key.     k(e) = 0 for a NaN vote; otherwise the order-preserving uint32 image of the fp32 vote: all bits flipped when
+ *            the sign bit is set, else the sign bit set (-0.0 < +0.0, -inf the lowest number, NaN below everything).
+ *            Edge e precedes edge f iff k(e) > k(f), or k(e) == k(f) and e < f.
+ *   Greedy.  Every vertex starts with degree 0 in a component of its own.  Until no edge is eligible: take the first
+ *            eligible edge in the order above, add it, raise both degrees, merge the components.  Eligible: both
+ *            endpoints have degree < 2 and lie in different components (never an edge with an endpoint outside [0, n) or
+ *            with equal endpoints).  Eligibility only shrinks, so this equals one pass over the sorted list; the kernel
+ *            takes a workgroup-wide arg-max over (key, edge id) per round and sorts nothing.
+ *   Stitch.  The chosen edges form vertex-disjoint paths, an untouched vertex being a path of one.  Each path starts at
+ *            its endpoint of smaller id; the paths are ordered by their smallest vertex id and concatenated.
+ *   Output.  tours + vseg[b]: the cyclic sequence in canonical form (tour[0] = 0, tour[1] < tour[n-1]), local ids.
+ *            n_missing[b]: the cyclically consecutive pairs that no edge of the instance joins (0: a feasible tour).
+ *            costs[b]: the fp32 sum, from 0, in tour order with the closing pair last, of the weights of the pairs that
+ *            are edges (of several edges joining one pair, the one of smallest id); additions only, no FMA.
+ * The result depends on the instance and its votes alone, never on n_max, on the other instances or on the launch.  An
+ * instance with m == 0 gets the identity tour, n_missing = n and cost 0.  The arrays live on the device, so this entry
+ * point cannot see them: an instance with n outside [4, 256] gets costs[b] = NaN, n_missing[b] = -1 and no tour.
+ * B == 0 is a no-op; n_max > 256: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4 or a null pointer with B > 0: TSPGNN_EINVAL before
+ * any launch, the outputs untouched.
+ */
+int tspgnn_tour_from_votes(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
+                           int B, int n_max, int32_t* tours, float* costs, int32_t* n_missing, void* stream);
+
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 
 /*

@@ -1,0 +1,91 @@
+"""Times the vote decoder (tspgnn_tour_from_votes) beside the forward pass that produces its votes, in one process, at
+C2 (128 x n=40), the C4 ragged batch (512 graphs, n 20-80) and one n=200 batch (32 graphs), all at d = 64, T = 32.
+
+Per shape, after a warm-up of both: the forward as a replayed captured graph and as eager launches, and the decode launch
+alone, each as the median and the minimum over --reps windows of --inner back-to-back calls between two device events
+(tools/baseline_bench.py's rule -- a timing ends in a device synchronise -- with events, because a decode launch is far
+shorter than a host clock resolves).  One JSON line per shape, also appended to --out.
+
+    python tools/decode_bench.py [--shapes c2,c4,n200] [--reps 20] [--inner 10] [--out profiles/decode_bench.txt]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tsp-gnn_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import tspgnn  # noqa: E402
+from oracle import params as P  # noqa: E402
+
+SHAPES = {"c2": [40] * 128, "c4": list(np.random.RandomState(0).randint(20, 81, size=512)), "n200": [200] * 32}
+
+
+def windows(fn, reps, inner):
+    """Milliseconds per call of fn over `reps` windows of `inner` calls: (median, min)."""
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(inner):
+            fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) / inner)
+    return float(np.median(out)), float(np.min(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="c2,c4,n200")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--timesteps", type=int, default=32)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.txt"))
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "decode_bench needs an MI355X"
+    d = 64
+    model = tspgnn.build_network(d)
+    sess = tspgnn.Session(model)
+    sess.run(tspgnn.global_variables_initializer())
+    model.store.load(P.init_params(d, seed=1, perturb=True))
+    lines = []
+    for name in a.shapes.split(","):
+        sizes = SHAPES[name]
+        EV, W, C, route_exists, n_vertices, n_edges = tspgnn.synthetic_batch(sizes, seed=1234)
+        feed = {model["EV"]: EV, model["W"]: W, model["C"]: C, model["time_steps"]: a.timesteps,
+                model["route_exists"]: route_exists, model["n_vertices"]: n_vertices, model["n_edges"]: n_edges}
+        b = sess.prepare(feed)
+        replay = sess.capture_forward(b)            # (warms the forward up, f16x2 range guard included)
+        votes = replay()["E_vote"]
+        for _ in range(3):
+            dec = tspgnn.tours_from_votes(b, votes)
+        torch.cuda.synchronize()
+        assert int((dec.n_missing != 0).sum()) == 0    # complete graphs: every decoded tour is feasible
+        graph = windows(replay, a.reps, a.inner)
+        eager = windows(lambda: sess.forward_device(b), a.reps, max(1, a.inner // 5))
+        decode = windows(lambda: tspgnn.tours_from_votes(b, votes), a.reps, a.inner)
+        rounds = int(max(sizes)) - 1                 # greedy rounds of the largest instance: the launch's critical path
+        row = {"shape": name, "graphs": len(sizes), "n": [int(min(sizes)), int(max(sizes))], "M": int(b.M), "d": d,
+               "T": a.timesteps, "arith": model["gnn"].active_arith(),
+               "forward_graph_ms": round(graph[0], 4), "forward_graph_min_ms": round(graph[1], 4),
+               "forward_eager_ms": round(eager[0], 4), "decode_ms": round(decode[0], 4),
+               "decode_min_ms": round(decode[1], 4), "decode_us_per_round": round(1e3 * decode[0] / rounds, 3),
+               "decode_over_forward": round(decode[0] / graph[0], 4)}
+        print(json.dumps(row), flush=True)
+        lines.append(json.dumps(row))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as out:
+        out.write("# tools/decode_bench.py --shapes %s --reps %d --inner %d: ms per call, median and min over the windows\n"
+                  % (a.shapes, a.reps, a.inner))
+        out.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

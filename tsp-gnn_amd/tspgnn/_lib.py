@@ -107,6 +107,8 @@ SIGNATURES = {
                            c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_anneal_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_from_votes": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p],
     "tspgnn_metric_closure": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "tspgnn_gather_batch": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p],

@@ -4,7 +4,8 @@
 reference's feed / fetch; the sweeps call them exactly like the scripts' loops (acceptance_curve.py:87-99,
 test_varying_sizes.py:82-114).  ``baseline_curve`` is the measurement behind figures/test_varying_dev_baseline.png, for
 which the reference has no script: the decision-TSP predictor built on a nearest-neighbour or annealing tour
-(tspgnn/baselines.py)."""
+(tspgnn/baselines.py); ``decoded_tour_curve`` is the same measurement on the tour decoded from the network's own edge
+votes (tspgnn/decode.py)."""
 from itertools import islice
 
 import numpy as np
@@ -82,5 +83,31 @@ def baseline_curve(instances_or_loader, deviations, method="nn", **solver_kw):
     res = solve([(Ma, Mw) for Ma, Mw, _ in instances], **solver_kw)
     Q = np.array([dataset._target(Ma, Mw, [int(v) for v in route]) for Ma, Mw, route in instances])
     out = curve_from_costs([r.cost for r in res], [r.feasible for r in res], Q, deviations)
+    out["deviations"] = np.asarray(deviations, dtype=np.float64)
+    return out
+
+
+def decoded_tour_curve(sess, model, instances_or_loader, time_steps, deviations, polish=False, **decode_kw):
+    """baseline_curve with the network as the constructive heuristic: the tour decoded from its edge votes at its own cost
+    estimate (decode.decode_tours with target_costs=None, so no label enters), or with polish=True that tour after one
+    descent of the tour search, thresholded against C = (1 +/- dev) Q like a nearest-neighbour or annealing tour.  The
+    decoded cost counts only when the tour is feasible (n_missing == 0).  decode_kw go to decode_tours.  Returns
+    {'tpr', 'fpr', 'acc', 'deviations'} as baseline_curve does."""
+    from . import dataset, decode
+    from .instance_loader import read_graph
+    if hasattr(instances_or_loader, "filenames"):
+        instances = [read_graph(f) for f in instances_or_loader.filenames]
+    else:
+        instances = list(instances_or_loader)
+    res = decode.decode_tours(sess, model, instances, time_steps, polish=polish, **decode_kw)
+    Q = np.array([dataset._target(Ma, Mw, [int(v) for v in route]) for Ma, Mw, route in instances])
+    if polish:
+        edge = [dataset._edge_mask(Ma) for Ma, _, _ in instances]
+        cost = [r.polished_cost for r in res]
+        feasible = [all(A[a, b] for a, b in zip(r.polished_tour, r.polished_tour[1:] + r.polished_tour[:1]))
+                    for A, r in zip(edge, res)]
+    else:
+        cost, feasible = [r.cost for r in res], [r.feasible for r in res]
+    out = curve_from_costs(cost, feasible, Q, deviations)
     out["deviations"] = np.asarray(deviations, dtype=np.float64)
     return out

@@ -282,6 +282,7 @@ class Session(object):
         b.WC = self._f32(np.stack([W, C], axis=1), pinned)
         b.labels = labels
         b.seg = torch.from_numpy(np.concatenate([[0], np.cumsum(n_edges)]).astype(np.int32)).to(self.device)
+        b.n_vertices, b.n_edges = n_vertices, n_edges   # host int64, as DeviceDataset.batch leaves them
         return b
 
     def forward(self, feed, global_stats=False):
