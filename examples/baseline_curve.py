@@ -11,7 +11,8 @@ Instances come from a directory of .graph files or are synthetic Euclidean graph
 label_tours.  One line per deviation, tab-separated: dev, then tpr / fpr / acc of nearest neighbour, then of annealing;
 with -checkpoint a last column has the network's accuracy at that deviation (experiments.get_accuracy, as the
 reference's test_varying_dev.py measures it), and with -decoded one more: the accuracy of the tour decoded from the
-network's edge votes at its own cost estimate, scored like the two heuristics (experiments.decoded_tour_curve).
+network's edge votes at its own cost estimate, scored like the two heuristics (experiments.decoded_tour_curve); -beam K
+decodes that tour by beam search of width K instead of greedy edge insertion.
 """
 import argparse
 import os
@@ -62,7 +63,8 @@ def decoded_curve(a, instances, devs):
     sess = Session(model)
     sess.run(global_variables_initializer(seed=a.seed))
     load_weights(sess, a.checkpoint)
-    return experiments.decoded_tour_curve(sess, model, instances, a.timesteps, devs)
+    beam_kw = {} if a.beam is None else {"beam": a.beam}
+    return experiments.decoded_tour_curve(sess, model, instances, a.timesteps, devs, **beam_kw)
 
 
 def main(argv=None):
@@ -73,6 +75,8 @@ def main(argv=None):
     p.add_argument("-checkpoint", default=None, help="TensorFlow-format checkpoint directory .../epoch=N")
     p.add_argument("-decoded", action="store_true",
                    help="with -checkpoint: one more column, the accuracy of the tour decoded from the network's edge votes")
+    p.add_argument("-beam", default=None, type=int,
+                   help="with -decoded: decode by beam search of this width, 1 .. 1024 (default: greedy edge insertion)")
     p.add_argument("--batch-size", default=16, type=int)
     p.add_argument("--instances", default=None, help="directory of .graph files")
     p.add_argument("--limit", default=0, type=int, help="first N files of --instances (0: all)")
@@ -83,6 +87,8 @@ def main(argv=None):
     a = p.parse_args(argv)
     if a.decoded and not a.checkpoint:
         p.error("-decoded needs -checkpoint")
+    if a.beam is not None and not a.decoded:
+        p.error("-beam needs -decoded")
 
     devs = [float(x) for x in a.devs.split(",")]
     instances = load_instances(a)

@@ -13,6 +13,12 @@ mean nothing.  One line per instance, tab-separated: n, the cost of the route th
 none), the network's cost estimate, the decoded tour's cost, its pairs that are not edges (n_missing), and the polished
 cost (nan without --polish); all costs unnormalised.  --write-graphs DIR writes every instance back as DIR/k.graph with
 the decoded (or polished) tour in its TOUR_SECTION.  How good a decoded tour is, is an observation, not a guarantee.
+
+-beam K decodes by beam search of width K (1 .. 1024) instead of greedy edge insertion, -select cost keeps the cheapest
+closed tour of the last beam instead of the best-scoring one; two more columns then follow: the tour's integer score and
+the number of closed entries of the last beam.
+
+    python examples/decode_tours.py --synthetic 32 -beam 128 -select cost --polish
 """
 import argparse
 import os
@@ -48,6 +54,8 @@ def main(argv=None):
     p.add_argument("--limit", default=0, type=int, help="first N files of --instances (0: all)")
     p.add_argument("--synthetic", default=64, type=int, help="number of synthetic instances without --instances")
     p.add_argument("--checkpoint", default=None, help="TensorFlow-format checkpoint directory .../epoch=N")
+    p.add_argument("-beam", default=None, type=int, help="beam width, 1 .. 1024 (default: the greedy decoder)")
+    p.add_argument("-select", default="score", choices=["score", "cost"], help="with -beam: what the last beam is chosen by")
     p.add_argument("--polish", action="store_true", help="one descent of the tour search from every decoded tour")
     p.add_argument("--max-rounds", default=1100, type=int, help="bisection rounds of the cost estimate (see binary_search.py)")
     p.add_argument("--write-graphs", default=None, help="directory for the instances with their decoded tours")
@@ -63,15 +71,17 @@ def main(argv=None):
         load_weights(sess, a.checkpoint)
     # decode_tours(target_costs=None) runs this same search with its default round limit; untrained weights need more
     estimates = [r[0] for r in get_costs(sess, model, instances, a.timesteps, max_rounds=a.max_rounds)]
-    res = decode_tours(sess, model, instances, a.timesteps, target_costs=estimates, polish=a.polish)
+    beam_kw = {} if a.beam is None else {"beam": a.beam, "select": a.select}
+    res = decode_tours(sess, model, instances, a.timesteps, target_costs=estimates, polish=a.polish, **beam_kw)
     if os.path.dirname(a.out):
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as out:
         for (Ma, Mw, route), r in zip(instances, res):
             n = Ma.shape[0]
             polished = float("nan") if r.polished_cost is None else r.polished_cost
-            out.write("{}\t{}\t{}\t{}\t{}\t{}\n".format(n, cycle_cost(Mw, [int(v) for v in route]), n * r.target_cost,
-                                                          r.cost, r.n_missing, polished))
+            more = "" if a.beam is None else "\t{}\t{}".format(r.score, r.n_closed)
+            out.write("{}\t{}\t{}\t{}\t{}\t{}{}\n".format(n, cycle_cost(Mw, [int(v) for v in route]), n * r.target_cost,
+                                                            r.cost, r.n_missing, polished, more))
     if a.write_graphs:
         os.makedirs(a.write_graphs, exist_ok=True)
         for k, ((Ma, Mw, _), r) in enumerate(zip(instances, res)):
@@ -79,6 +89,14 @@ def main(argv=None):
                         route=r.polished_tour if a.polish else r.tour)
     feasible = sum(r.feasible for r in res)
     print("%d instances, %d decoded tours feasible; wrote %s" % (len(res), feasible, a.out))
+    carried = np.array([cycle_cost(Mw, [int(v) for v in route]) for _, Mw, route in instances])
+    if np.isfinite(carried).any():      # the observation of DESIGN section 12: cost over the cost of the carried route
+        ratio = np.array([r.cost for r in res]) / carried
+        line = "decoded / carried route: mean %.3f, min %.3f, max %.3f" % (np.nanmean(ratio), np.nanmin(ratio),
+                                                                          np.nanmax(ratio))
+        if a.polish:
+            line += "; polished: mean %.3f" % np.nanmean(np.array([r.polished_cost for r in res]) / carried)
+        print(line)
     return res
 
 

@@ -683,6 +683,59 @@ int tspgnn_tour_anneal_tri(const float* W, const long long* w_off, const int* n,
 int tspgnn_tour_from_votes(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
                            int B, int n_max, int32_t* tours, float* costs, int32_t* n_missing, void* stream);
 
+/*
+ * Integer edge scores for tspgnn_tour_beam: score[e] = q(vote[e]) for the M votes of a batch, one launch, both arrays on
+ * the device.  q(v) = clamp(rint(65536 * logsigmoid(v)), -2^22, 0) as int32, with logsigmoid(v) = min(v, 0) -
+ * log1p(exp(-|v|)) evaluated in fp64 and rint rounding half to even; a NaN vote gives -2^22.  So +inf gives 0 and -inf
+ * gives -2^22, and q never decreases as the vote rises.  The fixed point is chosen so that the sum over a tour of at most
+ * 256 edges lies in [-2^30, 0]: every score sum of the beam search is exact int32 arithmetic.
+ * M == 0 is a no-op; M < 0 or a null pointer with M > 0: TSPGNN_EINVAL before any launch.
+ */
+int tspgnn_vote_scores_i32(const float* vote, long long M, int32_t* score, void* stream);
+
+/* Bytes of workspace tspgnn_tour_beam needs for B instances at n_max and beam: per instance two n_max x n_max int32
+ * tables, n_max x beam words of parent trace and n_max x beam bytes of paths; 0 for an empty or unsupported request. */
+long long tspgnn_tour_beam_workspace_bytes(int B, int n_max, int beam);
+
+/*
+ * A tour per instance by beam search over integer edge scores, one workgroup per instance.  The batch is read exactly as
+ * tspgnn_tour_from_votes reads it (uv, wc, seg, vseg; local ids uv - vseg[b]; 4 <= n <= n_max <= 256), with score:[M] int32
+ * in place of the votes (tspgnn_vote_scores_i32, or any integers: they are clamped to [-2^22, 0] on input).  beam: the
+ * width, 1 .. 1024; select: 0 = by score, 1 = by cost.  The result is exactly this sequential process on instance b:
+ *   Pairs.    For an unordered pair {a, b}, a != b, both in [0, n): e(a,b) is the smallest edge id joining the pair, or
+ *             none (an edge with an endpoint outside [0, n), or with equal endpoints, joins nothing);
+ *             q(a,b) = clamp(score[e(a,b)], -2^22, 0); w(a,b) = wc[e(a,b)][0].
+ *   Lists.    L_0 = [(path [0], S = 0)].  For k = 0 .. n-2 the candidates of L_k are all (i, u) with i an index into L_k,
+ *             u not on path i, and e(last_i, u) existing; candidate (i, u) carries the score S_i + q(last_i, u).
+ *             Candidates are ordered by score descending, then i ascending, then u ascending (a strict total order);
+ *             L_{k+1} is the first min(beam, #candidates) candidates in that order, in that order, entry (i, u) being
+ *             path i extended by u.
+ *   Stranded. If L_{k+1} is empty (only on incomplete graphs), the tour is the path of L_k[0] followed by the unvisited
+ *             vertices in ascending id; scores[b] = S of that entry and n_closed[b] = 0.
+ *   Final.    Otherwise every entry i of L_{n-1} is a Hamiltonian path.  closed_i: e(last_i, 0) exists.
+ *             F_i = S_i + q(last_i, 0) if closed, else S_i.  C_i = the fp32 cost of the entry's tour in canonical form,
+ *             summed as costs[b] below.  select = 0: the chosen entry is the first by (closed first, F descending, i
+ *             ascending); select = 1: the first by (closed first, C ascending, i ascending), C compared as fp32 numbers
+ *             (-0.0 before +0.0, a NaN after every number).  scores[b] = F of the chosen entry; n_closed[b] = the number
+ *             of closed entries.
+ *   Output.   tours + vseg[b]: the tour in canonical form (tour[0] = 0, tour[1] < tour[n-1]), local ids.  n_missing[b]:
+ *             the cyclically consecutive pairs that no edge joins.  costs[b]: one running fp32 sum from 0 in canonical
+ *             tour order, the closing pair last, of w over the pairs that are edges; additions only, no FMA.
+ * The result depends on the instance, its scores, beam and select alone: never on n_max, on the other instances, on the
+ * workgroup shape (256 / 512 / 1024 threads for n_max <= 64 / 128 / 256) or on what the workspace held before the launch.
+ * beam = 1 is the walk from vertex 0 to the best-scoring unvisited neighbour; an instance with m == 0 gets the identity
+ * tour, n_missing = n, cost 0 and score 0.  The kernel takes an exact top-`beam` per step: a radix select on the composite
+ * key (-score, i, u) and a sort of the survivors; it runs n - 1 steps and has no communication between workgroups.
+ * workspace: 16-byte aligned device memory of at least tspgnn_tour_beam_workspace_bytes(B, n_max, beam) bytes, contents
+ * irrelevant.  The arrays live on the device, so this entry point cannot see them: an instance with n outside [4, n_max]
+ * gets costs[b] = NaN, n_missing[b] = -1, scores[b] = 0, n_closed[b] = -1 and no tour.
+ * B == 0 is a no-op; n_max > 256 or beam > 1024: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4, beam < 1, select outside {0, 1},
+ * a null pointer or a workspace that is short or misaligned: TSPGNN_EINVAL; all before any launch, the outputs untouched.
+ */
+int tspgnn_tour_beam(const int32_t* score, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
+                     int B, int n_max, int beam, int select, void* workspace, long long workspace_bytes, int32_t* tours,
+                     float* costs, int32_t* n_missing, int32_t* scores, int32_t* n_closed, void* stream);
+
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 
 /*

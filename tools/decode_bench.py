@@ -4,9 +4,13 @@ C2 (128 x n=40), the C4 ragged batch (512 graphs, n 20-80) and one n=200 batch (
 Per shape, after a warm-up of both: the forward as a replayed captured graph and as eager launches, and the decode launch
 alone, each as the median and the minimum over --reps windows of --inner back-to-back calls between two device events
 (tools/baseline_bench.py's rule -- a timing ends in a device synchronise -- with events, because a decode launch is far
-shorter than a host clock resolves).  One JSON line per shape, also appended to --out.
+shorter than a host clock resolves).  One JSON line per shape, also written to --out.
 
-    python tools/decode_bench.py [--shapes c2,c4,n200] [--reps 20] [--inner 10] [--out profiles/decode_bench.txt]
+--beam K[,K...] times the beam decoder as well (tspgnn_vote_scores_i32 once, then tspgnn_tour_beam per width and per
+select, at the default workspace cap), adds its columns to the shape's line and appends to --out instead of replacing it.
+
+    python tools/decode_bench.py [--shapes c2,c4,n200] [--reps 20] [--inner 10] [--beam 1,16,128,1024]
+                                 [--out profiles/decode_bench.txt]
 """
 import argparse
 import json
@@ -47,6 +51,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--timesteps", type=int, default=32)
+    ap.add_argument("--beam", default="", help="beam widths to time, comma-separated (none: the greedy decoder only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_bench.txt"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decode_bench needs an MI355X"
@@ -78,12 +83,30 @@ def main():
                "forward_eager_ms": round(eager[0], 4), "decode_ms": round(decode[0], 4),
                "decode_min_ms": round(decode[1], 4), "decode_us_per_round": round(1e3 * decode[0] / rounds, 3),
                "decode_over_forward": round(decode[0] / graph[0], 4)}
+        if a.beam:
+            scores = tspgnn.edge_scores(votes)
+            row["scores_ms"] = round(windows(lambda: tspgnn.edge_scores(votes), a.reps, a.inner)[0], 4)
+            row["beam"] = {}
+            for width in (int(k) for k in a.beam.split(",")):
+                launches = len(tspgnn.decode.beam_ranges(len(sizes), int(max(sizes)), width)[0])
+                inner = max(1, a.inner // (1 + width // 64))     # wide beams run for milliseconds: shorter windows
+                for select in ("score", "cost"):
+                    for _ in range(2):
+                        out = tspgnn.beam_tours(b, scores, width, select)
+                    torch.cuda.synchronize()
+                    assert int((out.n_missing != 0).sum()) == 0 and int((out.n_closed <= 0).sum()) == 0
+                    t = windows(lambda: tspgnn.beam_tours(b, scores, width, select), a.reps, inner)
+                    row["beam"]["%d/%s" % (width, select)] = {"ms": round(t[0], 4), "min_ms": round(t[1], 4),
+                                                              "launches": launches,
+                                                              "over_forward": round(t[0] / graph[0], 3),
+                                                              "mean_cost": round(float(out.costs.mean()), 4)}
+            row["greedy_mean_cost"] = round(float(dec.costs.mean()), 4)
         print(json.dumps(row), flush=True)
         lines.append(json.dumps(row))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as out:
-        out.write("# tools/decode_bench.py --shapes %s --reps %d --inner %d: ms per call, median and min over the windows\n"
-                  % (a.shapes, a.reps, a.inner))
+    with open(a.out, "a" if a.beam else "w") as out:
+        out.write("# tools/decode_bench.py --shapes %s --reps %d --inner %d%s: ms per call, median and min over the windows\n"
+                  % (a.shapes, a.reps, a.inner, " --beam " + a.beam if a.beam else ""))
         out.write("\n".join(lines) + "\n")
 
 

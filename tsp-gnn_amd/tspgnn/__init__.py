@@ -20,7 +20,8 @@ from .variables import VariableStore, get_default_store, reset_default_store
 from . import tf_checkpoint
 from .util import load_weights, save_weights
 from .train import run_batch, run_batches_accumulated, summarize_epoch
-from .decode import tours_from_votes, decode_tours, DecodedBatch, DecodedTour
+from .decode import (tours_from_votes, decode_tours, DecodedBatch, DecodedTour, edge_scores, beam_tours, BeamBatch,
+                     BeamTour)
 from . import experiments
 
 __all__ = [
@@ -30,5 +31,5 @@ __all__ = [
     "load_weights", "save_weights", "run_batch", "run_batches_accumulated", "summarize_epoch", "solve_tours", "label_tours", "prove_tours", "solve", "certify", "create_graph",
     "create_dataset", "TourResult", "nearest_neighbor_tours", "anneal_tours", "decide",
     "metric_closure", "DeviceDataset", "draw_instances", "draw_streams",
-    "tours_from_votes", "decode_tours", "DecodedBatch", "DecodedTour",
+    "tours_from_votes", "decode_tours", "DecodedBatch", "DecodedTour", "edge_scores", "beam_tours", "BeamBatch", "BeamTour",
 ]

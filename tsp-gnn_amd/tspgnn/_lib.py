@@ -109,6 +109,9 @@ SIGNATURES = {
                                c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_from_votes": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p],
+    "tspgnn_vote_scores_i32": [c_void_p, c_longlong, c_void_p, c_void_p],
+    "tspgnn_tour_beam": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                         c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tspgnn_metric_closure": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "tspgnn_gather_batch": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p],
@@ -143,7 +146,8 @@ HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn
                   "tspgnn_host_read_graph", "tspgnn_host_count_edges", "tspgnn_host_pack_batch", "tspgnn_host_stage_batch",
                   "tspgnn_host_f64_repr")
 
-# size queries: name -> argtypes; these return long long (floats of workspace; tspgnn_tour_branch_bound_ws: bytes)
+# size queries: name -> argtypes; these return long long (floats of workspace; tspgnn_tour_branch_bound_ws and
+# tspgnn_tour_beam_workspace_bytes: bytes)
 SIZE_QUERIES = {
     "tspgnn_lnlstm_bwd_workspace_floats": [c_int],
     "tspgnn_wgrad_workspace_floats": [c_longlong, c_int, c_int],
@@ -152,6 +156,7 @@ SIZE_QUERIES = {
     "tspgnn_einit_bwd_workspace_floats": [c_int, c_int],
     "tspgnn_adam_workspace_floats": [],
     "tspgnn_tour_branch_bound_ws": [c_int, c_int],
+    "tspgnn_tour_beam_workspace_bytes": [c_int, c_int, c_int],
 }
 
 

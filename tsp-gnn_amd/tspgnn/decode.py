@@ -11,6 +11,11 @@ it in NumPy.
 ``tours_from_votes`` is the launch alone, ``decode_tours`` the pipeline from instances to records, with the network's own
 cost estimate (``get_costs``) as the target when none is given and an optional descent of the existing tour search from
 the decoded tour (``polish=True``).  How good the decoded tours are is an observation, not a guarantee.
+
+``decode_tours(..., beam=K)`` decodes by beam search instead: ``edge_scores`` turns the votes into integer
+log-probabilities (tspgnn_vote_scores_i32), ``beam_tours`` keeps the K best partial paths from vertex 0 under their sum
+(tspgnn_tour_beam, csrc/tour_beam.hip) and returns the best-scoring closed tour of the last list, or with
+``select="cost"`` the cheapest.  tests/beam_reference.py restates it in NumPy.
 """
 import collections
 
@@ -36,6 +41,19 @@ tour's pairs that are edges, unnormalised; n_missing: the pairs that are not edg
 prediction: the network's answer at target_cost; target_cost: the per-vertex target the instance was packed at (the unit
 get_costs returns); polished_tour / polished_cost: label_tours' tour and fp64 cost from the decoded tour (None without
 polish=True)."""
+
+MAX_BEAM = 1024                               # tspgnn_tour_beam: 1 <= beam <= 1024
+SELECT = {"score": 0, "cost": 1}
+DEFAULT_BEAM_WORKSPACE_BYTES = 256 << 20      # beam_tours splits a batch into launches whose workspace stays below this
+
+BeamBatch = collections.namedtuple("BeamBatch", ["tours", "costs", "n_missing", "scores", "n_closed", "vseg"])
+BeamBatch.__doc__ = """beam_tours' device tensors: tours, costs, n_missing and vseg as DecodedBatch; scores int32 [B], the
+integer score of the chosen entry; n_closed int32 [B], the entries of the last list that an edge closes (0: stranded)."""
+
+BeamTour = collections.namedtuple("BeamTour", DecodedTour._fields + ("score", "n_closed"))
+BeamTour.__doc__ = """One instance decoded by beam search: the fields of DecodedTour, then score: the tour's integer score
+(65536 x the sum of its edges' log-probabilities, each rounded and clamped to [-2^22, 0]); n_closed: how many entries of
+the final list an edge closes (0: the search stranded and the tour was filled up by vertex id)."""
 
 
 def vote_key(votes):
@@ -98,8 +116,74 @@ def tours_from_votes(batch, votes, n_vertices=None):
     return DecodedBatch(tours, costs, n_missing, vseg)
 
 
-def _decode_chunk(sess, model, chunk, targets, time_steps):
-    """[(tour, cost, n_missing, prediction)] of one batch: pack at the targets, forward, decode, one read-back."""
+def edge_scores(votes):
+    """tspgnn_vote_scores_i32 on a float32 device tensor of votes, on the current stream: q(v) = clamp(rint(65536
+    logsigmoid(v)), -2^22, 0) -> int32 tensor of the same length (NaN -> -2^22).  Does not wait for the device."""
+    if not torch.is_tensor(votes) or votes.dtype != torch.float32 or not votes.is_cuda:
+        raise ValueError("edge_scores: votes must be a float32 tensor on a GPU")
+    votes = votes.reshape(-1)
+    if not votes.is_contiguous():
+        raise ValueError("edge_scores: the votes must be contiguous")
+    scores = torch.empty(votes.numel(), dtype=torch.int32, device=votes.device)
+    with torch.cuda.device(votes.device):
+        _lib.call("tspgnn_vote_scores_i32", _lib.ptr(votes), votes.numel(), _lib.ptr(scores), _lib.current_stream())
+    return scores
+
+
+def beam_ranges(B, n_max, beam, workspace_bytes=None):
+    """The instance ranges [(start, stop)] beam_tours launches one after the other, and the bytes of workspace they share:
+    as many instances per launch as tspgnn_tour_beam_workspace_bytes allows under the cap (at least one)."""
+    cap = DEFAULT_BEAM_WORKSPACE_BYTES if workspace_bytes is None else int(workspace_bytes)
+    per = int(_lib.lib.tspgnn_tour_beam_workspace_bytes(1, n_max, beam))
+    if per <= 0:
+        raise ValueError("beam_tours: no workspace for n_max=%d, beam=%d" % (n_max, beam))
+    g = max(1, min(B, cap // per))
+    return [(s, min(s + g, B)) for s in range(0, B, g)], int(_lib.lib.tspgnn_tour_beam_workspace_bytes(g, n_max, beam))
+
+
+def beam_tours(batch, scores, beam, select="score", n_vertices=None, workspace_bytes=None):
+    """tspgnn_tour_beam on a resident batch and its integer edge scores (``edge_scores(forward_device(batch)["E_vote"])``,
+    int32 [M] on the batch's device), on the current stream -> BeamBatch of device tensors.  beam: 1 .. 1024; select:
+    "score" or "cost".  Nothing here waits for the device, so the launch may follow forward_device and edge_scores
+    directly.  The workspace is sized by the library's query; when a batch would need more than ``workspace_bytes``
+    (default DEFAULT_BEAM_WORKSPACE_BYTES, 256 MiB) it is decoded in several launches over instance ranges that share one
+    workspace -- instances are independent, so the ranges change nothing."""
+    if select not in SELECT:
+        raise ValueError("beam_tours: select must be 'score' or 'cost', got %r" % (select,))
+    beam = int(beam)
+    if not 1 <= beam <= MAX_BEAM:
+        raise ValueError("beam_tours: beam=%d; the decoder takes 1 <= beam <= %d" % (beam, MAX_BEAM))
+    if not torch.is_tensor(scores) or scores.dtype != torch.int32 or scores.device != batch.seg.device:
+        raise ValueError("beam_tours: scores must be an int32 tensor on the batch's device")
+    scores = scores.reshape(-1)
+    if scores.numel() != batch.M or not scores.is_contiguous():
+        raise ValueError("beam_tours: one contiguous score per edge (%d), got %d" % (batch.M, scores.numel()))
+    vseg, n_max = _vseg(batch, n_vertices)
+    dev = batch.seg.device
+    tours = torch.empty(batch.N, dtype=torch.int32, device=dev)
+    costs = torch.empty(batch.B, dtype=torch.float32, device=dev)
+    n_missing, out_scores, n_closed = (torch.empty(batch.B, dtype=torch.int32, device=dev) for _ in range(3))
+    uv, wc = batch.adj.uv, batch.WC
+    if batch.M == 0:   # no edge anywhere: the kernel reads none of the three, but refuses null pointers
+        scores = torch.zeros(1, dtype=torch.int32, device=dev)
+        uv = torch.zeros((1, 2), dtype=torch.int32, device=dev)
+        wc = torch.zeros((1, 2), dtype=torch.float32, device=dev)
+    if batch.B == 0:
+        return BeamBatch(tours, costs, n_missing, out_scores, n_closed, vseg)
+    ranges, ws_bytes = beam_ranges(batch.B, n_max, beam, workspace_bytes)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        for start, stop in ranges:      # seg and vseg hold global offsets: a range is the same arrays from `start` on
+            _lib.call("tspgnn_tour_beam", _lib.ptr(scores), _lib.ptr(uv), _lib.ptr(wc), _lib.ptr(batch.seg) + 4 * start,
+                      _lib.ptr(vseg) + 4 * start, stop - start, n_max, beam, SELECT[select], _lib.ptr(ws), ws_bytes,
+                      _lib.ptr(tours), _lib.ptr(costs) + 4 * start, _lib.ptr(n_missing) + 4 * start,
+                      _lib.ptr(out_scores) + 4 * start, _lib.ptr(n_closed) + 4 * start, _lib.current_stream())
+    return BeamBatch(tours, costs, n_missing, out_scores, n_closed, vseg)
+
+
+def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="score", workspace_bytes=None):
+    """[(tour, cost, n_missing, prediction, score, n_closed)] of one batch: pack at the targets, forward, decode, one
+    read-back.  beam None: the greedy decoder, score and n_closed None."""
     EV, W, C, route_exists, n_vertices, n_edges = InstanceLoader.create_batch(chunk, target_cost=0.0)
     C[:, 0] = np.repeat(np.asarray(targets, dtype=np.float64), n_edges)
     feed = {model["EV"]: EV, model["W"]: W, model["C"]: C, model["time_steps"]: time_steps,
@@ -109,17 +193,23 @@ def _decode_chunk(sess, model, chunk, targets, time_steps):
 
     def run():
         out = sess.forward_device(b)
-        return tours_from_votes(b, out["E_vote"], n_vertices), out["predictions"]
+        if beam is None:
+            return tours_from_votes(b, out["E_vote"], n_vertices), out["predictions"]
+        return beam_tours(b, edge_scores(out["E_vote"]), beam, select, n_vertices, workspace_bytes), out["predictions"]
 
     dec, pred = sess._on_bf16x3_if_flagged(run)   # (one synchronising look at the f16x2 range guard)
     tours, costs = dec.tours.cpu().numpy(), dec.costs.cpu().numpy()
     missing, pred = dec.n_missing.cpu().numpy(), pred.cpu().numpy()
     v0 = np.concatenate([[0], np.cumsum(n_vertices)])
-    return [([int(v) for v in tours[v0[i]:v0[i + 1]]], float(costs[i]), int(missing[i]), float(pred[i]))
+    extra = [(None, None)] * len(chunk)
+    if beam is not None:
+        extra = list(zip((int(s) for s in dec.scores.cpu().numpy()), (int(c) for c in dec.n_closed.cpu().numpy())))
+    return [([int(v) for v in tours[v0[i]:v0[i + 1]]], float(costs[i]), int(missing[i]), float(pred[i])) + extra[i]
             for i in range(len(chunk))]
 
 
-def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=False, max_graphs=None, **search_kw):
+def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=False, max_graphs=None, beam=None,
+                 select="score", workspace_bytes=None, **search_kw):
     """A tour per instance from the network's edge votes.
 
     instances: list of (Ma, Mw, route) as for get_costs (4 <= n <= 256; the route is not used by the decoder).
@@ -130,7 +220,11 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
     polish=True hands the decoded tours to the tour search as its starting tours (label_tours with restarts=1, kicks=0,
     lower_bound=False: one descent from the network's tour on the penalised weights, which repairs an infeasible stitch
     where the graph allows); ``search_kw`` go to label_tours and may raise the restart and kick counts.
-    Returns a list of DecodedTour in input order."""
+    beam=None decodes by greedy edge insertion (tspgnn_tour_from_votes).  beam=K, 1 .. 1024, decodes by beam search
+    instead: edge_scores and beam_tours per chunk, ``select`` "score" (the best-scoring closed tour of the last list) or
+    "cost" (its cheapest), ``workspace_bytes`` beam_tours' cap; the records are then BeamTour, DecodedTour's fields
+    followed by score and n_closed.
+    Returns a list of DecodedTour (BeamTour with a beam) in input order."""
     sess._require_gpu("decode_tours")
     instances = list(instances)
     for k, inst in enumerate(instances):
@@ -138,6 +232,13 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
         if not MIN_N <= n <= MAX_N:
             raise ValueError("decode_tours: instance %d has %d vertices; the decoder takes %d <= n <= %d"
                              % (k, n, MIN_N, MAX_N))
+    if beam is None and (select != "score" or workspace_bytes is not None):
+        raise TypeError("decode_tours: select and workspace_bytes only apply with beam=K")
+    if beam is not None:
+        if select not in SELECT:
+            raise ValueError("decode_tours: select must be 'score' or 'cost', got %r" % (select,))
+        if not 1 <= int(beam) <= MAX_BEAM:
+            raise ValueError("decode_tours: beam=%r; the decoder takes 1 <= beam <= %d" % (beam, MAX_BEAM))
     if search_kw and not polish:
         raise TypeError("decode_tours: %s only apply with polish=True" % ", ".join(sorted(search_kw)))
     if target_costs is None:
@@ -148,7 +249,8 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
             raise ValueError("decode_tours: target_costs must hold one cost per instance")
     rows = []
     for start, stop in plan_chunks(len(instances), 1, DEFAULT_MAX_GRAPHS if max_graphs is None else max_graphs):
-        rows += _decode_chunk(sess, model, instances[start:stop], targets[start:stop], time_steps)
+        rows += _decode_chunk(sess, model, instances[start:stop], targets[start:stop], time_steps, beam, select,
+                              workspace_bytes)
     polished = [(None, None)] * len(instances)
     if polish and instances:
         from .dataset import label_tours
@@ -156,5 +258,8 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
         kw.update(search_kw)
         res = label_tours([(x[0], x[1]) for x in instances], init_tours=[r[0] for r in rows], device=sess.device, **kw)
         polished = [(r.tour, r.cost) for r in res]
-    return [DecodedTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1])
-            for (tour, cost, missing, pred), target, p in zip(rows, targets, polished)]
+    if beam is None:
+        return [DecodedTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1])
+                for (tour, cost, missing, pred, _, _), target, p in zip(rows, targets, polished)]
+    return [BeamTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1], score, closed)
+            for (tour, cost, missing, pred, score, closed), target, p in zip(rows, targets, polished)]
