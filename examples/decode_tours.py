@@ -19,6 +19,11 @@ closed tour of the last beam instead of the best-scoring one; two more columns t
 the number of closed entries of the last beam.
 
     python examples/decode_tours.py --synthetic 32 -beam 128 -select cost --polish
+
+-guide K[,KN] (with -polish) lets the polish add only edges that the votes rank: per vertex its K best-voted neighbours,
+then the KN nearest of the rest (tspgnn.vote_neighbors; decode_tours(guide=(K, KN))).
+
+    python examples/decode_tours.py --synthetic 32 -polish -guide 4,4
 """
 import argparse
 import os
@@ -56,7 +61,8 @@ def main(argv=None):
     p.add_argument("--checkpoint", default=None, help="TensorFlow-format checkpoint directory .../epoch=N")
     p.add_argument("-beam", default=None, type=int, help="beam width, 1 .. 1024 (default: the greedy decoder)")
     p.add_argument("-select", default="score", choices=["score", "cost"], help="with -beam: what the last beam is chosen by")
-    p.add_argument("--polish", action="store_true", help="one descent of the tour search from every decoded tour")
+    p.add_argument("--polish", "-polish", action="store_true", help="one descent of the tour search from every decoded tour")
+    p.add_argument("-guide", default=None, help="K[,KN]: with -polish, candidate rows from the votes (K + KN <= 32)")
     p.add_argument("--max-rounds", default=1100, type=int, help="bisection rounds of the cost estimate (see binary_search.py)")
     p.add_argument("--write-graphs", default=None, help="directory for the instances with their decoded tours")
     p.add_argument("--seed", default=0, type=int)
@@ -72,6 +78,8 @@ def main(argv=None):
     # decode_tours(target_costs=None) runs this same search with its default round limit; untrained weights need more
     estimates = [r[0] for r in get_costs(sess, model, instances, a.timesteps, max_rounds=a.max_rounds)]
     beam_kw = {} if a.beam is None else {"beam": a.beam, "select": a.select}
+    if a.guide is not None:
+        beam_kw["guide"] = tuple(int(k) for k in (a.guide + ",0").split(",")[:2])
     res = decode_tours(sess, model, instances, a.timesteps, target_costs=estimates, polish=a.polish, **beam_kw)
     if os.path.dirname(a.out):
         os.makedirs(os.path.dirname(a.out), exist_ok=True)

@@ -527,6 +527,35 @@ int tspgnn_tour_search_knn_tri(const float* W, const long long* w_off, const int
                                void* stream);
 
 /*
+ * tspgnn_tour_search_knn with the candidate table handed in by the caller instead of built from the weights: the same
+ * starts, kicks, random keys, moves, fp32 deltas, codes, candidate rule, threshold, move cap, acceptance and canonical
+ * output; only S differs.  cand + c_off[i] holds instance i's table, n[i] x columns bytes, row-major, on the device.
+ * Entry (x, s) = y puts the pair {x, y} into S iff y < n[i] and y != x; any other entry contributes nothing (x itself is
+ * the conventional "skip").  Duplicate entries, asymmetric rows and an empty S are all legal: the result is a function of
+ * the set S.  With an empty S every descent stops at once, and a chain keeps the cheapest of its start and kicked tours.
+ * With the table N(x) of tspgnn_tour_search_knn (the neighbors nearest by (W[x][y], y), rows padded with x) the tours and
+ * costs equal tspgnn_tour_search_knn's bit for bit.  Any candidate rule -- the network's edge votes
+ * (tspgnn_vote_neighbors), alpha-nearness, quadrant neighbours, a union of rules -- is thus a table, with no new kernel.
+ * LDS and chain limits are tspgnn_tour_search_knn's with neighbors = columns.  columns outside [1, 32], restarts above what
+ * fits (the message names the limit) or a null cand / c_off: TSPGNN_EINVAL; n_max > 128: TSPGNN_EUNSUPPORTED; all before
+ * any launch, the outputs untouched.  n_inst == 0 is a no-op.
+ */
+int tspgnn_tour_search_cand(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                            const long long* t_off, const long long* index, const uint8_t* cand, const long long* c_off,
+                            int n_inst, int n_max, int restarts, int kicks, int columns, unsigned long long seed,
+                            int32_t* tours, float* costs, void* stream);
+
+/*
+ * tspgnn_tour_search_cand on the packed strict upper triangle of tspgnn_tour_search_tri, n_max <= 256 (above:
+ * TSPGNN_EUNSUPPORTED).  LDS: 2 n_max (n_max - 1) + n_max * columns + 13 restarts n_max bytes must fit 163 712, as for
+ * tspgnn_tour_search_knn_tri.  For n <= 128 the tours and costs equal tspgnn_tour_search_cand's bit for bit.
+ */
+int tspgnn_tour_search_cand_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                                const long long* t_off, const long long* index, const uint8_t* cand,
+                                const long long* c_off, int n_inst, int n_max, int restarts, int kicks, int columns,
+                                unsigned long long seed, int32_t* tours, float* costs, void* stream);
+
+/*
  * tspgnn_tour_lower_bound on the packed triangle of tspgnn_tour_search_tri (dataset.py:9-50): the same subgradient
  * ascent, fp64 re-evaluation and margin; a lane owns the vertices l, l+64, l+128 and l+192.  n_max <= 256
  * (above: TSPGNN_EUNSUPPORTED).  For n <= 128, lb[i] equals tspgnn_tour_lower_bound's bit for bit.
@@ -735,6 +764,35 @@ long long tspgnn_tour_beam_workspace_bytes(int B, int n_max, int beam);
 int tspgnn_tour_beam(const int32_t* score, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
                      int B, int n_max, int beam, int select, void* workspace, long long workspace_bytes, int32_t* tours,
                      float* costs, int32_t* n_missing, int32_t* scores, int32_t* n_closed, void* stream);
+
+/*
+ * Candidate rows for tspgnn_tour_search_cand from the network's edge votes, one workgroup per instance.  The batch is read
+ * exactly as tspgnn_tour_from_votes reads it (vote, uv, wc, seg, vseg; local ids uv - vseg[b]; 4 <= n <= n_max <= 256),
+ * and with it the vertex CSR the batch carries: rowptr:[N+1] int32, and eid row g = the ids of the edges that list global
+ * vertex g as an endpoint.  tab: uint8 [N][K], K = k_vote + k_near; row vseg[b] + x is the candidate row of local vertex
+ * x of instance b.  The result is exactly this sequential process on instance b and its vertex x:
+ *   Pairs.  For y != x in [0, n): e(x,y) is the smallest edge id in CSR row x that joins x and y, or none.  An id of the
+ *           row joins x to the other endpoint of that edge; it joins nothing when it lies outside seg[b] .. seg[b+1], when
+ *           the edge does not list x, or when the other endpoint is x or lies outside [0, n).  v(x,y) = vote[e(x,y)] and
+ *           w(x,y) = wc[e(x,y)][0].  The result depends on the set of edge ids in a row, not on their order.  The
+ *           neighbours of x are the y for which e(x,y) exists.
+ *   Vote.   For s = 0 .. k_vote-1: among the neighbours of x not yet in the row, take the first by (vote key of v(x,y)
+ *           descending, y ascending); the key is tspgnn_tour_from_votes' (-0.0 < +0.0, -inf the lowest number, NaN below
+ *           everything).  Write y to slot s.  If no neighbour is left, write x ("skip", which tspgnn_tour_search_cand
+ *           ignores).
+ *   Near.   For s = k_vote .. K-1: among the neighbours not yet in the row, take the first by (weight key of w(x,y)
+ *           ascending, y ascending): the same order-preserving image of the fp32 bits, a NaN weight coming last.  Write
+ *           y to slot s; if no neighbour is left, write x.
+ * A row depends on the instance, its votes and weights alone: never on n_max, on the other instances or on the launch.
+ * The kernel resolves multi-edges by an atomic minimum in LDS, then takes K wave-wide arg-max rounds per vertex; it sorts
+ * nothing, needs no workspace and has no communication between workgroups.  The arrays live on the device, so this entry
+ * point cannot see them: an instance with n outside [4, n_max] gets its rows zero-filled.
+ * B == 0 is a no-op; n_max > 256: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4, k_vote < 0, k_near < 0, K outside [1, 32] or a
+ * null pointer with B > 0: TSPGNN_EINVAL; all before any launch, the outputs untouched.
+ */
+int tspgnn_vote_neighbors(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
+                          const int32_t* rowptr, const int32_t* eid, int B, int n_max, int k_vote, int k_near,
+                          uint8_t* tab, void* stream);
 
 /* ------------------------------------------------------------------ backward (tf.gradients, model.py:166) */
 

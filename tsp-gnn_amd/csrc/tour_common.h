@@ -116,6 +116,14 @@ __device__ __forceinline__ void write_canonical(const int* t, int n, int32_t* ou
     }
 }
 
+// The decoders' vote key (tour_decode.hip, tour_guided.hip): 0 for a NaN, otherwise the order-preserving uint32 image of
+// the fp32 value -- all bits flipped when the sign bit is set, else the sign bit set.  Larger key = larger vote.
+__device__ __forceinline__ uint32_t vote_key(float vote) {
+    const uint32_t b = __float_as_uint(vote);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
 // Wave-wide minimum of an int; every lane gets it.
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll

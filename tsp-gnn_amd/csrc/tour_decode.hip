@@ -57,12 +57,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     }
 }
 
-__device__ __forceinline__ uint32_t vote_key(float vote) {
-    const uint32_t b = __float_as_uint(vote);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // (key, edge id) as one word whose maximum is the first edge in the order: the id enters complemented.  0 = no edge.
 __device__ __forceinline__ unsigned long long candidate(uint32_t key, uint32_t e) {
     return ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - e);

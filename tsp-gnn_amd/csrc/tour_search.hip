@@ -5,6 +5,8 @@
 //                            re-evaluated in fp64 so that the reported value is a lower bound under rounding.
 //   tspgnn_tour_search_knn   the same search with its descent restricted to the moves that add an edge between near
 //                            neighbours (descend_knn below): about 13 n K evaluations per applied move, not 5.3 n^2.
+//   tspgnn_tour_search_cand  that search with the candidate table handed in by the caller, one row of `columns` vertex
+//                            ids per vertex, instead of built from the weights (stage_candidates below).
 // All are issue-bound on LDS reads and VALU work: an instance reads its n*n weights from memory once.
 // Each has two layouts of the weights, one device body: the dense matrix (tspgnn_tour_search / _lower_bound, n <= 128)
 // and the packed strict upper triangle (the _tri entry points, n <= 256, 130 560 B at n = 256).  The bodies read a weight
@@ -132,14 +134,38 @@ struct Knn {
     int kk;
 };
 
+// Every thread drops the second copy of a mutual pair: entry (x, y) with y < x and x in row y becomes x ("skip").  A
+// thread meets at most n kk / 64 <= 128 entries, whose verdicts wait in two 64-bit masks for the barrier between the
+// reading and the writing of the table.  The table is complete on entry (a barrier behind its last write); ends with a
+// barrier.
+template <class WA>
+__device__ void dedup_neighbors(uint8_t* tab, int n, int kk, int wave, int waves, int lane) {
+    static_assert(WA::kMaxN * 32 / kWave <= 128, "the two dedup masks hold a thread's entries");
+    const int tid = wave * kWave + lane, nt = waves * kWave, m = n * kk;
+    uint64_t dup0 = 0, dup1 = 0;
+    int it = 0;
+    for (int e = tid; e < m; e += nt, ++it) {
+        const int x = e / kk, y = tab[e];
+        bool dup = false;
+        if (y < x)
+            for (int s = 0; s < kk; ++s) dup |= tab[y * kk + s] == x;
+        if (dup) {
+            if (it < 64) dup0 |= 1ull << it;
+            else dup1 |= 1ull << (it - 64);
+        }
+    }
+    __syncthreads();
+    it = 0;
+    for (int e = tid; e < m; e += nt, ++it)
+        if ((it < 64 ? dup0 >> it : dup1 >> (it - 64)) & 1) tab[e] = (uint8_t)(e / kk);
+    __syncthreads();
+}
+
 // The workgroup builds the table: wave `wave` of `waves` selects rows wave, wave + waves, ... by kk rounds of argmin
-// over (w, y), a lane holding vertices lane, lane + 64, ...; then every thread drops the second copy of a mutual pair.
-// A thread meets at most n kk / 64 <= 128 entries, whose verdicts wait in two 64-bit masks for the barrier between the
-// reading and the writing of the table.  Ends with a barrier.
+// over (w, y), a lane holding vertices lane, lane + 64, ...; then dedup_neighbors.  Ends with a barrier.
 template <class WA>
 __device__ void build_neighbors(const WA& W, uint8_t* tab, int n, int kk, int wave, int waves, int lane) {
     constexpr int V = WA::kMaxN / kWave;
-    static_assert(WA::kMaxN * 32 / kWave <= 128, "the two dedup masks hold a thread's entries");
     for (int x = wave; x < n; x += waves) {
         float key[V];
         bool avail[V];
@@ -167,24 +193,22 @@ __device__ void build_neighbors(const WA& W, uint8_t* tab, int n, int kk, int wa
         }
     }
     __syncthreads();
-    const int tid = wave * kWave + lane, nt = waves * kWave, m = n * kk;
-    uint64_t dup0 = 0, dup1 = 0;
-    int it = 0;
-    for (int e = tid; e < m; e += nt, ++it) {
-        const int x = e / kk, y = tab[e];
-        bool dup = false;
-        if (y < x)
-            for (int s = 0; s < kk; ++s) dup |= tab[y * kk + s] == x;
-        if (dup) {
-            if (it < 64) dup0 |= 1ull << it;
-            else dup1 |= 1ull << (it - 64);
-        }
+    dedup_neighbors<WA>(tab, n, kk, wave, waves, lane);
+}
+
+// _cand: the caller's table in place of build_neighbors'.  Entry (x, s) = y stands for the pair {x, y} when y < n and
+// y != x; any other entry becomes x ("skip").  Rows may be asymmetric, repeat an entry or hold nothing: descend_knn's
+// result is a function of the pair set.  Then dedup_neighbors, which keeps that set.  Ends with a barrier.
+template <class WA>
+__device__ void stage_candidates(const uint8_t* __restrict__ src, uint8_t* tab, int n, int columns, int wave, int waves,
+                                 int lane) {
+    const int tid = wave * kWave + lane, nt = waves * kWave, m = n * columns;
+    for (int e = tid; e < m; e += nt) {
+        const int x = e / columns, y = src[e];
+        tab[e] = (uint8_t)(y < n && y != x ? y : x);
     }
     __syncthreads();
-    it = 0;
-    for (int e = tid; e < m; e += nt, ++it)
-        if ((it < 64 ? dup0 >> it : dup1 >> (it - 64)) & 1) tab[e] = (uint8_t)(e / kk);
-    __syncthreads();
+    dedup_neighbors<WA>(tab, n, columns, wave, waves, lane);
 }
 
 // One lane's running best over the candidates it generates.
@@ -280,12 +304,20 @@ __device__ void double_bridge(const int* src, int* dst, int n, uint64_t r, int l
     wave_sync();
 }
 
-// kKnn: the chains descend by descend_knn over the neighbour table of `neighbors` columns; otherwise by descend().
-template <class WA, bool kKnn>
+// Where the descent's candidate table comes from: none (descend(), the whole neighbourhood), the `neighbors` nearest by
+// weight (build_neighbors), or the caller's rows of `neighbors` columns (stage_candidates).
+enum TabSrc { kTabNone = 0, kTabNearest = 1, kTabGiven = 2 };
+
+// kTab != kTabNone: the chains descend by descend_knn over a table of `neighbors` columns; otherwise by descend().
+// cand / c_off are read by kTabGiven alone; they come last, so the other instantiations read their arguments where they
+// always did.
+template <class WA, TabSrc kTab>
 __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     const float* __restrict__ Wg, const long long* __restrict__ w_off, const int* __restrict__ n_arr,
     const int32_t* __restrict__ init, const long long* __restrict__ t_off, const long long* __restrict__ index, int n_max,
-    int kicks, int neighbors, unsigned long long seed, int32_t* __restrict__ tours, float* __restrict__ costs) {
+    int kicks, int neighbors, unsigned long long seed, int32_t* __restrict__ tours, float* __restrict__ costs,
+    const uint8_t* __restrict__ cand, const long long* __restrict__ c_off) {
+    constexpr bool kKnn = kTab != kTabNone;
     extern __shared__ float lds[];
     __shared__ float s_cost[kMaxChains];
     __shared__ int s_tour[kMaxChains];
@@ -310,8 +342,13 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     if constexpr (kKnn) {
         nb.tab = reinterpret_cast<uint8_t*>(reinterpret_cast<int*>(lds + WA::floats(n_max)) + chains * 3 * n_max);
         nb.pos = nb.tab + n_max * neighbors + wave * n_max;
-        nb.kk = min(neighbors, n - 1);
-        build_neighbors(W, nb.tab, n, nb.kk, wave, chains, lane);
+        if constexpr (kTab == kTabGiven) {
+            nb.kk = neighbors;
+            stage_candidates<WA>(cand + c_off[inst], nb.tab, n, nb.kk, wave, chains, lane);
+        } else {
+            nb.kk = min(neighbors, n - 1);
+            build_neighbors(W, nb.tab, n, nb.kk, wave, chains, lane);
+        }
     }
 
     // starting tour: chain 0 takes init_tours when given and a permutation of 0..n-1; otherwise Fisher-Yates
@@ -404,16 +441,19 @@ __global__ __launch_bounds__(kWave) void tour_lower_bound_kernel(const float* __
     if (lane == 0) lb[inst] = L;
 }
 
-// neighbors: 0 = the full-scan kernel (kKnn false); the _knn entry points pass their 1..32.
-template <class WA, bool kKnn>
+// neighbors: 0 = the full-scan kernel (kTabNone); the _knn entry points pass their 1..32, the _cand entry points their
+// columns with the table (cand, c_off), which the others leave null.
+template <class WA, TabSrc kTab>
 int search(const char* entry, const char* what, const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
            const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks, int neighbors,
-           unsigned long long seed, int32_t* tours, float* costs, void* stream) {
+           unsigned long long seed, int32_t* tours, float* costs, void* stream, const uint8_t* cand = nullptr,
+           const long long* c_off = nullptr) {
+    constexpr bool kKnn = kTab != kTabNone;
     TSPGNN_REQUIRE(n_inst >= 0, "%s: n_inst=%d", what, n_inst);
     if (n_inst == 0) return TSPGNN_OK;
     if constexpr (kKnn)
-        TSPGNN_REQUIRE(neighbors >= 1 && neighbors <= kMaxNeighbors, "%s: neighbors=%d not in [1, %d]", what, neighbors,
-                       kMaxNeighbors);
+        TSPGNN_REQUIRE(neighbors >= 1 && neighbors <= kMaxNeighbors, "%s: %s=%d not in [1, %d]", what,
+                       kTab == kTabGiven ? "columns" : "neighbors", neighbors, kMaxNeighbors);
     if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
     TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
     TSPGNN_REQUIRE(restarts >= 1 && restarts <= kMaxChains, "%s: restarts=%d not in [1, %d]", what, restarts,
@@ -422,12 +462,13 @@ int search(const char* entry, const char* what, const float* W, const long long*
     TSPGNN_REQUIRE(restarts <= fit, "%s: restarts=%d: at n_max=%d at most %d chains fit in LDS", what, restarts, n_max, fit);
     TSPGNN_REQUIRE(kicks >= 0, "%s: kicks=%d", what, kicks);
     TSPGNN_REQUIRE(W && w_off && n && t_off && tours && costs, "%s: null pointer", what);
+    if constexpr (kTab == kTabGiven) TSPGNN_REQUIRE(cand && c_off, "%s: null pointer", what);
     size_t lds = (WA::floats(n_max) + (size_t)3 * restarts * n_max) * sizeof(float);
     if (kKnn) lds += (size_t)n_max * neighbors + (size_t)restarts * n_max;
-    int rc = allow_lds(tour_search_kernel<WA, kKnn>, lds);
+    int rc = allow_lds(tour_search_kernel<WA, kTab>, lds);
     if (rc) return rc;
-    tour_search_kernel<WA, kKnn><<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
-        W, w_off, n, init_tours, t_off, index, n_max, kicks, neighbors, seed, tours, costs);
+    tour_search_kernel<WA, kTab><<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
+        W, w_off, n, init_tours, t_off, index, n_max, kicks, neighbors, seed, tours, costs, cand, c_off);
     return launched(entry);
 }
 
@@ -455,7 +496,7 @@ using namespace tspgnn;
 extern "C" int tspgnn_tour_search(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                   const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
                                   int kicks, unsigned long long seed, int32_t* tours, float* costs, void* stream) {
-    return search<SquareW, false>("tspgnn_tour_search", "tour_search", W, w_off, n, init_tours, t_off, index, n_inst,
+    return search<SquareW, kTabNone>("tspgnn_tour_search", "tour_search", W, w_off, n, init_tours, t_off, index, n_inst,
                                   n_max, restarts, kicks, 0, seed, tours, costs, stream);
 }
 
@@ -468,7 +509,7 @@ extern "C" int tspgnn_tour_lower_bound(const float* W, const long long* w_off, c
 extern "C" int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                       const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
                                       int kicks, unsigned long long seed, int32_t* tours, float* costs, void* stream) {
-    return search<TriW, false>("tspgnn_tour_search_tri", "tour_search_tri", W, w_off, n, init_tours, t_off, index, n_inst,
+    return search<TriW, kTabNone>("tspgnn_tour_search_tri", "tour_search_tri", W, w_off, n, init_tours, t_off, index, n_inst,
                                n_max, restarts, kicks, 0, seed, tours, costs, stream);
 }
 
@@ -482,7 +523,7 @@ extern "C" int tspgnn_tour_search_knn(const float* W, const long long* w_off, co
                                       const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
                                       int kicks, int neighbors, unsigned long long seed, int32_t* tours, float* costs,
                                       void* stream) {
-    return search<SquareW, true>("tspgnn_tour_search_knn", "tour_search_knn", W, w_off, n, init_tours, t_off, index, n_inst,
+    return search<SquareW, kTabNearest>("tspgnn_tour_search_knn", "tour_search_knn", W, w_off, n, init_tours, t_off, index, n_inst,
                                  n_max, restarts, kicks, neighbors, seed, tours, costs, stream);
 }
 
@@ -490,6 +531,25 @@ extern "C" int tspgnn_tour_search_knn_tri(const float* W, const long long* w_off
                                           const long long* t_off, const long long* index, int n_inst, int n_max,
                                           int restarts, int kicks, int neighbors, unsigned long long seed, int32_t* tours,
                                           float* costs, void* stream) {
-    return search<TriW, true>("tspgnn_tour_search_knn_tri", "tour_search_knn_tri", W, w_off, n, init_tours, t_off, index,
+    return search<TriW, kTabNearest>("tspgnn_tour_search_knn_tri", "tour_search_knn_tri", W, w_off, n, init_tours, t_off, index,
                               n_inst, n_max, restarts, kicks, neighbors, seed, tours, costs, stream);
+}
+
+extern "C" int tspgnn_tour_search_cand(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                                       const long long* t_off, const long long* index, const uint8_t* cand,
+                                       const long long* c_off, int n_inst, int n_max, int restarts, int kicks, int columns,
+                                       unsigned long long seed, int32_t* tours, float* costs, void* stream) {
+    return search<SquareW, kTabGiven>("tspgnn_tour_search_cand", "tour_search_cand", W, w_off, n, init_tours, t_off,
+                                      index, n_inst, n_max, restarts, kicks, columns, seed, tours, costs, stream, cand,
+                                      c_off);
+}
+
+extern "C" int tspgnn_tour_search_cand_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
+                                           const long long* t_off, const long long* index, const uint8_t* cand,
+                                           const long long* c_off, int n_inst, int n_max, int restarts, int kicks,
+                                           int columns, unsigned long long seed, int32_t* tours, float* costs,
+                                           void* stream) {
+    return search<TriW, kTabGiven>("tspgnn_tour_search_cand_tri", "tour_search_cand_tri", W, w_off, n, init_tours, t_off,
+                                   index, n_inst, n_max, restarts, kicks, columns, seed, tours, costs, stream, cand,
+                                   c_off);
 }

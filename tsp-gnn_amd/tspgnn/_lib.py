@@ -96,6 +96,10 @@ SIGNATURES = {
                                c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_search_knn_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                    c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_search_cand": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                c_int, c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
+    "tspgnn_tour_search_cand_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_int, c_int, c_int, c_int, ctypes.c_ulonglong, c_void_p, c_void_p, c_void_p],
     "tspgnn_tour_lower_bound_tri": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "tspgnn_tour_branch_bound": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
@@ -112,6 +116,8 @@ SIGNATURES = {
     "tspgnn_vote_scores_i32": [c_void_p, c_longlong, c_void_p, c_void_p],
     "tspgnn_tour_beam": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                          c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tspgnn_vote_neighbors": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                              c_int, c_void_p, c_void_p],
     "tspgnn_metric_closure": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "tspgnn_gather_batch": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p],

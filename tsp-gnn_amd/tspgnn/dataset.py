@@ -143,7 +143,8 @@ def _target(Ma, Mw, tour):
 
 
 def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=0, init_tours=None, lower_bound=True,
-                device=None, lb_iters=DEFAULT_LB_ITERS, chunk=DEFAULT_CHUNK, index=None, timings=None, neighbors=None):
+                device=None, lb_iters=DEFAULT_LB_ITERS, chunk=DEFAULT_CHUNK, index=None, timings=None, neighbors=None,
+                candidates=None):
     """Solve symmetric TSP instances on the GPU, many at once.
 
     instances: list of (Ma, Mw); Ma upper-triangular or symmetric (nonzero = edge), Mw [n,n] with w(i,j) = Mw[min, max].
@@ -157,17 +158,23 @@ def solve_tours(instances, restarts=DEFAULT_RESTARTS, kicks=DEFAULT_KICKS, seed=
     neighbors: None = every descent step scans the whole 2-opt + Or-opt neighbourhood (tspgnn_tour_search).  K in 1..32 =
     it scans only the moves that add an edge {x, y} with y among the K nearest vertices of x or x among y's
     (tspgnn_tour_search_knn): many times fewer evaluations per step, so more kicks in the same time.
+    candidates: None, or one array-like [n, K] per instance, the same K in 1..32 for all, values 0..255: the caller's own
+    candidate table in place of the K nearest (tspgnn_tour_search_cand).  Entry (x, s) = y lets the descent add the edge
+    {x, y} when y < n and y != x; any other value (x itself by convention) stands for nothing.  Rows may be asymmetric,
+    repeat a vertex or be empty of pairs; results then depend on (seed, index, restarts, kicks, candidates) only.
+    Exclusive with ``neighbors``.  The tables of instances with n < 4 are checked and not used.
     timings: optional dict that receives the seconds spent in 'pack', 'search' and 'bound' (device-synchronised).
     n < 4 is solved on the host; n > 128 raises ValueError before anything is launched.
 
     Returns a list of TourResult (tour, cost, lb, feasible, target).
     """
     t0 = time.perf_counter()
-    _check_neighbors(neighbors)
+    _check_neighbors(neighbors, candidates)
     checked, index = _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, MAX_N)
+    candidates = _check_candidates(candidates, checked)
     return _solve(checked, index, tri=False, restarts=restarts, kicks=kicks, seed=seed, init_tours=init_tours,
                   lower_bound=lower_bound, device=device, lb_iters=lb_iters, chunk=chunk, timings=timings, t0=t0,
-                  neighbors=neighbors)[0]
+                  neighbors=neighbors, candidates=candidates)[0]
 
 
 def _check_counts(restarts, kicks, lb_iters, chunk):
@@ -177,7 +184,9 @@ def _check_counts(restarts, kicks, lb_iters, chunk):
         raise ValueError("kicks, lb_iters and chunk must be non-negative / positive")
 
 
-def _check_neighbors(neighbors):
+def _check_neighbors(neighbors, candidates=None):
+    if neighbors is not None and candidates is not None:
+        raise ValueError("neighbors and candidates are exclusive: the search descends over one candidate table")
     if neighbors is None:
         return
     if isinstance(neighbors, bool) or not isinstance(neighbors, (int, np.integer)) or not 1 <= neighbors <= MAX_NEIGHBORS:
@@ -194,6 +203,36 @@ def _validate(instances, restarts, kicks, lb_iters, chunk, index, init_tours, ma
     if init_tours is not None and len(init_tours) != B:
         raise ValueError("init_tours must hold one entry (or None) per instance")
     return checked, index
+
+
+def _check_candidates(candidates, checked):
+    """candidates=: None, or one [n, K] table per checked instance -> a list of uint8 arrays, K the same for all."""
+    if candidates is None:
+        return None
+    candidates = list(candidates)
+    if len(candidates) != len(checked):
+        raise ValueError("candidates must hold one [n, K] table per instance")
+    out, K = [], None
+    for k, (tab, (_, _, n)) in enumerate(zip(candidates, checked)):
+        raw = np.asarray(tab)
+        if raw.ndim != 2 or raw.shape[0] != n:
+            raise ValueError("candidates[%d] has shape %s; an instance of %d vertices takes [%d, K]"
+                             % (k, raw.shape, n, n))
+        if K is None:
+            K = raw.shape[1]
+            if not 1 <= K <= MAX_NEIGHBORS:
+                raise ValueError("candidates: K=%d columns; the search takes 1 <= K <= %d" % (K, MAX_NEIGHBORS))
+        if raw.shape[1] != K:
+            raise ValueError("candidates[%d] has %d columns, candidates[0] has %d: one K for all"
+                             % (k, raw.shape[1], K))
+        if raw.dtype.kind not in "iu" or (raw.size and (raw.min() < 0 or raw.max() > 255)):
+            raise ValueError("candidates[%d] must hold integers in 0..255" % k)
+        out.append(np.ascontiguousarray(raw, dtype=np.uint8))
+    return out
+
+
+def _cand_columns(candidates):
+    return None if not candidates else candidates[0].shape[1]
 
 
 def _device(device):
@@ -242,19 +281,25 @@ def _byte_chunks(order, ns, chunk_bytes):
 # the (Ma, Mw, n) it was made from; big: the positions of the n >= 4 instances in launch order.  Per launched instance: ns
 # int32, w_off / t_off (its first float in W, its first vertex in init and the kernels' tours), mean_w (None unless asked
 # for).  W: the penalised fp32 matrices, flat; init: the starting tours, -1 where there is none; has_init: some instance
-# came with one.  groups: {n: positions in big}; stacked: {n: (edge masks, fp64 weights)} of a group.
+# came with one.  groups: {n: positions in big}; stacked: {n: (edge masks, fp64 weights)} of a group.  cand / c_off: the
+# candidate tables of the launched instances, flat uint8, each one's first byte and their column count (None without
+# candidates=).
 Packed = collections.namedtuple("Packed", ["out", "checked", "big", "ns", "w_off", "t_off", "W", "init", "has_init",
-                                           "mean_w", "groups", "stacked"])
+                                           "mean_w", "groups", "stacked", "cand", "c_off", "columns"],
+                            defaults=(None, None, None))
 # What the tour kernels read and write for G instances of one layout: ns, the host copy of n, then the device arrays (init
-# None: no starting tours; cost None: prove_tours; idx and lb None for the baselines, which take neither).
-LabelArrays = collections.namedtuple("LabelArrays", "ns W w_off t_off n idx init tours cost lb")
+# None: no starting tours; cost None: prove_tours; idx and lb None for the baselines, which take neither; cand, c_off and
+# columns None unless the search descends over the caller's tables).
+LabelArrays = collections.namedtuple("LabelArrays", "ns W w_off t_off n idx init tours cost lb cand c_off columns",
+                                     defaults=(None, None, None))
 
 
-def _pack(checked, tri, init_tours=None, lower_bound=False, incumbents=None, mean_weight=False):
+def _pack(checked, tri, init_tours=None, lower_bound=False, incumbents=None, mean_weight=False, candidates=None):
     """Checked instances -> Packed: n < 4 solved on the host (lb = nan unless lower_bound), the rest packed for the square
     (tri=False) or triangle kernels, grouped by n so that the penalties, costs and targets are array operations.
     incumbents: one tour per instance, taken as its starting tour unchecked (prove_tours has checked them).
-    mean_weight: also the mean real edge weight per instance (annealing's temperature unit)."""
+    mean_weight: also the mean real edge weight per instance (annealing's temperature unit).
+    candidates: _check_candidates' tables, one per checked instance; they are laid out in launch order beside the tours."""
     out = [None] * len(checked)
     for k, (Ma, Mw, n) in enumerate(checked):
         if n < 4:
@@ -292,7 +337,12 @@ def _pack(checked, tri, init_tours=None, lower_bound=False, incumbents=None, mea
                 init[t_off[p]:t_off[p] + n] = it
         stacked[n] = (A, Mw)
     has_init = init_tours is not None and any(t is not None for t in init_tours)
-    return Packed(out, checked, big, ns, w_off, t_off, Wflat, init, has_init, mean_w, groups, stacked)
+    cand = c_off = K = None
+    if candidates:
+        K = _cand_columns(candidates)
+        c_off = (t_off * K).astype(np.int64)
+        cand = np.concatenate([candidates[k].reshape(-1) for k in big]) if big else np.zeros(0, dtype=np.uint8)
+    return Packed(out, checked, big, ns, w_off, t_off, Wflat, init, has_init, mean_w, groups, stacked, cand, c_off, K)
 
 
 def _upload(pk, dev, index=None, bound=False):
@@ -303,7 +353,10 @@ def _upload(pk, dev, index=None, bound=False):
                        _to_device(pk.init, dev) if pk.has_init else None,
                        torch.empty(int(pk.ns.sum()), dtype=torch.int32, device=dev),
                        torch.empty(G, dtype=torch.float32, device=dev),
-                       torch.empty(G, dtype=torch.float64, device=dev) if bound else None)
+                       torch.empty(G, dtype=torch.float64, device=dev) if bound else None,
+                       None if pk.cand is None else _to_device(pk.cand, dev),
+                       None if pk.cand is None else _to_device(pk.c_off, dev),
+                       pk.columns)
 
 
 def _finish(pk, tours, lbs=None):
@@ -328,24 +381,29 @@ def _launch_labels(dev, a, *, restarts, kicks, seed, lb_iters, chunk, tri, neigh
     """The launches of one size class over the LabelArrays ``a``, already on ``dev`` (inside torch.cuda.device(dev)): the
     search, ``chunk`` instances per launch, then the branch and bound (exact = (max_nodes, node_iters, opt_tol), tri=False
     only) or the bound (lower_bound).  search=False: a.tours already holds the incumbents (a.cost None: the root's step
-    then aims at the incumbent's own cost).  -> (t1, t2, t3, d_stat, d_nodes): perf_counter before the search, after it
-    and after the bound, each device-synchronised, and the branch and bound's int32 device arrays (None without exact)."""
-    ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost, d_lb = a
+    then aims at the incumbent's own cost).  a.cand: the search is the _cand entry point over the caller's tables of
+    a.columns columns, a launch reading its instances' tables through a.c_off.  -> (t1, t2, t3, d_stat, d_nodes):
+    perf_counter before the search, after it and after the bound, each device-synchronised, and the branch and bound's
+    int32 device arrays (None without exact)."""
+    ns, d_W, d_woff, d_toff, d_n, d_idx, d_init, d_tours, d_cost, d_lb = a[:10]
     G = len(ns)
     search_fn, bound_fn = ("tspgnn_tour_search_tri", "tspgnn_tour_lower_bound_tri") if tri else \
         ("tspgnn_tour_search", "tspgnn_tour_lower_bound")
     knn = ()
     if neighbors is not None:
         search_fn, knn = search_fn.replace("_search", "_search_knn"), (int(neighbors),)
+    if a.cand is not None:
+        search_fn, knn = search_fn.replace("_search", "_search_cand"), (int(a.columns),)
     d_stat = d_nodes = None
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
     st = _lib.current_stream()
     for c0, c1 in _spans(G if search else 0, chunk):
         _lib.call(search_fn, _lib.ptr(d_W), _lib.ptr(d_woff[c0:c1]), _lib.ptr(d_n[c0:c1]),
-                  _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]), c1 - c0, int(ns[c0:c1].max()),
-                  int(restarts), int(kicks), *knn, int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(d_tours),
-                  _lib.ptr(d_cost[c0:c1]), st)
+                  _lib.ptr(d_init), _lib.ptr(d_toff[c0:c1]), _lib.ptr(d_idx[c0:c1]),
+                  *(() if a.cand is None else (_lib.ptr(a.cand), _lib.ptr(a.c_off[c0:c1]))), c1 - c0,
+                  int(ns[c0:c1].max()), int(restarts), int(kicks), *knn, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                  _lib.ptr(d_tours), _lib.ptr(d_cost[c0:c1]), st)
     torch.cuda.synchronize(dev)
     t2 = time.perf_counter()
     if exact is not None:
@@ -371,14 +429,15 @@ def _launch_labels(dev, a, *, restarts, kicks, seed, lb_iters, chunk, tri, neigh
 
 
 def _solve(checked, index, *, tri, lb_iters, chunk, t0, restarts=1, kicks=0, seed=0, init_tours=None, lower_bound=True,
-           device=None, timings=None, exact=None, incumbents=None, neighbors=None):
+           device=None, timings=None, exact=None, incumbents=None, neighbors=None, candidates=None):
     """solve_tours on checked instances, n < 4 on the host and the rest on the square kernels (tri=False, n <= 128) or
-    the triangle kernels (tri=True, n <= 256); neighbors=K: the search is the _knn entry point of that layout.
+    the triangle kernels (tri=True, n <= 256); neighbors=K: the search is the _knn entry point of that layout;
+    candidates (one checked table per instance): its _cand entry point.
     exact = (max_nodes, node_iters, opt_tol): the branch and bound takes the place of the bound launch (tri=False only).
     incumbents: one tour per instance; the search is skipped and the branch and bound starts from these.  t0: perf_counter
     where timings['pack'] begins.  -> (results, status, nodes): with exact the branch and bound's int64 status and node
     count per instance (n < 4: proved, 0 nodes), otherwise None."""
-    pk = _pack(checked, tri, init_tours, lower_bound=lower_bound, incumbents=incumbents)
+    pk = _pack(checked, tri, init_tours, lower_bound=lower_bound, incumbents=incumbents, candidates=candidates)
     status = nodes = None
     if exact is not None:
         status, nodes = np.zeros(len(checked), dtype=np.int64), np.zeros(len(checked), dtype=np.int64)
@@ -404,10 +463,10 @@ def _solve(checked, index, *, tri, lb_iters, chunk, t0, restarts=1, kicks=0, see
     return _finish(pk, tours, lbs), status, nodes
 
 
-def _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chunk=1):
+def _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chunk=1, candidates=None):
     """label_tours' settings, checked in label_tours' order (None: DEFAULT_* / DEFAULT_*_LARGE): -> ((restarts, kicks,
     lb_iters) for n <= 128, the same for n 129-256, the branch and bound's (max_nodes, node_iters, opt_tol) or None)."""
-    _check_neighbors(neighbors)
+    _check_neighbors(neighbors, candidates)
     bb = None
     if exact:
         bb = (DEFAULT_BB_NODES if max_nodes is None else max_nodes, DEFAULT_BB_ITERS, 1e-9)
@@ -505,7 +564,7 @@ def prove_tours(instances, results, max_nodes=DEFAULT_BB_NODES, node_iters=DEFAU
 
 def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, init_tours=None, lower_bound=True,
                 device=None, chunk=DEFAULT_CHUNK, index=None, timings=None, exact=False, max_nodes=None, stats=None,
-                neighbors=None):
+                neighbors=None, candidates=None):
     """solve_tours for instances of up to MAX_N_TRI = 256 vertices, split by n: n < 4 on the host, 4-128 on the square
     kernels (exactly solve_tours), 129-256 on the packed-triangle kernels (tspgnn_tour_search_tri /
     tspgnn_tour_lower_bound_tri); n > 256 raises ValueError before anything is launched.
@@ -518,15 +577,19 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
     steps per node and lb_iters at the root) takes the place of the bound launch: lb is its bound and the tour the best it
     holds.  stats then receives prove_tours' 'status', 'nodes' and 'seconds'; n > 128 is 'skipped' and keeps the plain
     bound.  timings gets the launch under 'exact'.
+    candidates: solve_tours' (tspgnn_tour_search_cand / _cand_tri), exclusive with neighbors; for n > 128 restarts may not
+    exceed tri_chains_fit(largest n, K).  Everything about them is checked before any device work.
     """
     t0 = time.perf_counter()
-    small, large, bb = _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chunk)
+    small, large, bb = _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chunk, candidates)
     if bb is not None:
         timings = {} if timings is None else timings
         before = timings.get("exact", 0.0)
     checked, index = _validate(instances, *small, chunk, index, init_tours, MAX_N_TRI)
     ns = [c[2] for c in checked]
-    _check_chains_fit(large[0], max([n for n in ns if n > MAX_N], default=0), neighbors)
+    candidates = _check_candidates(candidates, checked)
+    _check_chains_fit(large[0], max([n for n in ns if n > MAX_N], default=0),
+                      neighbors if candidates is None else _cand_columns(candidates))
     out = [None] * len(checked)
     status, nodes = np.full(len(checked), 2, dtype=np.int64), np.zeros(len(checked), dtype=np.int64)
     for tri, sel in _split(ns):
@@ -534,7 +597,8 @@ def label_tours(instances, restarts=None, kicks=None, lb_iters=None, seed=0, ini
         res, st, nd = _solve([checked[i] for i in sel], index[sel], tri=tri, restarts=r, kicks=k, seed=seed,
                              init_tours=None if init_tours is None else [init_tours[i] for i in sel],
                              lower_bound=lower_bound, device=device, lb_iters=it, chunk=chunk, timings=timings,
-                             t0=t0 if not tri else time.perf_counter(), exact=None if tri else bb, neighbors=neighbors)
+                             t0=t0 if not tri else time.perf_counter(), exact=None if tri else bb, neighbors=neighbors,
+                             candidates=None if candidates is None else [candidates[i] for i in sel])
         for i, x in zip(sel, res):
             out[i] = x
         if st is not None:

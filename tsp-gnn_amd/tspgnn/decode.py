@@ -16,6 +16,11 @@ the decoded tour (``polish=True``).  How good the decoded tours are is an observ
 log-probabilities (tspgnn_vote_scores_i32), ``beam_tours`` keeps the K best partial paths from vertex 0 under their sum
 (tspgnn_tour_beam, csrc/tour_beam.hip) and returns the best-scoring closed tour of the last list, or with
 ``select="cost"`` the cheapest.  tests/beam_reference.py restates it in NumPy.
+
+``vote_neighbors`` turns the same votes into per-vertex candidate rows (tspgnn_vote_neighbors, csrc/tour_guided.hip): the
+k_vote neighbours the network ranks highest, then the k_near nearest of the rest.  ``decode_tours(..., polish=True,
+guide=K | (k_vote, k_near))`` hands those rows to the polish, whose descent then adds only edges the rows name
+(label_tours(candidates=), tspgnn_tour_search_cand).  tests/guided_reference.py restates the rows in NumPy.
 """
 import collections
 
@@ -42,6 +47,7 @@ prediction: the network's answer at target_cost; target_cost: the per-vertex tar
 get_costs returns); polished_tour / polished_cost: label_tours' tour and fp64 cost from the decoded tour (None without
 polish=True)."""
 
+MAX_GUIDE = 32                                # tspgnn_vote_neighbors: 1 <= k_vote + k_near <= 32
 MAX_BEAM = 1024                               # tspgnn_tour_beam: 1 <= beam <= 1024
 SELECT = {"score": 0, "cost": 1}
 DEFAULT_BEAM_WORKSPACE_BYTES = 256 << 20      # beam_tours splits a batch into launches whose workspace stays below this
@@ -116,6 +122,50 @@ def tours_from_votes(batch, votes, n_vertices=None):
     return DecodedBatch(tours, costs, n_missing, vseg)
 
 
+def _guide_counts(guide, what):
+    """guide=K | (k_vote, k_near) -> (k_vote, k_near), checked against tspgnn_vote_neighbors' limits."""
+    pair = (guide, 0) if isinstance(guide, (int, np.integer)) and not isinstance(guide, bool) else guide
+    try:
+        k_vote, k_near = pair
+        ok = all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in (k_vote, k_near))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or k_vote < 0 or k_near < 0 or not 1 <= k_vote + k_near <= MAX_GUIDE:
+        raise ValueError("%s: %r; the rows take k_vote >= 0 and k_near >= 0 with 1 <= k_vote + k_near <= %d"
+                         % (what, guide, MAX_GUIDE))
+    return int(k_vote), int(k_near)
+
+
+def vote_neighbors(batch, votes, k_vote, k_near=0, n_vertices=None):
+    """tspgnn_vote_neighbors on a resident batch and its vote tensor, as tours_from_votes takes them, on the current
+    stream -> a uint8 device tensor [N, k_vote + k_near]: row vseg[b] + x holds, for local vertex x of instance b, the
+    k_vote neighbours of highest vote (ties to the smaller id), then the k_near nearest by weight among the rest, in local
+    ids; a vertex with fewer neighbours pads its row with x itself, which the search ignores.  include/tspgnn.h states the
+    process in full.  The batch must carry its vertex CSR (``batch.adj.csr_t``, as every prepared batch does).  Nothing
+    here waits for the device, so the launch may follow forward_device directly."""
+    k_vote, k_near = _guide_counts((k_vote, k_near), "vote_neighbors: k_vote, k_near")
+    if not torch.is_tensor(votes) or votes.dtype != torch.float32 or votes.device != batch.seg.device:
+        raise ValueError("vote_neighbors: votes must be a float32 tensor on the batch's device")
+    votes = votes.reshape(-1)
+    if votes.numel() != batch.M or not votes.is_contiguous():
+        raise ValueError("vote_neighbors: one contiguous vote per edge (%d), got %d" % (batch.M, votes.numel()))
+    vseg, n_max = _vseg(batch, n_vertices)
+    dev = batch.seg.device
+    tab = torch.empty((batch.N, k_vote + k_near), dtype=torch.uint8, device=dev)
+    uv, wc = batch.adj.uv, batch.WC
+    rowptr, eid = batch.adj.csr_t[0], batch.adj.csr_t[1]
+    if batch.M == 0:   # no edge anywhere: the kernel reads none of the four, but refuses null pointers
+        votes = torch.zeros(1, dtype=torch.float32, device=dev)
+        uv = torch.zeros((1, 2), dtype=torch.int32, device=dev)
+        wc = torch.zeros((1, 2), dtype=torch.float32, device=dev)
+        eid = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.call("tspgnn_vote_neighbors", _lib.ptr(votes), _lib.ptr(uv), _lib.ptr(wc), _lib.ptr(batch.seg),
+                  _lib.ptr(vseg), _lib.ptr(rowptr), _lib.ptr(eid), batch.B, n_max, k_vote, k_near, _lib.ptr(tab),
+                  _lib.current_stream())
+    return tab
+
+
 def edge_scores(votes):
     """tspgnn_vote_scores_i32 on a float32 device tensor of votes, on the current stream: q(v) = clamp(rint(65536
     logsigmoid(v)), -2^22, 0) -> int32 tensor of the same length (NaN -> -2^22).  Does not wait for the device."""
@@ -181,9 +231,10 @@ def beam_tours(batch, scores, beam, select="score", n_vertices=None, workspace_b
     return BeamBatch(tours, costs, n_missing, out_scores, n_closed, vseg)
 
 
-def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="score", workspace_bytes=None):
-    """[(tour, cost, n_missing, prediction, score, n_closed)] of one batch: pack at the targets, forward, decode, one
-    read-back.  beam None: the greedy decoder, score and n_closed None."""
+def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="score", workspace_bytes=None, guide=None):
+    """[(tour, cost, n_missing, prediction, score, n_closed, table)] of one batch: pack at the targets, forward, decode,
+    one read-back.  beam None: the greedy decoder, score and n_closed None.  guide = (k_vote, k_near): vote_neighbors
+    follows the forward on the same stream and table is the instance's uint8 [n, K] rows; otherwise None."""
     EV, W, C, route_exists, n_vertices, n_edges = InstanceLoader.create_batch(chunk, target_cost=0.0)
     C[:, 0] = np.repeat(np.asarray(targets, dtype=np.float64), n_edges)
     feed = {model["EV"]: EV, model["W"]: W, model["C"]: C, model["time_steps"]: time_steps,
@@ -193,23 +244,29 @@ def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="sc
 
     def run():
         out = sess.forward_device(b)
+        tab = None if guide is None else vote_neighbors(b, out["E_vote"], guide[0], guide[1], n_vertices)
         if beam is None:
-            return tours_from_votes(b, out["E_vote"], n_vertices), out["predictions"]
-        return beam_tours(b, edge_scores(out["E_vote"]), beam, select, n_vertices, workspace_bytes), out["predictions"]
+            return tours_from_votes(b, out["E_vote"], n_vertices), out["predictions"], tab
+        return (beam_tours(b, edge_scores(out["E_vote"]), beam, select, n_vertices, workspace_bytes), out["predictions"],
+                tab)
 
-    dec, pred = sess._on_bf16x3_if_flagged(run)   # (one synchronising look at the f16x2 range guard)
+    dec, pred, tab = sess._on_bf16x3_if_flagged(run)   # (one synchronising look at the f16x2 range guard)
     tours, costs = dec.tours.cpu().numpy(), dec.costs.cpu().numpy()
     missing, pred = dec.n_missing.cpu().numpy(), pred.cpu().numpy()
     v0 = np.concatenate([[0], np.cumsum(n_vertices)])
     extra = [(None, None)] * len(chunk)
     if beam is not None:
         extra = list(zip((int(s) for s in dec.scores.cpu().numpy()), (int(c) for c in dec.n_closed.cpu().numpy())))
+    tabs = [None] * len(chunk)
+    if tab is not None:
+        tab = tab.cpu().numpy()
+        tabs = [tab[v0[i]:v0[i + 1]] for i in range(len(chunk))]
     return [([int(v) for v in tours[v0[i]:v0[i + 1]]], float(costs[i]), int(missing[i]), float(pred[i])) + extra[i]
-            for i in range(len(chunk))]
+            + (tabs[i],) for i in range(len(chunk))]
 
 
 def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=False, max_graphs=None, beam=None,
-                 select="score", workspace_bytes=None, **search_kw):
+                 select="score", workspace_bytes=None, guide=None, **search_kw):
     """A tour per instance from the network's edge votes.
 
     instances: list of (Ma, Mw, route) as for get_costs (4 <= n <= 256; the route is not used by the decoder).
@@ -220,11 +277,22 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
     polish=True hands the decoded tours to the tour search as its starting tours (label_tours with restarts=1, kicks=0,
     lower_bound=False: one descent from the network's tour on the penalised weights, which repairs an infeasible stitch
     where the graph allows); ``search_kw`` go to label_tours and may raise the restart and kick counts.
+    guide=K or (k_vote, k_near), with polish=True: the polish descends over candidate rows made from the votes --
+    vote_neighbors per chunk behind the forward, the rows read back with the tours, label_tours(candidates=rows) -- so it
+    may add only edges among a vertex's k_vote best-voted neighbours and the k_near nearest of the rest.  Exclusive with
+    ``neighbors`` in search_kw.  The records are unchanged.
     beam=None decodes by greedy edge insertion (tspgnn_tour_from_votes).  beam=K, 1 .. 1024, decodes by beam search
     instead: edge_scores and beam_tours per chunk, ``select`` "score" (the best-scoring closed tour of the last list) or
     "cost" (its cheapest), ``workspace_bytes`` beam_tours' cap; the records are then BeamTour, DecodedTour's fields
     followed by score and n_closed.
     Returns a list of DecodedTour (BeamTour with a beam) in input order."""
+    if guide is not None:
+        if not polish:
+            raise TypeError("decode_tours: guide only applies with polish=True")
+        if search_kw.get("neighbors") is not None or search_kw.get("candidates") is not None:
+            raise ValueError("decode_tours: guide and neighbors / candidates are exclusive: the polish descends over "
+                             "one candidate table")
+        guide = _guide_counts(guide, "decode_tours: guide")
     sess._require_gpu("decode_tours")
     instances = list(instances)
     for k, inst in enumerate(instances):
@@ -250,16 +318,18 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
     rows = []
     for start, stop in plan_chunks(len(instances), 1, DEFAULT_MAX_GRAPHS if max_graphs is None else max_graphs):
         rows += _decode_chunk(sess, model, instances[start:stop], targets[start:stop], time_steps, beam, select,
-                              workspace_bytes)
+                              workspace_bytes, guide)
     polished = [(None, None)] * len(instances)
     if polish and instances:
         from .dataset import label_tours
         kw = dict(restarts=1, kicks=0, lower_bound=False)
         kw.update(search_kw)
+        if guide is not None:
+            kw["candidates"] = [r[6] for r in rows]
         res = label_tours([(x[0], x[1]) for x in instances], init_tours=[r[0] for r in rows], device=sess.device, **kw)
         polished = [(r.tour, r.cost) for r in res]
     if beam is None:
         return [DecodedTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1])
-                for (tour, cost, missing, pred, _, _), target, p in zip(rows, targets, polished)]
+                for (tour, cost, missing, pred, _, _, _), target, p in zip(rows, targets, polished)]
     return [BeamTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1], score, closed)
-            for (tour, cost, missing, pred, score, closed), target, p in zip(rows, targets, polished)]
+            for (tour, cost, missing, pred, score, closed, _), target, p in zip(rows, targets, polished)]
