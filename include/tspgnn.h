@@ -684,30 +684,42 @@ int tspgnn_tour_anneal_tri(const float* W, const long long* w_off, const int* n,
 /* ------------------------------------------------------------------ tours from the edge votes (tspgnn/decode.py) */
 
 /*
- * A tour per instance from the network's per-edge logits (E_vote, model.py:106-128), one workgroup per instance, reading
- * the batch as Session.prepare / DeviceDataset.batch leave it on the device: vote:[M] fp32; uv:[M][2] the global endpoint
- * ids; wc:[M][2], column 0 the edge weight; seg:[B+1] the edge prefix sums; vseg:[B+1] the vertex prefix sums.  Instance b
- * has n = vseg[b+1] - vseg[b] vertices and the edges e = 0 .. m-1 of seg[b] .. seg[b+1], endpoints in local ids
- * uv - vseg[b].  4 <= n <= n_max <= 256.  The result is exactly this sequential process:
- *   Key.     k(e) = 0 for a NaN vote; otherwise the order-preserving uint32 image of the fp32 vote: all bits flipped when
- *            the sign bit is set, else the sign bit set (-0.0 < +0.0, -inf the lowest number, NaN below everything).
- *            Edge e precedes edge f iff k(e) > k(f), or k(e) == k(f) and e < f.
+ * tspgnn_tour_from_votes, tspgnn_tour_beam and tspgnn_vote_neighbors read the network's per-edge logits (E_vote,
+ * model.py:106-128) of a batch as Session.prepare / DeviceDataset.batch leave it on the device, one workgroup per
+ * instance.  What the three have in common is stated here once:
+ *   Batch.  vote:[M] fp32; uv:[M][2] the global endpoint ids; wc:[M][2], column 0 the edge weight; seg:[B+1] the edge
+ *           prefix sums; vseg:[B+1] the vertex prefix sums.  Instance b has n = vseg[b+1] - vseg[b] vertices and the edges
+ *           e = 0 .. m-1 of seg[b] .. seg[b+1], endpoints in local ids uv - vseg[b].  4 <= n <= n_max <= 256.
+ *   Pairs.  An edge joins its local endpoints a and b only when both lie in [0, n) and a != b; any other edge joins
+ *           nothing.  For an unordered pair {a, b}: e(a,b) is the smallest edge id joining it, or none, and
+ *           w(a,b) = wc[e(a,b)][0].
+ *   Key.    The order-preserving uint32 image of an fp32 value: all bits flipped when the sign bit is set, else the sign
+ *           bit set, so -0.0 < +0.0 and -inf is the lowest number.  The vote key gives a NaN the image 0, below
+ *           everything; the ascending key of costs and weights gives it 0xffffffff, after every number.
+ *   Tour.   tours + vseg[b]: the cyclic sequence in canonical form (tour[0] = 0, tour[1] < tour[n-1]), local ids.
+ *           n_missing[b]: the cyclically consecutive pairs that no edge joins (0: a feasible tour).  costs[b]: one running
+ *           fp32 sum from 0 in canonical tour order, the closing pair last, of w over the pairs that are edges; additions
+ *           only, no FMA.
+ *   Checks. B == 0 is a no-op; n_max > 256: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4 or a null pointer with B > 0:
+ *           TSPGNN_EINVAL; all before any launch, the outputs untouched.  The arrays live on the device, so an entry point
+ *           cannot see them: what an instance with n outside [4, n_max] gets is said with each.
+ * A result depends on the instance and its votes (and the arguments named) alone: never on n_max, on the other instances
+ * or on the launch.  No kernel communicates between workgroups.
+ */
+
+/*
+ * A tour per instance from the votes by greedy edge insertion.  The result is exactly this sequential process:
+ *   Order.   Edge e precedes edge f iff its vote key is larger, or the keys are equal and e < f.
  *   Greedy.  Every vertex starts with degree 0 in a component of its own.  Until no edge is eligible: take the first
- *            eligible edge in the order above, add it, raise both degrees, merge the components.  Eligible: both
- *            endpoints have degree < 2 and lie in different components (never an edge with an endpoint outside [0, n) or
- *            with equal endpoints).  Eligibility only shrinks, so this equals one pass over the sorted list; the kernel
- *            takes a workgroup-wide arg-max over (key, edge id) per round and sorts nothing.
+ *            eligible edge in the order above, add it, raise both degrees, merge the components.  Eligible: the edge joins
+ *            its endpoints (Pairs), both have degree < 2 and they lie in different components.  Eligibility only shrinks,
+ *            so this equals one pass over the sorted list; the kernel takes a workgroup-wide arg-max over (key, edge id)
+ *            per round and sorts nothing.
  *   Stitch.  The chosen edges form vertex-disjoint paths, an untouched vertex being a path of one.  Each path starts at
  *            its endpoint of smaller id; the paths are ordered by their smallest vertex id and concatenated.
- *   Output.  tours + vseg[b]: the cyclic sequence in canonical form (tour[0] = 0, tour[1] < tour[n-1]), local ids.
- *            n_missing[b]: the cyclically consecutive pairs that no edge of the instance joins (0: a feasible tour).
- *            costs[b]: the fp32 sum, from 0, in tour order with the closing pair last, of the weights of the pairs that
- *            are edges (of several edges joining one pair, the one of smallest id); additions only, no FMA.
- * The result depends on the instance and its votes alone, never on n_max, on the other instances or on the launch.  An
- * instance with m == 0 gets the identity tour, n_missing = n and cost 0.  The arrays live on the device, so this entry
- * point cannot see them: an instance with n outside [4, 256] gets costs[b] = NaN, n_missing[b] = -1 and no tour.
- * B == 0 is a no-op; n_max > 256: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4 or a null pointer with B > 0: TSPGNN_EINVAL before
- * any launch, the outputs untouched.
+ *   Output.  tours, n_missing and costs as under Tour.
+ * An instance with m == 0 gets the identity tour, n_missing = n and cost 0; one with n outside [4, 256] gets
+ * costs[b] = NaN, n_missing[b] = -1 and no tour.
  */
 int tspgnn_tour_from_votes(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
                            int B, int n_max, int32_t* tours, float* costs, int32_t* n_missing, void* stream);
@@ -727,13 +739,10 @@ int tspgnn_vote_scores_i32(const float* vote, long long M, int32_t* score, void*
 long long tspgnn_tour_beam_workspace_bytes(int B, int n_max, int beam);
 
 /*
- * A tour per instance by beam search over integer edge scores, one workgroup per instance.  The batch is read exactly as
- * tspgnn_tour_from_votes reads it (uv, wc, seg, vseg; local ids uv - vseg[b]; 4 <= n <= n_max <= 256), with score:[M] int32
- * in place of the votes (tspgnn_vote_scores_i32, or any integers: they are clamped to [-2^22, 0] on input).  beam: the
- * width, 1 .. 1024; select: 0 = by score, 1 = by cost.  The result is exactly this sequential process on instance b:
- *   Pairs.    For an unordered pair {a, b}, a != b, both in [0, n): e(a,b) is the smallest edge id joining the pair, or
- *             none (an edge with an endpoint outside [0, n), or with equal endpoints, joins nothing);
- *             q(a,b) = clamp(score[e(a,b)], -2^22, 0); w(a,b) = wc[e(a,b)][0].
+ * A tour per instance by beam search over integer edge scores: the batch as above, with score:[M] int32 in place of the
+ * votes (tspgnn_vote_scores_i32, or any integers: they are clamped to [-2^22, 0] on input, q(a,b) =
+ * clamp(score[e(a,b)], -2^22, 0)).  beam: the width, 1 .. 1024; select: 0 = by score, 1 = by cost.  The result is exactly
+ * this sequential process on instance b:
  *   Lists.    L_0 = [(path [0], S = 0)].  For k = 0 .. n-2 the candidates of L_k are all (i, u) with i an index into L_k,
  *             u not on path i, and e(last_i, u) existing; candidate (i, u) carries the score S_i + q(last_i, u).
  *             Candidates are ordered by score descending, then i ascending, then u ascending (a strict total order);
@@ -743,52 +752,41 @@ long long tspgnn_tour_beam_workspace_bytes(int B, int n_max, int beam);
  *             vertices in ascending id; scores[b] = S of that entry and n_closed[b] = 0.
  *   Final.    Otherwise every entry i of L_{n-1} is a Hamiltonian path.  closed_i: e(last_i, 0) exists.
  *             F_i = S_i + q(last_i, 0) if closed, else S_i.  C_i = the fp32 cost of the entry's tour in canonical form,
- *             summed as costs[b] below.  select = 0: the chosen entry is the first by (closed first, F descending, i
- *             ascending); select = 1: the first by (closed first, C ascending, i ascending), C compared as fp32 numbers
- *             (-0.0 before +0.0, a NaN after every number).  scores[b] = F of the chosen entry; n_closed[b] = the number
- *             of closed entries.
- *   Output.   tours + vseg[b]: the tour in canonical form (tour[0] = 0, tour[1] < tour[n-1]), local ids.  n_missing[b]:
- *             the cyclically consecutive pairs that no edge joins.  costs[b]: one running fp32 sum from 0 in canonical
- *             tour order, the closing pair last, of w over the pairs that are edges; additions only, no FMA.
- * The result depends on the instance, its scores, beam and select alone: never on n_max, on the other instances, on the
- * workgroup shape (256 / 512 / 1024 threads for n_max <= 64 / 128 / 256) or on what the workspace held before the launch.
- * beam = 1 is the walk from vertex 0 to the best-scoring unvisited neighbour; an instance with m == 0 gets the identity
- * tour, n_missing = n, cost 0 and score 0.  The kernel takes an exact top-`beam` per step: a radix select on the composite
- * key (-score, i, u) and a sort of the survivors; it runs n - 1 steps and has no communication between workgroups.
+ *             summed as costs[b].  select = 0: the chosen entry is the first by (closed first, F descending, i
+ *             ascending); select = 1: the first by (closed first, ascending key of C, i ascending).  scores[b] = F of the
+ *             chosen entry; n_closed[b] = the number of closed entries.
+ *   Output.   tours, n_missing and costs as under Tour.
+ * The result depends on beam and select as well, but not on the workgroup shape (256 / 512 / 1024 threads for n_max <= 64
+ * / 128 / 256) or on what the workspace held before the launch.  beam = 1 is the walk from vertex 0 to the best-scoring
+ * unvisited neighbour; an instance with m == 0 gets the identity tour, n_missing = n, cost 0 and score 0.  The kernel
+ * takes an exact top-`beam` per step: a radix select on the composite key (-score, i, u) and a sort of the survivors; it
+ * runs n - 1 steps.
  * workspace: 16-byte aligned device memory of at least tspgnn_tour_beam_workspace_bytes(B, n_max, beam) bytes, contents
- * irrelevant.  The arrays live on the device, so this entry point cannot see them: an instance with n outside [4, n_max]
- * gets costs[b] = NaN, n_missing[b] = -1, scores[b] = 0, n_closed[b] = -1 and no tour.
- * B == 0 is a no-op; n_max > 256 or beam > 1024: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4, beam < 1, select outside {0, 1},
- * a null pointer or a workspace that is short or misaligned: TSPGNN_EINVAL; all before any launch, the outputs untouched.
+ * irrelevant.  An instance with n outside [4, n_max] gets costs[b] = NaN, n_missing[b] = -1, scores[b] = 0,
+ * n_closed[b] = -1 and no tour.
+ * Beyond Checks: beam > 1024: TSPGNN_EUNSUPPORTED; beam < 1, select outside {0, 1} or a workspace that is short or
+ * misaligned: TSPGNN_EINVAL.
  */
 int tspgnn_tour_beam(const int32_t* score, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
                      int B, int n_max, int beam, int select, void* workspace, long long workspace_bytes, int32_t* tours,
                      float* costs, int32_t* n_missing, int32_t* scores, int32_t* n_closed, void* stream);
 
 /*
- * Candidate rows for tspgnn_tour_search_cand from the network's edge votes, one workgroup per instance.  The batch is read
- * exactly as tspgnn_tour_from_votes reads it (vote, uv, wc, seg, vseg; local ids uv - vseg[b]; 4 <= n <= n_max <= 256),
- * and with it the vertex CSR the batch carries: rowptr:[N+1] int32, and eid row g = the ids of the edges that list global
- * vertex g as an endpoint.  tab: uint8 [N][K], K = k_vote + k_near; row vseg[b] + x is the candidate row of local vertex
- * x of instance b.  The result is exactly this sequential process on instance b and its vertex x:
- *   Pairs.  For y != x in [0, n): e(x,y) is the smallest edge id in CSR row x that joins x and y, or none.  An id of the
- *           row joins x to the other endpoint of that edge; it joins nothing when it lies outside seg[b] .. seg[b+1], when
- *           the edge does not list x, or when the other endpoint is x or lies outside [0, n).  v(x,y) = vote[e(x,y)] and
- *           w(x,y) = wc[e(x,y)][0].  The result depends on the set of edge ids in a row, not on their order.  The
- *           neighbours of x are the y for which e(x,y) exists.
+ * Candidate rows for tspgnn_tour_search_cand from the votes: the batch as above, and with it the vertex CSR the batch
+ * carries: rowptr:[N+1] int32, and eid row g = the ids of the edges that list global vertex g as an endpoint.  tab: uint8
+ * [N][K], K = k_vote + k_near; row vseg[b] + x is the candidate row of local vertex x of instance b.  The result is exactly
+ * this sequential process on instance b and its vertex x:
+ *   Row.    Pairs, read through CSR row x: e(x,y) is the smallest id in the row that joins x and y.  An id joins nothing
+ *           when it lies outside seg[b] .. seg[b+1] or when the edge does not list x.  Only the set of ids in the row
+ *           matters, not their order.  v(x,y) = vote[e(x,y)]; the neighbours of x are the y for which e(x,y) exists.
  *   Vote.   For s = 0 .. k_vote-1: among the neighbours of x not yet in the row, take the first by (vote key of v(x,y)
- *           descending, y ascending); the key is tspgnn_tour_from_votes' (-0.0 < +0.0, -inf the lowest number, NaN below
- *           everything).  Write y to slot s.  If no neighbour is left, write x ("skip", which tspgnn_tour_search_cand
- *           ignores).
- *   Near.   For s = k_vote .. K-1: among the neighbours not yet in the row, take the first by (weight key of w(x,y)
- *           ascending, y ascending): the same order-preserving image of the fp32 bits, a NaN weight coming last.  Write
- *           y to slot s; if no neighbour is left, write x.
- * A row depends on the instance, its votes and weights alone: never on n_max, on the other instances or on the launch.
+ *           descending, y ascending).  Write y to slot s.  If no neighbour is left, write x ("skip", which
+ *           tspgnn_tour_search_cand ignores).
+ *   Near.   For s = k_vote .. K-1: among the neighbours not yet in the row, take the first by (ascending key of w(x,y), y
+ *           ascending), a NaN weight coming last.  Write y to slot s; if no neighbour is left, write x.
  * The kernel resolves multi-edges by an atomic minimum in LDS, then takes K wave-wide arg-max rounds per vertex; it sorts
- * nothing, needs no workspace and has no communication between workgroups.  The arrays live on the device, so this entry
- * point cannot see them: an instance with n outside [4, n_max] gets its rows zero-filled.
- * B == 0 is a no-op; n_max > 256: TSPGNN_EUNSUPPORTED; B < 0, n_max < 4, k_vote < 0, k_near < 0, K outside [1, 32] or a
- * null pointer with B > 0: TSPGNN_EINVAL; all before any launch, the outputs untouched.
+ * nothing and needs no workspace.  An instance with n outside [4, n_max] gets its rows zero-filled.
+ * Beyond Checks: k_vote < 0, k_near < 0 or K outside [1, 32]: TSPGNN_EINVAL.
  */
 int tspgnn_vote_neighbors(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg, const int32_t* vseg,
                           const int32_t* rowptr, const int32_t* eid, int B, int n_max, int k_vote, int k_near,

@@ -6,26 +6,9 @@
 // in fp64, rounded half to even; NaN gives -2^22.  A tour has at most 256 edges, so every sum of scores lies in
 // [-2^30, 0]: exact integer arithmetic that a restatement reproduces bit for bit.
 //
-// The result of tspgnn_tour_beam is DEFINED as this sequential process over instance b (n vertices in local ids, the
-// edges e = 0 .. m-1 of seg[b] .. seg[b+1]):
-//   Pairs.    For an unordered pair {a, b}, a != b, both in [0, n): e(a,b) is the smallest edge id joining the pair, or
-//             none (an edge with an endpoint outside [0, n), or with equal endpoints, joins nothing);
-//             q(a,b) = clamp(score[e(a,b)], -2^22, 0); w(a,b) = wc[e(a,b)][0].
-//   Lists.    L_0 = [(path [0], S = 0)].  For k = 0 .. n-2 the candidates of L_k are all (i, u): i an index into L_k, u
-//             not on path i, e(last_i, u) exists; candidate (i, u) has the score S_i + q(last_i, u).  Candidates are
-//             ordered by score descending, then i ascending, then u ascending, a strict total order, and L_{k+1} is the
-//             first min(beam, #candidates) of them, in that order.
-//   Stranded. L_{k+1} empty: the tour is the path of L_k[0] followed by the unvisited vertices in ascending id;
-//             scores[b] = S of that entry, n_closed[b] = 0.
-//   Final.    Otherwise every entry i of L_{n-1} is a Hamiltonian path; closed_i: e(last_i, 0) exists;
-//             F_i = S_i + q(last_i, 0) if closed, else S_i; C_i = the fp32 cost of the entry's tour, summed as `costs`
-//             below.  select = 0: the chosen entry is the first by (closed first, F descending, i ascending); select = 1:
-//             by (closed first, C ascending, i ascending), C compared as fp32 numbers with -0.0 before +0.0 and a NaN
-//             after every number.  scores[b] = F of the chosen entry, n_closed[b] = the number of closed entries.
-//   Output.   As tspgnn_tour_from_votes: the tour in canonical form (tour[0] = 0, tour[1] < tour[n-1]); n_missing[b] the
-//             cyclically consecutive pairs that no edge joins; costs[b] one running fp32 sum from 0 in canonical tour
-//             order, the closing pair last, over the pairs that are edges; additions only, no FMA.
-// The result depends on the instance, its scores, beam and select alone: never on n_max, on the other instances, on the
+// include/tspgnn.h DEFINES the result of tspgnn_tour_beam as a sequential process: the batch, the pairs e(a,b), the
+// ascending key and the tour's outputs under "tours from the edge votes", then this entry point's Lists, Stranded and
+// Final.  It depends on the instance, its scores, beam and select alone: never on n_max, on the other instances, on the
 // workgroup shape or on what the workspace held.
 //
 // Layout.  One workgroup per instance: 256 / 512 / 1024 threads and visited masks of 1 / 2 / 4 64-bit words for
@@ -35,7 +18,7 @@
 // buffer of n_max x beam bytes for the costs of select = 1.  LDS holds the two lists (S, last vertex, mask per entry,
 // double-buffered), the 2 048-bin histogram of the radix select and the at most `beam` keys of the chosen candidates.
 // A step is an exact top-`beam` under the composite key (-score) << 18 | i << 8 | u (49 bits, ascending = the order
-// above, all keys distinct).  The candidates are never stored: every pass recomputes them from the lists and the q table,
+// of Lists, all keys distinct).  The candidates are never stored: every pass recomputes them from the lists and the q table,
 // a wave taking entries and its lanes the vertices.  The first pass finds their number and the smallest and largest key
 // (register minima, one LDS atomic each per wave).  With more candidates than `beam`, a radix select of 11 bits per pass
 // on key - smallest, starting at the digit that holds the highest bit of the span, finds the threshold; it ends as soon
@@ -47,14 +30,13 @@
 // Termination: n - 1 steps of at most 7 passes over the candidates; every loop is bounded by n, beam, m or the 2 048
 // bins; the trace walks take at most n steps.  No communication between workgroups.  Contraction is off as in
 // tour_decode.hip.
-#include "tour_common.h"
+#include "vote_common.h"
 
 #pragma clang fp contract(off)
 
 namespace tspgnn {
 namespace {
 
-constexpr int kBeamMaxN = 256;
 constexpr int kBeamMax = 1024;
 constexpr int kScoreMin = -(1 << 22);
 constexpr int kNoPair = INT_MIN;      // q table: no edge joins the pair
@@ -77,13 +59,6 @@ __global__ __launch_bounds__(256) void vote_scores_kernel(const float* __restric
 
 __host__ __device__ inline int clamp_score(int s) { return s < kScoreMin ? kScoreMin : (s > 0 ? 0 : s); }
 
-// order-preserving image of an fp32 cost: ascending numbers, -0.0 before +0.0, a NaN after everything
-__device__ __forceinline__ uint32_t cost_key(float c) {
-    const uint32_t b = __float_as_uint(c);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // per-instance workspace: the q table, the w table, the trace, the path buffer, each from a 16-byte boundary
 struct BeamWs {
     size_t table, trace, path, total;
@@ -104,7 +79,7 @@ inline int pow2_at_least(int x) {
     return p;
 }
 inline size_t beam_lds_bytes(int P, int W) {
-    return (size_t)P * 8 + (size_t)2 * P * W * 8 + (size_t)4 * P * 4 + kBins * 4 + 3 * kBeamMaxN * 4;
+    return (size_t)P * 8 + (size_t)2 * P * W * 8 + (size_t)4 * P * 4 + kBins * 4 + 3 * kVoteMaxN * 4;
 }
 
 template <int NT, int W>
@@ -124,8 +99,8 @@ __global__ __launch_bounds__(NT) void tour_beam_kernel(const int32_t* __restrict
     int* s_last = s_S + 2 * P;                                          // [2][P]
     unsigned* s_hist = reinterpret_cast<unsigned*>(s_last + 2 * P);     // [kBins]
     int* s_seq = reinterpret_cast<int*>(s_hist + kBins);                // [256] the chosen path, then the tour
-    float* s_w = reinterpret_cast<float*>(s_seq + kBeamMaxN);           // [256] weight of pair k
-    int* s_ex = reinterpret_cast<int*>(s_w + kBeamMaxN);                // [256] pair k is an edge
+    float* s_w = reinterpret_cast<float*>(s_seq + kVoteMaxN);           // [256] weight of pair k
+    int* s_ex = reinterpret_cast<int*>(s_w + kVoteMaxN);                // [256] pair k is an edge
     __shared__ int s_ctl[3];                                            // bin, below, count of a pass
     __shared__ unsigned s_cnt;
     __shared__ unsigned long long s_best, s_worst;
@@ -133,14 +108,13 @@ __global__ __launch_bounds__(NT) void tour_beam_kernel(const int32_t* __restrict
 
     const int inst = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int v0 = vseg[inst], n = vseg[inst + 1] - v0;
-    const long long e0 = seg[inst];
-    const long long m = (long long)seg[inst + 1] - e0;
+    const VoteInstance I(uv, seg, vseg, inst);
+    const int v0 = I.v0, n = I.n;
+    const long long e0 = I.e0, m = I.m;
     // the host module never sends these; a defensive no-op keeps every LDS and workspace index in bounds
-    if (n < 4 || n > kBeamMaxN || n > stride || n > 64 * W || m < 0) {
+    if (n < 4 || n > kVoteMaxN || n > stride || n > 64 * W || m < 0) {
         if (tid == 0) {
-            costs[inst] = __int_as_float(0x7fc00000);
-            n_missing[inst] = -1;
+            refuse_tour(costs + inst, n_missing + inst);
             scores[inst] = 0;
             n_closed[inst] = -1;
         }
@@ -152,18 +126,16 @@ __global__ __launch_bounds__(NT) void tour_beam_kernel(const int32_t* __restrict
     float* wtab = reinterpret_cast<float*>(ws + ws_table);
     uint32_t* trace = reinterpret_cast<uint32_t*>(ws + 2 * ws_table);
     unsigned char* pathbuf = ws + 2 * ws_table + ws_trace;
-    const int32_t* ep = uv + 2 * e0;
 
     // ---- the pair tables: smallest edge id per pair, then its clamped score and its weight
     for (int x = tid; x < n * n; x += NT) etab[(x / n) * stride + x % n] = INT_MAX;
     __threadfence();
     __syncthreads();
     for (long long e = tid; e < m; e += NT) {
-        const int a = ep[2 * e] - v0, b = ep[2 * e + 1] - v0;
-        if (a >= 0 && a < n && b >= 0 && b < n && a != b) {
+        I.with_ends(e, [&](int a, int b) {
             atomicMin(&etab[a * stride + b], (int)e);
             atomicMin(&etab[b * stride + a], (int)e);
-        }
+        });
     }
     __threadfence();
     __syncthreads();
@@ -394,12 +366,12 @@ __global__ __launch_bounds__(NT) void tour_beam_kernel(const int32_t* __restrict
                 float c = 0.f;
                 int a = 0;
                 for (int p = 1; p < n; ++p) {
-                    const int b = pathbuf[(size_t)(fwd ? p : n - p) * beam + j];
+                    const int b = pathbuf[(size_t)canonical_index_from0(fwd, p, n) * beam + j];
                     if (qtab[a * stride + b] != kNoPair) c += wtab[a * stride + b];
                     a = b;
                 }
                 if (qtab[a * stride] != kNoPair) c += wtab[a * stride];
-                key |= (unsigned long long)cost_key(c) << 10;
+                key |= (unsigned long long)ordered_key(c, kNanHighest) << 10;   // ascending, a NaN after every number
             }
             atomicMin(&s_best, key | (unsigned long long)j);
             if (closed) atomicAdd(&s_nclosed, 1);
@@ -420,11 +392,11 @@ __global__ __launch_bounds__(NT) void tour_beam_kernel(const int32_t* __restrict
     }
     __syncthreads();
 
-    // ---- canonical form, the pairs that are edges, the cost: as tour_from_votes_kernel
+    // ---- canonical form (the path starts at vertex 0), the pairs that are edges, the cost
     const bool fwd = s_seq[1] < s_seq[n - 1];
-    int mine[kBeamMaxN / 64];   // tour[tid], tour[tid + NT], ...: at most 256 / 256 = 1 .. 4 entries for NT >= 256
+    int mine[kVoteMaxN / 64];   // tour[tid], tour[tid + NT], ...: at most 256 / 256 = 1 .. 4 entries for NT >= 256
     int cnt = 0;
-    for (int p = tid; p < n; p += NT) mine[cnt++] = s_seq[p == 0 ? 0 : (fwd ? p : n - p)];
+    for (int p = tid; p < n; p += NT) mine[cnt++] = s_seq[p == 0 ? 0 : canonical_index_from0(fwd, p, n)];
     __syncthreads();
     cnt = 0;
     int32_t* out = tours + v0;
@@ -440,13 +412,8 @@ __global__ __launch_bounds__(NT) void tour_beam_kernel(const int32_t* __restrict
     }
     __syncthreads();
     if (tid == 0) {
-        float cost = 0.f;
-        int missing = 0;
-        for (int p = 0; p < n; ++p) {
-            if (s_ex[p]) cost += s_w[p];
-            else ++missing;
-        }
-        costs[inst] = cost;
+        int missing;
+        costs[inst] = sum_tour_pairs(n, [&](int p) { return s_ex[p] != 0; }, s_w, missing);
         n_missing[inst] = missing;
         scores[inst] = score_out;
         n_closed[inst] = closed_out;
@@ -482,7 +449,7 @@ extern "C" int tspgnn_vote_scores_i32(const float* vote, long long M, int32_t* s
 }
 
 extern "C" long long tspgnn_tour_beam_workspace_bytes(int B, int n_max, int beam) {
-    if (B <= 0 || n_max < 4 || n_max > kBeamMaxN || beam < 1 || beam > kBeamMax) return 0;
+    if (B <= 0 || n_max < 4 || n_max > kVoteMaxN || beam < 1 || beam > kBeamMax) return 0;
     return (long long)B * (long long)beam_ws(n_max, beam).total;
 }
 
@@ -490,11 +457,8 @@ extern "C" int tspgnn_tour_beam(const int32_t* score, const int32_t* uv, const f
                                 const int32_t* vseg, int B, int n_max, int beam, int select, void* workspace,
                                 long long workspace_bytes, int32_t* tours, float* costs, int32_t* n_missing,
                                 int32_t* scores, int32_t* n_closed, void* stream) {
-    TSPGNN_REQUIRE(B >= 0, "tour_beam: B=%d", B);
+    if (int rc = vote_entry("tour_beam", B, n_max, "beam", beam, kBeamMax)) return rc;
     if (B == 0) return TSPGNN_OK;
-    if (n_max > kBeamMaxN) return fail(TSPGNN_EUNSUPPORTED, "tour_beam: n_max=%d exceeds %d", n_max, kBeamMaxN);
-    if (beam > kBeamMax) return fail(TSPGNN_EUNSUPPORTED, "tour_beam: beam=%d exceeds %d", beam, kBeamMax);
-    TSPGNN_REQUIRE(n_max >= 4, "tour_beam: n_max=%d must be at least 4", n_max);
     TSPGNN_REQUIRE(beam >= 1, "tour_beam: beam=%d must be at least 1", beam);
     TSPGNN_REQUIRE(select == 0 || select == 1, "tour_beam: select=%d is neither 0 (score) nor 1 (cost)", select);
     TSPGNN_REQUIRE(score && uv && wc && seg && vseg && workspace && tours && costs && n_missing && scores && n_closed,

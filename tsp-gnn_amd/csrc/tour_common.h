@@ -1,6 +1,7 @@
 // Device and host helpers shared by the tour kernels (tour_search.hip, tour_baselines.hip, tour_exact.hip): the two LDS
-// layouts of an instance's weights, the counter-based generator, the wave reductions, the canonical write-out, the LDS
-// budget, and the Held-Karp 1-tree with its subgradient ascent (the bound kernel and the branch and bound).
+// layouts of an instance's weights, the counter-based generator, the wave reductions, the canonical form and its
+// write-out, the LDS budget, and the Held-Karp 1-tree with its subgradient ascent (the bound kernel and the branch and
+// bound).  What only the readers of the edge votes share sits on top of this header, in vote_common.h.
 #pragma once
 #include "common.h"
 
@@ -100,7 +101,19 @@ __device__ __forceinline__ float tour_cost(const WA& W, const int* t, int n, int
     return wave_sum(acc);
 }
 
-// One wave writes tour t (LDS) to out in canonical form: starts at vertex 0, tour[1] < tour[n-1].
+// Canonical form of a cyclic sequence of n vertices (starts at vertex 0, tour[1] < tour[n-1]): where its entry k sits in
+// the sequence, p0 being the position of vertex 0 and fwd saying that p0's successor is smaller than its predecessor.
+__device__ __forceinline__ int canonical_index(int p0, bool fwd, int k, int n) {
+    int q = fwd ? p0 + k : p0 - k;
+    if (q >= n) q -= n;
+    if (q < 0) q += n;
+    return q;
+}
+
+// The same for a sequence that starts at vertex 0 (p0 = 0), k in [1, n); entry 0 is entry 0.
+__device__ __forceinline__ int canonical_index_from0(bool fwd, int k, int n) { return fwd ? k : n - k; }
+
+// One wave writes tour t (LDS) to out in canonical form.
 __device__ __forceinline__ void write_canonical(const int* t, int n, int32_t* out, int lane) {
     int p0 = 0;
     for (int k = lane; k < n; k += kWave)
@@ -108,20 +121,7 @@ __device__ __forceinline__ void write_canonical(const int* t, int n, int32_t* ou
     p0 = wave_sum(p0);   // exactly one lane holds the position of vertex 0
     const int nxt = t[p0 + 1 < n ? p0 + 1 : 0], prv = t[p0 > 0 ? p0 - 1 : n - 1];
     const bool fwd = nxt < prv;
-    for (int k = lane; k < n; k += kWave) {
-        int q = fwd ? p0 + k : p0 - k;
-        if (q >= n) q -= n;
-        if (q < 0) q += n;
-        out[k] = t[q];
-    }
-}
-
-// The decoders' vote key (tour_decode.hip, tour_guided.hip): 0 for a NaN, otherwise the order-preserving uint32 image of
-// the fp32 value -- all bits flipped when the sign bit is set, else the sign bit set.  Larger key = larger vote.
-__device__ __forceinline__ uint32_t vote_key(float vote) {
-    const uint32_t b = __float_as_uint(vote);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0u;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    for (int k = lane; k < n; k += kWave) out[k] = t[canonical_index(p0, fwd, k, n)];
 }
 
 // Wave-wide minimum of an int; every lane gets it.

@@ -1,26 +1,10 @@
 // tspgnn_tour_from_votes (tspgnn/decode.py): a tour per instance from the network's per-edge logits, E_vote of
 // model.py:106-128, which the reference only ever averages (figures/route-examples.png draws them over the optimal
 // route).  One workgroup per instance, reading the batch as it lies on the device after Session.prepare /
-// DeviceDataset.batch: vote[M], the global endpoint ids uv[M][2], wc[M][2] (column 0 the edge weight), the edge prefix
-// sums seg[B+1] and the vertex prefix sums vseg[B+1].  No dense matrix, no host pass.
-//
-// The result is DEFINED as this sequential process over instance b (n = vseg[b+1] - vseg[b] vertices, the edges
-// e = 0 .. m-1 of seg[b] .. seg[b+1], endpoints in local ids uv - vseg[b]):
-//   Key.     k(e) = 0 for a NaN vote; otherwise the order-preserving uint32 image of the fp32 vote: all bits flipped
-//            when the sign bit is set, else the sign bit set.  So -0.0 < +0.0, -inf is the lowest number and NaN lies
-//            below everything.  Edge e precedes edge f iff k(e) > k(f), or k(e) == k(f) and e < f.
-//   Greedy.  Every vertex starts with degree 0 in a component of its own.  Repeat until no edge is eligible: take the
-//            first eligible edge in the order above, add it, raise both degrees, merge the two components.  An edge is
-//            eligible when both endpoints have degree < 2 and lie in different components (an edge with an endpoint
-//            outside [0, n), or with two equal endpoints, never is).
-//   Stitch.  The chosen edges form vertex-disjoint paths, an untouched vertex being a path of one.  Each path is
-//            oriented to start at its endpoint of smaller id, the paths are ordered by their smallest vertex id, and
-//            they are concatenated.  (On a complete graph there is exactly one path, a Hamiltonian one.)
-//   Output.  tours + vseg[b]: the cyclic sequence in canonical form (tour[0] = 0, tour[1] < tour[n-1]), local ids.
-//            n_missing[b]: the cyclically consecutive pairs that no edge of the instance joins; 0 = a feasible tour.
-//            costs[b]: the fp32 sum, taken by one lane in tour order with the closing pair last and starting from 0,
-//            of the weights of the pairs that are edges (of several edges joining a pair, the one of smallest id).
-// The result depends on the instance and its votes alone: never on n_max, on the other instances or on the launch.
+// DeviceDataset.batch.  No dense matrix, no host pass.  include/tspgnn.h DEFINES the result as a sequential process: the
+// batch, the pair rule, the key and the tour's outputs under "tours from the edge votes", then this entry point's Order,
+// Greedy and Stitch.  It depends on the instance and its votes alone: never on n_max, on the other instances or on the
+// launch.
 //
 // Eligibility only ever shrinks -- degrees rise, components merge -- so "the first eligible edge in a fixed order,
 // repeated" is one pass over the sorted list, and equally a workgroup-wide arg-max over (key, edge id) per round: no
@@ -34,7 +18,7 @@
 // Termination: the greedy loop runs at most n rounds (each but the last adds an edge, and a forest has at most n - 1);
 // every path walk takes at most n steps.  There is no inter-workgroup communication.  Costs are plain fp32 additions
 // (no products, and contraction is off as in dataset_build.hip).
-#include "tour_common.h"
+#include "vote_common.h"
 
 #include <type_traits>
 
@@ -43,7 +27,6 @@
 namespace tspgnn {
 namespace {
 
-constexpr int kDecodeMaxN = 256;
 constexpr int kSlots = 32;   // edges a thread keeps in registers
 
 // f(integral_constant<int, j>) for j = J .. N-1.  The slot arrays below are indexed by these compile-time constants
@@ -75,33 +58,29 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
                                                              int32_t* __restrict__ tours, float* __restrict__ costs,
                                                              int32_t* __restrict__ n_missing) {
     constexpr int kWaves = NT / kWave;
-    __shared__ int s_state[kDecodeMaxN];
-    __shared__ int s_nb[2][kDecodeMaxN];     // the chosen edges: a vertex's neighbours, -1 = none
-    __shared__ int s_len[kDecodeMaxN];       // of the path that starts at this vertex; 0 = no path starts here
-    __shared__ int s_min[kDecodeMaxN];       // that path's smallest vertex id
-    __shared__ int s_seq[kDecodeMaxN];       // the stitched sequence
-    __shared__ int s_tour[kDecodeMaxN];      // ... in canonical form
-    __shared__ int s_pos[kDecodeMaxN];       // position of a vertex in s_seq, then in s_tour
-    __shared__ int s_edge[kDecodeMaxN];      // smallest edge id joining tour[k] and tour[k+1]; INT_MAX = none
-    __shared__ float s_w[kDecodeMaxN];
+    __shared__ int s_state[kVoteMaxN];
+    __shared__ int s_nb[2][kVoteMaxN];     // the chosen edges: a vertex's neighbours, -1 = none
+    __shared__ int s_len[kVoteMaxN];       // of the path that starts at this vertex; 0 = no path starts here
+    __shared__ int s_min[kVoteMaxN];       // that path's smallest vertex id
+    __shared__ int s_seq[kVoteMaxN];       // the stitched sequence
+    __shared__ int s_tour[kVoteMaxN];      // ... in canonical form
+    __shared__ int s_pos[kVoteMaxN];       // position of a vertex in s_seq, then in s_tour
+    __shared__ int s_edge[kVoteMaxN];      // smallest edge id joining tour[k] and tour[k+1]; INT_MAX = none
+    __shared__ float s_w[kVoteMaxN];
     __shared__ unsigned long long s_best[kWaves];
     __shared__ uint32_t s_pay[kWaves];
 
     const int inst = blockIdx.x;
     const int tid = threadIdx.x;
-    const int v0 = vseg[inst], n = vseg[inst + 1] - v0;
-    const long long e0 = seg[inst];
-    const long long m = (long long)seg[inst + 1] - e0;
+    const VoteInstance I(uv, seg, vseg, inst);
+    const int v0 = I.v0, n = I.n;
+    const long long e0 = I.e0, m = I.m;
     // the host module never sends these; a defensive no-op keeps every LDS index in bounds
-    if (n < 4 || n > kDecodeMaxN || m < 0) {
-        if (tid == 0) {
-            costs[inst] = __int_as_float(0x7fc00000);
-            n_missing[inst] = -1;
-        }
+    if (n < 4 || n > kVoteMaxN || m < 0) {
+        if (tid == 0) refuse_tour(costs + inst, n_missing + inst);
         return;
     }
     const float* vt = vote + e0;
-    const int32_t* ep = uv + 2 * e0;
 
     for (int w = tid; w < n; w += NT) {
         s_state[w] = w;
@@ -119,12 +98,11 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
         key[j] = 0;
         if (j % 2 == 0) ends[j / 2] = 0;
         if (e < m) {
-            const int a = ep[2 * e] - v0, b = ep[2 * e + 1] - v0;
-            if (a >= 0 && a < n && b >= 0 && b < n && a != b) {
+            I.with_ends(e, [&](int a, int b) {
                 key[j] = vote_key(vt[e]);
                 ends[j / 2] |= ((uint32_t)a | ((uint32_t)b << 8)) << (16 * (j % 2));
                 live |= 1u << j;
-            }
+            });
         }
     });
     __syncthreads();
@@ -161,8 +139,7 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
             }
         });
         for (long long e = tid + (long long)kSlots * NT; e < m; e += NT) {   // a multigraph's surplus, from memory
-            const int a = ep[2 * e] - v0, b = ep[2 * e + 1] - v0;
-            if (a >= 0 && a < n && b >= 0 && b < n && a != b) {
+            I.with_ends(e, [&](int a, int b) {
                 const int sa = s_state[a], sb = s_state[b];
                 if (deg_of(sa) < 2 && deg_of(sb) < 2 && comp_of(sa) != comp_of(sb)) {
                     const uint32_t k = vote_key(vt[e]);
@@ -173,7 +150,7 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
                               ((uint32_t)comp_of(sb) << 24);
                     }
                 }
-            }
+            });
         }
         unsigned long long best = be == 0xffffffffu ? 0ull : candidate(bk, be);
 #pragma unroll
@@ -259,10 +236,7 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
     __syncthreads();   // s_pos is rewritten below
     int32_t* out = tours + v0;
     for (int k = tid; k < n; k += NT) {
-        int q = fwd ? p0 + k : p0 - k;
-        if (q >= n) q -= n;
-        if (q < 0) q += n;
-        const int v = s_seq[q];
+        const int v = s_seq[canonical_index(p0, fwd, k, n)];
         s_tour[k] = v;
         s_pos[v] = k;
         out[k] = v;
@@ -271,12 +245,11 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
 
     // ---- the pairs that are edges: pair k = (tour[k], tour[k+1]), the closing pair k = n - 1
     for (long long e = tid; e < m; e += NT) {
-        const int a = ep[2 * e] - v0, b = ep[2 * e + 1] - v0;
-        if (a >= 0 && a < n && b >= 0 && b < n && a != b) {
+        I.with_ends(e, [&](int a, int b) {
             const int pa = s_pos[a], pb = s_pos[b];
             if (pb == (pa + 1 < n ? pa + 1 : 0)) atomicMin(&s_edge[pa], (int)e);
             else if (pa == (pb + 1 < n ? pb + 1 : 0)) atomicMin(&s_edge[pb], (int)e);
-        }
+        });
     }
     __syncthreads();
     for (int k = tid; k < n; k += NT) {
@@ -285,13 +258,8 @@ __global__ __launch_bounds__(NT) void tour_from_votes_kernel(const float* __rest
     }
     __syncthreads();
     if (tid == 0) {
-        float cost = 0.f;
-        int missing = 0;
-        for (int k = 0; k < n; ++k) {
-            if (s_edge[k] != INT_MAX) cost += s_w[k];
-            else ++missing;
-        }
-        costs[inst] = cost;
+        int missing;
+        costs[inst] = sum_tour_pairs(n, [&](int k) { return s_edge[k] != INT_MAX; }, s_w, missing);
         n_missing[inst] = missing;
     }
 }
@@ -304,10 +272,8 @@ using namespace tspgnn;
 extern "C" int tspgnn_tour_from_votes(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg,
                                       const int32_t* vseg, int B, int n_max, int32_t* tours, float* costs,
                                       int32_t* n_missing, void* stream) {
-    TSPGNN_REQUIRE(B >= 0, "tour_from_votes: B=%d", B);
+    if (int rc = vote_entry("tour_from_votes", B, n_max)) return rc;
     if (B == 0) return TSPGNN_OK;
-    if (n_max > kDecodeMaxN) return fail(TSPGNN_EUNSUPPORTED, "tour_from_votes: n_max=%d exceeds %d", n_max, kDecodeMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "tour_from_votes: n_max=%d must be at least 4", n_max);
     TSPGNN_REQUIRE(vote && uv && wc && seg && vseg && tours && costs && n_missing, "tour_from_votes: null pointer");
     hipStream_t st = as_stream(stream);
     if (n_max <= 64)

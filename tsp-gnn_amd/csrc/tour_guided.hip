@@ -1,44 +1,22 @@
 // tspgnn_vote_neighbors (tspgnn/decode.py): per-vertex candidate rows from the network's per-edge logits, the table
-// tspgnn_tour_search_cand (tour_search.hip) descends over.  One workgroup per instance, reading the batch as
-// tspgnn_tour_from_votes reads it -- vote[M], the global endpoint ids uv[M][2], wc[M][2] (column 0 the edge weight), the
-// edge prefix sums seg[B+1], the vertex prefix sums vseg[B+1] -- and the vertex CSR the batch carries: rowptr[N+1], eid
-// row g = the ids of the edges that list global vertex g as an endpoint.
-//
-// The result is DEFINED as this sequential process over instance b (n = vseg[b+1] - vseg[b] vertices, local ids
-// uv - vseg[b]) and its local vertex x, whose row tab[(vseg[b] + x) K .. + K), K = k_vote + k_near, it fills:
-//   Pairs.  For y != x in [0, n): e(x,y) is the smallest edge id in CSR row x that joins x and y, or none.  An id of the
-//           row joins x to the other endpoint of that edge; it joins nothing when it lies outside seg[b] .. seg[b+1], when
-//           the edge does not list x, or when the other endpoint is x or lies outside [0, n).  v(x,y) = vote[e(x,y)],
-//           w(x,y) = wc[e(x,y)][0].  Only the set of ids in the row matters, not their order.  The neighbours of x are the
-//           y for which e(x,y) exists.
-//   Vote.   For s = 0 .. k_vote-1: among the neighbours not yet in the row, the first by (vote key of v(x,y) descending,
-//           y ascending), the key being tspgnn_tour_from_votes' (NaN lowest).  Slot s gets that y, or x ("skip") when no
-//           neighbour is left.
-//   Near.   For s = k_vote .. K-1: among the neighbours not yet in the row, the first by (weight key of w(x,y) ascending,
-//           y ascending); the weight key is the same order-preserving image, except that a NaN gets the highest key and
-//           comes last.  Slot s gets that y, or x when no neighbour is left.
-// A row depends on the instance, its votes and weights alone: never on n_max, on the other instances or on the launch.
+// tspgnn_tour_search_cand (tour_search.hip) descends over.  One workgroup per instance, reading the batch and the vertex
+// CSR it carries: rowptr[N+1], eid row g = the ids of the edges that list global vertex g as an endpoint.
+// include/tspgnn.h DEFINES the rows as a sequential process: the batch, the pair rule and the two keys under "tours from
+// the edge votes", then this entry point's Row, Vote and Near.  A row depends on the instance, its votes and weights
+// alone: never on n_max, on the other instances or on the launch.
 //
 // A wave takes the vertices wave, wave + waves, ...  Per vertex it resolves multi-edges in its own LDS array best_e[y]
 // (atomic-min over the CSR row), then a lane holds the <= 4 neighbours lane + 64 j with their two keys in registers and
 // the wave takes K arg-max rounds over (key, y) packed into one 64-bit word.  Lane s keeps slot s, so a row leaves in
 // one store of K consecutive bytes.  No sort, no workspace, no communication between workgroups; every loop has a fixed
 // trip count (the row length, K, n / waves).
-#include "tour_common.h"
+#include "vote_common.h"
 
 namespace tspgnn {
 namespace {
 
-constexpr int kGuideMaxN = 256;
-constexpr int kGuideSlots = kGuideMaxN / kWave;   // neighbours a lane holds
+constexpr int kGuideSlots = kVoteMaxN / kWave;   // neighbours a lane holds
 constexpr int kGuideMaxK = 32;
-
-// Weight key: ascending order of the fp32 values, -0.0 < +0.0, a NaN after +inf.
-__device__ __forceinline__ uint32_t weight_key(float w) {
-    const uint32_t b = __float_as_uint(w);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 // Wave-wide maximum of a 64-bit word; every lane gets it.
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -58,11 +36,11 @@ __global__ __launch_bounds__(NT) void vote_neighbors_kernel(const float* __restr
                                                             const int32_t* __restrict__ eid, int n_max, int k_vote,
                                                             int k_near, uint8_t* __restrict__ tab) {
     constexpr int kWaves = NT / kWave;
-    __shared__ int s_best[kWaves][kGuideMaxN];
+    __shared__ int s_best[kWaves][kVoteMaxN];
     const int inst = blockIdx.x;
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    const int v0 = vseg[inst], n = vseg[inst + 1] - v0;
-    const int e0 = seg[inst], e1 = seg[inst + 1];
+    const VoteInstance I(uv, seg, vseg, inst);
+    const int v0 = I.v0, n = I.n;
     const int K = k_vote + k_near;
     if (n < 4 || n > n_max) {   // the host module never sends these: zero rows, and every LDS index stays in bounds
         const long long bytes = n > 0 ? (long long)n * K : 0;
@@ -77,10 +55,8 @@ __global__ __launch_bounds__(NT) void vote_neighbors_kernel(const float* __restr
         const int r0 = rowptr[v0 + x], r1 = rowptr[v0 + x + 1];
         for (int r = r0 + lane; r < r1; r += kWave) {
             const int e = eid[r];
-            if (e < e0 || e >= e1) continue;
-            const int a = uv[2 * (long long)e] - v0, b = uv[2 * (long long)e + 1] - v0;
-            const int y = a == x ? b : b == x ? a : -1;
-            if (y >= 0 && y < n && y != x) atomicMin(&best_e[y], e);
+            int y;
+            if (I.other_end(e, x, y)) atomicMin(&best_e[y], e);
         }
         wave_sync();
         // this lane's neighbours: the arg-max words of the two phases, 0 = not a neighbour (or taken)
@@ -94,7 +70,7 @@ __global__ __launch_bounds__(NT) void vote_neighbors_kernel(const float* __restr
                 const unsigned long long tie = 0xffffffffu - (unsigned)y;   // the smaller y wins a tie
                 kv[j] = ((unsigned long long)vote_key(vote[e]) << 32) | tie;
                 // the smallest weight makes the largest word
-                kw[j] = ((unsigned long long)(~weight_key(wc[2 * (long long)e])) << 32) | tie;
+                kw[j] = ((unsigned long long)(~ordered_key(wc[2 * (long long)e], kNanHighest)) << 32) | tie;
             }
         }
         wave_sync();   // best_e is read: the next vertex may clear it
@@ -129,10 +105,8 @@ using namespace tspgnn;
 extern "C" int tspgnn_vote_neighbors(const float* vote, const int32_t* uv, const float* wc, const int32_t* seg,
                                      const int32_t* vseg, const int32_t* rowptr, const int32_t* eid, int B, int n_max,
                                      int k_vote, int k_near, uint8_t* tab, void* stream) {
-    TSPGNN_REQUIRE(B >= 0, "vote_neighbors: B=%d", B);
+    if (int rc = vote_entry("vote_neighbors", B, n_max)) return rc;
     if (B == 0) return TSPGNN_OK;
-    if (n_max > kGuideMaxN) return fail(TSPGNN_EUNSUPPORTED, "vote_neighbors: n_max=%d exceeds %d", n_max, kGuideMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "vote_neighbors: n_max=%d must be at least 4", n_max);
     TSPGNN_REQUIRE(k_vote >= 0 && k_near >= 0, "vote_neighbors: k_vote=%d, k_near=%d", k_vote, k_near);
     TSPGNN_REQUIRE(k_vote <= kGuideMaxK && k_near <= kGuideMaxK && k_vote + k_near >= 1 && k_vote + k_near <= kGuideMaxK,
                    "vote_neighbors: k_vote + k_near = %d + %d not in [1, %d]", k_vote, k_near, kGuideMaxK);

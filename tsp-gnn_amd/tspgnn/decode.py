@@ -95,26 +95,42 @@ def _vseg(batch, n_vertices):
     return vseg, batch._decode_vseg[2]
 
 
+_PER_EDGE = {torch.float32: ("vote", "a float32"), torch.int32: ("score", "an int32")}
+
+
+def _per_edge(who, batch, values, dtype):
+    """The votes (float32) or scores (int32) of a launch, flat: a tensor of ``dtype`` on the batch's device, one
+    contiguous value per edge."""
+    word, kind = _PER_EDGE[dtype]
+    if not torch.is_tensor(values) or values.dtype != dtype or values.device != batch.seg.device:
+        raise ValueError("%s: %ss must be %s tensor on the batch's device" % (who, word, kind))
+    values = values.reshape(-1)
+    if values.numel() != batch.M or not values.is_contiguous():
+        raise ValueError("%s: one contiguous %s per edge (%d), got %d" % (who, word, batch.M, values.numel()))
+    return values
+
+
+def _edge_inputs(batch, values, csr=False):
+    """(values, uv, wc[, eid]) as a launch takes them.  Without an edge anywhere the kernel reads none of them but refuses
+    null pointers: each is then a placeholder of one row."""
+    inputs = (values, batch.adj.uv, batch.WC) + ((batch.adj.csr_t[1],) if csr else ())
+    if batch.M == 0:
+        inputs = tuple(t.new_zeros((1,) + tuple(t.shape[1:])) for t in inputs)
+    return inputs
+
+
 def tours_from_votes(batch, votes, n_vertices=None):
     """tspgnn_tour_from_votes on a resident batch (Session.prepare / DeviceDataset.batch) and its vote tensor
     (``forward_device(batch)["E_vote"]``, float32 [M] on the batch's device), on the current stream.  -> DecodedBatch of
     device tensors.  n_vertices: the batch's own when it carries them.  Nothing here waits for the device, so the launch
     may follow forward_device directly; only the first call on a batch uploads the B + 1 vertex prefix sums."""
-    if not torch.is_tensor(votes) or votes.dtype != torch.float32 or votes.device != batch.seg.device:
-        raise ValueError("tours_from_votes: votes must be a float32 tensor on the batch's device")
-    votes = votes.reshape(-1)
-    if votes.numel() != batch.M or not votes.is_contiguous():
-        raise ValueError("tours_from_votes: one contiguous vote per edge (%d), got %d" % (batch.M, votes.numel()))
+    votes = _per_edge("tours_from_votes", batch, votes, torch.float32)
     vseg, n_max = _vseg(batch, n_vertices)
     dev = batch.seg.device
     tours = torch.empty(batch.N, dtype=torch.int32, device=dev)
     costs = torch.empty(batch.B, dtype=torch.float32, device=dev)
     n_missing = torch.empty(batch.B, dtype=torch.int32, device=dev)
-    uv, wc = batch.adj.uv, batch.WC
-    if batch.M == 0:   # no edge anywhere: the kernel reads none of the three, but refuses null pointers
-        votes = torch.zeros(1, dtype=torch.float32, device=dev)
-        uv = torch.zeros((1, 2), dtype=torch.int32, device=dev)
-        wc = torch.zeros((1, 2), dtype=torch.float32, device=dev)
+    votes, uv, wc = _edge_inputs(batch, votes)
     with torch.cuda.device(dev):
         _lib.call("tspgnn_tour_from_votes", _lib.ptr(votes), _lib.ptr(uv), _lib.ptr(wc), _lib.ptr(batch.seg),
                   _lib.ptr(vseg), batch.B, n_max, _lib.ptr(tours), _lib.ptr(costs), _lib.ptr(n_missing),
@@ -144,25 +160,15 @@ def vote_neighbors(batch, votes, k_vote, k_near=0, n_vertices=None):
     process in full.  The batch must carry its vertex CSR (``batch.adj.csr_t``, as every prepared batch does).  Nothing
     here waits for the device, so the launch may follow forward_device directly."""
     k_vote, k_near = _guide_counts((k_vote, k_near), "vote_neighbors: k_vote, k_near")
-    if not torch.is_tensor(votes) or votes.dtype != torch.float32 or votes.device != batch.seg.device:
-        raise ValueError("vote_neighbors: votes must be a float32 tensor on the batch's device")
-    votes = votes.reshape(-1)
-    if votes.numel() != batch.M or not votes.is_contiguous():
-        raise ValueError("vote_neighbors: one contiguous vote per edge (%d), got %d" % (batch.M, votes.numel()))
+    votes = _per_edge("vote_neighbors", batch, votes, torch.float32)
     vseg, n_max = _vseg(batch, n_vertices)
     dev = batch.seg.device
     tab = torch.empty((batch.N, k_vote + k_near), dtype=torch.uint8, device=dev)
-    uv, wc = batch.adj.uv, batch.WC
-    rowptr, eid = batch.adj.csr_t[0], batch.adj.csr_t[1]
-    if batch.M == 0:   # no edge anywhere: the kernel reads none of the four, but refuses null pointers
-        votes = torch.zeros(1, dtype=torch.float32, device=dev)
-        uv = torch.zeros((1, 2), dtype=torch.int32, device=dev)
-        wc = torch.zeros((1, 2), dtype=torch.float32, device=dev)
-        eid = torch.zeros(1, dtype=torch.int32, device=dev)
+    votes, uv, wc, eid = _edge_inputs(batch, votes, csr=True)
     with torch.cuda.device(dev):
         _lib.call("tspgnn_vote_neighbors", _lib.ptr(votes), _lib.ptr(uv), _lib.ptr(wc), _lib.ptr(batch.seg),
-                  _lib.ptr(vseg), _lib.ptr(rowptr), _lib.ptr(eid), batch.B, n_max, k_vote, k_near, _lib.ptr(tab),
-                  _lib.current_stream())
+                  _lib.ptr(vseg), _lib.ptr(batch.adj.csr_t[0]), _lib.ptr(eid), batch.B, n_max, k_vote, k_near,
+                  _lib.ptr(tab), _lib.current_stream())
     return tab
 
 
@@ -191,6 +197,18 @@ def beam_ranges(B, n_max, beam, workspace_bytes=None):
     return [(s, min(s + g, B)) for s in range(0, B, g)], int(_lib.lib.tspgnn_tour_beam_workspace_bytes(g, n_max, beam))
 
 
+def _beam_width(who, beam, select, shown="%d"):
+    """beam as the int tspgnn_tour_beam takes, once select and its range are checked.  shown: how a refusal prints the
+    width, "%d" (the int) or "%r" (the caller's value)."""
+    if select not in SELECT:
+        raise ValueError("%s: select must be 'score' or 'cost', got %r" % (who, select))
+    width = int(beam)
+    if not 1 <= width <= MAX_BEAM:
+        raise ValueError("%s: beam=%s; the decoder takes 1 <= beam <= %d"
+                         % (who, shown % (width if shown == "%d" else beam,), MAX_BEAM))
+    return width
+
+
 def beam_tours(batch, scores, beam, select="score", n_vertices=None, workspace_bytes=None):
     """tspgnn_tour_beam on a resident batch and its integer edge scores (``edge_scores(forward_device(batch)["E_vote"])``,
     int32 [M] on the batch's device), on the current stream -> BeamBatch of device tensors.  beam: 1 .. 1024; select:
@@ -198,26 +216,14 @@ def beam_tours(batch, scores, beam, select="score", n_vertices=None, workspace_b
     directly.  The workspace is sized by the library's query; when a batch would need more than ``workspace_bytes``
     (default DEFAULT_BEAM_WORKSPACE_BYTES, 256 MiB) it is decoded in several launches over instance ranges that share one
     workspace -- instances are independent, so the ranges change nothing."""
-    if select not in SELECT:
-        raise ValueError("beam_tours: select must be 'score' or 'cost', got %r" % (select,))
-    beam = int(beam)
-    if not 1 <= beam <= MAX_BEAM:
-        raise ValueError("beam_tours: beam=%d; the decoder takes 1 <= beam <= %d" % (beam, MAX_BEAM))
-    if not torch.is_tensor(scores) or scores.dtype != torch.int32 or scores.device != batch.seg.device:
-        raise ValueError("beam_tours: scores must be an int32 tensor on the batch's device")
-    scores = scores.reshape(-1)
-    if scores.numel() != batch.M or not scores.is_contiguous():
-        raise ValueError("beam_tours: one contiguous score per edge (%d), got %d" % (batch.M, scores.numel()))
+    beam = _beam_width("beam_tours", beam, select)
+    scores = _per_edge("beam_tours", batch, scores, torch.int32)
     vseg, n_max = _vseg(batch, n_vertices)
     dev = batch.seg.device
     tours = torch.empty(batch.N, dtype=torch.int32, device=dev)
     costs = torch.empty(batch.B, dtype=torch.float32, device=dev)
     n_missing, out_scores, n_closed = (torch.empty(batch.B, dtype=torch.int32, device=dev) for _ in range(3))
-    uv, wc = batch.adj.uv, batch.WC
-    if batch.M == 0:   # no edge anywhere: the kernel reads none of the three, but refuses null pointers
-        scores = torch.zeros(1, dtype=torch.int32, device=dev)
-        uv = torch.zeros((1, 2), dtype=torch.int32, device=dev)
-        wc = torch.zeros((1, 2), dtype=torch.float32, device=dev)
+    scores, uv, wc = _edge_inputs(batch, scores)
     if batch.B == 0:
         return BeamBatch(tours, costs, n_missing, out_scores, n_closed, vseg)
     ranges, ws_bytes = beam_ranges(batch.B, n_max, beam, workspace_bytes)
@@ -231,10 +237,13 @@ def beam_tours(batch, scores, beam, select="score", n_vertices=None, workspace_b
     return BeamBatch(tours, costs, n_missing, out_scores, n_closed, vseg)
 
 
+_Decoded = collections.namedtuple("_Decoded", ["tour", "cost", "n_missing", "prediction", "score", "n_closed", "table"])
+
+
 def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="score", workspace_bytes=None, guide=None):
-    """[(tour, cost, n_missing, prediction, score, n_closed, table)] of one batch: pack at the targets, forward, decode,
-    one read-back.  beam None: the greedy decoder, score and n_closed None.  guide = (k_vote, k_near): vote_neighbors
-    follows the forward on the same stream and table is the instance's uint8 [n, K] rows; otherwise None."""
+    """One _Decoded per instance of one batch: pack at the targets, forward, decode, one read-back.  beam None: the
+    greedy decoder, score and n_closed None.  guide = (k_vote, k_near): vote_neighbors follows the forward on the same
+    stream and table is the instance's uint8 [n, K] rows; otherwise None."""
     EV, W, C, route_exists, n_vertices, n_edges = InstanceLoader.create_batch(chunk, target_cost=0.0)
     C[:, 0] = np.repeat(np.asarray(targets, dtype=np.float64), n_edges)
     feed = {model["EV"]: EV, model["W"]: W, model["C"]: C, model["time_steps"]: time_steps,
@@ -254,15 +263,15 @@ def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="sc
     tours, costs = dec.tours.cpu().numpy(), dec.costs.cpu().numpy()
     missing, pred = dec.n_missing.cpu().numpy(), pred.cpu().numpy()
     v0 = np.concatenate([[0], np.cumsum(n_vertices)])
-    extra = [(None, None)] * len(chunk)
+    scores = closed = tabs = [None] * len(chunk)
     if beam is not None:
-        extra = list(zip((int(s) for s in dec.scores.cpu().numpy()), (int(c) for c in dec.n_closed.cpu().numpy())))
-    tabs = [None] * len(chunk)
+        scores, closed = dec.scores.cpu().numpy().tolist(), dec.n_closed.cpu().numpy().tolist()
     if tab is not None:
         tab = tab.cpu().numpy()
         tabs = [tab[v0[i]:v0[i + 1]] for i in range(len(chunk))]
-    return [([int(v) for v in tours[v0[i]:v0[i + 1]]], float(costs[i]), int(missing[i]), float(pred[i])) + extra[i]
-            + (tabs[i],) for i in range(len(chunk))]
+    return [_Decoded(tour=tours[v0[i]:v0[i + 1]].tolist(), cost=float(costs[i]), n_missing=int(missing[i]),
+                     prediction=float(pred[i]), score=scores[i], n_closed=closed[i], table=tabs[i])
+            for i in range(len(chunk))]
 
 
 def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=False, max_graphs=None, beam=None,
@@ -303,10 +312,7 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
     if beam is None and (select != "score" or workspace_bytes is not None):
         raise TypeError("decode_tours: select and workspace_bytes only apply with beam=K")
     if beam is not None:
-        if select not in SELECT:
-            raise ValueError("decode_tours: select must be 'score' or 'cost', got %r" % (select,))
-        if not 1 <= int(beam) <= MAX_BEAM:
-            raise ValueError("decode_tours: beam=%r; the decoder takes 1 <= beam <= %d" % (beam, MAX_BEAM))
+        _beam_width("decode_tours", beam, select, shown="%r")
     if search_kw and not polish:
         raise TypeError("decode_tours: %s only apply with polish=True" % ", ".join(sorted(search_kw)))
     if target_costs is None:
@@ -325,11 +331,13 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
         kw = dict(restarts=1, kicks=0, lower_bound=False)
         kw.update(search_kw)
         if guide is not None:
-            kw["candidates"] = [r[6] for r in rows]
-        res = label_tours([(x[0], x[1]) for x in instances], init_tours=[r[0] for r in rows], device=sess.device, **kw)
-        polished = [(r.tour, r.cost) for r in res]
-    if beam is None:
-        return [DecodedTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1])
-                for (tour, cost, missing, pred, _, _, _), target, p in zip(rows, targets, polished)]
-    return [BeamTour(tour, cost, missing, missing == 0, pred, target, p[0], p[1], score, closed)
-            for (tour, cost, missing, pred, score, closed, _), target, p in zip(rows, targets, polished)]
+            kw["candidates"] = [r.table for r in rows]
+        res = label_tours([(x[0], x[1]) for x in instances], init_tours=[r.tour for r in rows], device=sess.device, **kw)
+        polished = [(p.tour, p.cost) for p in res]
+    records = []
+    for r, target, (polished_tour, polished_cost) in zip(rows, targets, polished):
+        fields = dict(tour=r.tour, cost=r.cost, n_missing=r.n_missing, feasible=r.n_missing == 0,
+                      prediction=r.prediction, target_cost=target, polished_tour=polished_tour,
+                      polished_cost=polished_cost)
+        records.append(DecodedTour(**fields) if beam is None else BeamTour(score=r.score, n_closed=r.n_closed, **fields))
+    return records
