@@ -259,6 +259,17 @@ struct CellTaskTableH2 {
 // mean pass (a compile-time variant: the same choice as a branch inside the tile loop cost 47 spilled registers).
 // WT: write-through output stores (st4o).  12 wavefronts per workgroup (<= 168 registers; a 16-wavefront build spilled and
 // was 4 % slower).
+// H2_GATE_FORM: which of the tile's f32 pair arithmetic is written in the single-issue form of mfma_tile.h -- 0 none, 1 the
+// five LayerNorms and the gates, 2 also the gather-init adds, 3 also the rescale of the MLP epilogues.  Every value computes
+// the same bits (tests/test_gpu_cell_fwd_bits.py); 3 measured fastest (profiles/gate_forms_ab.txt: C2 forward -0.9 %, its whole
+// range below the packed form's in alternating runs on each of three boxes).  Other values: A/B builds only (tools/build_variant.sh -DH2_GATE_FORM=n).
+#ifndef H2_GATE_FORM
+#define H2_GATE_FORM 3
+#endif
+constexpr int kGateForm = H2_GATE_FORM >= 1 ? kSingle : kPacked;
+constexpr int kInitForm = H2_GATE_FORM >= 2 ? kSingle : kPacked;
+constexpr int kMlpForm = H2_GATE_FORM >= 3 ? kSingle : kPacked;
+
 template <int D, bool CENTERED, bool WT>
 __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTableH2 tt) {
     constexpr int NT4 = D / 4, TPG = D / 16, KBH = D / 32;
@@ -335,7 +346,11 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTa
 #pragma unroll
             for (int t = 0; t < NT4; ++t) acc[t] = ld4(zu + t * 256);
 #pragma unroll
-            for (int t = 0; t < NT4; ++t) acc[t] += ld4(zv + t * 256);
+            for (int t = 0; t < NT4; ++t) {
+                const f32x4 z2 = ld4(zv + t * 256);
+                acc[t].lo = add2<kInitForm>(acc[t].lo, z2.lo);
+                acc[t].hi = add2<kInitForm>(acc[t].hi, z2.hi);
+            }
         } else if (zbias != nullptr) {
             // (an idle wavefront of a lock-step round keeps z == 0 in EVERY mode -- it skips the GEMM, and a partial z is
             // not a row of the batch: a variance of exactly 0 is ignored by the range guard, see ln_gate<..., TRACK>)
@@ -363,7 +378,7 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTa
     // gates + state stores; returns h' in registers (the D layout is the next GEMM's B operand)
     auto cell = [&](f32x4 (&acc)[NT4], f32x4 (&cf)[TPG], unsigned rc, bool valid, f32x4 (&hn)[TPG]) {
         f32x4 nc[TPG];
-        lstm_gates<D, true, H2_LN_SWAP != 0, CENTERED, true>(acc, cf, lds_ln, g, hn, nc, kH2GateEps, &vmin);
+        lstm_gates<D, true, H2_LN_SWAP != 0, CENTERED, true, kGateForm>(acc, cf, lds_ln, g, hn, nc, kH2GateEps, &vmin);
         if (valid) {
             float* hd = h_out + h2_state_row<D>(rc, g, out_blk);
             float* cd = c_out + h2_state_row<D>(rc, g, out_blk);
@@ -415,7 +430,7 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTa
                 for (int l = 0; l < n_layers; ++l) {
                     const _Float16* wh = reinterpret_cast<const _Float16*>(lds_mlp + (size_t)l * LAYER_BYTES);
                     const float* bias = reinterpret_cast<const float*>(lds_mlp + (size_t)l * LAYER_BYTES + 2 * D * D * 2);
-                    dense_layer_h2<D>(hn, wh, wh + D * D, bias, (relu_mask >> l) & 1u, g, rl, wit);
+                    dense_layer_h2<D, kMlpForm>(hn, wh, wh + D * D, bias, (relu_mask >> l) & 1u, g, rl, wit);
                     if (mlp_acts != nullptr && l < n_layers - 1 && valid) {
                         float* dst = mlp_acts + ((size_t)l * acts_stride + (size_t)rc * D + g * 4);
 #pragma unroll
@@ -508,7 +523,7 @@ __global__ __launch_bounds__(768) void lnlstm_mlp_fwd_h2_kernel(const CellTaskTa
                 for (int l = 0; l < n_layers; ++l) {
                     const _Float16* wh = reinterpret_cast<const _Float16*>(lds_wb + (size_t)l * LAYER_BYTES);
                     const float* bias = reinterpret_cast<const float*>(lds_wb + (size_t)l * LAYER_BYTES + 2 * D * D * 2);
-                    dense_layer_h2<D>(hn, wh, wh + D * D, bias, (relu_mask >> l) & 1u, g, rl, wit);
+                    dense_layer_h2<D, kMlpForm>(hn, wh, wh + D * D, bias, (relu_mask >> l) & 1u, g, rl, wit);
                     if (mlp_acts != nullptr && l < n_layers - 1 && valid) {
                         float* dst = mlp_acts + ((size_t)l * acts_stride + (size_t)rc * D + g * 4);
 #pragma unroll

@@ -277,7 +277,8 @@ __device__ __forceinline__ void kblock_h2_side(f32x4 (&acc)[NT], f32x4 (&side)[N
 
 // One Dense(D) layer on the lane's part of a 16-row tile, activations chained in registers (D layout).  `bias` holds
 // 2^s * b; the output comes back at its true scale.
-template <int D>
+// FORM (mfma_tile.h): the rescale of the epilogue as one packed or two single-issue multiplies per pair.
+template <int D, int FORM = kPacked>
 __device__ __forceinline__ void dense_layer_h2(f32x4 (&a)[D / 16], const _Float16* wh, const _Float16* wl, const float* bias,
                                                bool relu, int g, int rl, float& wit) {
     constexpr int NT = D / 16, KB = D / 32;
@@ -300,8 +301,8 @@ __device__ __forceinline__ void dense_layer_h2(f32x4 (&a)[D / 16], const _Float1
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[t][r] = fmaxf(acc[t][r], 0.f);
         }
-        a[t].lo = acc[t].lo * inv;
-        a[t].hi = acc[t].hi * inv;
+        a[t].lo = mul2<FORM>(acc[t].lo, inv);
+        a[t].hi = mul2<FORM>(acc[t].hi, inv);
     }
 }
 

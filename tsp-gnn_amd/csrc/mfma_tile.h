@@ -89,10 +89,38 @@ __device__ __forceinline__ void ksteps(f32x4 (&acc)[NT], const float* w0, const 
 // lane groups of the row hold the rest.  Written on float pairs so that it compiles to packed fp32 VALU
 // instructions (v_pk_add/mul/fma_f32: two values per lane per issue) -- the LayerNorm / gate arithmetic shares
 // the SIMD's issue port with the MFMAs (no co-execution), so every VALU instruction saved
-// is kernel time.  tf.contrib.layers.layer_norm semantics: biased variance, variance_epsilon = 1e-12.
+// is kernel time.  (The f16x2 forward cell launch, three wavefronts per SIMD, is the exception: there the single-issue
+// FORM below is faster, profiles/valu_mfma_coissue.txt.)  tf.contrib.layers.layer_norm semantics: biased variance,
+// variance_epsilon = 1e-12.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
+// FORM: how the pair arithmetic below is written.  kPacked is the <2 x float> form above (v_pk_*_f32); kSingle does the
+// same IEEE operation per element, in the same order, as two single-issue instructions (v_fma_f32 / v_mul_f32 / v_add_f32
+// round exactly as their packed twins, so the two forms agree bit for bit).  A single-issue VALU instruction can issue
+// beside another wavefront's MFMA where a packed one cannot (tools/valu_rate_probe.hip, mixed mode); a file that uses
+// kSingle is built with SLP vectorisation off (csrc/Makefile), or the optimiser packs the pairs again.
+constexpr int kPacked = 0, kSingle = 1;
+
+template <int FORM = kPacked>
+__device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) {
+    if constexpr (FORM == kPacked) return __builtin_elementwise_fma(a, b, c);
+    else return f32x2{__builtin_fmaf(a[0], b[0], c[0]), __builtin_fmaf(a[1], b[1], c[1])};
+}
+template <int FORM>
+__device__ __forceinline__ f32x2 add2(f32x2 a, f32x2 b) {
+    if constexpr (FORM == kPacked) return a + b;
+    else return f32x2{a[0] + b[0], a[1] + b[1]};
+}
+template <int FORM>
+__device__ __forceinline__ f32x2 sub2(f32x2 a, f32x2 b) {
+    if constexpr (FORM == kPacked) return a - b;
+    else return f32x2{a[0] - b[0], a[1] - b[1]};
+}
+template <int FORM>
+__device__ __forceinline__ f32x2 mul2(f32x2 a, f32x2 b) {
+    if constexpr (FORM == kPacked) return a * b;
+    else return f32x2{a[0] * b[0], a[1] * b[1]};
+}
 
 // The same sum (same order, bit-identical) by gfx950's lane-swap VALU instructions instead of two ds_bpermute round
 // trips: v_permlane16_swap(v, v) leaves {even rows of v, odd rows of v} duplicated in the two results, so their sum is
@@ -116,7 +144,7 @@ __device__ __forceinline__ float sum_over_lane_groups16_swap(float v) {
 // (bit pattern - 1) -- positive floats order like their bit patterns, and a variance of exactly 0 (a constant row: exact
 // operands) wraps to the maximum and is ignored.  The f16x2 kernels turn it into bit 1 of the task's range_flag: a z whose
 // spread is below the absolute error of its operands' fp16 pieces (h2_tile.h, kH2VarFloor).
-template <int TPG, bool SWAP = false, bool CENTERED = false, bool TRACK = false>
+template <int TPG, bool SWAP = false, bool CENTERED = false, bool TRACK = false, int FORM = kPacked>
 __device__ __forceinline__ void ln_gate(f32x4 (&v)[TPG], const float* gamma, const float* beta, int g, int D,
                                         float eps = 1e-12f, unsigned* vmin = nullptr) {
     auto lane_sum = [](float x) { return SWAP ? sum_over_lane_groups16_swap(x) : sum_over_lane_groups16(x); };
@@ -124,20 +152,20 @@ __device__ __forceinline__ void ln_gate(f32x4 (&v)[TPG], const float* gamma, con
     if constexpr (CENTERED) {
 #pragma unroll
         for (int t = 0; t < TPG; ++t) {
-            q2 = fma2(v[t].lo, v[t].lo, q2);
-            q2 = fma2(v[t].hi, v[t].hi, q2);
+            q2 = fma2<FORM>(v[t].lo, v[t].lo, q2);
+            q2 = fma2<FORM>(v[t].hi, v[t].hi, q2);
         }
     } else {
-        f32x2 s2 = v[0].lo + v[0].hi;
+        f32x2 s2 = add2<FORM>(v[0].lo, v[0].hi);
 #pragma unroll
-        for (int t = 1; t < TPG; ++t) s2 += v[t].lo + v[t].hi;
+        for (int t = 1; t < TPG; ++t) s2 = add2<FORM>(s2, add2<FORM>(v[t].lo, v[t].hi));
         const float mean = lane_sum(s2[0] + s2[1]) * (1.0f / (float)D);
         const f32x2 m2 = {mean, mean};
 #pragma unroll
         for (int t = 0; t < TPG; ++t) {  // centred values replace v: y = (x - mean) * (rstd * gamma) + beta
-            const f32x2 a = v[t].lo - m2, b = v[t].hi - m2;
-            q2 = fma2(a, a, q2);
-            q2 = fma2(b, b, q2);
+            const f32x2 a = sub2<FORM>(v[t].lo, m2), b = sub2<FORM>(v[t].hi, m2);
+            q2 = fma2<FORM>(a, a, q2);
+            q2 = fma2<FORM>(b, b, q2);
             v[t].lo = a;
             v[t].hi = b;
         }
@@ -153,26 +181,28 @@ __device__ __forceinline__ void ln_gate(f32x4 (&v)[TPG], const float* gamma, con
     for (int t = 0; t < TPG; ++t) {
         const f32x4 ga = ld4(gamma + t * 16 + g * 4);
         const f32x4 be = ld4(beta + t * 16 + g * 4);
-        v[t].lo = fma2(v[t].lo, ga.lo * r2, be.lo);
-        v[t].hi = fma2(v[t].hi, ga.hi * r2, be.hi);
+        v[t].lo = fma2<FORM>(v[t].lo, mul2<FORM>(ga.lo, r2), be.lo);
+        v[t].hi = fma2<FORM>(v[t].hi, mul2<FORM>(ga.hi, r2), be.hi);
     }
 }
 
 // 1/(1+e^-(x+shift)) on a pair: packed multiply-add feeding the two transcendental pairs (v_exp_f32, v_rcp_f32).
+template <int FORM = kPacked>
 __device__ __forceinline__ f32x2 sigmoid2(f32x2 x, float shift = 0.f) {
     constexpr float L = -1.4426950408889634f;
     const f32x2 l2 = {L, L}, sh = {L * shift, L * shift}, one = {1.f, 1.f};
-    const f32x2 t = fma2(x, l2, sh);
+    const f32x2 t = fma2<FORM>(x, l2, sh);
     const f32x2 e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-    const f32x2 d = e + one;
+    const f32x2 d = add2<FORM>(e, one);
     return f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 __device__ __forceinline__ f32x2 relu2(f32x2 x) { return f32x2{fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)}; }
 // the same on an argument that already is t = -log2(e) * (x + shift): 1 / (1 + 2^t)
+template <int FORM = kPacked>
 __device__ __forceinline__ f32x2 sigmoid2_pre(f32x2 t) {
     const f32x2 one = {1.f, 1.f};
     const f32x2 e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
-    const f32x2 d = e + one;
+    const f32x2 d = add2<FORM>(e, one);
     return f32x2{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
 
@@ -182,7 +212,7 @@ __device__ __forceinline__ f32x2 sigmoid2_pre(f32x2 t) {
 // beta_f), so their LayerNorm output is the exponent of the sigmoid directly -- one packed multiply-add per pair less;
 // eps_z: the epsilon of the four gate LayerNorms (a caller whose z is scaled by 2^s passes 2^2s * 1e-12, which makes
 // the normalised gates those of the unscaled z exactly -- a power-of-two scale commutes with every rounding).
-template <int D, bool PRE = false, bool SWAP = false, bool CENTERED = false, bool TRACK = false>
+template <int D, bool PRE = false, bool SWAP = false, bool CENTERED = false, bool TRACK = false, int FORM = kPacked>
 __device__ __forceinline__ void lstm_gates(f32x4 (&acc)[D / 4], f32x4 (&cf)[D / 16], const float* lds_ln, int g,
                                            f32x4 (&hn)[D / 16], f32x4 (&nc)[D / 16], float eps_z = 1e-12f,
                                            unsigned* vmin = nullptr) {
@@ -195,29 +225,29 @@ __device__ __forceinline__ void lstm_gates(f32x4 (&acc)[D / 4], f32x4 (&cf)[D / 
         gf[t] = acc[2 * TPG + t];
         go[t] = acc[3 * TPG + t];
     }
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(gi, lds_ln + 0 * D, lds_ln + 1 * D, g, D, eps_z, vmin);
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(gj, lds_ln + 2 * D, lds_ln + 3 * D, g, D, eps_z, vmin);
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(gf, lds_ln + 4 * D, lds_ln + 5 * D, g, D, eps_z, vmin);
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(go, lds_ln + 6 * D, lds_ln + 7 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(gi, lds_ln + 0 * D, lds_ln + 1 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(gj, lds_ln + 2 * D, lds_ln + 3 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(gf, lds_ln + 4 * D, lds_ln + 5 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(go, lds_ln + 6 * D, lds_ln + 7 * D, g, D, eps_z, vmin);
 #pragma unroll
     for (int t = 0; t < TPG; ++t) {
         if constexpr (PRE) {
-            nc[t].lo = fma2(sigmoid2_pre(gi[t].lo), relu2(gj[t].lo), cf[t].lo * sigmoid2_pre(gf[t].lo));
-            nc[t].hi = fma2(sigmoid2_pre(gi[t].hi), relu2(gj[t].hi), cf[t].hi * sigmoid2_pre(gf[t].hi));
+            nc[t].lo = fma2<FORM>(sigmoid2_pre<FORM>(gi[t].lo), relu2(gj[t].lo), mul2<FORM>(cf[t].lo, sigmoid2_pre<FORM>(gf[t].lo)));
+            nc[t].hi = fma2<FORM>(sigmoid2_pre<FORM>(gi[t].hi), relu2(gj[t].hi), mul2<FORM>(cf[t].hi, sigmoid2_pre<FORM>(gf[t].hi)));
         } else {
-            nc[t].lo = fma2(sigmoid2(gi[t].lo), relu2(gj[t].lo), cf[t].lo * sigmoid2(gf[t].lo, 1.0f));
-            nc[t].hi = fma2(sigmoid2(gi[t].hi), relu2(gj[t].hi), cf[t].hi * sigmoid2(gf[t].hi, 1.0f));
+            nc[t].lo = fma2<FORM>(sigmoid2<FORM>(gi[t].lo), relu2(gj[t].lo), mul2<FORM>(cf[t].lo, sigmoid2<FORM>(gf[t].lo, 1.0f)));
+            nc[t].hi = fma2<FORM>(sigmoid2<FORM>(gi[t].hi), relu2(gj[t].hi), mul2<FORM>(cf[t].hi, sigmoid2<FORM>(gf[t].hi, 1.0f)));
         }
     }
-    ln_gate<TPG, SWAP>(nc, lds_ln + 8 * D, lds_ln + 9 * D, g, D);
+    ln_gate<TPG, SWAP, false, false, FORM>(nc, lds_ln + 8 * D, lds_ln + 9 * D, g, D);
 #pragma unroll
     for (int t = 0; t < TPG; ++t) {
         if constexpr (PRE) {
-            hn[t].lo = relu2(nc[t].lo) * sigmoid2_pre(go[t].lo);
-            hn[t].hi = relu2(nc[t].hi) * sigmoid2_pre(go[t].hi);
+            hn[t].lo = mul2<FORM>(relu2(nc[t].lo), sigmoid2_pre<FORM>(go[t].lo));
+            hn[t].hi = mul2<FORM>(relu2(nc[t].hi), sigmoid2_pre<FORM>(go[t].hi));
         } else {
-            hn[t].lo = relu2(nc[t].lo) * sigmoid2(go[t].lo);
-            hn[t].hi = relu2(nc[t].hi) * sigmoid2(go[t].hi);
+            hn[t].lo = mul2<FORM>(relu2(nc[t].lo), sigmoid2<FORM>(go[t].lo));
+            hn[t].hi = mul2<FORM>(relu2(nc[t].hi), sigmoid2<FORM>(go[t].hi));
         }
     }
 }
@@ -228,18 +258,18 @@ __device__ __forceinline__ void lstm_gates(f32x4 (&acc)[D / 4], f32x4 (&cf)[D / 
 //   stage f:      cs = c * sig(LN_f(z_f))                     (cs arrives holding the old c)
 //   stage (i, j): cs = LN_s(sig(LN_i(z_i)) * relu(LN_j(z_j)) + cs)   = the new (normalised) c
 //   stage o:      h' = relu(c') * sig(LN_o(z_o))
-template <int D, bool SWAP, bool CENTERED = false, bool TRACK = false>
+template <int D, bool SWAP, bool CENTERED = false, bool TRACK = false, int FORM = kPacked>
 __device__ __forceinline__ void lstm_stage_f(f32x4 (&zf)[D / 16], f32x4 (&cs)[D / 16], const float* lds_ln, int g,
                                              float eps_z = 1e-12f, unsigned* vmin = nullptr) {
     constexpr int TPG = D / 16;
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(zf, lds_ln + 4 * D, lds_ln + 5 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(zf, lds_ln + 4 * D, lds_ln + 5 * D, g, D, eps_z, vmin);
 #pragma unroll
     for (int t = 0; t < TPG; ++t) {
-        cs[t].lo = cs[t].lo * sigmoid2_pre(zf[t].lo);
-        cs[t].hi = cs[t].hi * sigmoid2_pre(zf[t].hi);
+        cs[t].lo = mul2<FORM>(cs[t].lo, sigmoid2_pre<FORM>(zf[t].lo));
+        cs[t].hi = mul2<FORM>(cs[t].hi, sigmoid2_pre<FORM>(zf[t].hi));
     }
 }
-template <int D, bool SWAP, bool CENTERED = false, bool TRACK = false>
+template <int D, bool SWAP, bool CENTERED = false, bool TRACK = false, int FORM = kPacked>
 __device__ __forceinline__ void lstm_stage_ij(f32x4 (&zij)[D / 8], f32x4 (&cs)[D / 16], const float* lds_ln, int g,
                                               float eps_z = 1e-12f, unsigned* vmin = nullptr) {
     constexpr int TPG = D / 16;
@@ -249,24 +279,24 @@ __device__ __forceinline__ void lstm_stage_ij(f32x4 (&zij)[D / 8], f32x4 (&cs)[D
         gi[t] = zij[t];
         gj[t] = zij[TPG + t];
     }
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(gi, lds_ln + 0 * D, lds_ln + 1 * D, g, D, eps_z, vmin);
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(gj, lds_ln + 2 * D, lds_ln + 3 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(gi, lds_ln + 0 * D, lds_ln + 1 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(gj, lds_ln + 2 * D, lds_ln + 3 * D, g, D, eps_z, vmin);
 #pragma unroll
     for (int t = 0; t < TPG; ++t) {
-        cs[t].lo = fma2(sigmoid2_pre(gi[t].lo), relu2(gj[t].lo), cs[t].lo);
-        cs[t].hi = fma2(sigmoid2_pre(gi[t].hi), relu2(gj[t].hi), cs[t].hi);
+        cs[t].lo = fma2<FORM>(sigmoid2_pre<FORM>(gi[t].lo), relu2(gj[t].lo), cs[t].lo);
+        cs[t].hi = fma2<FORM>(sigmoid2_pre<FORM>(gi[t].hi), relu2(gj[t].hi), cs[t].hi);
     }
-    ln_gate<TPG, SWAP>(cs, lds_ln + 8 * D, lds_ln + 9 * D, g, D);
+    ln_gate<TPG, SWAP, false, false, FORM>(cs, lds_ln + 8 * D, lds_ln + 9 * D, g, D);
 }
-template <int D, bool SWAP, bool CENTERED = false, bool TRACK = false>
+template <int D, bool SWAP, bool CENTERED = false, bool TRACK = false, int FORM = kPacked>
 __device__ __forceinline__ void lstm_stage_o(f32x4 (&zo)[D / 16], const f32x4 (&nc)[D / 16], const float* lds_ln, int g,
                                              f32x4 (&hn)[D / 16], float eps_z = 1e-12f, unsigned* vmin = nullptr) {
     constexpr int TPG = D / 16;
-    ln_gate<TPG, SWAP, CENTERED, TRACK>(zo, lds_ln + 6 * D, lds_ln + 7 * D, g, D, eps_z, vmin);
+    ln_gate<TPG, SWAP, CENTERED, TRACK, FORM>(zo, lds_ln + 6 * D, lds_ln + 7 * D, g, D, eps_z, vmin);
 #pragma unroll
     for (int t = 0; t < TPG; ++t) {
-        hn[t].lo = relu2(nc[t].lo) * sigmoid2_pre(zo[t].lo);
-        hn[t].hi = relu2(nc[t].hi) * sigmoid2_pre(zo[t].hi);
+        hn[t].lo = mul2<FORM>(relu2(nc[t].lo), sigmoid2_pre<FORM>(zo[t].lo));
+        hn[t].hi = mul2<FORM>(relu2(nc[t].hi), sigmoid2_pre<FORM>(zo[t].hi));
     }
 }
 
