@@ -489,10 +489,14 @@ int tspgnn_tour_lower_bound(const float* W, const long long* w_off, const int* n
  * tspgnn_tour_search for instances of up to 256 vertices (dataset.py:9-50): the same search, moves, kicks, keys and
  * canonical output, on the packed strict upper triangle.  W + w_off[i] holds n[i] (n[i] - 1) / 2 fp32 values, row-major:
  * w(a, b) for a < b sits at a (2 n - 3 - a) / 2 - 1 + b.  4 <= n[i] <= n_max <= 256; n_max > 256: TSPGNN_EUNSUPPORTED.
- * The workgroup keeps the triangle and three tours of n_max int32 ids per chain in LDS, 2 n_max (n_max - 1) +
- * 12 restarts n_max bytes, which must fit 163 712 (160 KiB less 128 static): at n_max = 256 restarts <= 10, at
- * n_max <= 242 all 16 fit.  A larger restarts is TSPGNN_EINVAL, and the message names the limit.  For n <= 128 the tours
- * and costs equal tspgnn_tour_search's bit for bit, given the same seed, index, restarts and kicks.
+ * The LDS of every chain kernel (the searches, tspgnn_tour_nearest_neighbor, tspgnn_tour_anneal; csrc/tour_common.h,
+ * ChainLds): the weights (4 n_max (n_max | 1) bytes dense, 2 n_max (n_max - 1) packed), per chain three tours of n_max
+ * int32 ids, and for a search with a table of K columns (_knn: neighbors, _cand: columns) n_max K bytes of table and
+ * n_max more bytes per chain -- weights + K n_max + chains (12 + [K > 0]) n_max bytes, which must fit 163 712 (160 KiB
+ * less 128 static).  The dense layout always holds all 16 chains; the triangle holds 16 up to n_max = 242 and 10 at
+ * n_max = 256 (9 with K = 8).  tspgnn_tour_chains_fit gives the limit; a larger restarts is TSPGNN_EINVAL, and the message
+ * names the limit.  For n <= 128 the tours and costs equal tspgnn_tour_search's bit for bit, given the same seed, index,
+ * restarts and kicks.
  */
 int tspgnn_tour_search_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                            const long long* t_off, const long long* index, int n_inst, int n_max, int restarts, int kicks,
@@ -517,9 +521,9 @@ int tspgnn_tour_search_knn(const float* W, const long long* w_off, const int* n,
 
 /*
  * tspgnn_tour_search_knn on the packed strict upper triangle of tspgnn_tour_search_tri, n_max <= 256 (above:
- * TSPGNN_EUNSUPPORTED) (dataset.py:9-50).  LDS: 2 n_max (n_max - 1) + n_max * neighbors + 13 restarts n_max bytes must
- * fit 163 712: at n_max = 256 and neighbors = 8 restarts <= 9.  A larger restarts is TSPGNN_EINVAL, and the message names
- * the limit.  For n <= 128 the tours and costs equal tspgnn_tour_search_knn's bit for bit.
+ * TSPGNN_EUNSUPPORTED) (dataset.py:9-50).  restarts <= tspgnn_tour_chains_fit(1, n_max, neighbors) (the LDS layout:
+ * tspgnn_tour_search_tri); a larger restarts is TSPGNN_EINVAL, and the message names the limit.  For n <= 128 the tours
+ * and costs equal tspgnn_tour_search_knn's bit for bit.
  */
 int tspgnn_tour_search_knn_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                const long long* t_off, const long long* index, int n_inst, int n_max, int restarts,
@@ -547,8 +551,8 @@ int tspgnn_tour_search_cand(const float* W, const long long* w_off, const int* n
 
 /*
  * tspgnn_tour_search_cand on the packed strict upper triangle of tspgnn_tour_search_tri, n_max <= 256 (above:
- * TSPGNN_EUNSUPPORTED).  LDS: 2 n_max (n_max - 1) + n_max * columns + 13 restarts n_max bytes must fit 163 712, as for
- * tspgnn_tour_search_knn_tri.  For n <= 128 the tours and costs equal tspgnn_tour_search_cand's bit for bit.
+ * TSPGNN_EUNSUPPORTED).  restarts <= tspgnn_tour_chains_fit(1, n_max, columns), as for tspgnn_tour_search_knn_tri.  For
+ * n <= 128 the tours and costs equal tspgnn_tour_search_cand's bit for bit.
  */
 int tspgnn_tour_search_cand_tri(const float* W, const long long* w_off, const int* n, const int32_t* init_tours,
                                 const long long* t_off, const long long* index, const uint8_t* cand,
@@ -608,6 +612,13 @@ int tspgnn_tour_branch_bound(const float* W, const long long* w_off, const int* 
 /* Bytes of workspace tspgnn_tour_branch_bound needs for n_inst instances at n_max (dataset.py:9-50): n_inst *
  * TSPGNN_BB_MAX_DEPTH * n_max floats; 0 for an empty or unsupported request. */
 long long tspgnn_tour_branch_bound_ws(int n_inst, int n_max);
+
+/* The chains (restarts of the searches, chains of tspgnn_tour_anneal, waves of tspgnn_tour_nearest_neighbor's every-start
+ * run) that fit in LDS at n_max, 16 at the most: tri != 0 the packed triangle (n_max <= 256), else the dense matrix
+ * (n_max <= 128); neighbors = 0 the full scan, 1..32 the columns of the _knn / _cand table.  0 for an n_max outside
+ * [4, the layout's limit] or neighbors outside [0, 32].  Host only: touches no device.  The layout behind it is stated
+ * at tspgnn_tour_search_tri. */
+long long tspgnn_tour_chains_fit(int tri, int n_max, int neighbors);
 
 /*
  * Metric closure of `count` weight matrices, in place: batched Floyd-Warshall in fp64, one workgroup per instance.

@@ -160,3 +160,41 @@ def test_reference_chain_at_zero_temperature_is_a_descent():
     assert ref.cost64(W, best) <= ref.cost64(W, start)
     # no budget: the start itself
     assert ref.chain(W, start, 1, 0, 0, np.zeros(0, dtype=np.float32), 100)[0] == start
+
+
+def _nn(n_inst, n_max, start, W=16):
+    p = ctypes.c_void_p(16)
+    return (ctypes.c_void_p(W), p, p, p, n_inst, n_max, start, p, p, None)
+
+
+def _sa(n_inst, n_max, chains, levels, W=16):
+    p = ctypes.c_void_p(16)
+    return (ctypes.c_void_p(W), p, p, None, p, None, p, p, n_inst, n_max, chains, levels, 0, p, p, None)
+
+
+# Two arguments wrong at once: which one an entry point names is the order of its checks.  Codes and messages as the
+# library gave them before check_layout moved to csrc/tour_common.h.
+TWO_FAULTS = [
+    ("tspgnn_tour_nearest_neighbor", _nn(4, 129, -2), -2, "tour_nearest_neighbor: n_max=129 exceeds 128"),
+    ("tspgnn_tour_nearest_neighbor", _nn(4, 3, -2), -1, "tour_nearest_neighbor: n_max=3 must be at least 4"),
+    ("tspgnn_tour_nearest_neighbor", _nn(4, 20, -2, W=0), -1,
+     "tour_nearest_neighbor: start=-2 must be a vertex (>= 0) or -1 for every start"),
+    ("tspgnn_tour_nearest_neighbor", _nn(-1, 0, -2, W=0), -1, "tour_nearest_neighbor: n_inst=-1"),
+    ("tspgnn_tour_nearest_neighbor_tri", _nn(4, 257, -2, W=0), -2, "tour_nearest_neighbor_tri: n_max=257 exceeds 256"),
+    ("tspgnn_tour_nearest_neighbor_tri", _nn(4, 256, -5, W=0), -1,
+     "tour_nearest_neighbor_tri: start=-5 must be a vertex (>= 0) or -1 for every start"),
+    ("tspgnn_tour_anneal", _sa(4, 129, 0, -1), -2, "tour_anneal: n_max=129 exceeds 128"),
+    ("tspgnn_tour_anneal", _sa(4, 3, 17, -1), -1, "tour_anneal: n_max=3 must be at least 4"),
+    ("tspgnn_tour_anneal", _sa(4, 20, 17, -1), -1, "tour_anneal: chains=17 not in [1, 16]"),
+    ("tspgnn_tour_anneal", _sa(4, 20, 4, -1, W=0), -1, "tour_anneal: levels=-1"),
+    ("tspgnn_tour_anneal", _sa(-1, 129, 0, -1, W=0), -1, "tour_anneal: n_inst=-1"),
+    ("tspgnn_tour_anneal_tri", _sa(4, 257, 0, -1), -2, "tour_anneal_tri: n_max=257 exceeds 256"),
+    ("tspgnn_tour_anneal_tri", _sa(4, 256, 11, -1), -1, "tour_anneal_tri: chains=11: at n_max=256 at most 10 chains fit in LDS"),
+    ("tspgnn_tour_anneal_tri", _sa(4, 256, 17, -1, W=0), -1, "tour_anneal_tri: chains=17 not in [1, 16]"),
+]
+
+
+@pytest.mark.parametrize("entry,args,code,message", TWO_FAULTS, ids=["%s-%d" % (t[0][12:], k) for k, t in enumerate(TWO_FAULTS)])
+def test_two_faults_at_once_name_the_first_check(entry, args, code, message):
+    assert getattr(_lib.lib, entry)(*args) == code
+    assert _lib.lib.tspgnn_last_error().decode() == message

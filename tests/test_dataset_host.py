@@ -176,3 +176,66 @@ def test_solve_tours_rejects_bad_instances_without_gpu():
         dataset.solve_tours([(np.ones((5, 5)), np.ones((5, 5)))], restarts=17)
     with pytest.raises(ValueError):
         dataset.solve_tours([(np.ones((5, 5)), np.ones((5, 5)))], init_tours=[[0, 1, 2, 3, 3]])
+
+
+def _search(n_inst, n_max, restarts, kicks, W=16):
+    p = ctypes.c_void_p(16)
+    return (ctypes.c_void_p(W), p, p, None, p, None, n_inst, n_max, restarts, kicks, 0, p, p, None)
+
+
+def _knn(n_inst, n_max, restarts, kicks, neighbors):
+    p = ctypes.c_void_p(16)
+    return (p, p, p, None, p, None, n_inst, n_max, restarts, kicks, neighbors, 0, p, p, None)
+
+
+def _cand(n_inst, n_max, restarts, kicks, columns, W=16, cand=16):
+    p = ctypes.c_void_p(16)
+    return (ctypes.c_void_p(W), p, p, None, p, None, ctypes.c_void_p(cand), p, n_inst, n_max, restarts, kicks, columns, 0,
+            p, p, None)
+
+
+def _bound(n_inst, n_max, iters, W=16):
+    p = ctypes.c_void_p(16)
+    return (ctypes.c_void_p(W), p, p, p, n_inst, n_max, iters, p, None)
+
+
+# Two arguments wrong at once: which one an entry point names is the order of its checks.  Codes and messages as the
+# library gave them before the entry points shared check_layout (csrc/tour_common.h).
+TWO_FAULTS = [
+    ("tspgnn_tour_search", _search(4, 129, 0, 8), -2, "tour_search: n_max=129 exceeds 128"),
+    ("tspgnn_tour_search", _search(4, 3, 17, 8), -1, "tour_search: n_max=3 must be at least 4"),
+    ("tspgnn_tour_search", _search(4, 20, 17, -1), -1, "tour_search: restarts=17 not in [1, 16]"),
+    ("tspgnn_tour_search", _search(-1, 129, 4, 8, W=0), -1, "tour_search: n_inst=-1"),
+    ("tspgnn_tour_search", _search(4, 20, 4, -1, W=0), -1, "tour_search: kicks=-1"),
+    ("tspgnn_tour_search_tri", _search(4, 257, 0, 8), -2, "tour_search_tri: n_max=257 exceeds 256"),
+    ("tspgnn_tour_search_tri", _search(4, 256, 11, -1), -1,
+     "tour_search_tri: restarts=11: at n_max=256 at most 10 chains fit in LDS"),
+    ("tspgnn_tour_search_tri", _search(4, 3, 0, -1), -1, "tour_search_tri: n_max=3 must be at least 4"),
+    ("tspgnn_tour_search_knn", _knn(4, 129, 4, 8, 0), -1, "tour_search_knn: neighbors=0 not in [1, 32]"),
+    ("tspgnn_tour_search_knn", _knn(4, 129, 0, 8, 8), -2, "tour_search_knn: n_max=129 exceeds 128"),
+    ("tspgnn_tour_search_knn", _knn(-1, 20, 4, 8, 33), -1, "tour_search_knn: n_inst=-1"),
+    ("tspgnn_tour_search_knn_tri", _knn(4, 3, 4, 8, 33), -1, "tour_search_knn_tri: neighbors=33 not in [1, 32]"),
+    ("tspgnn_tour_search_knn_tri", _knn(4, 256, 10, -1, 8), -1,
+     "tour_search_knn_tri: restarts=10: at n_max=256 at most 9 chains fit in LDS"),
+    ("tspgnn_tour_search_knn_tri", _knn(4, 257, 17, 8, 8), -2, "tour_search_knn_tri: n_max=257 exceeds 256"),
+    ("tspgnn_tour_search_cand", _cand(4, 300, 4, 8, 33), -1, "tour_search_cand: columns=33 not in [1, 32]"),
+    ("tspgnn_tour_search_cand", _cand(4, 20, 4, -1, 8, cand=0), -1, "tour_search_cand: kicks=-1"),
+    ("tspgnn_tour_search_cand", _cand(4, 20, 4, 8, 8, W=0, cand=0), -1, "tour_search_cand: null pointer"),
+    ("tspgnn_tour_search_cand_tri", _cand(4, 257, 4, 8, 0), -1, "tour_search_cand_tri: columns=0 not in [1, 32]"),
+    ("tspgnn_tour_search_cand_tri", _cand(4, 256, 10, 8, 8, cand=0), -1,
+     "tour_search_cand_tri: restarts=10: at n_max=256 at most 9 chains fit in LDS"),
+    ("tspgnn_tour_search_cand_tri", _cand(4, 3, 0, 8, 8), -1, "tour_search_cand_tri: n_max=3 must be at least 4"),
+    ("tspgnn_tour_lower_bound", _bound(4, 129, 0), -2, "tour_lower_bound: n_max=129 exceeds 128"),
+    ("tspgnn_tour_lower_bound", _bound(4, 3, 0), -1, "tour_lower_bound: n_max=3 must be at least 4"),
+    ("tspgnn_tour_lower_bound", _bound(4, 20, 0, W=0), -1, "tour_lower_bound: iters=0"),
+    ("tspgnn_tour_lower_bound", _bound(-1, 129, 0, W=0), -1, "tour_lower_bound: n_inst=-1"),
+    ("tspgnn_tour_lower_bound_tri", _bound(4, 257, 0), -2, "tour_lower_bound_tri: n_max=257 exceeds 256"),
+    ("tspgnn_tour_lower_bound_tri", _bound(4, 3, 0, W=0), -1, "tour_lower_bound_tri: n_max=3 must be at least 4"),
+    ("tspgnn_tour_lower_bound_tri", _bound(4, 256, 0, W=0), -1, "tour_lower_bound_tri: iters=0"),
+]
+
+
+@pytest.mark.parametrize("entry,args,code,message", TWO_FAULTS, ids=["%s-%d" % (t[0][12:], k) for k, t in enumerate(TWO_FAULTS)])
+def test_two_faults_at_once_name_the_first_check(entry, args, code, message):
+    assert getattr(_lib.lib, entry)(*args) == code
+    assert _lib.lib.tspgnn_last_error().decode() == message

@@ -259,3 +259,19 @@ def test_prove_tours_rejects_bad_arguments_without_gpu():
         dataset.prove_tours([tri], [r._replace(tour=[0, 1, 1])])
     with pytest.raises(ValueError, match="max_nodes"):
         dataset.label_tours([tri], exact=True, max_nodes=0)
+
+
+# Two arguments wrong at once: which one the entry point names is the order of its checks.  Codes and messages as the
+# library gave them before the entry point took check_layout of csrc/tour_common.h.
+@pytest.mark.parametrize("kw,code,message", [
+    (dict(n_max=129, root_iters=0, node_iters=0, max_nodes=0, opt_tol=-1.0), -2, "n_max=129 exceeds 128"),
+    (dict(n_max=3, root_iters=0, max_nodes=0), -1, "n_max=3 must be at least 4"),
+    (dict(root_iters=0, node_iters=1, max_nodes=0), -1, "root_iters=0, node_iters=1"),
+    (dict(root_iters=1, node_iters=0, max_nodes=70000, opt_tol=-1.0), -1, "root_iters=1, node_iters=0"),
+    (dict(max_nodes=70000, opt_tol=-1.0), -1, "max_nodes=70000 not in [1, 65536]"),
+    (dict(opt_tol=-1.0, W=None), -1, "opt_tol=-1 must be finite and >= 0"),
+    (dict(n_inst=-1, n_max=129, root_iters=0, W=None), -1, "n_inst=-1"),
+])
+def test_two_faults_at_once_name_the_first_check(kw, code, message):
+    assert _bb(**kw) == code
+    assert _lib.lib.tspgnn_last_error().decode() == "tour_branch_bound: " + message

@@ -106,6 +106,28 @@ def test_lds_budget_matches_the_kernel():
     assert b"at most 12" in L.tspgnn_last_error()
 
 
+def test_chains_fit_query_is_the_closed_form():
+    """tspgnn_tour_chains_fit against this file's own statement of the budget (above), for every n of both layouts and
+    every table width: the weights, n K bytes of table, and per chain 12 n bytes of tours plus n of positions with a
+    table, in 163 712 bytes; 16 chains at the most."""
+    q = _lib.lib.tspgnn_tour_chains_fit
+    for tri, top in ((0, 128), (1, 256)):
+        for n in range(4, 257):
+            weights = 2 * n * (n - 1) if tri else 4 * n * (n | 1)
+            for K in range(0, 33):
+                want = min(16, (163712 - weights - n * K) // ((13 if K else 12) * n)) if n <= top else 0
+                assert q(tri, n, K) == want, (tri, n, K)
+                if want:
+                    assert weights + n * K + (13 if K else 12) * want * n <= 163712
+        for n, K in ((3, 0), (0, 8), (-1, 0), (top + 1, 0), (top + 1, 8), (20, -1), (20, 33), (top, 33)):
+            assert q(tri, n, K) == 0, (tri, n, K)
+    assert q(1, 256, 0) == 10 and q(1, 256, 8) == 9 and q(1, 256, 32) == 7 and q(0, 128, 32) == 16
+    for n in (129, 200, 242, 243, 256):
+        assert dataset.tri_chains_fit(n) == dataset.tri_chains_fit(n, None) == q(1, n, 0)
+        for K in (1, 8, 32):
+            assert dataset.tri_chains_fit(n, K) == q(1, n, K)
+
+
 def test_knn_entry_points_reject_bad_arguments_without_gpu():
     L = _lib.lib
     p = ctypes.c_void_p(16)

@@ -63,21 +63,20 @@ __global__ __launch_bounds__(kWave* kMaxChains) void nearest_neighbor_kernel(
     const float* __restrict__ Wg, const long long* __restrict__ w_off, const int* __restrict__ n_arr,
     const long long* __restrict__ t_off, int n_max, int start, int32_t* __restrict__ tours, float* __restrict__ costs) {
     extern __shared__ float lds[];
-    __shared__ float s_cost[kMaxChains];
-    __shared__ int s_start[kMaxChains];
+    __shared__ ChainPosts post;
     const int inst = blockIdx.x;
     const int n = n_arr[inst];
     const int waves = blockDim.x / kWave;
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    if (n < 4 || n > n_max) {   // the host never sends these; a defensive no-op keeps every LDS index in bounds
-        if (threadIdx.x == 0) costs[inst] = __int_as_float(0x7fc00000);
+    if (never_sent(n, n_max)) {
+        if (threadIdx.x == 0) refuse(&costs[inst]);
         return;
     }
     const WA W = WA::stage(lds, Wg + w_off[inst], n, threadIdx.x, blockDim.x);
-    // per wave: the tour under construction and the wave's best (the third slot of the chain layout stays unused)
-    int* base = reinterpret_cast<int*>(lds + WA::floats(n_max)) + wave * 3 * n_max;
-    int* cur = base;
-    int* best = base + n_max;
+    const ChainLds<WA> ws{lds, n_max, waves, 0};
+    // per wave: the tour under construction and the wave's best (the third tour of the chain layout stays unused)
+    int* cur = ws.tour(wave, 0);
+    int* best = ws.tour(wave, 1);
     __syncthreads();
 
     float bc = FLT_MAX;
@@ -98,22 +97,10 @@ __global__ __launch_bounds__(kWave* kMaxChains) void nearest_neighbor_kernel(
             }
         }
     }
-    if (lane == 0) {
-        s_cost[wave] = bc;
-        s_start[wave] = bs;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    int bw = 0;   // wave 0 always has start 0 (or the one start); a wave past n has none (INT_MAX)
-    for (int c = 1; c < waves; ++c) {
-        if (s_start[c] != INT_MAX && (s_cost[c] < bc || (s_cost[c] == bc && s_start[c] < bs))) {
-            bc = s_cost[c];
-            bs = s_start[c];
-            bw = c;
-        }
-    }
-    write_canonical(base + bw * 3 * n_max + n_max, n, tours + t_off[inst], lane);
-    if (lane == 0) costs[inst] = bc;
+    // ties to the smaller start.  Wave 0 always has start 0 (or the one start); a wave past n has none and posts
+    // (+inf, INT_MAX), which is below no pair that wave 0 can post
+    if (bs == INT_MAX) bc = __int_as_float(0x7f800000);
+    chain_winner(ws, post, wave, lane, bc, bs, n, tours + t_off[inst], &costs[inst]);
 }
 
 template <class WA>
@@ -123,7 +110,7 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_anneal_kernel(
     const float* __restrict__ inv_temp, const int* __restrict__ per_level_arr, int n_max, int levels,
     unsigned long long seed, int32_t* __restrict__ tours, float* __restrict__ costs) {
     extern __shared__ float lds[];
-    __shared__ float s_cost[kMaxChains];
+    __shared__ ChainPosts post;
     const int inst = blockIdx.x;
     const long long gi = index ? index[inst] : inst;
     const int n = n_arr[inst];
@@ -132,36 +119,21 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_anneal_kernel(
     const int chains = blockDim.x / kWave;
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
     // the host module never sends these; a defensive no-op keeps every LDS index in bounds and the trip count bounded
-    if (n < 4 || n > n_max || per_level < 0 || budget > (long long)INT_MAX) {
-        if (threadIdx.x == 0) costs[inst] = __int_as_float(0x7fc00000);
+    if (never_sent(n, n_max) || per_level < 0 || budget > (long long)INT_MAX) {
+        if (threadIdx.x == 0) refuse(&costs[inst]);
         return;
     }
     const WA W = WA::stage(lds, Wg + w_off[inst], n, threadIdx.x, blockDim.x);
-    // per chain: three tours of n vertex ids (current, best, scratch) after the weights
-    int* base = reinterpret_cast<int*>(lds + WA::floats(n_max)) + wave * 3 * n_max;
-    int* cur = base;
-    int* best = base + n_max;
-    int* scr = base + 2 * n_max;
+    const ChainLds<WA> ws{lds, n_max, chains, 0};
+    // the chain's three tours: current, best, scratch
+    int* cur = ws.tour(wave, 0);
+    int* best = ws.tour(wave, 1);
+    int* scr = ws.tour(wave, 2);
     __syncthreads();
 
     // starting tour: chain 0 takes init_tours when given and a permutation of 0..n-1; otherwise nearest neighbour from
     // vertex chain % n
-    bool have = false;
-    if (wave == 0 && init) {
-        const int32_t* it = init + t_off[inst];
-        for (int k = lane; k < n; k += kWave) scr[k] = 0;
-        wave_sync();
-        int bad = 0;
-        for (int k = lane; k < n; k += kWave) {
-            const int v = it[k];
-            cur[k] = v;
-            if (v < 0 || v >= n) bad = 1;
-            else atomicAdd(&scr[v], 1);
-        }
-        wave_sync();
-        for (int k = lane; k < n; k += kWave) bad |= scr[k] != 1;
-        have = wave_sum(bad) == 0;
-    }
+    const bool have = wave == 0 && init && load_permutation(init + t_off[inst], cur, scr, n, lane);
     if (!have) nearest_neighbor(W, n, wave % n, cur, lane);
     for (int k = lane; k < n; k += kWave) best[k] = cur[k];
     wave_sync();
@@ -186,10 +158,8 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_anneal_kernel(
                 i = j;
                 j = x;
             }
-            // 2-exchange: reverse positions i+1..j (0 <= i, i+1 < j <= n-1, not the whole cycle); anything else is void
-            if (j > i + 1 && !(i == 0 && j == n - 1)) {
-                const int a = cur[i], b = cur[i + 1], c = cur[j], e = cur[j + 1 < n ? j + 1 : 0];
-                d = (W(a, c) + W(b, e)) - (W(a, b) + W(c, e));
+            two_exchange(W, cur, n, i, j, [&](float dm) {   // anything else is void
+                d = dm;
                 if (d <= 0.f) {
                     acc = true;
                 } else {
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_anneal_kernel(
                     const float u = ((float)(unsigned)((r >> 40) & 0x7fffff) + 0.5f) * 0x1p-23f;
                     acc = u < expf(-(d * itl));
                 }
-            }
+            });
         }
         const unsigned long long m = __ballot(acc);
         unsigned adv = kWave;
@@ -229,27 +199,7 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_anneal_kernel(
         }
     }
     wave_sync();
-    const float c = tour_cost(W, best, n, lane);
-    if (lane == 0) s_cost[wave] = c;
-    __syncthreads();
-    if (wave != 0) return;
-    float bc = s_cost[0];
-    int bw = 0;
-    for (int k = 1; k < chains; ++k) {
-        if (s_cost[k] < bc) {
-            bc = s_cost[k];
-            bw = k;
-        }
-    }
-    write_canonical(base + bw * 3 * n_max + n_max, n, tours + t_off[inst], lane);
-    if (lane == 0) costs[inst] = bc;
-}
-
-template <class WA>
-int check_layout(const char* what, int n_max) {
-    if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
-    return TSPGNN_OK;
+    chain_winner(ws, post, wave, lane, tour_cost(W, best, n, lane), 0, n, tours + t_off[inst], &costs[inst]);
 }
 
 template <class WA>
@@ -261,8 +211,8 @@ int nearest(const char* entry, const char* what, const float* W, const long long
     if (rc) return rc;
     TSPGNN_REQUIRE(start >= -1, "%s: start=%d must be a vertex (>= 0) or -1 for every start", what, start);
     TSPGNN_REQUIRE(W && w_off && n && t_off && tours && costs, "%s: null pointer", what);
-    const int waves = start >= 0 ? 1 : chains_fit<WA>(n_max);
-    const size_t lds = (WA::floats(n_max) + (size_t)3 * waves * n_max) * sizeof(float);
+    const int waves = start >= 0 ? 1 : ChainLds<WA>::fit(n_max, 0);
+    const size_t lds = ChainLds<WA>{nullptr, n_max, waves, 0}.bytes();
     rc = allow_lds(nearest_neighbor_kernel<WA>, lds);
     if (rc) return rc;
     nearest_neighbor_kernel<WA><<<(unsigned)n_inst, kWave * waves, lds, as_stream(stream)>>>(W, w_off, n, t_off, n_max, start,
@@ -279,12 +229,12 @@ int anneal(const char* entry, const char* what, const float* W, const long long*
     int rc = check_layout<WA>(what, n_max);
     if (rc) return rc;
     TSPGNN_REQUIRE(chains >= 1 && chains <= kMaxChains, "%s: chains=%d not in [1, %d]", what, chains, kMaxChains);
-    TSPGNN_REQUIRE(chains <= chains_fit<WA>(n_max), "%s: chains=%d: at n_max=%d at most %d chains fit in LDS", what, chains,
-                   n_max, chains_fit<WA>(n_max));
+    const int fit = ChainLds<WA>::fit(n_max, 0);
+    TSPGNN_REQUIRE(chains <= fit, "%s: chains=%d: at n_max=%d at most %d chains fit in LDS", what, chains, n_max, fit);
     TSPGNN_REQUIRE(levels >= 0, "%s: levels=%d", what, levels);
     TSPGNN_REQUIRE(W && w_off && n && t_off && per_level && tours && costs && (inv_temp || levels == 0),
                    "%s: null pointer", what);
-    const size_t lds = (WA::floats(n_max) + (size_t)3 * chains * n_max) * sizeof(float);
+    const size_t lds = ChainLds<WA>{nullptr, n_max, chains, 0}.bytes();
     rc = allow_lds(tour_anneal_kernel<WA>, lds);
     if (rc) return rc;
     tour_anneal_kernel<WA><<<(unsigned)n_inst, kWave * chains, lds, as_stream(stream)>>>(

@@ -1,7 +1,9 @@
 // Device and host helpers shared by the tour kernels (tour_search.hip, tour_baselines.hip, tour_exact.hip): the two LDS
 // layouts of an instance's weights, the counter-based generator, the wave reductions, the canonical form and its
-// write-out, the LDS budget, and the Held-Karp 1-tree with its subgradient ascent (the bound kernel and the branch and
-// bound).  What only the readers of the edge votes share sits on top of this header, in vote_common.h.
+// write-out, the Held-Karp 1-tree with its subgradient ascent (the bound kernel and the branch and bound), the entry
+// points' n_max check, the refusal of an instance the host never sends, the starting-tour check, the 2-exchange move, and
+// the chain kernels' workspace in LDS with its budget and the chain winner.  What only the readers of the edge votes
+// share sits on top of this header, in vote_common.h.
 #pragma once
 #include "common.h"
 
@@ -411,26 +413,115 @@ int allow_lds(K kernel, size_t bytes) {
     return TSPGNN_OK;
 }
 
-// Static LDS of a chain kernel (per chain one float and one int: s_cost, s_tour); the dynamic part must fit beside it.
-constexpr size_t kSearchStaticLds = kMaxChains * (sizeof(float) + sizeof(int));
-
-// The chains that fit at n_max: the weights plus three tours of n_max int32 ids per chain.
+// What every tour entry point checks of n_max, in this order: the layout's limit, then the smallest instance.
 template <class WA>
-int chains_fit(int n_max) {
-    const size_t free_bytes = kLdsBytes - kSearchStaticLds - WA::floats(n_max) * sizeof(float);
-    const size_t c = free_bytes / ((size_t)3 * n_max * sizeof(int));
-    return c < (size_t)kMaxChains ? (int)c : kMaxChains;
+int check_layout(const char* what, int n_max) {
+    if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
+    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
+    return TSPGNN_OK;
 }
 
-// The _knn search (tour_search.hip) adds bytes: one neighbour table of n_max x neighbors ids for the workgroup and one
-// position array of n_max per chain.
+// An instance the host never sends (n outside [4, n_max]) is refused before the first LDS access, which keeps every LDS
+// index in bounds: one thread puts a NaN in place of its cost, or of its bound, and nothing else is written.  (The vote
+// kernels' form is vote_common.h's refuse_tour.)
+__device__ __forceinline__ bool never_sent(int n, int n_max) { return n < 4 || n > n_max; }
+__device__ __forceinline__ void refuse(float* cost) { *cost = __int_as_float(0x7fc00000); }
+__device__ __forceinline__ void refuse(double* lb) { *lb = __longlong_as_double(0x7ff8000000000000ll); }
+
+// One wave copies n vertex ids from global memory into the LDS tour t and says whether they are a permutation of
+// 0..n-1 (cnt: n ints of LDS scratch).  The callers take every later LDS index from t: on "no" they replace or drop it.
+__device__ __forceinline__ bool load_permutation(const int32_t* src, int* t, int* cnt, int n, int lane) {
+    for (int k = lane; k < n; k += kWave) cnt[k] = 0;
+    wave_sync();
+    int bad = 0;
+    for (int k = lane; k < n; k += kWave) {
+        const int v = src[k];
+        t[k] = v;
+        if (v < 0 || v >= n) bad = 1;
+        else atomicAdd(&cnt[v], 1);
+    }
+    wave_sync();
+    for (int k = lane; k < n; k += kWave) bad |= cnt[k] != 1;
+    return wave_sum(bad) == 0;
+}
+
+// The 2-exchange move (i, j) of tour t, i <= j: reverse positions i+1..j.  It is a move when i + 1 < j <= n - 1 and the
+// segment is not the whole cycle; f(d) then gets its fp32 cost change.  (A callback, as vote_common.h's with_ends: the
+// body sits under the same branches as a spelled-out test.)
+template <class WA, class F>
+__device__ __forceinline__ void two_exchange(const WA& W, const int* t, int n, int i, int j, F&& f) {
+    if (j > i + 1 && !(i == 0 && j == n - 1)) {
+        const int a = t[i], b = t[i + 1], c = t[j], e = t[j + 1 < n ? j + 1 : 0];
+        f((W(a, c) + W(b, e)) - (W(a, b) + W(c, e)));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ chain workspace
+// A chain kernel (the searches, nearest neighbour, the annealing) runs one workgroup per instance and one wave64 per
+// chain.  Its static LDS is what the chains post for the pick of the winner: a cost and a tag (chain_winner below: the
+// tie-break; the search: where the chain's best tour lies).
+struct ChainPosts {
+    float cost[kMaxChains];
+    int tag[kMaxChains];
+};
+static_assert(sizeof(ChainPosts) == kMaxChains * (sizeof(float) + sizeof(int)), "the static LDS beside ChainLds::bytes()");
+
+// Its dynamic LDS -- THE statement of the layout (include/tspgnn.h and DESIGN.md §12 give the byte formula):
+//   the weights, WA::floats(n_max) fp32;
+//   per chain three tours of n_max int32 vertex ids;
+//   with a candidate table (neighbors > 0) the workgroup's byte table [n_max][neighbors], then per chain a byte position
+//   array [n_max].
+// Together with ChainPosts it must fit kLdsBytes.  The carve uses n_max, never an instance's own n.
 constexpr int kMaxNeighbors = 32;
 template <class WA>
-int knn_chains_fit(int n_max, int neighbors) {
-    const size_t free_bytes =
-        kLdsBytes - kSearchStaticLds - WA::floats(n_max) * sizeof(float) - (size_t)n_max * (size_t)neighbors;
-    const size_t c = free_bytes / ((size_t)3 * n_max * sizeof(int) + (size_t)n_max);
-    return c < (size_t)kMaxChains ? (int)c : kMaxChains;
+struct ChainLds {
+    float* lds;                      // the workgroup's dynamic LDS (host: null)
+    int n_max, chains, neighbors;    // neighbors = 0: no table, no positions
+
+    static size_t weight_bytes(int n_max) { return WA::floats(n_max) * sizeof(float); }
+    static size_t chain_bytes(int n_max, int neighbors) { return (size_t)3 * n_max * sizeof(int) + (neighbors ? n_max : 0); }
+    // the dynamic LDS bytes of a launch
+    size_t bytes() const {
+        return weight_bytes(n_max) + (size_t)n_max * neighbors + (size_t)chains * chain_bytes(n_max, neighbors);
+    }
+    // the chains that fit at n_max, kMaxChains at the most
+    static int fit(int n_max, int neighbors) {
+        const size_t free_bytes = kLdsBytes - sizeof(ChainPosts) - weight_bytes(n_max) - (size_t)n_max * (size_t)neighbors;
+        const size_t c = free_bytes / chain_bytes(n_max, neighbors);
+        return c < (size_t)kMaxChains ? (int)c : kMaxChains;
+    }
+
+    __device__ __forceinline__ int* tour(int chain, int slot) const {
+        return reinterpret_cast<int*>(lds + WA::floats(n_max)) + (chain * 3 + slot) * n_max;
+    }
+    __device__ __forceinline__ uint8_t* table() const { return reinterpret_cast<uint8_t*>(tour(chains, 0)); }
+    __device__ __forceinline__ uint8_t* positions(int chain) const { return table() + n_max * neighbors + chain * n_max; }
+};
+
+// The chain winner of nearest neighbour and the annealing.  Every wave of the workgroup calls this once: its chain's best
+// tour is tour 1 of its workspace, of fp32 cost `cost`.  Wave 0 takes the smallest (cost, tie), equal pairs to the lower
+// chain, and writes that tour to tour_out in canonical form and its cost to *cost_out.  (The search keeps its own pick:
+// its best tour is any of the chain's three, and this routine in its place cost the full scan 1.6 % at n = 200,
+// profiles/chain_refactor_ab.txt.)
+template <class WA>
+__device__ __forceinline__ void chain_winner(const ChainLds<WA>& ws, ChainPosts& post, int wave, int lane, float cost,
+                                             int tie, int n, int32_t* tour_out, float* cost_out) {
+    if (lane == 0) {
+        post.cost[wave] = cost;
+        post.tag[wave] = tie;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    float bc = post.cost[0];
+    int bw = 0;
+    for (int c = 1; c < ws.chains; ++c) {
+        if (post.cost[c] < bc || (post.cost[c] == bc && post.tag[c] < post.tag[bw])) {
+            bc = post.cost[c];
+            bw = c;
+        }
+    }
+    write_canonical(ws.tour(bw, 1), n, tour_out, lane);
+    if (lane == 0) *cost_out = bc;
 }
 
 }  // namespace

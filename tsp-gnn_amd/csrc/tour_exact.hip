@@ -144,25 +144,12 @@ __global__ __launch_bounds__(kWave) void tour_branch_bound_kernel(
     __shared__ double s_lr[kDepth];
     const int inst = blockIdx.x, lane = threadIdx.x;
     const int n = n_arr[inst];
-    const double nan = __longlong_as_double(0x7ff8000000000000ll), dinf = __longlong_as_double(0x7ff0000000000000ll);
-    int bad = n < 4 || n > n_max;
+    const double dinf = __longlong_as_double(0x7ff0000000000000ll);
     int32_t* tg = tours + t_off[inst];
-    if (!bad) {   // the incumbent must be a permutation of 0..n-1: every later LDS index comes from it
-        for (int k = lane; k < n; k += kWave) cnt[k] = 0;
-        wave_sync();
-        for (int k = lane; k < n; k += kWave) {
-            const int v = tg[k];
-            inc_t[k] = v;
-            if (v < 0 || v >= n) bad = 1;
-            else atomicAdd(&cnt[v], 1);
-        }
-        wave_sync();
-        for (int k = lane; k < n; k += kWave) bad |= cnt[k] != 1;
-        bad = wave_sum(bad) != 0;
-    }
-    if (bad) {
+    // the incumbent must be a permutation of 0..n-1: every later LDS index comes from it
+    if (never_sent(n, n_max) || !load_permutation(tg, inc_t, cnt, n, lane)) {
         if (lane == 0) {
-            lb[inst] = nan;
+            refuse(&lb[inst]);
             nodes_out[inst] = 0;
             status_out[inst] = TSPGNN_BB_BAD;
         }
@@ -343,15 +330,15 @@ extern "C" int tspgnn_tour_branch_bound(const float* W, const long long* w_off, 
     const char* what = "tour_branch_bound";
     TSPGNN_REQUIRE(n_inst >= 0, "%s: n_inst=%d", what, n_inst);
     if (n_inst == 0) return TSPGNN_OK;
-    if (n_max > kN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, kN);
-    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
+    int rc = check_layout<SquareW>(what, n_max);
+    if (rc) return rc;
     TSPGNN_REQUIRE(root_iters >= 1 && node_iters >= 1, "%s: root_iters=%d, node_iters=%d", what, root_iters, node_iters);
     TSPGNN_REQUIRE(max_nodes >= 1 && max_nodes <= kMaxNodes, "%s: max_nodes=%d not in [1, %d]", what, max_nodes,
                    kMaxNodes);
     TSPGNN_REQUIRE(opt_tol >= 0.0 && opt_tol < (double)FLT_MAX, "%s: opt_tol=%g must be finite and >= 0", what, opt_tol);
     TSPGNN_REQUIRE(W && w_off && n && t_off && workspace && tours && lb && nodes && status, "%s: null pointer", what);
     const size_t lds = SquareW::floats(n_max) * sizeof(float) + (size_t)n_max * cons_stride(n_max);
-    int rc = allow_lds(tour_branch_bound_kernel, lds);
+    rc = allow_lds(tour_branch_bound_kernel, lds);
     if (rc) return rc;
     tour_branch_bound_kernel<<<(unsigned)n_inst, kWave, lds, as_stream(stream)>>>(
         W, w_off, n, t_off, upper, n_max, root_iters, node_iters, max_nodes, opt_tol, static_cast<float*>(workspace), tours,

@@ -76,15 +76,13 @@ __device__ float descend(const WA& W, int*& t, int*& u, int n, int lane) {
         // 2-opt: reverse positions i+1..j (0 <= i, i+1 < j <= n-1, not the whole cycle)
         for (Strider p(n, lane); p.i < n; p.step()) {
             const int i = p.i, j = p.j;
-            if (j > i + 1 && !(i == 0 && j == n - 1)) {
-                const int a = t[i], b = t[i + 1], c = t[j], e = t[j + 1 < n ? j + 1 : 0];
-                const float d = (W(a, c) + W(b, e)) - (W(a, b) + W(c, e));
+            two_exchange(W, t, n, i, j, [&](float d) {
                 const int cd = (i << 8) | j;
                 if (d < best || (d == best && cd < code)) {
                     best = d;
                     code = cd;
                 }
-            }
+            });
         }
         // Or-opt: move the segment t[i..i+L-1] (cyclic) between t[p] and t[p+1], either orientation
         for (int L = 1; L <= 3 && L <= n - 3; ++L) {
@@ -228,9 +226,7 @@ struct KnnScan {
     __device__ __forceinline__ int wrap(int p) const { return p < 0 ? p + n : p >= n ? p - n : p; }
     // descend()'s 2-opt move (i, j), when it is one
     __device__ __forceinline__ void two_opt(int i, int j) {
-        if (i < 0 || !(j > i + 1) || (i == 0 && j == n - 1)) return;
-        const int a = t[i], b = t[i + 1], c = t[j], e = t[j + 1 < n ? j + 1 : 0];
-        take((W(a, c) + W(b, e)) - (W(a, b) + W(c, e)), (i << 8) | j);
+        if (i >= 0) two_exchange(W, t, n, i, j, [&](float d) { take(d, (i << 8) | j); });
     }
     // descend()'s Or-opt move (L, i, q) in the orientation rv, when it is one; i and q in [0, n)
     __device__ __forceinline__ void or_opt(int L, int i, int q, int rv) {
@@ -319,29 +315,27 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     const uint8_t* __restrict__ cand, const long long* __restrict__ c_off) {
     constexpr bool kKnn = kTab != kTabNone;
     extern __shared__ float lds[];
-    __shared__ float s_cost[kMaxChains];
-    __shared__ int s_tour[kMaxChains];
+    __shared__ ChainPosts post;
     const int inst = blockIdx.x;
     const long long gi = index ? index[inst] : inst;
     const int n = n_arr[inst];
     const int chains = blockDim.x / kWave;
     const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-    if (n < 4 || n > n_max) {   // the host never sends these; a defensive no-op keeps every LDS index in bounds
-        if (threadIdx.x == 0) costs[inst] = __int_as_float(0x7fc00000);
+    if (never_sent(n, n_max)) {
+        if (threadIdx.x == 0) refuse(&costs[inst]);
         return;
     }
     const WA W = WA::stage(lds, Wg + w_off[inst], n, threadIdx.x, blockDim.x);
-    // per chain: three tours of n vertex ids (current, work, scratch) after the weights
-    int* base = reinterpret_cast<int*>(lds + WA::floats(n_max)) + wave * 3 * n_max;
-    int* cur = base;
-    int* work = base + n_max;
-    int* scr = base + 2 * n_max;
+    const ChainLds<WA> ws{lds, n_max, chains, kKnn ? neighbors : 0};
+    // the chain's three tours: current, work, scratch
+    int* cur = ws.tour(wave, 0);
+    int* work = ws.tour(wave, 1);
+    int* scr = ws.tour(wave, 2);
     __syncthreads();
-    // _knn: after every chain's tours the neighbour table [n_max][neighbors], then one pos[n_max] per chain, all bytes
     Knn nb{};
     if constexpr (kKnn) {
-        nb.tab = reinterpret_cast<uint8_t*>(reinterpret_cast<int*>(lds + WA::floats(n_max)) + chains * 3 * n_max);
-        nb.pos = nb.tab + n_max * neighbors + wave * n_max;
+        nb.tab = ws.table();
+        nb.pos = ws.positions(wave);
         if constexpr (kTab == kTabGiven) {
             nb.kk = neighbors;
             stage_candidates<WA>(cand + c_off[inst], nb.tab, n, nb.kk, wave, chains, lane);
@@ -352,22 +346,7 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
     }
 
     // starting tour: chain 0 takes init_tours when given and a permutation of 0..n-1; otherwise Fisher-Yates
-    bool have = false;
-    if (wave == 0 && init) {
-        const int32_t* it = init + t_off[inst];
-        for (int k = lane; k < n; k += kWave) scr[k] = 0;
-        wave_sync();
-        int bad = 0;
-        for (int k = lane; k < n; k += kWave) {
-            const int v = it[k];
-            cur[k] = v;
-            if (v < 0 || v >= n) bad = 1;
-            else atomicAdd(&scr[v], 1);
-        }
-        wave_sync();
-        for (int k = lane; k < n; k += kWave) bad |= scr[k] != 1;
-        have = wave_sum(bad) == 0;
-    }
+    const bool have = wave == 0 && init && load_permutation(init + t_off[inst], cur, scr, n, lane);
     if (!have) {
         for (int k = lane; k < n; k += kWave) cur[k] = k;
         wave_sync();
@@ -396,21 +375,22 @@ __global__ __launch_bounds__(kWave* kMaxChains) void tour_search_kernel(
             best = c;
         }
     }
+    // the winner, ties to the lower chain (the descents have swapped cur among the chain's three tours)
     if (lane == 0) {
-        s_cost[wave] = best;
-        s_tour[wave] = (int)(cur - reinterpret_cast<int*>(lds));
+        post.cost[wave] = best;
+        post.tag[wave] = (int)(cur - reinterpret_cast<int*>(lds));
     }
     __syncthreads();
     if (wave != 0) return;
-    float bc = s_cost[0];
+    float bc = post.cost[0];
     int bw = 0;
     for (int c = 1; c < chains; ++c) {
-        if (s_cost[c] < bc) {
-            bc = s_cost[c];
+        if (post.cost[c] < bc) {
+            bc = post.cost[c];
             bw = c;
         }
     }
-    write_canonical(reinterpret_cast<const int*>(lds) + s_tour[bw], n, tours + t_off[inst], lane);
+    write_canonical(reinterpret_cast<const int*>(lds) + post.tag[bw], n, tours + t_off[inst], lane);
     if (lane == 0) costs[inst] = bc;
 }
 
@@ -427,8 +407,8 @@ __global__ __launch_bounds__(kWave) void tour_lower_bound_kernel(const float* __
     __shared__ int deg[WA::kMaxN];
     const int inst = blockIdx.x, lane = threadIdx.x;
     const int n = n_arr[inst];
-    if (n < 4 || n > n_max) {
-        if (lane == 0) lb[inst] = __longlong_as_double(0x7ff8000000000000ll);
+    if (never_sent(n, n_max)) {
+        if (lane == 0) refuse(&lb[inst]);
         return;
     }
     const WA W = WA::stage(lds, Wg + w_off[inst], n, lane, kWave);
@@ -454,18 +434,17 @@ int search(const char* entry, const char* what, const float* W, const long long*
     if constexpr (kKnn)
         TSPGNN_REQUIRE(neighbors >= 1 && neighbors <= kMaxNeighbors, "%s: %s=%d not in [1, %d]", what,
                        kTab == kTabGiven ? "columns" : "neighbors", neighbors, kMaxNeighbors);
-    if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
+    int rc = check_layout<WA>(what, n_max);
+    if (rc) return rc;
     TSPGNN_REQUIRE(restarts >= 1 && restarts <= kMaxChains, "%s: restarts=%d not in [1, %d]", what, restarts,
                    kMaxChains);
-    const int fit = kKnn ? knn_chains_fit<WA>(n_max, neighbors) : chains_fit<WA>(n_max);
+    const int fit = ChainLds<WA>::fit(n_max, neighbors);
     TSPGNN_REQUIRE(restarts <= fit, "%s: restarts=%d: at n_max=%d at most %d chains fit in LDS", what, restarts, n_max, fit);
     TSPGNN_REQUIRE(kicks >= 0, "%s: kicks=%d", what, kicks);
     TSPGNN_REQUIRE(W && w_off && n && t_off && tours && costs, "%s: null pointer", what);
     if constexpr (kTab == kTabGiven) TSPGNN_REQUIRE(cand && c_off, "%s: null pointer", what);
-    size_t lds = (WA::floats(n_max) + (size_t)3 * restarts * n_max) * sizeof(float);
-    if (kKnn) lds += (size_t)n_max * neighbors + (size_t)restarts * n_max;
-    int rc = allow_lds(tour_search_kernel<WA, kTab>, lds);
+    const size_t lds = ChainLds<WA>{nullptr, n_max, restarts, neighbors}.bytes();
+    rc = allow_lds(tour_search_kernel<WA, kTab>, lds);
     if (rc) return rc;
     tour_search_kernel<WA, kTab><<<(unsigned)n_inst, kWave * restarts, lds, as_stream(stream)>>>(
         W, w_off, n, init_tours, t_off, index, n_max, kicks, neighbors, seed, tours, costs, cand, c_off);
@@ -477,12 +456,12 @@ int lower_bound(const char* entry, const char* what, const float* W, const long 
                 int n_max, int iters, double* lb, void* stream) {
     TSPGNN_REQUIRE(n_inst >= 0, "%s: n_inst=%d", what, n_inst);
     if (n_inst == 0) return TSPGNN_OK;
-    if (n_max > WA::kMaxN) return fail(TSPGNN_EUNSUPPORTED, "%s: n_max=%d exceeds %d", what, n_max, WA::kMaxN);
-    TSPGNN_REQUIRE(n_max >= 4, "%s: n_max=%d must be at least 4", what, n_max);
+    int rc = check_layout<WA>(what, n_max);
+    if (rc) return rc;
     TSPGNN_REQUIRE(iters >= 1, "%s: iters=%d", what, iters);
     TSPGNN_REQUIRE(W && w_off && n && upper && lb, "%s: null pointer", what);
     const size_t lds = WA::floats(n_max) * sizeof(float);
-    int rc = allow_lds(tour_lower_bound_kernel<WA>, lds);
+    rc = allow_lds(tour_lower_bound_kernel<WA>, lds);
     if (rc) return rc;
     tour_lower_bound_kernel<WA><<<(unsigned)n_inst, kWave, lds, as_stream(stream)>>>(W, w_off, n, upper, n_max, iters, lb);
     return launched(entry);
@@ -552,4 +531,14 @@ extern "C" int tspgnn_tour_search_cand_tri(const float* W, const long long* w_of
     return search<TriW, kTabGiven>("tspgnn_tour_search_cand_tri", "tour_search_cand_tri", W, w_off, n, init_tours, t_off,
                                    index, n_inst, n_max, restarts, kicks, columns, seed, tours, costs, stream, cand,
                                    c_off);
+}
+
+template <class WA>
+static long long chains_fit_query(int n_max, int neighbors) {
+    if (n_max < 4 || n_max > WA::kMaxN || neighbors < 0 || neighbors > kMaxNeighbors) return 0;
+    return ChainLds<WA>::fit(n_max, neighbors);
+}
+
+extern "C" long long tspgnn_tour_chains_fit(int tri, int n_max, int neighbors) {
+    return tri ? chains_fit_query<TriW>(n_max, neighbors) : chains_fit_query<SquareW>(n_max, neighbors);
 }

@@ -153,7 +153,7 @@ HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn
                   "tspgnn_host_f64_repr")
 
 # size queries: name -> argtypes; these return long long (floats of workspace; tspgnn_tour_branch_bound_ws and
-# tspgnn_tour_beam_workspace_bytes: bytes)
+# tspgnn_tour_beam_workspace_bytes: bytes; tspgnn_tour_chains_fit: chains)
 SIZE_QUERIES = {
     "tspgnn_lnlstm_bwd_workspace_floats": [c_int],
     "tspgnn_wgrad_workspace_floats": [c_longlong, c_int, c_int],
@@ -162,6 +162,7 @@ SIZE_QUERIES = {
     "tspgnn_einit_bwd_workspace_floats": [c_int, c_int],
     "tspgnn_adam_workspace_floats": [],
     "tspgnn_tour_branch_bound_ws": [c_int, c_int],
+    "tspgnn_tour_chains_fit": [c_int, c_int, c_int],
     "tspgnn_tour_beam_workspace_bytes": [c_int, c_int, c_int],
 }
 

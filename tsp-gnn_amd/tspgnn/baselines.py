@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .dataset import (DEFAULT_CHUNK, MAX_N, MAX_N_TRI, _add_time, _device, _finish, _pack, _spans, _split, _upload,
-                      _validate, tri_chains_fit)
+from .dataset import (DEFAULT_CHUNK, MAX_N, MAX_N_TRI, _add_time, _check_chains_fit, _device, _finish, _pack, _spans,
+                      _split, _upload, _validate)
 
 # Annealing defaults, chosen from the t_hot x sweeps grid of DESIGN.md §12 (2^10 instances at n 20-40, 80 and 200 on the
 # MI355X).  Temperatures are multiples of the instance's mean real edge weight, and a level runs sweeps * n^2 proposals.
@@ -92,7 +92,7 @@ def anneal_tours(instances, chains=DEFAULT_CHAINS, levels=DEFAULT_LEVELS, sweeps
     """Simulated annealing over 2-exchange moves (Metropolis acceptance), many instances at once.
 
     instances, init_tours, index, seed, device, chunk: as for label_tours (n up to 256).  chains: wave64 chains per
-    instance (1..16; for n > 128 at most tri_chains_fit(largest n)).  Chain 0 starts from the instance's init_tours entry
+    instance (1..16; for n > 128 at most dataset.tri_chains_fit(largest n)).  Chain 0 starts from the instance's init_tours entry
     when there is one, otherwise from the nearest-neighbour tour from vertex 0; chain c from the one from vertex c % n.
     The default schedule has ``levels`` temperatures, geometric from t_hot to t_cold, both multiples of the instance's mean
     real edge weight, and sweeps * n^2 proposals per level.  inv_temp ([levels] or [len(instances), levels], 1 / T, inf
@@ -105,9 +105,7 @@ def anneal_tours(instances, chains=DEFAULT_CHAINS, levels=DEFAULT_LEVELS, sweeps
     chains = int(chains)
     checked, index = _validate(instances, 1, 0, 1, chunk, index, init_tours, MAX_N_TRI)
     B = len(checked)
-    n_big = max([c[2] for c in checked if c[2] > MAX_N], default=0)
-    if n_big and chains > tri_chains_fit(n_big):
-        raise ValueError("chains=%d: at n=%d at most %d chains fit in LDS" % (chains, n_big, tri_chains_fit(n_big)))
+    _check_chains_fit(chains, max([c[2] for c in checked if c[2] > MAX_N], default=0), None, "chains")
     if inv_temp is None:
         temps = geometric_schedule(int(levels), t_hot, t_cold)
         inv = None

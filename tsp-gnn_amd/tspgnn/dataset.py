@@ -480,21 +480,19 @@ def _label_settings(restarts, kicks, lb_iters, neighbors, exact, max_nodes, chun
     return small, large, bb
 
 
-def _check_chains_fit(restarts, n_big, neighbors):
-    """n_big: the largest n above MAX_N among the instances (0: none), where ``restarts`` chains must fit in LDS."""
+def _check_chains_fit(restarts, n_big, neighbors, word="restarts"):
+    """n_big: the largest n above MAX_N among the instances (0: none), where ``restarts`` chains must fit in LDS;
+    ``word``: what the caller calls its chains."""
     if n_big and restarts > tri_chains_fit(n_big, neighbors):
-        raise ValueError("restarts=%d: at n=%d at most %d chains fit in LDS"
-                         % (restarts, n_big, tri_chains_fit(n_big, neighbors)))
+        raise ValueError("%s=%d: at n=%d at most %d chains fit in LDS"
+                         % (word, restarts, n_big, tri_chains_fit(n_big, neighbors)))
 
 
 def tri_chains_fit(n, neighbors=None):
-    """The most restarts tspgnn_tour_search_tri takes at n_max = n: its LDS holds the n (n-1) / 2 fp32 triangle and
-    three tours of n int32 ids per chain in 163 712 bytes (160 KiB less its 128 static bytes): 10 at n = 256.
-    neighbors=K: tspgnn_tour_search_knn_tri's, which also holds n K bytes of neighbour table and n bytes of positions
-    per chain: 9 at n = 256 with K = 8."""
-    if neighbors is None:
-        return min(16, (163712 - 2 * n * (n - 1)) // (12 * n))
-    return min(16, (163712 - 2 * n * (n - 1) - n * neighbors) // (13 * n))
+    """The most restarts tspgnn_tour_search_tri takes at n_max = n (10 at n = 256), or with neighbors=K
+    tspgnn_tour_search_knn_tri (9 at n = 256 with K = 8): the library's own rule, tspgnn_tour_chains_fit (the LDS layout
+    behind it: include/tspgnn.h, tspgnn_tour_search_tri)."""
+    return int(_lib.lib.tspgnn_tour_chains_fit(1, int(n), 0 if neighbors is None else int(neighbors)))
 
 
 def _bb_stats(stats, status, nodes, seconds):
