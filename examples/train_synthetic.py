@@ -14,6 +14,8 @@ accuracy printed here says nothing about TSP -- the point is the call sequence a
 With -generate SAMPLES the instances are create_dataset's (seeded with -seed) and the tours are the GPU search's labels:
 DeviceDataset.generate(SAMPLES, 20, 40), no matrix on the host and no file; -write_dir PATH also writes them as .graph
 files (DeviceDataset.write_directory, formatted on the GPU) for the reference's train.py / test.py to read.
+With --instances DIR -device_dataset -reader device the .graph files are parsed and packed on the GPU from their raw bytes
+(DeviceDataset.from_directory(reader='device')) instead of one host parse per file.
 """
 import argparse
 import os
@@ -45,6 +47,9 @@ if __name__ == '__main__':
     p.add_argument('-device_dataset', action='store_true',
                    help='upload the instances once (tspgnn.DeviceDataset) and assemble every batch on the GPU from instance '
                         'ids: epochs through DeviceDataset.get_batches instead of InstanceLoader / create_batch')
+    p.add_argument('-reader', default='host', choices=('host', 'device'),
+                   help='with --instances DIR -device_dataset: who reads the .graph files (DeviceDataset.from_directory('
+                        'reader=)): the host parser per file, or the GPU reader over chunks of raw text')
     p.add_argument('-generate', default=0, type=int, metavar='SAMPLES',
                    help='train on DeviceDataset.generate(SAMPLES, 20, 40): the instances drawn from the reference\'s stream, '
                         'labelled and packed on the GPU, instead of a directory or synthetic instances')
@@ -56,6 +61,8 @@ if __name__ == '__main__':
     a = p.parse_args()
     if a.accumulate < 1:
         p.error('-accumulate K needs K >= 1')
+    if a.reader == 'device' and (a.instances is None or not a.device_dataset or a.generate):
+        p.error('-reader device needs --instances DIR -device_dataset (and no -generate)')
     if a.write_dir is not None and not a.generate:
         p.error('-write_dir needs -generate SAMPLES')
     rng = np.random.RandomState(a.seed)
@@ -81,7 +88,7 @@ if __name__ == '__main__':
             print('wrote {} bytes of .graph files to {} ({})'.format(
                 w['bytes'], a.write_dir, ', '.join('{} {:.3f}'.format(k, v) for k, v in w['times'].items())), flush=True)
     elif a.device_dataset:   # the same instances every epoch, shuffled per epoch like InstanceLoader.reset()
-        dataset = DeviceDataset.from_directory(a.instances) if a.instances is not None else DeviceDataset(
+        dataset = DeviceDataset.from_directory(a.instances, reader=a.reader) if a.instances is not None else DeviceDataset(
             [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize * a.batches)])
     GNN = build_network(a.d)
     with Session() as sess:

@@ -1138,6 +1138,65 @@ int tspgnn_graph_text_write(const long long* tab, const long long* d_tab, const 
                             const long long* bytes, const long long* host_bytes, char* text, long long n_text,
                             int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ ".graph" text read on the device (csrc/graph_parse.hip)
+ *
+ * Python's float(token) of count tokens: token i is the len[i] (int32) bytes at off[i] (int64) of buf, n_buf the extent of
+ * buf.  -> bits[i], the double as uint64, and status[i] (uint8): 0 parsed; 1 malformed, float(token) would raise too (also:
+ * a token that leaves buf); 2 well-formed for strtod or float() but outside the device grammar -- the host reader can
+ * still read a file with such a token.  bits[i] is 0 unless status[i] is 0.
+ *   Grammar: [+-]? ( digits [. digits?] | . digits ) ( [eE] [+-]? digits )?, or [+-]?inf, or nan, lower case only: the
+ * spellings tspgnn_f64_repr emits.  After its leading zeros the mantissa holds at most 19 digits, integer and fraction
+ * digits together; the exponent field may have any number of digits and saturates (1e9999 is inf, 1e-9999 is 0.0); a
+ * token is at most 48 bytes.  Status 2: more than 19 digits, 0x..., Infinity, NaN and every other case of inf / nan, a
+ * signed nan, '_' between digits, more than 48 bytes.
+ *   For status 0 the result is float(token) bit for bit: to nearest, ties to even, through subnormals, underflow to
+ * +-0.0 and overflow to +-inf, the sign of zero kept.  Integer arithmetic only, the same routine on host and device:
+ * mode 0 rounds from the 192-bit product with a 128-bit power of ten wherever that decides it and by exact multi-word
+ * comparison with the midpoint elsewhere; mode 1 sends every token through the exact comparison (for tests).
+ * tspgnn_host_f64_parse takes HOST pointers and launches nothing; tspgnn_f64_parse takes device arrays (one thread per
+ * token).  NULL, count < 0 or n_buf < 0: TSPGNN_EINVAL before any launch; count == 0: no-op.
+ */
+int tspgnn_host_f64_parse(const unsigned char* buf, long long n_buf, const long long* off, const int32_t* len,
+                          long long count, int mode, unsigned long long* bits, unsigned char* status);
+int tspgnn_f64_parse(const unsigned char* buf, long long n_buf, const long long* off, const int32_t* len, long long count,
+                     int mode, unsigned long long* bits, unsigned char* status, void* stream);
+
+/*
+ * count ".graph" files side by side in the device byte buffer text (n_text bytes), file i in [b0, b0 + bytes), read as
+ * tspgnn_host_read_graph reads them (instance_loader.py:95-127), one 256-thread workgroup per file.  tab is passed twice,
+ * on the HOST (every row is checked against the extents before anything launches) and on the device (d_tab); every load
+ * and store of a kernel is guarded by the file's extent and the row's.
+ *   The first DIMENSION; n the integer after it, past ':', blanks and tabs; EDGE_DATA_SECTION, EDGE_WEIGHT_SECTION and
+ * TOUR_SECTION each the first occurrence at or after the previous section's first line; pair lines "i j" until the first
+ * line that contains the two bytes "-1" (or does not begin with an integer); the weights the first n^2 tokens of the
+ * weight section separated by blank, tab, CR, LF, VT, FF, later tokens ignored; the tour the integers on the line after
+ * TOUR_SECTION, separated by blanks and tabs.  Unlike strtol this reader stays on a line: a pair line with one integer
+ * is status 5 and a blank pair line is skipped.
+ *
+ * tspgnn_graph_text_scan: tab[count][2] = b0, bytes -> info[i][8] (device, int32) = status, n, tour length, the offsets
+ * in the file of the first lines of the three sections (-1: absent), the number of pair lines, 0.  It reads everything
+ * but the weights.
+ *
+ * tspgnn_graph_text_parse: tab[count][5] = b0, bytes, n, c0, t0 with n what the scan gave -> the uint8 mask A[c0 .. c0 +
+ * n^2), all of it, zeros included, symmetric as tspgnn_build_instances makes it (a pair i < j sets [i][j] and [j][i]);
+ * Mw[c0 ..) in fp64 (tspgnn_f64_parse, mode 0); tours[t0 .. t0 + n) in int32; m[i], the number of set pairs
+ * (tspgnn_build_instances' m); status[i] (int32).  n_cells and n_tour are the extents.
+ *
+ * status: 0 read; 3 no DIMENSION, or n <= 0 (parse: n differs from the row's); 4 a section is missing; 5 a pair outside
+ * [0, n); 6 fewer than n^2 weight tokens, or a malformed one; 7 a tour entry outside [0, n); 8 n outside [4, 256],
+ * tspgnn_pack_dataset's range; 9 a pair with i >= j (tspgnn_pack_dataset lists the pairs of np.triu(A)); 10 tour length
+ * != n; 11 a weight token outside the device grammar.  3 to 7 mirror the host reader's codes; the lowest that applies is
+ * reported.  A non-zero status in either launch means the caller uses nothing of that file.
+ *
+ * TSPGNN_EINVAL before any launch: a NULL pointer, count < 0, n_max outside [4, 256] or an n outside [4, n_max] (parse), a
+ * file above 2^30 bytes, an offset that leaves its array.  count == 0: no-op.
+ */
+int tspgnn_graph_text_scan(const long long* tab, const long long* d_tab, const char* text, long long n_text, int count,
+                           int32_t* info, void* stream);
+int tspgnn_graph_text_parse(const long long* tab, const long long* d_tab, const char* text, long long n_text, int count,
+                            int n_max, long long n_cells, long long n_tour, unsigned char* A, double* Mw, int32_t* tours,
+                            int32_t* m, int32_t* status, void* stream);
+
 /* ------------------------------------------------------------------ host-side batch packing (no GPU work) */
 
 /*

@@ -4,7 +4,7 @@ at dev = 0.02 and the gap (cost - lb) / cost distribution; one JSON line per sha
 
     python tools/dataset_bench.py [--shapes train,test,n80,n200,n256] [--restarts R] [--kicks K] [--lb-iters I] [--out DIR]
         [--exact [--max-nodes N]] [--neighbors K] [--distances euc_2D|random] [--closure host|device] [--resident]
-        [--writer host|device|both]
+        [--writer host|device|both] [--reader host|device|both]
 
 Without --restarts / --kicks / --lb-iters each shape runs label_tours' defaults for its n.
 --exact labels with the branch and bound (label_tours(exact=True), n <= 128) and adds the proved fraction, the nodes per
@@ -21,6 +21,12 @@ GPU writer (graph_text.write_instances, the call create_dataset makes) and "both
 labelled instances; a device run adds one JSON line with its wall seconds ("total_s") and its stages (upload, the sizes
 and write launches, their sum "format_s", the download, the file writes).  With --resident every generated dataset is also written twice by DeviceDataset.write_directory and
 twice by to_instances() + write_graph, alternated, one JSON line each ("writer").
+--reader times DeviceDataset.from_directory over directories written first by write_directory -- 2^14 files with n 20-40
+and 256 files with n = 200 (--samples overrides both counts) -- and does nothing else: "host" is read_graph per file and
+the host packers, "device" the GPU reader (graph_text.read_files), "both" alternates the two twice over the same
+directory.  The page cache is warm for both: every file is read once, untimed, after it is written.  One JSON line per run
+with the wall seconds to the synchronised dataset ("total_s") and the MB/s of text; a device run adds its stages (file
+I/O, upload, the scan and parse launches with their downloads, the packing launch).
 """
 import argparse
 import json
@@ -141,6 +147,47 @@ def resident(a, name, samples, nmin, nmax):
             del ds
 
 
+READ_SHAPES = {"files_train": (2 ** 14, 20, 40), "files_n200": (2 ** 8, 200, 200)}
+
+
+def readers(a):
+    """--reader: the two readers of a .graph directory per shape of READ_SHAPES; one JSON line per run."""
+    order = {"host": ["host"], "device": ["device"], "both": ["host", "device"] * 2}[a.reader]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    warm = tempfile.mkdtemp(prefix="dsbench_warm_")   # the reader's code objects and the pinned allocator, untimed
+    DeviceDataset.generate(4, 20, 20, kicks=1, lb_iters=1, restarts=1).write_directory(warm)
+    for reader in order:
+        DeviceDataset.from_directory(warm, device=dev, reader=reader)
+    shutil.rmtree(warm)
+    for name, (samples, nmin, nmax) in READ_SHAPES.items():
+        samples = a.samples or samples
+        random.seed(1)
+        np.random.seed(1)
+        out = _scratch_dir(a) if a.out is None else os.path.join(a.out, name)
+        made = DeviceDataset.generate(samples, nmin, nmax, kicks=1, lb_iters=1, restarts=1)
+        written = made.write_directory(out)["bytes"]
+        del made
+        for f in os.listdir(out):   # warm page cache for both readers
+            with open(os.path.join(out, f), "rb") as fh:
+                fh.read()
+        for rep, reader in enumerate(order):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ds = DeviceDataset.from_directory(out, device=dev, reader=reader)
+            torch.cuda.synchronize()
+            total = time.perf_counter() - t0
+            stages = {}
+            if reader == "device":
+                stages = {k + "_s": round(v, 3) for k, v in ds.read_times.items() if k != "bytes"}
+            print(json.dumps({"shape": name, "files": samples, "n": [nmin, nmax], "reader": reader, "rep": rep // 2,
+                              "text_bytes": written, "total_s": round(total, 3),
+                              "MB_per_s": round(written / total / 1e6, 1), **stages, "edges": int(ds.m.sum())}),
+                  flush=True)
+            del ds
+        if a.out is None:
+            shutil.rmtree(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="train,test,n80")
@@ -158,10 +205,14 @@ def main():
                     help="time the host route and DeviceDataset.generate to a device-resident dataset, alternated twice")
     ap.add_argument("--writer", default="host", choices=("host", "device", "both"),
                     help="who formats the .graph files (create_dataset's writer=); both: alternated twice")
+    ap.add_argument("--reader", default=None, choices=("host", "device", "both"),
+                    help="time DeviceDataset.from_directory(reader=) over written directories, and nothing else")
     ap.add_argument("--no-write", action="store_true", help="solve only (no .graph files)")
     ap.add_argument("--out", default=None, help="directory for the .graph files (default: a temporary one)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "dataset_bench needs an MI355X"
+    if a.reader is not None:
+        return readers(a)
     # warm-up: load the code objects outside the timed runs
     for n in (20, 130):
         dataset.label_tours([(np.triu(np.ones((n, n)), 1), np.random.RandomState(0).rand(n, n))], kicks=1, lb_iters=1,

@@ -133,6 +133,10 @@ SIGNATURES = {
                                 c_void_p, c_void_p],
     "tspgnn_graph_text_write": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_longlong, c_longlong,
                                 c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p],
+    "tspgnn_f64_parse": [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p],
+    "tspgnn_graph_text_scan": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p],
+    "tspgnn_graph_text_parse": [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_int, c_longlong, c_longlong, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     # launch-plan queries (host only; the last argument is the plan structure to fill, see plan())
     "tspgnn_plan_linear": [c_int, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_mlp_bwd": [c_void_p, c_int, c_int, c_int, c_void_p],
@@ -150,7 +154,7 @@ SIGNATURES = {
 
 HOST_FUNCTIONS = ("tspgnn_host_pack_instance", "tspgnn_host_route_cost", "tspgnn_host_csr_by_vertex",
                   "tspgnn_host_read_graph", "tspgnn_host_count_edges", "tspgnn_host_pack_batch", "tspgnn_host_stage_batch",
-                  "tspgnn_host_f64_repr")
+                  "tspgnn_host_f64_repr", "tspgnn_host_f64_parse")
 
 # size queries: name -> argtypes; these return long long (floats of workspace; tspgnn_tour_branch_bound_ws and
 # tspgnn_tour_beam_workspace_bytes: bytes; tspgnn_tour_chains_fit: chains)
@@ -354,6 +358,8 @@ def _load():
     lib.tspgnn_host_read_graph.argtypes = [c_char_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.tspgnn_host_f64_repr.restype = c_int
     lib.tspgnn_host_f64_repr.argtypes = [c_void_p, c_longlong, c_void_p, c_void_p]
+    lib.tspgnn_host_f64_parse.restype = c_int
+    lib.tspgnn_host_f64_parse.argtypes = [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p]
     return lib
 
 

@@ -309,9 +309,78 @@ class DeviceDataset(object):
         return len(self.n)
 
     @classmethod
-    def from_directory(cls, path, device=None):
-        """Every file of a ``.graph`` directory (read_graph), in sorted order."""
-        return cls([read_graph(os.path.join(path, f)) for f in sorted(os.listdir(path))], device=device)
+    def from_directory(cls, path, device=None, reader="host", text_bytes=G.DEFAULT_TEXT_BYTES, keep_matrices=False):
+        """Every file of a ``.graph`` directory, in sorted order.  reader='host': read_graph per file and the host packers
+        (text_bytes and keep_matrices are not used).  reader='device': the raw bytes go up in chunks of at most
+        ``text_bytes`` of text and the files are taken apart (csrc/graph_parse.hip, graph_text.read_files) and packed
+        (tspgnn_pack_dataset) on the GPU: the same dataset arrays, without a host pass over cells, tokens or lines; the
+        result does not depend on text_bytes.  That route reads the files write_graph(np.triu(Ma), Mw, ...) makes -- 4 <= n
+        <= 256, pairs with i < j, a tour of n entries, weights in the spellings of repr -- and raises ValueError, naming the
+        first file and why, for a file it cannot read, before the dataset exists.  keep_matrices: the masks, fp64
+        matrices and tours stay on the device as generate keeps them, for to_instances() and write_directory().
+        ``read_times`` then holds the seconds of 'files', 'upload', 'scan', 'parse' and 'pack' and the 'bytes' of text."""
+        if reader not in ("host", "device"):
+            raise ValueError("DeviceDataset.from_directory: reader=%r must be 'host' or 'device'" % (reader,))
+        if reader == "host":
+            return cls([read_graph(os.path.join(path, f)) for f in sorted(os.listdir(path))], device=device)
+        dev = _default_device(device)
+        if dev.type != "cuda":
+            raise ValueError("DeviceDataset.from_directory: device=%r: the files are read by HIP kernels" % str(dev))
+        return cls._read(path, dev, text_bytes, keep_matrices)
+
+    @classmethod
+    def _read(cls, path, dev, text_bytes, keep):
+        """from_directory(reader='device'): one tspgnn_pack_dataset launch per chunk of read_files into chunk-sized arrays
+        (uv, eid and rowptr are instance-local, so the dataset's arrays are the chunks' concatenated), ``inst`` from the
+        host prefix sums."""
+        paths = [os.path.join(path, f) for f in sorted(os.listdir(path))]
+        times = {"files": 0.0, "upload": 0.0, "scan": 0.0, "parse": 0.0, "pack": 0.0, "bytes": 0}
+        parts, kept, ns, ms = [], [], [], []
+        with torch.cuda.device(dev):
+            st = _lib.current_stream()
+            for c in G.read_files(paths, dev, text_bytes, times):
+                t0 = _clock(dev)
+                C = c.hi - c.lo
+                ns.append(c.nc)
+                ms.append(c.m)
+                check_size(sum(int(m.sum()) for m in ms))
+                e0, M = _prefix(c.m)
+                v0, N = _prefix(c.nc)
+                tab = np.ascontiguousarray(np.stack([c.nc, c.c_off, c.t_off, c.m, e0, v0, np.arange(C)], axis=1)
+                                           .astype(np.int64))
+                d_tab = D._to_device(tab, dev)
+                d_uv = torch.empty((M, 2), dtype=torch.int32, device=dev)
+                d_w = torch.empty(M, dtype=torch.float32, device=dev)
+                d_eid = torch.empty(2 * M, dtype=torch.int32, device=dev)
+                d_rowptr = torch.empty(N + C, dtype=torch.int32, device=dev)
+                d_rc, d_fc, d_cyc = (torch.empty(C, dtype=torch.float64, device=dev) for _ in range(3))
+                d_feas = torch.empty(C, dtype=torch.int32, device=dev)
+                _lib.call("tspgnn_pack_dataset", tab.ctypes.data, _lib.ptr(d_tab), _lib.ptr(c.A), _lib.ptr(c.Mw),
+                          _lib.ptr(c.tours), C, int(c.nc.max()), c.n_cells, c.n_verts, M, N + C, C,
+                          _lib.ptr(d_uv) if M else None, _lib.ptr(d_w) if M else None, _lib.ptr(d_rowptr),
+                          _lib.ptr(d_eid) if M else None, _lib.ptr(d_rc), _lib.ptr(d_fc), _lib.ptr(d_cyc), _lib.ptr(d_feas),
+                          st)
+                parts.append((d_uv, d_w, d_rowptr, d_eid, d_rc))
+                if keep:
+                    kept.append(_Kept(np.arange(c.lo, c.hi, dtype=np.int64), c.nc, c.c_off, c.t_off, c.n_cells, c.n_verts,
+                                      c.A, c.Mw, c.tours))
+                D._add_time(times, "pack", _clock(dev) - t0)
+            n64 = np.concatenate(ns) if ns else np.zeros(0, dtype=np.int64)
+            m64 = np.concatenate(ms) if ms else np.zeros(0, dtype=np.int64)
+            I = len(n64)
+            e0, M = _prefix(m64)
+            v0, N = _prefix(n64)
+            inst = np.stack([n64, m64, e0, v0], axis=1).astype(np.int32).reshape(I, 4)
+            cat = lambda k, dtype, shape: (torch.cat([p[k] for p in parts]) if parts else
+                                           torch.empty(shape, dtype=dtype, device=dev))
+            ds = cls._adopt(dev, n64, m64, D._to_device(inst, dev), cat(0, torch.int32, (0, 2)), cat(1, torch.float32, 0),
+                            cat(2, torch.int32, 0), cat(3, torch.int32, 0), cat(4, torch.float64, 0))
+            if keep:
+                tours = (np.concatenate([k.tours.cpu().numpy() for k in kept]) if kept else np.zeros(0, dtype=np.int32))
+                ds.tours = (tours, np.concatenate([v0, [N]]).astype(np.int64))
+                ds._matrices = kept
+        ds.read_times = times
+        return ds
 
     # ------------------------------------------------------------------ made on the device
     @classmethod
@@ -395,7 +464,8 @@ class DeviceDataset(object):
         """A generated dataset as the list of (np.triu(Ma), Mw, route) DeviceDataset(...) and write_graph take, downloaded
         from the device: Ma from the edge list, Mw the fp64 matrices generate kept, route the label."""
         if self._matrices is None:
-            raise RuntimeError("DeviceDataset.to_instances: only a dataset made by generate() keeps its fp64 matrices")
+            raise RuntimeError("DeviceDataset.to_instances: only a dataset made by generate() keeps its fp64 matrices "
+                               "(or read with reader='device', keep_matrices=True)")
         I = len(self.n)
         uv = self._uv.cpu().numpy()
         e0 = np.concatenate([[0], np.cumsum(self.m)])
@@ -423,7 +493,8 @@ class DeviceDataset(object):
         result does not depend on text_bytes.  -> {'bytes': bytes written, 'times': {'format', 'download', 'files'
         seconds, and 'sizes' / 'write', the two launches 'format' is the sum of}}."""
         if self._matrices is None:
-            raise RuntimeError("DeviceDataset.to_instances: only a dataset made by generate() keeps its fp64 matrices")
+            raise RuntimeError("DeviceDataset.to_instances: only a dataset made by generate() keeps its fp64 matrices "
+                               "(or read with reader='device', keep_matrices=True)")
         self._require_gpu()
         os.makedirs(path, exist_ok=True)
         times = {"sizes": 0.0, "write": 0.0, "format": 0.0, "download": 0.0, "files": 0.0}
