@@ -26,7 +26,12 @@
 6. ``trained_d64.npz`` -- the oracle's own weights after 2 000 Adam steps at lr 1e-3 on synthetic batches: a network
    whose statistics are not those of the initialisers, for parity far from init ("trained").
 
-Usage:  python oracle/gen_golden.py [pack] [oracle] [anchors] [graph] [bf16] [grads] [trained]   (default: the first five)
+7. ``tour_optima.npz`` -- exact optima of the tour kernels' test instances (tests/tour_optima_cases.py) from an integer
+   program on scipy's HiGHS, with the node counts of the NumPy branch and bound on them (oracle/tour_optima.py;
+   "tour_optima": minutes; needs scipy and the built library).
+
+Usage:  python oracle/gen_golden.py [pack] [oracle] [anchors] [graph] [bf16] [grads] [trained] [tour_optima]
+(default: the first five)
 """
 import os
 import sys
@@ -312,6 +317,9 @@ if __name__ == "__main__":
         gen_grad_anchors()
     if "trained" in what:    # (not in the default list: 2 000 oracle training steps)
         gen_trained()
+    if "tour_optima" in what:   # (not in the default list: minutes of integer programs and of NumPy branch and bound)
+        from oracle import tour_optima
+        tour_optima.generate()
     for w in what:   # "bf16:<name>" / "anchors:<name>": one anchor only (the others take minutes and do not change)
         if w.startswith("bf16:"):
             gen_bf16_anchors(only=w[5:].split(","))
