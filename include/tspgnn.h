@@ -157,6 +157,9 @@ typedef struct tspgnn_lstm_task {
 } tspgnn_lstm_task;  /* fields as the arguments of tspgnn_lnlstm_fwd_f32 / tspgnn_lnlstm_gather_fwd_f32 */
 
 int tspgnn_mlp_fwd_multi_f32(const tspgnn_mlp_task* tasks, int n_tasks, int d, void* stream);
+/* The tasks whose K[dx + d, 4d] fits LDS (160 KiB with the LayerNorm parameters) share one launch; each of the others streams
+ * its K through LDS in a launch of its own, which starts z at zero: TSPGNN_EUNSUPPORTED -- before any task is launched -- where
+ * such a task is in gather-init or bias-init mode (tspgnn_plan_lstm_fwd_f32 answers the same). */
 int tspgnn_lnlstm_fwd_multi_f32(const tspgnn_lstm_task* tasks, int n_tasks, int d, void* stream);
 
 /*
@@ -1298,6 +1301,7 @@ typedef struct tspgnn_tasks_plan {    /* the ticket launches that only share out
 } tspgnn_tasks_plan;
 int tspgnn_plan_mlp_bwd(const tspgnn_mlp_bwd_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out); /* tspgnn_mlp_bwd_multi_f32 */
 int tspgnn_plan_mlp_fwd(const tspgnn_mlp_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out);     /* tspgnn_mlp_fwd_multi_h2 / _x3, tspgnn_mlp_head_fwd_h2 */
+int tspgnn_plan_mlp_fwd_f32(const tspgnn_mlp_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out); /* tspgnn_mlp_fwd_multi_f32 */
 /* tspgnn_mlp_fwd_multi_bf16; nw: the wavefronts per workgroup its dispatch chooses (16 at d = 128 without a projection, else 8) */
 int tspgnn_plan_mlp_fwd_bf16(const tspgnn_mlp_task_bf16* tasks, int n_tasks, int d, int nw, int cus, tspgnn_tasks_plan* out);
 
@@ -1351,6 +1355,12 @@ typedef struct tspgnn_cell_chunk_plan {  /* the cell launches whose only LDS dec
 int tspgnn_plan_cell_bwd(const tspgnn_lstm_bwd_task* tasks, int n_tasks, int d, int arith, int cus, tspgnn_cell_chunk_plan* out);
 /* tspgnn_lnlstm_fwd_multi_bf16; nw: the wavefronts per workgroup its dispatch chooses (12 for the staged kernel at d = 64, else 8) */
 int tspgnn_plan_lstm_fwd_bf16(const tspgnn_lstm_task_bf16* tasks, int n_tasks, int d, int nw, int cus, tspgnn_cell_chunk_plan* out);
+/* tspgnn_lnlstm_fwd_multi_f32: nw, grid, blk_end and lds_bytes describe the ONE launch of the resident tasks (chunked[k] == 0;
+ * grid 0: there is none), in which a chunked task owns no workgroup (blk_end[k] == blk_end[k-1]).  Every chunked task runs in
+ * a launch of its own: 8 wavefronts, K in chunks of qc[k] 16-row blocks, min(cus, ceil(tiles / 8)) workgroups, round r of 8
+ * tiles to workgroup r mod that.  qc[k] of a resident task: all (dx + d) / 16 blocks.  TSPGNN_EUNSUPPORTED: a gather-init or
+ * bias-init task whose K does not fit LDS -- the entry answers it before it launches any task. */
+int tspgnn_plan_lstm_fwd_f32(const tspgnn_lstm_task* tasks, int n_tasks, int d, int cus, tspgnn_cell_chunk_plan* out);
 
 /* Slices of the chunk range per workgroup in the second stage of the split reductions (wgrad, wcolsum). */
 int tspgnn_plan_reduce_slices(int n_chunks);

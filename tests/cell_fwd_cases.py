@@ -97,7 +97,8 @@ class FwdCell(object):
     def __init__(self, arith, d, rows, seed, dx=0, mode="plain", mlp_layers=0, relu_mask=None, mlp_out=True, proj=False,
                  acts=None, in_blocked=False, out_blocked=False, null_c=False, inplace=False, n_src=257, zbias_scale=1.0,
                  pad_fill=SENTINEL):
-        assert arith in ("h2", "x3") and mode in ("plain", "gather", "bias") and not (mode == "gather" and dx)
+        # ("f32": tests/dense_fwd_cases.py builds the fp32 entry's task from the same draw and reference)
+        assert arith in ("h2", "x3", "f32") and mode in ("plain", "gather", "bias") and not (mode == "gather" and dx)
         assert arith == "h2" or not (in_blocked or out_blocked or acts or null_c or inplace)
         assert not inplace or in_blocked == out_blocked
         rng = np.random.RandomState(seed)

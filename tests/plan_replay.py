@@ -1,9 +1,9 @@
 """The launch plans of the fp32 backward kernels (csrc/dense_bwd.hip), the training-tail kernels (csrc/train.hip), the
-forward cell and MLP launchers (csrc/dense_h2.hip, csrc/dense_x3.hip, csrc/bf16.hip) and the three cell backward launchers
+forward cell and MLP launchers (csrc/dense.hip, csrc/dense_h2.hip, csrc/dense_x3.hip, csrc/bf16.hip) and the three cell backward launchers
 (csrc/dense_bwd.hip, csrc/dense_bwd_h2.hip, csrc/dense_bwd_bf16.hip), asked of the library: every launcher-level figure
 here -- path, wavefronts, grid, blk_end, LDS chunking, mode, variant, chunk counts -- is what the tspgnn_plan_* queries
 answer, and those run the planner the launcher itself calls (csrc/launch_plan.h).  The GPU tests that claim a branch
-(tests/test_gpu_fp32_backward_plans.py, tests/test_gpu_batch_kernels.py, tests/test_gpu_cell_forward_edges.py, and through
+(tests/test_gpu_fp32_backward_plans.py, tests/test_gpu_batch_kernels.py, tests/test_gpu_cell_forward_edges.py, tests/test_gpu_fp32_forward_edges.py, and through
 tests/lstm_bwd_cases.py tests/test_gpu_h2_backward_kernels.py and tests/test_gpu_bf16_backward_kernels.py) derive
 their row counts from the device's CU count and assert the branch and its depth through these functions BEFORE they
 launch.  What remains in Python follows a KERNEL's own loop from the plan -- a workgroup's ticket range, its rounds, the
@@ -299,3 +299,47 @@ def mlp_fwd_bf16_plan(tasks, d, cus):
     structs = [_lib.MlpTaskB(rows=rows, n_layers=L, proj_w=int(proj)) for rows, L, proj in tasks]
     p = unsupported_as_value_error("tspgnn_plan_mlp_fwd_bf16", structs, len(tasks), d, nw, cus)
     return MlpFwdBf16Plan(p.nw, p.grid, blocks_of(p), p.lds_bytes)
+
+
+# ------------------------------------------------------------------- tspgnn_mlp_fwd_multi_f32, tspgnn_lnlstm_fwd_multi_f32
+def mlp_fwd_f32_plan(tasks, d, cus):
+    """tspgnn_plan_mlp_fwd_f32 -> MlpFwdPlan over the live tasks (rows > 0; the entry drops the others).  tasks: [(rows,
+    n_layers, has_proj)]; mlp_fwd_kernel walks [t_beg, t_end) by the plain workgroup index."""
+    structs = [_lib.MlpTask(rows=rows, n_layers=L, proj_w=int(proj), proj_out=int(proj)) for rows, L, proj in tasks]
+    p = _lib.plan("tspgnn_plan_mlp_fwd_f32", structs, len(tasks), d, cus)
+    blocks, live = blocks_of(p), [t for t in tasks if t[0] > 0]
+    assert len(blocks) == len(live)
+    return MlpFwdPlan(p.nw, p.grid, blocks, [ticket_ranges(tiles16(rows), b, xcd=False) for (rows, _, _), b in zip(live, blocks)])
+
+
+LstmFwdF32Plan = namedtuple("LstmFwdF32Plan", "nw grid blocks qc chunked lds_bytes ranges chunks chunk_grid rounds_per_wg")
+"""nw, grid, blocks, lds_bytes: the ONE launch of the resident tasks (lnlstm_fwd_kernel; grid 0: none; a chunked task has 0
+blocks there).  qc / chunked: per task.  ranges: per resident task every workgroup's [t_beg, t_end) (None: chunked).  Per
+chunked task (None: resident), its own launch of lnlstm_fwd_chunked_kernel at 8 wavefronts: chunks, the lengths in 16-row
+blocks of the stagings of K (q0 = 0; q0 < QT; q0 += qc); chunk_grid, its workgroups min(cus, rounds) with rounds =
+ceil(tiles / 8); rounds_per_wg, the (fewest, most) rounds of a workgroup (r = blockIdx.x; r < rounds; r += gridDim.x)."""
+
+
+def lstm_fwd_f32_plan(tasks, d, cus):
+    """tspgnn_plan_lstm_fwd_f32, over the live tasks (rows > 0; the entry drops the others).  tasks: (rows, dx, mode), mode
+    "plain", "gather" or "bias".  Raises ValueError where the launch answers TSPGNN_EUNSUPPORTED."""
+    structs = [_lib.LstmTask(rows=rows, dx=dx, uv=int(mode == "gather"), Zx=int(mode == "gather"), zbias=int(mode == "bias"),
+                             zscale=int(mode == "bias")) for rows, dx, mode in tasks]
+    p = unsupported_as_value_error("tspgnn_plan_lstm_fwd_f32", structs, len(tasks), d, cus)
+    c, live = _chunk_plan(p), [t for t in tasks if t[0] > 0]
+    assert len(c.blocks) == len(live)
+    ranges, chunks, grids, per_wg = [], [], [], []
+    for (rows, dx, _), blocks, qc, chunked in zip(live, c.blocks, c.qc, c.chunked):
+        tiles, QT = tiles16(rows), (dx + d) // 16
+        if not chunked:
+            ranges.append(ticket_ranges(tiles, blocks, xcd=False))
+            chunks.append(None), grids.append(None), per_wg.append(None)
+            continue
+        rounds = ceil_div(tiles, 8)                          # rounds = (tiles_total + 7) / 8
+        grid = min(cus, rounds)                              # launch_lnlstm: lstm_fwd_chunked_grid
+        walk = strided_walk(rounds, grid)
+        ranges.append(None)
+        chunks.append([min(QT, q0 + qc) - q0 for q0 in range(0, QT, qc)])
+        grids.append(grid)
+        per_wg.append((min(walk), max(walk)))
+    return LstmFwdF32Plan(c.nw, c.grid, c.blocks, c.qc, c.chunked, c.lds_bytes, ranges, chunks, grids, per_wg)

@@ -67,6 +67,27 @@ def test_the_table_reaches_every_branch():
         assert {r[1][0] for r in tab["lstm_fwd_bf16"] if r[0][1] == d} == set(plan_replay.LSTM_FWD_BF16_NW[d])
     assert {r[1][0] for r in tab["mlp_fwd_bf16"]} == {8, 16} and not any(isinstance(r[1], str) for r in tab["mlp_fwd_bf16"])
     assert {(r[0][0][0][1], r[0][0][0][2]) for r in tab["mlp_fwd_bf16"] if len(r[0][0]) == 1} == {(L, p) for L in (1, 2, 3, 4) for p in (False, True)}
+    # the fp32 forward launchers.  MLP, per record [nw, grid, blocks]: 16 wavefronts only where two workgroups fit a CU
+    mlp = [r for r in tab["mlp_fwd_f32"] if not isinstance(r[1], str)]
+    for d, nws in ((32, {4, 8, 16}), (64, {4, 8, 16}), (128, {4, 8})):
+        assert {r[1][0] for r in mlp if r[0][1] == d} == nws, d
+    assert {len(r[0][0]) for r in mlp} == {1, 2, 3, 4} and all(min(r[1][2]) >= 1 for r in mlp)
+    assert [r[0][1] for r in tab["mlp_fwd_f32"] if r[1] == "invalid"] == [128, 128]       # three layers, a projection
+    assert not any(r[1] == "unsupported" for r in tab["mlp_fwd_f32"])
+    # cell, per record [nw, grid, blocks, qc, chunked, lds_bytes, chunks, chunk_grid, rounds_per_wg]
+    recs = tab["lstm_fwd_f32"]
+    plans = [r[1] for r in recs if not isinstance(r[1], str)]
+    assert {p[0] for p in plans if p[1]} == {4, 8} and {c for p in plans for c in p[4]} == {False, True}
+    assert {len([t for t in r[0][0] if t[0]]) for r in recs} == {1, 2, 3, 4}
+    assert {r[1] for r in recs if isinstance(r[1], str)} == {"unsupported", "invalid"}
+    mixed = [p for p in plans if len(set(p[4])) == 2]
+    assert mixed and all(p[1] > 0 and all((b == 0) == c for b, c in zip(p[2], p[4])) for p in mixed)    # resident together, chunked apart
+    assert any(len(set(ch)) == 2 for p in plans for ch in p[6] if ch)                       # a last chunk shorter than qc
+    assert {lo != hi for p in plans for w in p[8] if w for lo, hi in [w]} == {False, True}  # workgroups that stride over rounds
+    for r in recs:          # a chunked gather-init / bias-init task: refused whatever else the launch holds
+        if r[0][1] != 128 or all(t[2] != "gather" for t in r[0][0]):
+            fits = lambda t: (t[1] + r[0][1]) * 16 * r[0][1] + 40 * r[0][1] + 16 <= 160 * 1024
+            assert (r[1] == "unsupported") == any(t[2] != "plain" and not fits(t) for t in r[0][0]), r[0]
 
 
 def test_queries_validate_as_their_entries_do():
@@ -104,6 +125,24 @@ def test_queries_validate_as_their_entries_do():
     assert status("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=5, n_layers=5)], 1, 64, 8, 256) == -1
     assert status("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=5, n_layers=2)], 1, 64, 8, -1) == -1
     assert status("tspgnn_plan_linear", 64, 0, 64, 100, -1) == -1
+    f32 = lambda **k: [_lib.MlpTask(rows=k.pop("rows", 5), n_layers=k.pop("n_layers", 2), **k)]
+    assert status("tspgnn_plan_mlp_fwd_f32", f32(), 1, 48, 256) == -1 and status("tspgnn_plan_mlp_fwd_f32", f32(n_layers=5), 1, 64, 256) == -1
+    assert status("tspgnn_plan_mlp_fwd_f32", f32(n_layers=3), 1, 128, 256) == -1 and status("tspgnn_plan_mlp_fwd_f32", f32(n_layers=3, rows=0), 1, 128, 256) == -1
+    assert status("tspgnn_plan_mlp_fwd_f32", f32(proj_w=1), 1, 64, 256) == -1 and status("tspgnn_plan_mlp_fwd_f32", f32(proj_w=1, proj_out=1), 1, 128, 256) == -1
+    assert status("tspgnn_plan_mlp_fwd_f32", f32(proj_w=1, proj_out=1), 1, 64, 256) == 0 and status("tspgnn_plan_mlp_fwd_f32", f32(), 1, 64, -1) == -1
+    assert status("tspgnn_plan_mlp_fwd_f32", f32() * 5, 5, 64, 256) == -1
+    lstm = lambda **k: [_lib.LstmTask(rows=k.pop("rows", 5), **k)]
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(dx=8), 1, 64, 256) == -1 and status("tspgnn_plan_lstm_fwd_f32", lstm(dx=16), 1, 64, 256) == 0
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(), 1, 48, 256) == -1 and status("tspgnn_plan_lstm_fwd_f32", lstm(rows=-1), 1, 64, 256) == -1
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(uv=1), 1, 64, 256) == -1 and status("tspgnn_plan_lstm_fwd_f32", lstm(uv=1, Zx=1), 1, 64, 256) == 0
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(uv=1, Zx=1), 1, 128, 256) == -1 and status("tspgnn_plan_lstm_fwd_f32", lstm(uv=1, Zx=1, dx=16), 1, 64, 256) == -1
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(zbias=1), 1, 64, 256) == -1 and status("tspgnn_plan_lstm_fwd_f32", lstm(zbias=1, zscale=1), 1, 64, 256) == 0
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(zbias=1, zscale=1, dx=80), 1, 64, 256) == 0
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(zbias=1, zscale=1, dx=96), 1, 64, 256) == -2      # a chunked K starts z at zero
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(dx=192) + lstm(zbias=1, zscale=1), 2, 128, 256) == -2
+    assert status("tspgnn_plan_lstm_fwd_f32", lstm(dx=192) + lstm(zbias=1, zscale=1), 2, 64, 256) == 0    # only the task that does not fit
+    assert _lib.plan("tspgnn_plan_mlp_fwd_f32", f32(rows=0), 1, 64, 256).grid == 0
+    assert _lib.plan("tspgnn_plan_lstm_fwd_f32", lstm(rows=0, dx=192, zbias=1, zscale=1), 1, 64, 256).nw == 0
     assert _lib.plan("tspgnn_plan_linear", 64, 0, 64, 0, 256).grid == 0
     assert _lib.plan("tspgnn_plan_wgrad", 0, 64, 64, 0, 256).n_chunks == 0
     assert _lib.plan("tspgnn_plan_cell_fwd", cell(rows=0), 1, 64, 0, 256).grid == 0
@@ -126,6 +165,9 @@ def queries_at(cus):
     calls += [("tspgnn_plan_cell_bwd", bwd, 2, 64, arith, cus) for arith in (0, 2, 3)]
     calls += [("tspgnn_plan_lstm_fwd_bf16", [_lib.LstmTaskB(rows=99840), _lib.LstmTaskB(rows=5120, dx=64)], 2, 64, 12, cus),
               ("tspgnn_plan_mlp_fwd_bf16", [_lib.MlpTaskB(rows=9000, n_layers=3), _lib.MlpTaskB(rows=700, n_layers=4, proj_w=1)], 2, 64, 8, cus)]
+    calls += [("tspgnn_plan_mlp_fwd_f32", [_lib.MlpTask(rows=9000, n_layers=3), _lib.MlpTask(rows=700, n_layers=4, proj_w=1, proj_out=1)], 2, 64, cus),
+              ("tspgnn_plan_lstm_fwd_f32", [_lib.LstmTask(rows=99840, uv=1, Zx=1), _lib.LstmTask(rows=5120, dx=64, zbias=1, zscale=1),
+                                            _lib.LstmTask(rows=65537, dx=192)], 3, 64, cus)]
     return [bytes(_lib.plan(*c)) for c in calls]
 
 

@@ -128,6 +128,16 @@ case("zbias-no-zscale", "tspgnn_lnlstm_fwd_multi_f32", [lstm(zbias=F)], 64, -1,
      "lnlstm_fwd: zbias needs zscale and excludes gather-init mode")
 case("zbias-gather", "tspgnn_lnlstm_fwd_multi_f32", [lstm(zbias=F, zscale=F, uv=F, Zx=F)], 64, -1,
      "lnlstm_fwd: zbias needs zscale and excludes gather-init mode")
+# A bias-init task whose K does not fit LDS (the chunked kernel starts z at zero): TSPGNN_EUNSUPPORTED from the launch's plan,
+# before its first HIP call -- also behind a task that could have run (plain, chunked) and behind one that fits.  (A
+# gather-init task has dx == 0 and d <= 64: its K always fits.)
+for cid, tasks, d in (("bias-chunked", [lstm(x=F, dx=96, zbias=F, zscale=F)], 64),
+                      ("bias-chunked-d=32", [lstm(x=F, dx=288, zbias=F, zscale=F)], 32),
+                      ("bias-chunked-d=128", [lstm(zbias=F, zscale=F)], 128),
+                      ("chunked-then-bias-chunked", [lstm(x=F, dx=192), lstm(x=F, dx=192, zbias=F, zscale=F)], 64),
+                      ("resident-then-bias-chunked", [lstm(uv=F, Zx=F), lstm(x=F, dx=64), lstm(x=F, dx=96, zbias=F, zscale=F)], 64)):
+    case(cid, "tspgnn_lnlstm_fwd_multi_f32", tasks, d, -2,
+         "lnlstm_fwd: gather-init / zbias need K[%d,%d] resident in LDS" % (d, 4 * d))
 # (the alias check runs on empty tasks too: NULL == NULL)
 case("empty-null-task", "tspgnn_lnlstm_fwd_multi_f32", [_lib.LstmTask()], 64, -1, "lnlstm_fwd: outputs may not alias inputs")
 case("empty-null-task", "tspgnn_lnlstm_fwd_multi_bf16", [_lib.LstmTaskB()], 64, 0, None)

@@ -170,6 +170,55 @@ def mlp_fwd_bf16_cases():
             yield ([(5000, 2, False), (5000, 1, True), (100, 4, True), (16 * 16 * cus + 1, 3, False)], d, cus)
 
 
+def mlp_fwd_f32_cases():
+    """(tasks, d, cus); tasks: plan_replay.mlp_fwd_f32_plan's (rows, n_layers, has_proj).  Two workgroups per CU at d = 32 and
+    64 (4, 8, then ONE of 16 wavefronts), one at d = 128 (4, 8); the shapes the entry's validation turns away come last."""
+    for d, per_cu, L in ((32, 2, 4), (64, 2, 3), (128, 1, 2)):
+        for cus in CUS:
+            full = cus * per_cu
+            for tiles in around(4 * full, 16 * full):
+                yield ([(16 * tiles - 15, L, False)], d, cus)
+            proj = d != 128
+            yield ([(1, 1, False), (40000, L, False)], d, cus)
+            yield ([(9000, L, False), (700, 2, proj)], d, cus)
+            yield ([(40000, 2, False), (17, L, proj), (333, 1, False)], d, cus)
+            yield ([(5000, 2, False), (5000, 1, proj), (100, L, proj), (16 * 16 * full + 1, 2, False)], d, cus)
+    yield ([(333, 3, False)], 128, 256)
+    yield ([(333, 2, True)], 128, 256)
+
+
+def lstm_fwd_f32_cases():
+    """(tasks, d, cus); tasks: plan_replay.lstm_fwd_f32_plan's (rows, dx, mode)."""
+    # the last resident and the first chunked input width at each d (d = 128 streams K even at dx = 0), a chunk shorter than
+    # qc, gather-init and bias-init where they fit
+    for d, dx in ((32, 0), (32, 272), (32, 288), (64, 0), (64, 80), (64, 96), (64, 192), (128, 0), (128, 32), (128, 128)):
+        yield ([(333, dx, "plain")], d, 256)
+    for d in (32, 64):
+        yield ([(333, 0, "gather")], d, 256)
+        yield ([(333, d, "bias")], d, 256)
+    for cus in CUS:
+        # four wavefronts up to 4 tiles per CU of the resident launch; a chunked task's rounds at, below and above the CUs
+        for tiles in around(4 * cus):
+            yield ([(16 * tiles - 15, 64, "plain")], 64, cus)
+            yield ([(16 * tiles - 31, 0, "gather"), (16, 64, "bias")], 64, cus)
+        for rounds in around(cus):
+            yield ([(16 * 8 * rounds - 15, 128, "plain")], 128, cus)
+        for N, M in STEPS:
+            yield ([(M, 0, "gather"), (N, 64, "bias")], 64, cus)
+            yield ([(M, 0, "plain"), (N, 128, "plain")], 128, cus)
+        # mixed launches: the resident tasks together, the chunked ones on their own
+        yield ([(7001, 0, "gather"), (333, 192, "plain")], 64, cus)
+        yield ([(333, 96, "plain"), (7001, 64, "bias")], 64, cus)
+        yield ([(5120, 64, "plain"), (0, 64, "plain"), (40000, 0, "gather")], 64, cus)
+        yield ([(2000, 64, "bias"), (300, 192, "plain"), (40000, 0, "gather")], 64, cus)
+        yield ([(2000, 64, "plain"), (40000, 0, "gather"), (5120, 96, "plain"), (300, 32, "bias")], 64, cus)
+    # refused: a bias-init task whose K does not fit (alone, and behind a task that could run), gather-init at d = 128
+    yield ([(333, 192, "bias")], 64, 256)
+    yield ([(333, 192, "plain"), (333, 96, "bias")], 64, 256)
+    yield ([(333, 128, "bias")], 128, 256)
+    yield ([(333, 0, "gather")], 128, 256)
+
+
 def answer(plan, *args):
     """A plan as a list, or how the query declined: "unsupported" (the launch is refused) or "invalid" (the entry's
     validation)."""
@@ -181,6 +230,16 @@ def answer(plan, *args):
         if getattr(e, "status", None) != -1:
             raise
         return "invalid"
+
+
+def mlp_fwd_f32_record(PR, *a):
+    p = PR.mlp_fwd_f32_plan(*a)
+    return [p.nw, p.grid, p.blocks]
+
+
+def lstm_fwd_f32_record(PR, *a):
+    p = PR.lstm_fwd_f32_plan(*a)
+    return [p.nw, p.grid, p.blocks, p.qc, p.chunked, p.lds_bytes, p.chunks, p.chunk_grid, p.rounds_per_wg]
 
 
 def table(PR):
@@ -212,6 +271,8 @@ def table(PR):
         "mlp_fwd_bf16": [[list(a), answer(PR.mlp_fwd_bf16_plan, *a)] for a in mlp_fwd_bf16_cases()],
         "reduce_slices": [[n, PR.reduce_slices(n)] for n in (1, 7, 8, 63, 64, 2048)],
         "strided_blocks": [[[t, cap], list(PR.strided_blocks(t, cap))] for cap in (1024, 4096) for t in around(256 * cap) + [1]],
+        "mlp_fwd_f32": [[list(a), answer(mlp_fwd_f32_record, PR, *a)] for a in mlp_fwd_f32_cases()],
+        "lstm_fwd_f32": [[list(a), answer(lstm_fwd_f32_record, PR, *a)] for a in lstm_fwd_f32_cases()],
     }
 
 

@@ -318,109 +318,81 @@ __global__ __launch_bounds__(512) void lnlstm_fwd_chunked_kernel(const float* __
 
 template <int D, int MAXL>
 static int launch_mlp(const tspgnn_mlp_task* tasks, int n, hipStream_t st) {
+    static_assert(MAXL == (D >= 128 ? 2 : 4), "plan_mlp_fwd_f32 sizes the LDS of a workgroup by this");
+    tspgnn_tasks_plan pl;
+    plan_mlp_fwd_f32(tasks, n, D, n_cus(), &pl);
     MlpTaskTable tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
     for (int k = 0; k < n; ++k) {
         tt.task[k] = tasks[k];
-        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
-        tiles_all += tiles16(tasks[k].rows);
+        tt.blk_end[k] = pl.blk_end[k];
     }
     tt.n = n;
-    // LDS per block decides residency: D=64 -> 65 KiB -> 2 blocks (16 waves) per CU.
-    const int lds_bytes = MAXL * (D * D + D) * 4 + 16;
-    const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
-    int grid = n_cus() * per_cu;
-    int nw = tiles_all <= (long long)grid * 4 ? 4 : 8;  // few tiles: one wavefront per SIMD, more workgroups
-    if (per_cu == 2 && tiles_all > (long long)grid * 16) {
-        // many tiles: ONE workgroup of 16 wavefronts per CU instead of two of 8 -- the whole CU shares one
-        // ticket counter, so its four SIMDs finish within one tile of each other
-        grid = n_cus();
-        nw = 16;
-    }
-    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
-    mlp_fwd_kernel<D, MAXL><<<grid, nw * 64, 0, st>>>(tt);
+    mlp_fwd_kernel<D, MAXL><<<pl.grid, pl.nw * 64, 0, st>>>(tt);
     return launched("tspgnn_mlp_fwd_f32");
 }
 
 template <int D>
-static int launch_lnlstm_chunked(const tspgnn_lstm_task& t, hipStream_t st) {
+static int launch_lnlstm_chunked(const tspgnn_lstm_task& t, int qc, int grid, hipStream_t st) {
     const int tiles = (t.rows + 15) / 16;
-    const size_t extra = (10 * D + 4) * sizeof(float);
-    // chunk = as many 16-row blocks of K as fit 128 KiB
-    const int qc = (int)((128 * 1024) / (16 * 4 * D * sizeof(float)));
-    const size_t chunked = (size_t)qc * 16 * 4 * D * sizeof(float) + extra;
-    const int rc = set_dynamic_lds(&lnlstm_fwd_chunked_kernel<D>, chunked, "lnlstm_fwd");
+    const size_t lds_bytes = (size_t)qc * 16 * 4 * D * sizeof(float) + (10 * D + 4) * sizeof(float);
+    const int rc = set_dynamic_lds(&lnlstm_fwd_chunked_kernel<D>, lds_bytes, "lnlstm_fwd");
     if (rc) return rc;
-    int grid = n_cus();
-    const int rounds = (tiles + 7) / 8;
-    if (grid > rounds) grid = rounds;
-    lnlstm_fwd_chunked_kernel<D><<<grid, 512, chunked, st>>>(t.x, t.dx, t.h, t.c, t.K, t.ln, t.h_out, t.c_out, t.rows,
-                                                             tiles, qc);
+    lnlstm_fwd_chunked_kernel<D><<<grid, 512, lds_bytes, st>>>(t.x, t.dx, t.h, t.c, t.K, t.ln, t.h_out, t.c_out, t.rows,
+                                                               tiles, qc);
     return launched("tspgnn_lnlstm_fwd_f32");
 }
 
+// The resident tasks in one launch, then every chunked task in a launch of its own (plan_lstm_fwd_f32, which also refuses
+// the launch -- before anything runs -- where a gather-init or bias-init task does not fit LDS).
 template <int D>
 static int launch_lnlstm(const tspgnn_lstm_task* tasks, int n, hipStream_t st) {
-    const size_t extra = (10 * D + 4) * sizeof(float);
-    const size_t kLdsMax = 160 * 1024;
-    size_t resident = 0;
-    bool all_fit = true;
-    for (int k = 0; k < n; ++k) {
-        const size_t r = (size_t)(tasks[k].dx + D) * 4 * D * sizeof(float) + extra;
-        if (r > kLdsMax) all_fit = false;
-        if (r > resident) resident = r;
-    }
-    if (!all_fit) {  // a K that does not fit LDS: one chunked launch per task
-        for (int k = 0; k < n; ++k) {
-            if (tasks[k].uv || tasks[k].zbias)
-                return fail(TSPGNN_EUNSUPPORTED, "lnlstm_fwd: gather-init / zbias need K[%d,%d] resident in LDS", D, 4 * D);
-            const int rc = launch_lnlstm_chunked<D>(tasks[k], st);
-            if (rc) return rc;
-        }
-        return TSPGNN_OK;
-    }
-    LstmTaskTable tt;
-    long long cost[kMaxTasks];
-    long long tiles_all = 0;
-    for (int k = 0; k < n; ++k) {
-        tt.task[k] = tasks[k];
-        const long long tiles = tiles16(tasks[k].rows);
-        cost[k] = tiles * ((tasks[k].dx + D) / 16 + 3);  // k-blocks + ~3 blocks' worth of epilogue
-        tiles_all += tiles;
-    }
-    tt.n = n;
-    // Few tiles (a lone vertex-side task): one wavefront per SIMD and more, smaller workgroups, so every
-    // tile gets a matrix pipe to itself; many tiles: one workgroup per CU, two wavefronts per SIMD.
-    int grid = n_cus();
-    const int nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
-    grid = split_blocks(cost, n, clamp_grid(grid, tiles_all, nw), tt.blk_end);
-    const int rc = set_dynamic_lds(&lnlstm_fwd_kernel<D, 8>, resident, "lnlstm_fwd");
+    const int cus = n_cus();
+    tspgnn_cell_chunk_plan pl;
+    int rc = plan_lstm_fwd_f32(tasks, n, D, cus, &pl);
     if (rc) return rc;
-    lnlstm_fwd_kernel<D, 8><<<grid, nw * 64, resident, st>>>(tt);
-    return launched("tspgnn_lnlstm_fwd_f32");
+    if (pl.grid > 0) {
+        LstmTaskTable tt;
+        tt.n = 0;
+        for (int k = 0; k < n; ++k) {
+            if (pl.chunked[k]) continue;
+            tt.task[tt.n] = tasks[k];
+            tt.blk_end[tt.n++] = pl.blk_end[k];
+        }
+        if ((rc = set_dynamic_lds(&lnlstm_fwd_kernel<D, 8>, pl.lds_bytes, "lnlstm_fwd"))) return rc;
+        lnlstm_fwd_kernel<D, 8><<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(tt);
+        if ((rc = launched("tspgnn_lnlstm_fwd_f32"))) return rc;
+    }
+    for (int k = 0; k < n; ++k) {
+        if (!pl.chunked[k]) continue;
+        if ((rc = launch_lnlstm_chunked<D>(tasks[k], pl.qc[k], lstm_fwd_chunked_grid(tasks[k].rows, cus), st))) return rc;
+    }
+    return TSPGNN_OK;
 }
 
 // (the projection's requirement holds for an empty task too, unlike check_mlp_task's)
-static int check_mlp_task_f32(tspgnn_mlp_task& t, int d) {
-    const int rc = check_mlp_shape(t, "mlp_fwd");
+// operands = false (the plan queries, which read no pointer as more than null or non-null) skips the requirements on the
+// operands' addresses alone: the null pointers and, for the cell, the aliasing.
+static int check_mlp_task_f32(tspgnn_mlp_task& t, int d, const char* p = "mlp_fwd", bool operands = true) {
+    const int rc = check_mlp_shape(t, p);
     if (rc) return rc;
-    TSPGNN_REQUIRE(d != 128 || t.n_layers <= 2, "mlp_fwd: d=128 holds at most 2 layers in LDS (got %d)", t.n_layers);
-    TSPGNN_REQUIRE(t.rows == 0 || (t.X && t.wb && t.Y), "mlp_fwd: null pointer");
-    TSPGNN_REQUIRE(!t.proj_w || (t.proj_out && (d == 32 || d == 64)), "mlp_fwd: projection needs proj_out and d in {32,64}");
+    TSPGNN_REQUIRE(d != 128 || t.n_layers <= 2, "%s: d=128 holds at most 2 layers in LDS (got %d)", p, t.n_layers);
+    TSPGNN_REQUIRE(!operands || t.rows == 0 || (t.X && t.wb && t.Y), "%s: null pointer", p);
+    TSPGNN_REQUIRE(!t.proj_w || (t.proj_out && (d == 32 || d == 64)), "%s: projection needs proj_out and d in {32,64}", p);
     default_stride(t.acts, &t.acts_stride, t.rows, d);
     return TSPGNN_OK;
 }
 
-static int check_lstm_task(const tspgnn_lstm_task& t, int d) {
-    TSPGNN_REQUIRE(t.rows >= 0, "lnlstm_fwd: rows=%d", t.rows);
-    TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 16 == 0, "lnlstm_fwd: dx=%d must be a non-negative multiple of 16", t.dx);
-    TSPGNN_REQUIRE(t.rows == 0 || (t.h && t.c && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x)),
-                   "lnlstm_fwd: null pointer");
-    TSPGNN_REQUIRE(t.h_out != t.h && t.c_out != t.c, "lnlstm_fwd: outputs may not alias inputs");
+static int check_lstm_task(const tspgnn_lstm_task& t, int d, const char* p = "lnlstm_fwd", bool operands = true) {
+    TSPGNN_REQUIRE(t.rows >= 0, "%s: rows=%d", p, t.rows);
+    TSPGNN_REQUIRE(t.dx >= 0 && t.dx % 16 == 0, "%s: dx=%d must be a non-negative multiple of 16", p, t.dx);
+    if (operands) {
+        TSPGNN_REQUIRE(t.rows == 0 || (t.h && t.c && t.K && t.ln && t.h_out && t.c_out && (t.dx == 0 || t.x)),
+                       "%s: null pointer", p);
+        TSPGNN_REQUIRE(t.h_out != t.h && t.c_out != t.c, "%s: outputs may not alias inputs", p);
+    }
     TSPGNN_REQUIRE(!t.uv || (t.dx == 0 && t.Zx && (d == 32 || d == 64)),
-                   "lnlstm_fwd: gather-init mode needs dx == 0, Zx and d in {32,64}");
-    TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "lnlstm_fwd: zbias needs zscale and excludes gather-init mode");
+                   "%s: gather-init mode needs dx == 0, Zx and d in {32,64}", p);
+    TSPGNN_REQUIRE(!t.zbias || (t.zscale && !t.uv), "%s: zbias needs zscale and excludes gather-init mode", p);
     return TSPGNN_OK;
 }
 
@@ -492,4 +464,32 @@ extern "C" int tspgnn_lnlstm_gather_fwd_f32(const int32_t* uv, const float* Zx, 
     TSPGNN_REQUIRE(rows == 0 || (uv && Zx), "lnlstm_gather_fwd: null pointer");
     const tspgnn_lstm_task t = {nullptr, 0, h, c, Kh, ln, h_out, c_out, rows, uv, Zx, nullptr, nullptr, nullptr};
     return tspgnn_lnlstm_fwd_multi_f32(&t, 1, d, stream);
+}
+
+extern "C" int tspgnn_plan_mlp_fwd_f32(const tspgnn_mlp_task* tasks, int n_tasks, int d, int cus, tspgnn_tasks_plan* out) {
+    const char* what = "plan_mlp_fwd_f32";
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "%s: d=%d must be 32, 64 or 128", what, d);
+    TSPGNN_REQUIRE(cus >= 0, "%s: cus=%d", what, cus);
+    *out = tspgnn_tasks_plan{};
+    tspgnn_mlp_task live[kMaxTasks];
+    int n;
+    const int rc = filter_live(tasks, n_tasks, live, &n, [=](tspgnn_mlp_task& t) { return check_mlp_task_f32(t, d, what, false); });
+    if (rc || n == 0) return rc;
+    plan_mlp_fwd_f32(live, n, d, cus ? cus : n_cus(), out);
+    return TSPGNN_OK;
+}
+
+extern "C" int tspgnn_plan_lstm_fwd_f32(const tspgnn_lstm_task* tasks, int n_tasks, int d, int cus, tspgnn_cell_chunk_plan* out) {
+    const char* what = "plan_lstm_fwd_f32";
+    TSPGNN_REQUIRE(tasks && out && n_tasks >= 1 && n_tasks <= kMaxTasks, "%s: 1..%d tasks", what, kMaxTasks);
+    TSPGNN_REQUIRE(d == 32 || d == 64 || d == 128, "%s: d=%d must be 32, 64 or 128", what, d);
+    TSPGNN_REQUIRE(cus >= 0, "%s: cus=%d", what, cus);
+    *out = tspgnn_cell_chunk_plan{};
+    tspgnn_lstm_task live[kMaxTasks];
+    int n;
+    int rc = filter_live(tasks, n_tasks, live, &n, [=](const tspgnn_lstm_task& t) { return check_lstm_task(t, d, what, false); });
+    if (rc || n == 0) return rc;
+    if ((rc = plan_lstm_fwd_f32(live, n, d, cus ? cus : n_cus(), out))) *out = tspgnn_cell_chunk_plan{};
+    return rc;
 }

@@ -293,6 +293,28 @@ inline void plan_mlp_fwd(const tspgnn_mlp_task* tasks, int n, int cus, tspgnn_ta
     plan_tasks(cost, tiles_all, n, cus, nw, p);
 }
 
+// tspgnn_mlp_fwd_multi_f32 (d = 128 holds two layers in LDS, else four).  The LDS of a workgroup decides how many fit a CU:
+// d = 64 -> 65 KiB -> two of 8 wavefronts.  Few tiles: one wavefront per SIMD and more workgroups.  Many tiles, two per CU:
+// ONE workgroup of 16 wavefronts per CU instead -- the whole CU shares one ticket counter, so its four SIMDs finish within
+// one tile of each other.
+inline void plan_mlp_fwd_f32(const tspgnn_mlp_task* tasks, int n, int d, int cus, tspgnn_tasks_plan* p) {
+    long long cost[kMaxTasks];
+    long long tiles_all = 0;
+    for (int k = 0; k < n; ++k) {
+        cost[k] = tiles16(tasks[k].rows) * (tasks[k].n_layers + (tasks[k].proj_w ? 5 : 0));
+        tiles_all += tiles16(tasks[k].rows);
+    }
+    const int lds_bytes = (d >= 128 ? 2 : 4) * (d * d + d) * 4 + 16;
+    const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
+    int grid = cus * per_cu;
+    int nw = tiles_all <= (long long)grid * 4 ? 4 : 8;
+    if (per_cu == 2 && tiles_all > (long long)grid * 16) {
+        grid = cus;
+        nw = 16;
+    }
+    plan_tasks(cost, tiles_all, n, grid, nw, p);
+}
+
 inline int pick_vec(int width) { return width % 64 == 0 ? 4 : (width % 32 == 0 ? 2 : 1); }
 
 // tspgnn_wgrad_f32 / tspgnn_wgrad_bf16x_f32 (and the workspace size): the split of the row range, the kernel, its grid
@@ -607,6 +629,59 @@ int launch_cell_bwd(void (*kernel)(Table), const tspgnn_lstm_bwd_task* tasks, in
     kernel<<<pl.grid, pl.nw * 64, pl.lds_bytes, st>>>(tt);
     if ((rc = launched(what))) return rc;
     return reduce_ln_partials(tasks, n, pl.blk_end, d, st, what_reduce);
+}
+
+// Workgroups of lnlstm_fwd_chunked_kernel for one task: its 8 wavefronts take one tile each per round, round r goes to
+// workgroup r mod grid.
+inline int lstm_fwd_chunked_grid(int rows, int cus) {
+    const long long rounds = (tiles16(rows) + 7) / 8;
+    return cus > rounds ? (int)rounds : cus;
+}
+
+// tspgnn_lnlstm_fwd_multi_f32.  A task whose K ([dx + d, 4d] floats) fits 160 KiB of LDS beside the LayerNorm parameters is
+// RESIDENT: all of them share one launch of lnlstm_fwd_kernel, which nw, grid, blk_end[] and lds_bytes describe (blk_end[k]
+// runs over the resident tasks in order; a chunked task owns no workgroup there, blk_end[k] == blk_end[k - 1]; grid 0: no
+// resident task).  A task whose K does not fit is CHUNKED: a launch of its own of lnlstm_fwd_chunked_kernel, 8 wavefronts,
+// K in chunks of qc[k] 16-row blocks (as many as fit 128 KiB), lstm_fwd_chunked_grid workgroups.  That kernel starts z at
+// zero: a chunked gather-init or bias-init task is TSPGNN_EUNSUPPORTED -- for the whole launch, before anything runs.
+inline int plan_lstm_fwd_f32(const tspgnn_lstm_task* tasks, int n, int d, int cus, tspgnn_cell_chunk_plan* p) {
+    const size_t extra = (10 * d + 4) * sizeof(float);
+    const size_t per_q = (size_t)16 * 4 * d * sizeof(float);
+    *p = tspgnn_cell_chunk_plan{};
+    long long cost[kMaxTasks];
+    int res[kMaxTasks];
+    int n_res = 0;
+    long long tiles_all = 0;
+    size_t resident = 0;
+    for (int k = 0; k < n; ++k) {
+        const int QT = (tasks[k].dx + d) / 16;
+        const size_t r = (size_t)QT * per_q + extra;
+        p->chunked[k] = r > 160 * 1024;
+        p->qc[k] = p->chunked[k] ? (int)((128 * 1024) / per_q) : QT;
+        if (p->chunked[k]) {
+            if (tasks[k].uv || tasks[k].zbias)
+                return fail(TSPGNN_EUNSUPPORTED, "lnlstm_fwd: gather-init / zbias need K[%d,%d] resident in LDS", d, 4 * d);
+            continue;
+        }
+        const long long tiles = tiles16(tasks[k].rows);
+        cost[n_res] = tiles * (QT + 3);  // k-blocks + ~3 blocks' worth of epilogue
+        res[n_res++] = k;
+        tiles_all += tiles;
+        if (r > resident) resident = r;
+    }
+    p->n = n;
+    // Few tiles (a lone vertex-side task): one wavefront per SIMD and more, smaller workgroups, so every tile gets a matrix
+    // pipe to itself; many tiles: one workgroup per CU, two wavefronts per SIMD.
+    p->nw = n_res && tiles_all <= (long long)cus * 4 ? 4 : 8;
+    if (n_res == 0) return TSPGNN_OK;
+    int end[kMaxTasks];
+    p->grid = split_blocks(cost, n_res, clamp_grid(cus, tiles_all, p->nw), end);
+    p->lds_bytes = (int)resident;
+    for (int k = 0, j = 0, used = 0; k < n; ++k) {
+        if (j < n_res && res[j] == k) used = end[j++];
+        p->blk_end[k] = used;
+    }
+    return TSPGNN_OK;
 }
 
 // tspgnn_lnlstm_fwd_multi_bf16 at the nw wavefronts per workgroup of the kernel its dispatch chose

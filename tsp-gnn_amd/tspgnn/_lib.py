@@ -141,12 +141,14 @@ SIGNATURES = {
     "tspgnn_plan_linear": [c_int, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_mlp_bwd": [c_void_p, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_mlp_fwd": [c_void_p, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_mlp_fwd_f32": [c_void_p, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_wgrad": [c_longlong, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_wcolsum": [c_longlong, c_int, c_int, c_void_p],
     "tspgnn_plan_einit_bwd": [c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_cell_fwd": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_cell_bwd": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_lstm_fwd_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
+    "tspgnn_plan_lstm_fwd_f32": [c_void_p, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_mlp_fwd_bf16": [c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "tspgnn_plan_reduce_slices": [c_int],
     "tspgnn_plan_strided_blocks": [c_longlong, c_int, c_int],
@@ -306,7 +308,8 @@ class CellChunkPlan(ctypes.Structure):
 PLANS = {"tspgnn_plan_linear": LinearPlan, "tspgnn_plan_mlp_bwd": TasksPlan, "tspgnn_plan_mlp_fwd": TasksPlan,
          "tspgnn_plan_wgrad": WgradPlan, "tspgnn_plan_wcolsum": WcolsumPlan, "tspgnn_plan_einit_bwd": EinitBwdPlan,
          "tspgnn_plan_cell_fwd": CellFwdPlan, "tspgnn_plan_cell_bwd": CellChunkPlan,
-         "tspgnn_plan_lstm_fwd_bf16": CellChunkPlan, "tspgnn_plan_mlp_fwd_bf16": TasksPlan}
+         "tspgnn_plan_lstm_fwd_bf16": CellChunkPlan, "tspgnn_plan_mlp_fwd_bf16": TasksPlan,
+         "tspgnn_plan_mlp_fwd_f32": TasksPlan, "tspgnn_plan_lstm_fwd_f32": CellChunkPlan}
 
 
 class TspgnnError(RuntimeError):
