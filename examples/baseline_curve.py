@@ -59,11 +59,13 @@ def network_accuracy(a, instances, devs):
 
 def decoded_curve(a, instances, devs):
     """The tour decoded from the network's edge votes as a decision-TSP predictor (experiments.decoded_tour_curve)."""
-    model = build_network(a.d)
+    model = build_network(a.d, route_head=a.votes == "route")
     sess = Session(model)
     sess.run(global_variables_initializer(seed=a.seed))
-    load_weights(sess, a.checkpoint)
+    load_weights(sess, a.checkpoint, missing_ok=a.votes == "route")
     beam_kw = {} if a.beam is None else {"beam": a.beam}
+    if a.votes != "decision":
+        beam_kw["votes"] = a.votes     # (decoded from E_route, the head trained on the tours' edges)
     return experiments.decoded_tour_curve(sess, model, instances, a.timesteps, devs, **beam_kw)
 
 
@@ -77,6 +79,8 @@ def main(argv=None):
                    help="with -checkpoint: one more column, the accuracy of the tour decoded from the network's edge votes")
     p.add_argument("-beam", default=None, type=int,
                    help="with -decoded: decode by beam search of this width, 1 .. 1024 (default: greedy edge insertion)")
+    p.add_argument("-votes", default="decision", choices=["decision", "route"],
+                   help="with -decoded: decode from E_vote (decision) or from the route head's E_route")
     p.add_argument("--batch-size", default=16, type=int)
     p.add_argument("--instances", default=None, help="directory of .graph files")
     p.add_argument("--limit", default=0, type=int, help="first N files of --instances (0: all)")

@@ -24,6 +24,9 @@ the number of closed entries of the last beam.
 then the KN nearest of the rest (tspgnn.vote_neighbors; decode_tours(guide=(K, KN))).
 
     python examples/decode_tours.py --synthetic 32 -polish -guide 4,4
+
+-votes route decodes from E_route, the head trained on the labelled tours' edges, instead of the decision's E_vote: the
+network is then built with route_head=True, and a checkpoint without the head leaves it as initialised.
 """
 import argparse
 import os
@@ -63,6 +66,8 @@ def main(argv=None):
     p.add_argument("-select", default="score", choices=["score", "cost"], help="with -beam: what the last beam is chosen by")
     p.add_argument("--polish", "-polish", action="store_true", help="one descent of the tour search from every decoded tour")
     p.add_argument("-guide", default=None, help="K[,KN]: with -polish, candidate rows from the votes (K + KN <= 32)")
+    p.add_argument("-votes", default="decision", choices=["decision", "route"],
+                   help="which per-edge logits the decoders read: E_vote (decision) or the route head's E_route")
     p.add_argument("--max-rounds", default=1100, type=int, help="bisection rounds of the cost estimate (see binary_search.py)")
     p.add_argument("--write-graphs", default=None, help="directory for the instances with their decoded tours")
     p.add_argument("--seed", default=0, type=int)
@@ -70,16 +75,18 @@ def main(argv=None):
     a = p.parse_args(argv)
 
     instances = load_instances(a)
-    model = build_network(a.d)
+    model = build_network(a.d, route_head=a.votes == "route")
     sess = Session(model)
     sess.run(global_variables_initializer(seed=a.seed))
     if a.checkpoint:
-        load_weights(sess, a.checkpoint)
+        load_weights(sess, a.checkpoint, missing_ok=a.votes == "route")
     # decode_tours(target_costs=None) runs this same search with its default round limit; untrained weights need more
     estimates = [r[0] for r in get_costs(sess, model, instances, a.timesteps, max_rounds=a.max_rounds)]
     beam_kw = {} if a.beam is None else {"beam": a.beam, "select": a.select}
     if a.guide is not None:
         beam_kw["guide"] = tuple(int(k) for k in (a.guide + ",0").split(",")[:2])
+    if a.votes != "decision":
+        beam_kw["votes"] = a.votes
     res = decode_tours(sess, model, instances, a.timesteps, target_costs=estimates, polish=a.polish, **beam_kw)
     if os.path.dirname(a.out):
         os.makedirs(os.path.dirname(a.out), exist_ok=True)

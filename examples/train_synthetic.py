@@ -16,6 +16,10 @@ DeviceDataset.generate(SAMPLES, 20, 40), no matrix on the host and no file; -wri
 files (DeviceDataset.write_directory, formatted on the GPU) for the reference's train.py / test.py to read.
 With --instances DIR -device_dataset -reader device the .graph files are parsed and packed on the GPU from their raw bytes
 (DeviceDataset.from_directory(reader='device')) instead of one host parse per file.
+-route_head [-route_loss W] trains the second per-edge head as well (build_network(d, route_head=True, route_loss=W)): a
+sigmoid cross entropy of E_route against "this edge lies on the instance's tour", added to the decision loss with weight W.
+The marks come from DeviceDataset(routes=True) with -device_dataset / -generate, or from route_edge_marks_host for the
+synthetic batches; a decision-only checkpoint under --checkpoints starts such a run (load_weights(missing_ok=True)).
 """
 import argparse
 import os
@@ -27,7 +31,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tsp-gnn_amd"))
 from tspgnn import (DeviceDataset, InstanceLoader, Session, build_network, global_variables_initializer, load_weights,  # noqa: E402
-                    random_instance, save_weights, write_graph)
+                    random_instance, route_edge_marks_host, save_weights, write_graph)
 from tspgnn.train import run_batch, run_batches_accumulated, summarize_epoch  # noqa: E402
 
 
@@ -58,7 +62,13 @@ if __name__ == '__main__':
     p.add_argument('-accumulate', default=1, type=int, metavar='K',
                    help='gradient accumulation: every K consecutive batches of an epoch form ONE optimiser step on their '
                         'union (run_batches_accumulated; a short last group is a smaller step); 1: a step per batch')
+    p.add_argument('-route_head', action='store_true',
+                   help='also train E_route, the per-edge head supervised by the tours\' edges (needs the tours with the '
+                        'batches: synthetic instances, -device_dataset or -generate)')
+    p.add_argument('-route_loss', default=1.0, type=float, metavar='W', help='with -route_head: the weight of the route loss')
     a = p.parse_args()
+    if a.route_head and a.instances is not None and not a.device_dataset:
+        p.error('-route_head with --instances DIR needs -device_dataset: InstanceLoader batches do not carry their tours')
     if a.accumulate < 1:
         p.error('-accumulate K needs K >= 1')
     if a.reader == 'device' and (a.instances is None or not a.device_dataset or a.generate):
@@ -78,7 +88,7 @@ if __name__ == '__main__':
     if a.generate:
         random.seed(a.seed)
         np.random.seed(a.seed)
-        dataset = DeviceDataset.generate(a.generate, 20, 40)
+        dataset = DeviceDataset.generate(a.generate, 20, 40, routes=a.route_head)
         t = dataset.summary['times']
         print('generated {} instances in {:.2f} s ({}); certified at dev 0.02: {:.3f}'.format(
             a.generate, t['total'], ', '.join('{} {:.3f}'.format(k, v) for k, v in t.items() if k != 'total'),
@@ -88,16 +98,18 @@ if __name__ == '__main__':
             print('wrote {} bytes of .graph files to {} ({})'.format(
                 w['bytes'], a.write_dir, ', '.join('{} {:.3f}'.format(k, v) for k, v in w['times'].items())), flush=True)
     elif a.device_dataset:   # the same instances every epoch, shuffled per epoch like InstanceLoader.reset()
-        dataset = DeviceDataset.from_directory(a.instances, reader=a.reader) if a.instances is not None else DeviceDataset(
-            [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize * a.batches)])
-    GNN = build_network(a.d)
+        dataset = (DeviceDataset.from_directory(a.instances, reader=a.reader, routes=a.route_head)
+                   if a.instances is not None else
+                   DeviceDataset([random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize * a.batches)],
+                                 routes=a.route_head))
+    GNN = build_network(a.d, route_head=a.route_head, route_loss=a.route_loss)
     with Session() as sess:
         sess.run(global_variables_initializer(seed=a.seed))
         first = 0
         if a.checkpoints is not None and os.path.isdir(a.checkpoints):
             saved = sorted(int(x.split('=')[1]) for x in os.listdir(a.checkpoints) if x.startswith('epoch='))
             if saved:
-                first = load_weights(sess, '{}/epoch={}'.format(a.checkpoints, saved[-1])) + 1
+                first = load_weights(sess, '{}/epoch={}'.format(a.checkpoints, saved[-1]), missing_ok=a.route_head) + 1
         for epoch in range(first, first + a.epochs):
             stats = []
             if dataset is not None:
@@ -109,7 +121,9 @@ if __name__ == '__main__':
                 def synthetic():
                     for _ in range(a.batches):
                         base = [random_instance(int(rng.randint(20, 41)), rng) for _ in range(a.batchsize)]
-                        yield InstanceLoader.create_batch([inst for inst in base for _ in (0, 1)], dev=a.dev)   # each twice
+                        twice = [inst for inst in base for _ in (0, 1)]
+                        batch = InstanceLoader.create_batch(twice, dev=a.dev)
+                        yield batch + (route_edge_marks_host(twice)[0],) if a.route_head else batch
                 batches = synthetic()
             if a.accumulate == 1:
                 for b, batch in enumerate(batches):

@@ -1015,6 +1015,43 @@ int tspgnn_adam_clip_step_f32(float* theta, float* g, float* m, float* v, int n,
                               float* gnorm_out, float* workspace, int* step_counter, const unsigned* skip_flag,
                               void* stream);
 
+/* ------------------------------------------------------------------ route head (csrc/route_head.hip, tspgnn/route_head.py) */
+
+/*
+ * Which edges of a resident batch lie on the instances' labelled tours.  The batch as under "tours from the edge votes":
+ * uv:[M][2] global endpoint ids, seg:[B+1] edge prefix sums, vseg:[B+1] vertex prefix sums.  tours: int32 local vertex ids;
+ * problem p's tour is the n_p = vseg[p+1] - vseg[p] entries from tours + tour_off[p], or from tours + vseg[p] when
+ * tour_off is NULL (the tours concatenated in batch order).  3 <= n_p <= n_max <= 16384 (an int32 position table in LDS).
+ *   marks[e]     1.0 where the edge joins its endpoints (both local ids in [0, n), different) and they are cyclically
+ *                consecutive in the tour -- |pos[a] - pos[b]| in {1, n - 1}, the closing pair (tour[n-1], tour[0])
+ *                included --, else 0.0.  Every entry of seg[0] .. seg[B] is written.
+ *   n_missing[p] the tour's n pairs that no edge joins (a pair joined by several edges counts once).
+ *   status[p]    0; 1 when the tour is no permutation of 0 .. n-1, 2 when n is outside [3, n_max]: then the problem's
+ *                marks are zeros and n_missing[p] = -1.
+ * One workgroup per problem; no floating-point arithmetic.  B == 0 is a no-op; n_max > 16384: TSPGNN_EUNSUPPORTED; B < 0,
+ * n_max < 3 or a null pointer (tour_off aside): TSPGNN_EINVAL, before any launch.
+ */
+int tspgnn_route_edge_marks(const int32_t* uv, const int32_t* seg, const int32_t* vseg, const int32_t* tours,
+                            const int32_t* tour_off, int B, int n_max, float* marks, int32_t* n_missing, int32_t* status,
+                            void* stream);
+
+/*
+ * Per-edge sigmoid cross entropy of logits:[M] against marks:[M] (0 / 1), a mean over each problem's m_p edges and then
+ * over the B problems:
+ *   route_loss = (1/B) sum_p (1/m_p) sum_{e in p} w_e sce(x_e, y_e),   sce(x, y) = max(x, 0) - x y + log1p(exp(-|x|)),
+ *   w_e = 1 for y_e = 0 and pos_weight for y_e = 1; pos_weight == 0 is the balanced rule w_e = (m_p - k_p) / max(k_p, 1),
+ *   k_p the problem's marked edges.
+ *   dlogit[e] = scale w_e (sigmoid(x_e) - y_e) / (B m_p)      (dlogit NULL: the statistics alone)
+ *   stats[6]  = route_loss; the mean over the problems of (TP_p + TN_p) / m_p; TP, FP, TN, FN over the batch, an edge
+ *               counted as predicted where x_e > 0 (TP: predicted and marked, FP: predicted and not marked, ...).
+ * A problem without edges adds nothing.  Deterministic: one workgroup per problem, a thread's edges in ascending order, a
+ * fixed tree over the workgroup, then the problems' partials in problem order; no floating-point atomics.  workspace:
+ * tspgnn_edge_bce_workspace_floats(B) floats.  B < 1, pos_weight < 0 or a null pointer: TSPGNN_EINVAL.
+ */
+long long tspgnn_edge_bce_workspace_floats(int B);
+int tspgnn_edge_bce_f32(const float* logits, const float* marks, const int32_t* seg, int B, float pos_weight, float scale,
+                        float* dlogit, float* stats, float* workspace, void* stream);
+
 /* ------------------------------------------------------------------ batches from a device-resident dataset */
 
 /*

@@ -22,6 +22,7 @@ from .util import load_weights, save_weights
 from .train import run_batch, run_batches_accumulated, summarize_epoch
 from .decode import (tours_from_votes, decode_tours, DecodedBatch, DecodedTour, edge_scores, beam_tours, BeamBatch,
                      BeamTour, vote_neighbors)
+from .route_head import route_edge_marks_host
 from . import experiments
 
 __all__ = [
@@ -32,5 +33,5 @@ __all__ = [
     "create_dataset", "TourResult", "nearest_neighbor_tours", "anneal_tours", "decide",
     "metric_closure", "DeviceDataset", "draw_instances", "draw_streams",
     "tours_from_votes", "decode_tours", "DecodedBatch", "DecodedTour", "edge_scores", "beam_tours", "BeamBatch", "BeamTour",
-    "vote_neighbors",
+    "vote_neighbors", "route_edge_marks_host",
 ]

@@ -118,6 +118,10 @@ SIGNATURES = {
                          c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "tspgnn_vote_neighbors": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                               c_int, c_void_p, c_void_p],
+    "tspgnn_route_edge_marks": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p],
+    "tspgnn_edge_bce_f32": [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                            c_void_p],
     "tspgnn_metric_closure": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     "tspgnn_gather_batch": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_int, c_int, c_int, ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p],
@@ -170,6 +174,7 @@ SIZE_QUERIES = {
     "tspgnn_tour_branch_bound_ws": [c_int, c_int],
     "tspgnn_tour_chains_fit": [c_int, c_int, c_int],
     "tspgnn_tour_beam_workspace_bytes": [c_int, c_int, c_int],
+    "tspgnn_edge_bce_workspace_floats": [c_int],
 }
 
 

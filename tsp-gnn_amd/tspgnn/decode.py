@@ -240,10 +240,15 @@ def beam_tours(batch, scores, beam, select="score", n_vertices=None, workspace_b
 _Decoded = collections.namedtuple("_Decoded", ["tour", "cost", "n_missing", "prediction", "score", "n_closed", "table"])
 
 
-def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="score", workspace_bytes=None, guide=None):
+VOTE_SOURCES = {"decision": "E_vote", "route": "E_route"}   # decode_tours(votes=...): the forward output the decoders read
+
+
+def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="score", workspace_bytes=None, guide=None,
+                  votes="decision"):
     """One _Decoded per instance of one batch: pack at the targets, forward, decode, one read-back.  beam None: the
     greedy decoder, score and n_closed None.  guide = (k_vote, k_near): vote_neighbors follows the forward on the same
-    stream and table is the instance's uint8 [n, K] rows; otherwise None."""
+    stream and table is the instance's uint8 [n, K] rows; otherwise None.  votes: the key of VOTE_SOURCES."""
+    key = VOTE_SOURCES[votes]
     EV, W, C, route_exists, n_vertices, n_edges = InstanceLoader.create_batch(chunk, target_cost=0.0)
     C[:, 0] = np.repeat(np.asarray(targets, dtype=np.float64), n_edges)
     feed = {model["EV"]: EV, model["W"]: W, model["C"]: C, model["time_steps"]: time_steps,
@@ -253,10 +258,10 @@ def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="sc
 
     def run():
         out = sess.forward_device(b)
-        tab = None if guide is None else vote_neighbors(b, out["E_vote"], guide[0], guide[1], n_vertices)
+        tab = None if guide is None else vote_neighbors(b, out[key], guide[0], guide[1], n_vertices)
         if beam is None:
-            return tours_from_votes(b, out["E_vote"], n_vertices), out["predictions"], tab
-        return (beam_tours(b, edge_scores(out["E_vote"]), beam, select, n_vertices, workspace_bytes), out["predictions"],
+            return tours_from_votes(b, out[key], n_vertices), out["predictions"], tab
+        return (beam_tours(b, edge_scores(out[key]), beam, select, n_vertices, workspace_bytes), out["predictions"],
                 tab)
 
     dec, pred, tab = sess._on_bf16x3_if_flagged(run)   # (one synchronising look at the f16x2 range guard)
@@ -275,7 +280,7 @@ def _decode_chunk(sess, model, chunk, targets, time_steps, beam=None, select="sc
 
 
 def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=False, max_graphs=None, beam=None,
-                 select="score", workspace_bytes=None, guide=None, **search_kw):
+                 select="score", workspace_bytes=None, guide=None, votes="decision", **search_kw):
     """A tour per instance from the network's edge votes.
 
     instances: list of (Ma, Mw, route) as for get_costs (4 <= n <= 256; the route is not used by the decoder).
@@ -294,7 +299,14 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
     instead: edge_scores and beam_tours per chunk, ``select`` "score" (the best-scoring closed tour of the last list) or
     "cost" (its cheapest), ``workspace_bytes`` beam_tours' cap; the records are then BeamTour, DecodedTour's fields
     followed by score and n_closed.
+    votes="decision" (the default) decodes from E_vote, the per-edge logits the decision averages; votes="route" from
+    E_route, the head trained on the labelled tours' edges (build_network(d, route_head=True)) -- it selects what goes to
+    tours_from_votes, edge_scores / beam_tours and vote_neighbors, and nothing else.
     Returns a list of DecodedTour (BeamTour with a beam) in input order."""
+    if votes not in VOTE_SOURCES:
+        raise ValueError("decode_tours: votes must be 'decision' or 'route', got %r" % (votes,))
+    if votes == "route" and not getattr(model, "route_head", False):
+        raise ValueError("decode_tours: votes='route' needs a network built with route_head=True")
     if guide is not None:
         if not polish:
             raise TypeError("decode_tours: guide only applies with polish=True")
@@ -324,7 +336,7 @@ def decode_tours(sess, model, instances, time_steps, target_costs=None, polish=F
     rows = []
     for start, stop in plan_chunks(len(instances), 1, DEFAULT_MAX_GRAPHS if max_graphs is None else max_graphs):
         rows += _decode_chunk(sess, model, instances[start:stop], targets[start:stop], time_steps, beam, select,
-                              workspace_bytes, guide)
+                              workspace_bytes, guide, votes)
     polished = [(None, None)] * len(instances)
     if polish and instances:
         from .dataset import label_tours

@@ -279,8 +279,12 @@ class DeviceDataset(object):
 
     ``device='cpu'`` is plumbing only (host tests): the arrays stay on the host and batch() raises."""
 
-    def __init__(self, instances, device=None):
+    def __init__(self, instances, device=None, routes=False):
+        """``routes=True`` keeps the instances' tours on the device as well (int32, 4 sum n bytes): ``batch`` then adds one
+        tspgnn_route_edge_marks launch and the batch carries ``route_edges``, the marks a route-head network trains on
+        (build_network(d, route_head=True)); every route must be a permutation of its instance's vertices (ValueError)."""
         self.device = _default_device(device)
+        instances = list(instances)
         host = preprocess(instances)
         self.n, self.m = host["n"], host["m"]
         I = len(self.n)
@@ -288,11 +292,34 @@ class DeviceDataset(object):
         self._inst, self._uv, self._w, self._rowptr, self._eid, self._cost = (
             D._to_device(a, self.device) for a in (inst, host["uv"], host["w"], host["rowptr"], host["eid"], host["cost"]))
         self._init_batching()
+        if routes:
+            from .route_head import check_tour
+            tours = [check_tour(k, r, int(self.n[k])) for k, (_, _, r) in enumerate(instances)]
+            self._keep_routes(np.concatenate(tours) if tours else np.zeros(0, dtype=np.int64))
 
     def _init_batching(self):
         self._plans = {}     # (e_start bytes, v_start bytes) -> (device int32 plan or None, meta or None)
         self._ring, self._next = [None] * _RING, 0   # [pinned int32 buffer, its device copy, event of the launch that read it]
         self.summary = self.tours = self._matrices = None   # generate() fills these
+        self._routes = self._route_v0 = None                # routes=True: the tours on the device, their int32 offsets (host)
+
+    def _keep_routes(self, flat, on_device=None):
+        """routes=True: ``flat`` -- every instance's tour in local ids, concatenated in instance order (host array) -- is
+        checked (a permutation per instance; ValueError naming the first that is not, before anything is kept) and kept on
+        the device as int32; ``on_device``: the same values already there."""
+        from .route_head import MAX_N, MIN_N, check_tour
+        flat = np.asarray(flat).reshape(-1)
+        v0, N = _prefix(self.n)
+        if len(self.n) and (self.n.min() < MIN_N or self.n.max() > MAX_N):
+            raise ValueError("DeviceDataset(routes=True): instances of %d..%d vertices; the marks take %d <= n <= %d"
+                             % (self.n.min(), self.n.max(), MIN_N, MAX_N))
+        if flat.shape[0] != N:
+            raise ValueError("DeviceDataset(routes=True): the routes hold %d entries for %d vertices: every route is a "
+                             "permutation of its instance's vertices" % (flat.shape[0], N))
+        for k in range(len(self.n)):
+            check_tour(k, flat[v0[k]:v0[k] + self.n[k]], int(self.n[k]))
+        self._routes = on_device if on_device is not None else D._to_device(flat.astype(np.int32), self.device)
+        self._route_v0 = v0.astype(np.int32)
 
     @classmethod
     def _adopt(cls, device, n, m, inst, uv, w, rowptr, eid, cost):
@@ -309,7 +336,8 @@ class DeviceDataset(object):
         return len(self.n)
 
     @classmethod
-    def from_directory(cls, path, device=None, reader="host", text_bytes=G.DEFAULT_TEXT_BYTES, keep_matrices=False):
+    def from_directory(cls, path, device=None, reader="host", text_bytes=G.DEFAULT_TEXT_BYTES, keep_matrices=False,
+                       routes=False):
         """Every file of a ``.graph`` directory, in sorted order.  reader='host': read_graph per file and the host packers
         (text_bytes and keep_matrices are not used).  reader='device': the raw bytes go up in chunks of at most
         ``text_bytes`` of text and the files are taken apart (csrc/graph_parse.hip, graph_text.read_files) and packed
@@ -318,24 +346,25 @@ class DeviceDataset(object):
         <= 256, pairs with i < j, a tour of n entries, weights in the spellings of repr -- and raises ValueError, naming the
         first file and why, for a file it cannot read, before the dataset exists.  keep_matrices: the masks, fp64
         matrices and tours stay on the device as generate keeps them, for to_instances() and write_directory().
-        ``read_times`` then holds the seconds of 'files', 'upload', 'scan', 'parse' and 'pack' and the 'bytes' of text."""
+        ``read_times`` then holds the seconds of 'files', 'upload', 'scan', 'parse' and 'pack' and the 'bytes' of text.
+        routes=True, with either reader: the files' tours stay on the device for the route marks (see __init__)."""
         if reader not in ("host", "device"):
             raise ValueError("DeviceDataset.from_directory: reader=%r must be 'host' or 'device'" % (reader,))
         if reader == "host":
-            return cls([read_graph(os.path.join(path, f)) for f in sorted(os.listdir(path))], device=device)
+            return cls([read_graph(os.path.join(path, f)) for f in sorted(os.listdir(path))], device=device, routes=routes)
         dev = _default_device(device)
         if dev.type != "cuda":
             raise ValueError("DeviceDataset.from_directory: device=%r: the files are read by HIP kernels" % str(dev))
-        return cls._read(path, dev, text_bytes, keep_matrices)
+        return cls._read(path, dev, text_bytes, keep_matrices, routes)
 
     @classmethod
-    def _read(cls, path, dev, text_bytes, keep):
+    def _read(cls, path, dev, text_bytes, keep, routes=False):
         """from_directory(reader='device'): one tspgnn_pack_dataset launch per chunk of read_files into chunk-sized arrays
         (uv, eid and rowptr are instance-local, so the dataset's arrays are the chunks' concatenated), ``inst`` from the
         host prefix sums."""
         paths = [os.path.join(path, f) for f in sorted(os.listdir(path))]
         times = {"files": 0.0, "upload": 0.0, "scan": 0.0, "parse": 0.0, "pack": 0.0, "bytes": 0}
-        parts, kept, ns, ms = [], [], [], []
+        parts, kept, ns, ms, read_tours = [], [], [], [], []
         with torch.cuda.device(dev):
             st = _lib.current_stream()
             for c in G.read_files(paths, dev, text_bytes, times):
@@ -361,6 +390,8 @@ class DeviceDataset(object):
                           _lib.ptr(d_eid) if M else None, _lib.ptr(d_rc), _lib.ptr(d_fc), _lib.ptr(d_cyc), _lib.ptr(d_feas),
                           st)
                 parts.append((d_uv, d_w, d_rowptr, d_eid, d_rc))
+                if routes:
+                    read_tours.append(c.tours)    # int32 [n_verts], the chunk's tours in file order
                 if keep:
                     kept.append(_Kept(np.arange(c.lo, c.hi, dtype=np.int64), c.nc, c.c_off, c.t_off, c.n_cells, c.n_verts,
                                       c.A, c.Mw, c.tours))
@@ -379,13 +410,16 @@ class DeviceDataset(object):
                 tours = (np.concatenate([k.tours.cpu().numpy() for k in kept]) if kept else np.zeros(0, dtype=np.int32))
                 ds.tours = (tours, np.concatenate([v0, [N]]).astype(np.int64))
                 ds._matrices = kept
+            if routes:
+                flat = torch.cat(read_tours) if read_tours else torch.zeros(0, dtype=torch.int32, device=dev)
+                ds._keep_routes(flat.cpu().numpy(), on_device=flat.to(torch.int32).contiguous())
         ds.read_times = times
         return ds
 
     # ------------------------------------------------------------------ made on the device
     @classmethod
     def generate(cls, samples, nmin, nmax, conn_min=1, conn_max=1, distances="euc_2D", metric=True, device=None,
-                 exact=False, chunk_bytes=1 << 30, **solve_kw):
+                 exact=False, chunk_bytes=1 << 30, routes=False, **solve_kw):
         """The dataset DeviceDataset([(np.triu(Ma), Mw, tour)]) of draw_instances(nmin, nmax, conn_min, conn_max, samples,
         distances, metric) labelled by label_tours(init_tours=planted cycles, index=arange(samples), exact=exact,
         **solve_kw) -- byte for byte, the global ``random`` / ``np.random`` consumed exactly alike -- with only the 1-D
@@ -406,7 +440,8 @@ class DeviceDataset(object):
         tspgnn_host_route_cost on Mw, as DeviceDataset(instances) keeps it; summary['target'] is n times that cost on the
         file form of Mw, as create_dataset reports it (they differ only when the closing pair (route[-1], route[1]) is no
         edge).  The fp64 weight matrices, the uint8 masks and the int32 tours of every chunk stay on the device (9 sum n^2 +
-        4 sum n bytes) for to_instances() and write_directory()."""
+        4 sum n bytes) for to_instances() and write_directory().  routes=True: the labels also serve as the batches' route
+        marks (see __init__): one more int32 copy of them in instance order, made after the summary's clock stops."""
         t_begin = time.perf_counter()
         cfg = _generate_settings(samples, nmin, nmax, distances, metric, device, exact, chunk_bytes, solve_kw)
         t0 = time.perf_counter()
@@ -425,6 +460,8 @@ class DeviceDataset(object):
         summary = _summary(ds.n, chunks, file_cost, cyc, feas, exact, times)
         times["total"] = time.perf_counter() - t_begin
         ds.summary = summary
+        if routes:
+            ds._keep_routes(ds.tours[0])
         return ds
 
     @classmethod
@@ -605,6 +642,11 @@ class DeviceDataset(object):
         self.gather(idx, dev, target_cost, b._buf, b._offsets)
         b.T = int(time_steps)
         b.route_exists, b.n_vertices, b.n_edges = labels, self.n[idx], self.m[idx]
+        if self._routes is not None and B:
+            # one more launch: the marks of the instances' tours, into the batch's own route_edges (under out=: in place)
+            from .route_head import launch_marks
+            tour_off = torch.from_numpy(self._route_v0[idx]).to(self.device)
+            launch_marks(b, self._routes, tour_off)
         return b
 
     def get_batches(self, batch_size, dev, time_steps, shuffle=True, rng=None):

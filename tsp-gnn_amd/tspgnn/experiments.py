@@ -91,7 +91,8 @@ def decoded_tour_curve(sess, model, instances_or_loader, time_steps, deviations,
     """baseline_curve with the network as the constructive heuristic: the tour decoded from its edge votes at its own cost
     estimate (decode.decode_tours with target_costs=None, so no label enters), or with polish=True that tour after one
     descent of the tour search, thresholded against C = (1 +/- dev) Q like a nearest-neighbour or annealing tour.  The
-    decoded cost counts only when the tour is feasible (n_missing == 0).  decode_kw go to decode_tours.  Returns
+    decoded cost counts only when the tour is feasible (n_missing == 0).  decode_kw go to decode_tours -- votes="route"
+    among them: the curve of the tours decoded from the route head's E_route instead of E_vote.  Returns
     {'tpr', 'fpr', 'acc', 'deviations'} as baseline_curve does."""
     from . import dataset, decode
     from .instance_loader import read_graph

@@ -27,11 +27,13 @@ from .graphnn import GEMM_ARITH, GraphNN, LSTMStateTuple, to_f32
 from .instance_loader import SparseEV
 from .mlp import Mlp
 from .range_guard import decode, flag_bits
+from . import route_head as RH
 
 LEARNING_RATE = 2e-5          # model.py:13
 L2NORM_SCALING = 1e-10        # model.py:14
 GLOBAL_NORM_CLIP = 0.65       # model.py:15
 STAT_FETCHES = ("loss", "acc", "TP", "FP", "TN", "FN")
+ROUTE_STAT_FETCHES = ("route_loss", "route_acc", "route_TP", "route_FP", "route_TN", "route_FN")   # out["route_stats"]
 
 
 class Placeholder(object):
@@ -79,7 +81,7 @@ class DeviceBatch(object):
 
     def tensors(self):
         """Every device tensor of the batch (for stream bookkeeping when it was uploaded on another stream)."""
-        out = [getattr(self, k, None) for k in ("WC", "labels", "seg")]
+        out = [getattr(self, k, None) for k in ("WC", "labels", "seg", "route_edges")]   # (route_edges: a route-head batch)
         adj = getattr(self, "adj", None)
         if adj is not None:
             out.append(adj.uv)
@@ -94,12 +96,24 @@ class Network(dict):
     """The dict build_network returns, plus the objects Session needs."""
 
 
-def build_network(d, store=None, float_dtype=torch.float32, MLP_depth=3, Msg_last_activation=None):
+def build_network(d, store=None, float_dtype=torch.float32, MLP_depth=3, Msg_last_activation=None, route_head=False,
+                  route_loss=1.0, route_pos_weight=None):
     """model.py:9-170.  ``float_dtype=torch.bfloat16`` (the reference GraphNN's own float_dtype argument,
     graphnn.py:18) stores the embeddings as bf16 with fp32 accumulation (BASELINE config 5); training in that mode is
     mixed precision: bf16 tape, fp32 gradients and fp32 master variables (GraphNN.backward).  ``MLP_depth`` and
     ``Msg_last_activation`` are GraphNN's own (graphnn.py:15-16): hidden layers of the message MLPs, and the activation of
-    their last layer."""
+    their last layer.
+
+    ``route_head=True`` adds a second per-edge head next to E_vote (which the network only ever averages into the decision
+    logit): ``E_route``, an Mlp of E_vote's shape on the same final edge states, declared AFTER every other variable (the
+    flat layout of a network without it is a prefix), trained with a per-edge sigmoid cross entropy against the placeholder
+    ``route_edges`` (float32 [M], 1 where the edge lies on the instance's labelled tour: route_head.py).  ``train_step``
+    then optimises loss + ``route_loss`` * route_loss + L2; the ``loss`` fetch stays the decision loss.  The edge loss is a
+    mean over a problem's edges and then over the problems, a marked edge weighing ``route_pos_weight`` (None: balanced,
+    (m - k) / max(k, 1) per problem of m edges with k marked).  New fetches: ``E_route`` (the per-edge logits),
+    ``route_loss``, ``route_acc`` (the mean over the problems of the fraction of edges whose logit > 0 agrees with the
+    mark), ``route_TP / FP / TN / FN`` (edge counts at that threshold).  Without ``route_head`` nothing changes: the same
+    variables, launches and numbers."""
     d = int(d)
     store = store if store is not None else V.reset_default_store()
     GNN = Network()
@@ -157,6 +171,28 @@ def build_network(d, store=None, float_dtype=torch.float32, MLP_depth=3, Msg_las
     )
     for key in ("last_states", "predictions", "TP", "FP", "TN", "FN", "acc", "loss", "train_step"):
         GNN[key] = Fetch(key)
+    GNN.route_head = bool(route_head)
+    if GNN.route_head:
+        GNN.route_loss_weight = float(route_loss)
+        GNN.route_pos_weight = 0.0 if route_pos_weight is None else float(route_pos_weight)   # 0: the balanced rule
+        weight_ok = route_pos_weight is None or (math.isfinite(GNN.route_pos_weight) and GNN.route_pos_weight > 0)
+        if not math.isfinite(GNN.route_loss_weight) or not weight_ok:
+            raise ValueError("build_network: route_loss=%r must be finite and route_pos_weight=%r positive (or None)"
+                             % (route_loss, route_pos_weight))
+        GNN.E_route_MLP = Mlp(
+            layer_sizes=[d for _ in range(3)],
+            activations=["relu" for _ in range(3)],
+            output_size=1,
+            name="E_route",
+            name_internal_layers=True,
+            kernel_initializer=V.xavier_uniform,
+            bias_initializer=V.zeros_init,
+            input_size=d,
+            store=store,
+        )
+        GNN["route_edges"] = Placeholder("route_edges", np.float32, 1)
+        for key in ("E_route",) + ROUTE_STAT_FETCHES:
+            GNN[key] = Fetch(key)
     build_network.last = GNN
     return GNN
 
@@ -266,6 +302,7 @@ class Session(object):
         C = np.asarray(feed[m["C"]], dtype=np.float32).reshape(-1)
         if W.shape[0] != M or C.shape[0] != M:
             raise ValueError("W and C must have one row per edge (%d), got %d and %d" % (M, W.shape[0], C.shape[0]))
+        marks = self._route_marks(feed, M)
         n_edges = np.asarray(feed[m["n_edges"]]).astype(np.int64).reshape(-1)
         n_vertices = np.asarray(feed[m["n_vertices"]]).astype(np.int64).reshape(-1)
         B = n_vertices.shape[0]
@@ -283,7 +320,42 @@ class Session(object):
         b.labels = labels
         b.seg = torch.from_numpy(np.concatenate([[0], np.cumsum(n_edges)]).astype(np.int32)).to(self.device)
         b.n_vertices, b.n_edges = n_vertices, n_edges   # host int64, as DeviceDataset.batch leaves them
+        if marks is not None:
+            b.route_edges = self._f32(marks, pinned)
         return b
+
+    def _route_marks(self, feed, M):
+        """The feed of model['route_edges'] as a float32 host array of M zeros and ones, or None when the network has no
+        route head or the feed no marks."""
+        m = self.model
+        if not getattr(m, "route_head", False) or m["route_edges"] not in feed:
+            return None
+        marks = np.array(feed[m["route_edges"]], dtype=np.float32).reshape(-1)    # (a copy: never the caller's memory)
+        if marks.shape[0] != M:
+            raise ValueError("feed for model['route_edges']: one mark per edge (%d), got %d" % (M, marks.shape[0]))
+        if not np.all((marks == 0) | (marks == 1)):
+            raise ValueError("feed for model['route_edges']: the marks are 0 or 1")
+        return marks
+
+    def mark_routes(self, batch, tours):
+        """The marks of a resident DeviceBatch from its instances' tours, by tspgnn_route_edge_marks (route_head.py):
+        ``tours`` a list of one sequence of local vertex ids per instance, or the tuple (int32 array, offsets[B + 1]).  Sets
+        ``batch.route_edges`` (refilled in place when the batch already has them) and returns n_missing, the tour pairs
+        per instance that are no edge of its graph.  ValueError naming the instance for a tour that is no permutation."""
+        self._require_gpu("mark_routes")
+        return RH.mark_routes(batch, tours)
+
+    def _has_marks(self, feed):
+        if isinstance(feed, DeviceBatch):
+            return getattr(feed, "route_edges", None) is not None
+        return self.model["route_edges"] in feed
+
+    def _require_marks(self, feed, what):
+        """A route-head network trains on marks: ``what`` without them is refused, naming the placeholder."""
+        if getattr(self.model, "route_head", False) and not self._has_marks(feed):
+            raise ValueError("%s of a route-head network: You must feed a value for placeholder route_edges "
+                             "(model['route_edges']: route_edge_marks_host, or Session.mark_routes on a resident batch)"
+                             % what)
 
     def forward(self, feed, global_stats=False):
         """Runs model.py:33-157 on the device; returns a dict of device tensors.  Rank-local by default, like the
@@ -308,17 +380,25 @@ class Session(object):
         last = m["gnn"]({"EV": b.adj}, {"V": V0, "E": E0}, b.T)               # model.py:118-122
         Eh = to_f32(last["E"].h)                                              # (bf16 storage: widened once)
         arith = m["gnn"].active_arith()
-        vote = (m.E_vote_MLP.forward_split(Eh, arith) if arith else m.E_vote_MLP(Eh)).view(-1)   # model.py:128
-        if arith == "h2" and not m["gnn"].check_h2_weights():     # (the vote head's packing vetoed f16x2: bf16x3)
-            vote = m.E_vote_MLP.forward_split(Eh, m["gnn"].active_arith()).view(-1)
+        heads = [m.E_vote_MLP] + ([m.E_route_MLP] if m.route_head else [])    # (the route head takes the vote head's path)
+        votes = [(h.forward_split(Eh, arith) if arith else h(Eh)).view(-1) for h in heads]       # model.py:128
+        if arith == "h2" and not m["gnn"].check_h2_weights():     # (a head's packing vetoed f16x2: bf16x3)
+            votes = [h.forward_split(Eh, m["gnn"].active_arith()).view(-1) for h in heads]
+        vote = votes[0]
         logits = torch.empty(b.B, dtype=torch.float32, device=self.device)
         _lib.call("tspgnn_segment_mean_f32", _lib.ptr(vote), _lib.ptr(b.seg), _lib.ptr(logits), b.B, st)
         pred = torch.empty(b.B, dtype=torch.float32, device=self.device)
         stats = torch.empty(6, dtype=torch.float32, device=self.device)
         _lib.call("tspgnn_bce_metrics_f32", _lib.ptr(logits), _lib.ptr(b.labels), _lib.ptr(pred), _lib.ptr(stats),
                   b.B, st)
-        return {"last_states": last, "E_vote": vote, "logits": logits, "predictions": pred, "stats": stats,
-                "range_guard": self.store.h2_guard()}
+        out = {"last_states": last, "E_vote": vote, "logits": logits, "predictions": pred, "stats": stats,
+               "range_guard": self.store.h2_guard()}
+        if m.route_head:
+            out["E_route"] = votes[1]
+            marks = getattr(b, "route_edges", None)
+            if marks is not None and b.M:
+                out["route_stats"] = RH.edge_bce(votes[1], marks, b.seg, b.B, m.route_pos_weight, 0.0, False)[1]
+        return out
 
     # ---- f16x2 range guard (GraphNN.active_arith): the default arithmetic's fp16 pieces overflow where the reference's
     # fp32 does not.  Weights are vetted when they are packed; an ACTIVATION that leaves the range sets bit 0 of the
@@ -404,6 +484,8 @@ class Session(object):
                        if self.model[k] not in feed_dict]
             if missing:
                 raise ValueError("You must feed a value for placeholder(s) %s" % ", ".join(missing))
+            if any(n in ROUTE_STAT_FETCHES for n in names):
+                self._require_marks(feed_dict, "fetching " + ", ".join(n for n in names if n in ROUTE_STAT_FETCHES))
             if "train_step" in names:
                 out = self.train_step(feed_dict)   # (looks after the f16x2 range flag itself)
             else:
@@ -421,6 +503,10 @@ class Session(object):
                 stats = out["stats"].cpu().numpy()
             if f.name == "predictions":
                 results.append(out["predictions"].cpu().numpy())
+            elif f.name == "E_route":
+                results.append(out["E_route"].cpu().numpy())
+            elif f.name in ROUTE_STAT_FETCHES:     # (of the local batch, in a data-parallel session too)
+                results.append(np.float32(out["route_stats"].cpu().numpy()[ROUTE_STAT_FETCHES.index(f.name)]))
             elif f.name == "last_states":
                 results.append({v: LSTMStateTuple(c=s.c.cpu().numpy(), h=s.h.to(torch.float32).cpu().numpy())
                                 for v, s in out["last_states"].items()})
@@ -434,6 +520,7 @@ class Session(object):
         """Forward + backward of ``loss`` (the L2 term is added by the optimiser kernel).  Leaves the
         gradient of the local mean loss in ``store.grad``; returns the forward outputs (``keep_tape``: plus the
         message passing's tape under "tape", for inspection -- it holds every step's states)."""
+        self._require_marks(feed, "the gradient")
         self._require_gpu("a training step")
         m, d, st = self.model, self.model.d, _lib.current_stream()
         m["gnn"].check_training()     # (a network that does not train is refused before the gradients are zeroed)
@@ -478,6 +565,7 @@ class Session(object):
         dEh = torch.empty((b.M, d), **f32)
         mv.backward_data(dY3, acts, acts.stride(0), Y3, dpre, dpre.stride(0), dEh, accumulate=False)
         mv.backward_weights([EhT] + [acts[l] for l in range(n_sq - 1)], [dpre[l] for l in range(n_sq)], b.M)
+        route = self._route_head_grads(b, EhT, dEh) if m.route_head else None
         d0 = m["gnn"].backward(tape, {"E": (dEh, None)})
         dE0, dV0 = d0["E"][0], d0["V"][0]
         mi = m.edge_init_MLP
@@ -490,9 +578,41 @@ class Session(object):
             _lib.call("tspgnn_wcolsum_f32", _lib.ptr(dV0), None, b.N, d, 1.0 / math.sqrt(float(d)),
                       _lib.ptr(store.grad_view("V_init")), None, _lib.ptr(ws), st)
         out = {"last_states": last, "E_vote": vote, "logits": logits, "predictions": pred, "stats": stats, "batch": b}
+        if route is not None:
+            out["E_route"], out["route_stats"] = route
         if keep_tape:
             out["tape"] = tape
         return out
+
+    def _route_head_grads(self, b, EhT, dEh):
+        """The route head's part of loss_and_grads, along the lines the vote head takes: its forward on the final edge
+        states keeping the hidden activations, the per-edge cross entropy against ``b.route_edges`` with the gradient
+        scaled by the network's route_loss weight (tspgnn_edge_bce_f32), the head's weight gradients, and its data gradient
+        ADDED to ``dEh`` -- so the message passing's backward sees d(loss + route_loss_weight * route_loss) / d E.h.
+        -> (E_route logits [M], route_stats [6]: route_loss, route_acc, TP, FP, TN, FN of this batch)."""
+        m, d, st, store = self.model, self.model.d, _lib.current_stream(), self.store
+        f32 = dict(dtype=torch.float32, device=self.device)
+        mr = m.E_route_MLP
+        n_sq = mr.n_square
+        Y3 = torch.empty((b.M, d), **f32)
+        acts = torch.empty((max(n_sq - 1, 1), b.M, d), **f32)
+        mr.forward_saving(EhT, Y3, acts, acts.stride(0))
+        head = mr.layer_names[-1]
+        logit = torch.empty(b.M, **f32)
+        _lib.call("tspgnn_rowdot_f32", _lib.ptr(Y3), _lib.ptr(store.view(head + "/kernel")),
+                  _lib.ptr(store.view(head + "/bias")), _lib.ptr(logit), b.M, d, st)
+        dlogit, stats = RH.edge_bce(logit, b.route_edges, b.seg, b.B, m.route_pos_weight, m.route_loss_weight, True)
+        dY3 = torch.empty((b.M, d), **f32)
+        _lib.call("tspgnn_rowdot_bwd_f32", _lib.ptr(dlogit), _lib.ptr(store.view(head + "/kernel")), _lib.ptr(dY3), b.M,
+                  d, st)
+        ws = _lib.workspace("tspgnn_wcolsum_workspace_floats", b.M, d, device=self.device)
+        _lib.call("tspgnn_wcolsum_f32", _lib.ptr(Y3), _lib.ptr(dlogit), b.M, d, 1.0,
+                  _lib.ptr(store.grad_view(head + "/kernel")), _lib.ptr(store.grad_view(head + "/bias")), _lib.ptr(ws),
+                  st)
+        dpre = torch.empty((n_sq, b.M, d), **f32)
+        mr.backward_data(dY3, acts, acts.stride(0), Y3, dpre, dpre.stride(0), dEh, accumulate=True)
+        mr.backward_weights([EhT] + [acts[l] for l in range(n_sq - 1)], [dpre[l] for l in range(n_sq)], b.M)
+        return logit, stats
 
     # The data-parallel step (SURVEY.md §8e G2).  The loss is a mean over the GLOBAL batch (model.py:157), so rank r's
     # gradient of its local mean counts with weight B_r / B.  Everything that must cross ranks rides in ONE bucket:
@@ -688,7 +808,12 @@ class Session(object):
         made identical (bit 2).  In a data-parallel session the word every rank reads is the all-reduced one, so all ranks
         repeat together -- and the "do we need to re-synchronise?" question rides in the step's ONE all-reduce instead of
         a collective and a host round trip of its own before every step: the price is one wasted forward +
-        backward in the step after a checkpoint restore."""
+        backward in the step after a checkpoint restore.
+
+        A route-head network needs its marks (model['route_edges'] in the feed, or ``route_edges`` on the DeviceBatch) and
+        steps on loss + route_loss_weight * route_loss; ``out["route_stats"]`` are those of THIS rank's batch -- they do
+        not ride in the all-reduced bucket, whose layout is unchanged."""
+        self._require_marks(feed, "train_step")
         return self._guarded_step(lambda: self._train_step_once(feed))
 
     def _guarded_step(self, once):
@@ -737,10 +862,14 @@ class Session(object):
         session), ``global_norm`` the optimiser launch's, ``predictions`` the list of the micro-batches' prediction
         tensors and ``batches`` the list of their DeviceBatches.  train_step's guard rules hold for the WHOLE step: the
         word is armed once before the first micro-batch, read once after the optimiser launch, and a flagged (skipped)
-        step is repeated from its first micro-batch."""
+        step is repeated from its first micro-batch.  With a route head the gradient of the route loss accumulates like the
+        decision loss's (both are means over problems, so the B_k weights are right as they stand); ``route_stats`` and
+        ``E_route`` are the LAST micro-batch's (of this rank)."""
         feeds = list(feeds)
         if not feeds:
             raise ValueError("train_step_accumulated: an optimiser step needs at least one micro-batch")
+        for f in feeds:
+            self._require_marks(f, "train_step_accumulated")
         self._require_gpu("a training step")
         batches = [f if isinstance(f, DeviceBatch) else self.prepare(f) for f in feeds]
         return self._guarded_step(lambda: self._accumulated_step_once(batches))
@@ -767,7 +896,9 @@ class Session(object):
         then the accumulated bucket's hand-over, the all-reduce, the unpack and graph B.  ``refill(k)`` is where the
         caller writes micro-batch k into the captured batch's buffers -- ``ds.batch(ids_k, ..., out=batch)``, which
         refuses other shapes; without it the resident batch is taken K times (timing only).  ``out["stats"]`` are the
-        union's; ``out["predictions"]`` are the last micro-batch's."""
+        union's; ``out["predictions"]`` are the last micro-batch's.  A route-head batch carries its marks
+        (``batch.route_edges``; Session.mark_routes and DeviceDataset.batch(out=) refill them in place), and
+        ``out["route_stats"]`` are the local batch's, with micro-batches the last one's."""
         if micro_batches is not None and int(micro_batches) < 1:
             raise ValueError("capture_train_step: micro_batches=%r must be at least 1" % (micro_batches,))
         b = batch if isinstance(batch, DeviceBatch) else self.prepare(batch)

@@ -16,13 +16,32 @@ _FEED_ORDER = ("EV", "W", "C", "route_exists", "n_vertices", "n_edges")
 _STAT_KEYS = ("loss", "acc", "predictions", "TP", "FP", "TN", "FN")
 
 
+_ROUTE_KEYS = ("route_loss", "route_acc")
+
+
+def _route_model(model):
+    return bool(getattr(model, "route_head", False))
+
+
 def _feed_for(model, batch, time_steps):
-    """feed_dict of one ``InstanceLoader`` batch (a 6-tuple in ``_FEED_ORDER``)."""
-    if len(batch) != len(_FEED_ORDER):
+    """feed_dict of one ``InstanceLoader`` batch (a 6-tuple in ``_FEED_ORDER``).  For a route-head network the tuple may
+    carry a seventh item, the per-edge route marks (tspgnn.route_edge_marks_host of the batch's instances): it feeds
+    ``model['route_edges']``."""
+    marked = _route_model(model) and len(batch) == len(_FEED_ORDER) + 1
+    if len(batch) != len(_FEED_ORDER) and not marked:
         raise ValueError("run_batch: a batch is the 6-tuple (%s), got %d items" % (", ".join(_FEED_ORDER), len(batch)))
     feed = {model[key]: value for key, value in zip(_FEED_ORDER, batch)}
     feed[model["time_steps"]] = time_steps
+    if marked:
+        feed[model["route_edges"]] = batch[len(_FEED_ORDER)]
     return feed
+
+
+def _route_fields(route_stats):
+    """The log fields of a route-head batch: the local batch's route loss and edge accuracy (None: no marks, no fields)."""
+    if route_stats is None:
+        return ()
+    return (("route_loss", "%.4f" % route_stats[0]), ("route_acc", "%.4f" % route_stats[1]))
 
 
 def _batch_means(sess, labels, predictions):
@@ -53,23 +72,31 @@ def _run_device_batch(sess, batch, time_steps, train):
     stats = out["stats"].cpu().numpy()
     values = {key: np.float32(stats[k]) for k, key in enumerate(("loss", "acc", "TP", "FP", "TN", "FN"))}
     values["predictions"] = out["predictions"].cpu().numpy()
+    if "route_stats" in out:
+        values["route_stats"] = out["route_stats"].cpu().numpy()
     return values
 
 
 def run_batch(sess, model, batch, batch_i, epoch_i, time_steps, train=False, verbose=True):
     """One ``sess.run`` over ``batch``; with ``train`` the optimiser step is fetched first (train.py:36-42).  ``batch``:
     the create_batch 6-tuple, or a DeviceBatch of DeviceDataset.batch / get_batches (labels and counts from its host
-    arrays)."""
+    arrays).  A route-head network is fed the marks the batch has -- a DeviceBatch's ``route_edges``
+    (DeviceDataset(routes=True), Session.mark_routes) or the tuple's seventh item -- and the line then shows the route loss
+    and edge accuracy of this rank's batch beside the existing fields; the returned tuple is unchanged."""
     from .model import DeviceBatch
     if isinstance(batch, DeviceBatch):
         stats = _run_device_batch(sess, batch, time_steps, train)
         labels, n_vertices, n_edges = batch.route_exists, batch.n_vertices, batch.n_edges
     else:
-        fetches = [model[key] for key in _STAT_KEYS]
+        feed = _feed_for(model, batch, time_steps)
+        keys = _STAT_KEYS + (_ROUTE_KEYS if _route_model(model) and model["route_edges"] in feed else ())
+        fetches = [model[key] for key in keys]
         if train:
             fetches.insert(0, model["train_step"])
-        values = sess.run(fetches, feed_dict=_feed_for(model, batch, time_steps))
-        stats = dict(zip(_STAT_KEYS, values[len(values) - len(_STAT_KEYS):]))
+        values = sess.run(fetches, feed_dict=feed)
+        stats = dict(zip(keys, values[len(values) - len(keys):]))
+        if len(keys) > len(_STAT_KEYS):
+            stats["route_stats"] = [stats[k] for k in _ROUTE_KEYS]
         labels, n_vertices, n_edges = batch[3], batch[4], batch[5]
     mean_label, mean_pred = _batch_means(sess, labels, stats["predictions"])
     if verbose:
@@ -79,7 +106,7 @@ def run_batch(sess, model, batch, batch_i, epoch_i, time_steps, train=False, ver
             ("loss", "%.4f" % stats["loss"]), ("acc", "%.4f" % stats["acc"]),
             ("label_mean", "%.4f" % mean_label),
             ("decided_yes", "%.4f" % float(np.mean(np.round(stats["predictions"])))),
-        ))
+        ) + _route_fields(stats.get("route_stats")))
     return (stats["loss"], stats["acc"], mean_label, mean_pred,
             stats["TP"], stats["FP"], stats["TN"], stats["FN"])
 
@@ -88,7 +115,8 @@ def run_batches_accumulated(sess, model, batches, batch_i, epoch_i, time_steps, 
     """ONE optimiser step over ``batches`` (Session.train_step_accumulated): create_batch 6-tuples or DeviceBatches, each
     a micro-batch whose gradient counts with weight B_k / B.  Returns run_batch's 8-tuple for their union: loss and acc
     are the B-weighted means, TP .. FN the sums, the label / prediction means are taken over all graphs (reduced across
-    ranks as run_batch's are)."""
+    ranks as run_batch's are).  With a route head: marks as in run_batch, and the line shows the route loss and edge
+    accuracy of the LAST micro-batch (of this rank)."""
     from .model import DeviceBatch
     feeds, labels, n_vertices, n_edges = [], [], [], []
     for batch in batches:
@@ -114,7 +142,7 @@ def run_batches_accumulated(sess, model, batches, batch_i, epoch_i, time_steps, 
             ("loss", "%.4f" % stats["loss"]), ("acc", "%.4f" % stats["acc"]),
             ("label_mean", "%.4f" % mean_label),
             ("decided_yes", "%.4f" % float(np.mean(np.round(predictions)))),
-        ))
+        ) + _route_fields(out["route_stats"].cpu().numpy() if "route_stats" in out else None))
     return (stats["loss"], stats["acc"], mean_label, mean_pred,
             stats["TP"], stats["FP"], stats["TN"], stats["FN"])
 

@@ -22,9 +22,12 @@ def _epoch_of(path):
     return int(tail.replace("epoch=", ""))     # util.py:10 -- raises ValueError for other directory names
 
 
-def load_weights(sess, path, scope=None):
+def load_weights(sess, path, scope=None, missing_ok=False):
     """Restore the variables (all of them, or those under ``scope``) and, when the checkpoint holds them, the
-    Adam moments and step count.  Returns the epoch encoded in the directory name ``.../epoch=N``."""
+    Adam moments and step count.  Returns the epoch encoded in the directory name ``.../epoch=N``.
+    ``missing_ok=True``: variables the checkpoint lacks keep the values they have and are printed instead of raising --
+    how a decision-only checkpoint starts a route-head run (build_network(d, route_head=True): E_route/* stay as
+    initialised).  The Adam slots are restored only when the checkpoint holds them for EVERY variable, as without it."""
     if not os.path.exists(path):
         raise Exception('Path does not exist!')
     print('Restoring saved model ... ')
@@ -33,9 +36,11 @@ def load_weights(sess, path, scope=None):
     store = sess.store
     names = [n for n in store.names() if scope is None or n.startswith(scope)]
     missing = [n for n in names if n not in ckpt]
-    if missing:
+    if missing and not missing_ok:
         raise KeyError("checkpoint %s lacks variables: %s" % (path, ", ".join(missing[:5])))
-    store.load({n: ckpt[n] for n in names})
+    if missing:
+        print('Not in the checkpoint, left as they are: %s' % ", ".join(missing))
+    store.load({n: ckpt[n] for n in names if n in ckpt})
     if "beta1_power" in ckpt and all((n + "/Adam") in ckpt and (n + "/Adam_1") in ckpt for n in names):
         sess._ensure_adam()
         for slot, buf in (("/Adam", sess._adam["m"]), ("/Adam_1", sess._adam["v"])):
